@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ALS iteration throughput of the MI355X-native cmfrec hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one ALS iteration (B half-step + A half-step, src/collective.c:9827-10045) over a
@@ -70,6 +70,25 @@ def algorithmic_bytes(nnz, rows, k, w=8):
     return nnz * k * w + nnz * (4 + w) + (rows + 1) * 8 + 2 * rows * k * w + k * k * w
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: each (name, 2-D float32 / float64 array) as out_dir/<name>.npy.  The arrays share DUMP_BYTES equally; one
+    larger than its share is written as a sample of its rows: the same rows (ascending, drawn with a fixed seed) in every run
+    with the same shapes, so that two builds can be compared row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096            # (room for the .npy header)
+    for i, (name, a) in enumerate(arrays):
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("%s: float32 or float64 expected, got %s" % (name, a.dtype))
+        rows = max(1, share // max(1, a[:1].nbytes))
+        if rows < len(a):
+            a = a[np.sort(np.random.default_rng(seed + i).choice(len(a), size=rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -91,7 +110,16 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "fit", "c4shard", "c5shard", "c5"],
                     help="c2 (default, the metric's config): implicit CG LastFM shape; c1 / c3: the explicit "
                          "MovieLens10M-shaped configs of BASELINE.json (single GPU, side measurements)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the factors A and B the last timed step left as DIR/A.npy and DIR/B.npy "
+                         "(a fixed, seeded sample of rows where a matrix exceeds its share of %d MB; the inputs are the same in "
+                         "every run with the same arguments), to compare two builds output for output; c2 on one GPU only"
+                         % (DUMP_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and (args.workload != "c2" or args.gpus != 1):
+        ap.error("--dump-outputs writes the outputs of the headline path: --workload c2 on one GPU")
 
     import torch
     import torch.distributed as dist
@@ -104,6 +132,8 @@ def main():
         raise SystemExit("bench.py needs a GPU (no CPU fallback)")
     torch.cuda.set_device(local_rank)
     use_dist = world > 1 or args.force_dist
+    if use_dist and args.dump_outputs is not None:
+        raise SystemExit("--dump-outputs writes the outputs of the single-GPU headline path, not of the sharded engine")
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -174,6 +204,11 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     rows_per_s = (m + n) / (elapsed / args.steps)
+    if args.dump_outputs is not None:
+        # read before anything below runs more iterations on this session (in-line bins, CPU parity)
+        f = sess.get_factors()
+        dump_outputs(args.dump_outputs, [("A", f["A"]), ("B", f["B"])])
+        del f
 
     # ---- roofline of the dominant kernel (per nnz-bin launch of the CG row kernel) ----
     names = {0: "vh_pass+vh_update x4 (rows > 1024 nnz, split rows)", 1: "cg_rows_kernel<W=8> (257..1024 nnz)",

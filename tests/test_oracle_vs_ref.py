@@ -1,20 +1,18 @@
-"""CPU: the oracle against the REAL reference run live (oracle/_ref, built from /root/reference by
-oracle/Makefile) on fresh seeded problems, both precisions, 1 vs many threads.  Skipped where the
-reference library is not available (it is built in the build container and shipped to the GPU box
-as a binary; /root/reference itself never travels)."""
+"""CPU: the oracle against the REAL reference (oracle/_ref, compiled from the reference's sources by oracle/Makefile) on fresh seeded
+problems, both precisions, 1 vs many threads: run live where oracle/_ref was built, else replayed from its recorded answers to
+the same calls (tests/golden/ref_calls/test_oracle_vs_ref.*.npz, tests/reference_calls.py)."""
 import numpy as np
 import pytest
 
 from conftest import make_coo, rel_err
-from oracle.bindings import Reference, ref_available
+from reference_calls import reference
 
-pytestmark = pytest.mark.skipif(not ref_available(np.float64), reason="oracle/_ref not built")
 TOL = {np.float64: 1e-11, np.float32: 2e-4}
 
 
 @pytest.fixture(scope="module")
 def refs():
-    return {np.float64: Reference(np.float64), np.float32: Reference(np.float32)}
+    return {np.float64: reference(np.float64), np.float32: reference(np.float32)}
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -752,21 +750,19 @@ def test_standalone_fixtures_are_the_reference(dtype):
     compiled reference run live: what the GPU tests of the same names compare the product with is what the reference returns here
     (the summation order of its BLAS may differ between hosts: tolerance of the fixture's precision, ids exact)."""
     import golden_cases as gc
-    if not ref_available(dtype):
-        pytest.skip("oracle/_ref for this precision not built")
-    lib = Reference(dtype).lib
+    R = reference(dtype, replay=False)
     tol = 1e-10 if dtype is np.float64 else 1e-4
     g = gc.load("g29_precompute_standalone", dtype)
     d = gc.precompute_problem(dtype)
     for tag, cases, call in (("e", gc.PRECOMPUTE_EXPLICIT_CASES, gc.precompute_explicit_call), ("i", gc.PRECOMPUTE_IMPLICIT_CASES, gc.precompute_implicit_call)):
         for ci, (name, opts) in enumerate(cases):
-            for key, v in call(lib, d, opts, dtype).items():
+            for key, v in R.apply(call, d, opts, dtype).items():
                 ref = g["%s%d_%s" % (tag, ci, key)]
                 assert np.abs(v.astype(np.float64) - ref).max() <= tol * max(np.abs(ref).max(), 1e-30), (name, key)
     g = gc.load("g30_topn_old", dtype)
     d = gc.topn_problem(dtype)
     for ci, (name, opts) in enumerate(gc.TOPN_CASES):
-        got = gc.topn_call(lib, d, opts, dtype)
+        got = R.apply(gc.topn_call, d, opts, dtype)
         assert np.array_equal(got["ids"], g["c%d_ids" % ci]), name
         assert np.abs(got["scores"] - g["c%d_scores" % ci]).max() <= tol * np.abs(g["c%d_scores" % ci]).max(), name
 
@@ -874,9 +870,7 @@ def test_round6_fixtures_are_the_reference():
     precision: what the GPU tests compare the product with is what the reference returns on this host too."""
     import golden_cases as gc
     dtype = np.float64
-    if not ref_available(dtype):
-        pytest.skip("oracle/_ref for this precision not built")
-    R = Reference(dtype)
+    R = reference(dtype, replay=False)
     def check(fixture, cases, run):
         g = gc.load(fixture, dtype)
         for ci, case in enumerate(cases):
