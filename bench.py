@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ALS iteration throughput of the MI355X-native cmfrec hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one ALS iteration (B half-step + A half-step, src/collective.c:9827-10045) over a
@@ -17,13 +17,17 @@ followed by an all-gather of the updated factor rows over RCCL (torch.distribute
 enqueued on the session's stream (no host synchronisation inside the loop; the A-step's all-gather
 runs part by part beside the kernels of the following parts).
 
-Prints ONE JSON line (rank 0) with the contract fields + "roofline" + "cpu_baseline".
+Prints ONE JSON line (rank 0) with the contract fields + "roofline" (from the timed steps' own HIP events).  A plain run does
+only what that line needs: set-up, warm-up, the timed steps, --dump-outputs.  --full adds what takes runs of its own: the CPU
+baseline ("cpu_baseline", "parity_vs_reference"), the per-bin legs with the nnz bins in line (roofline "inline", "dominant_inline",
+per_kernel[].inline_*), the N = 1 point of the scaling series ("scale_point") and the other BASELINE configurations ("side_points").
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -45,8 +49,8 @@ def synth_block(m, n, nnz, seed):
     cw = 1.0 / np.arange(1, n + 1) ** 0.8; cw = rng.permutation(cw); cw /= cw.sum()
     draws = int(1.35 * nnz)
     rcdf = np.cumsum(rw); ccdf = np.cumsum(cw)
-    r = np.minimum(np.searchsorted(rcdf, rng.random(draws)), m - 1).astype(np.int64)
-    c = np.minimum(np.searchsorted(ccdf, rng.random(draws)), n - 1).astype(np.int64)
+    r = np.minimum(searchsorted(rcdf, rng.random(draws)), m - 1).astype(np.int64)
+    c = np.minimum(searchsorted(ccdf, rng.random(draws)), n - 1).astype(np.int64)
     lin = np.unique(r * n + c)
     lin = rng.permutation(lin)[:nnz]
     if len(lin) < nnz:
@@ -56,9 +60,21 @@ def synth_block(m, n, nnz, seed):
     return row, col, val
 
 
+def searchsorted(a, v):
+    """np.searchsorted(a, v), chunk by chunk on a few threads (numpy releases the GIL there): the same indices in a fraction of
+    the time it takes on one for the tens of millions of draws of a full-size workload."""
+    nthreads = min(8, len(os.sched_getaffinity(0)))
+    with ThreadPoolExecutor(nthreads) as ex:
+        return np.concatenate(list(ex.map(lambda part: np.searchsorted(a, part), np.array_split(v, 4 * nthreads))))
+
+
 def to_csr(row, col, val, nrows):
     """Stable COO -> CSR (entries keep COO order inside a row, like helpers.c:1375-1491)."""
-    order = np.argsort(row, kind="stable")
+    # row << 32 | position is unique per entry (row >= 0, fewer than 2^32 entries), so its sorted order is the stable order of
+    # the rows -- and numpy sorts 64-bit keys several times faster than it argsorts stably
+    key = (row.astype(np.uint64) << np.uint64(32)) | np.arange(len(row), dtype=np.uint64)
+    key.sort()
+    order = (key & np.uint64(0xFFFFFFFF)).astype(np.intp)
     indptr = np.zeros(nrows + 1, np.uint64)
     np.cumsum(np.bincount(row, minlength=nrows), out=indptr[1:])
     return indptr, col[order].astype(np.int32), val[order]
@@ -94,9 +110,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scale-point", action="store_true", help="skip the N = 1 point of the scaling series (config 4 on one GPU)")
-    ap.add_argument("--no-side-points", action="store_true", help="skip the other BASELINE configurations (c1, c3, c4shard, c5shard, whole fit)")
+    ap.add_argument("--full", action="store_true",
+                    help="the headline on one GPU and, after it, everything else the line can carry: the CPU baseline with its "
+                         "parity check, the per-bin legs with the nnz bins in line, the N = 1 point of the scaling series and the "
+                         "other BASELINE configurations (the --no-* options below leave parts out); a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
+    ap.add_argument("--no-scale-point", action="store_true",
+                    help="with --full: skip the N = 1 point of the scaling series (config 4 on one GPU) and the side points")
+    ap.add_argument("--no-side-points", action="store_true",
+                    help="with --full: skip the other BASELINE configurations (c1, c3, c4shard, c5shard, whole fit)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debug only; invalid as a result)")
     ap.add_argument("--force-dist", action="store_true", help="use the sharded engine + collectives even with 1 rank (test)")
     ap.add_argument("--item-blocks", default="dealt", choices=["dealt", "contiguous"],
@@ -205,7 +227,7 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     rows_per_s = (m + n) / (elapsed / args.steps)
     if args.dump_outputs is not None:
-        # read before anything below runs more iterations on this session (in-line bins, CPU parity)
+        # read before anything below runs more iterations on this session (--full: in-line bins, CPU parity)
         f = sess.get_factors()
         dump_outputs(args.dump_outputs, [("A", f["A"]), ("B", f["B"])])
         del f
@@ -285,8 +307,8 @@ def main():
                                      **({"runs_beside_other_kernels": True} if d["overlapped"] else {}))
                                 for d in kernels])
 
-    # ---- the same kernels with the bins in line: every bin's own duration (what rocprofv3's per-kernel averages show) ----
-    if side_by_side and os.environ.get("CMFREC_HIP_BINS_PAR") is None:
+    # ---- --full: the same kernels with the bins in line: every bin's own duration (what rocprofv3's per-kernel averages show) ----
+    if args.full and side_by_side and os.environ.get("CMFREC_HIP_BINS_PAR") is None:
         def _name(which, b):
             return ("gram_wave+gram_cg (rows > 1024 nnz, single gather, CG on the row's Gramian)"
                     if b == 0 and sess.vh_mode(which) == 2 else names[b])
@@ -319,10 +341,10 @@ def main():
         roofline["matrix_pipe"] = {"executed_TFLOPs": round(mf, 1), "peak_fp64_TFLOPs": 78.6, "frac": round(mf / 78.6, 3),
                                    "note": "flops the kernel issues (16-wide tiles over k = 50 and full diagonal tiles included); "
                                            "tools/microbench/mfma_rate.hip measures 47 TFLOP/s for this instruction on the part"}
-    # ---- CPU baseline: the reference itself (oracle/_ref) on this host, rank 0 / N=1 only ----
+    # ---- --full: CPU baseline: the reference itself (oracle/_ref) on this host, rank 0 / N=1 only ----
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         def compare(ref):
             # the same iterations from the same start on the GPU, against the CPU run's factors (whole fit 1e-6 in fp64)
             sess.set_factors(A=A0_blk, B=np.zeros((n, K)))
@@ -343,9 +365,9 @@ def main():
                     "tolerance": 1e-6, "workload": "the full C2 workload of this line, same start (A0 uniform 2^-7, B0 = 0)"}
         cpu, parity = cpu_baseline(row, col, val, m_blk, n, A0_blk, compare=compare)
 
-    # ---- the N = 1 point of the scaling series: BASELINE.json configs[3] on this one GPU, through the distributed engine ----
+    # ---- --full: the N = 1 point of the scaling series: BASELINE.json configs[3] on this one GPU, through the distributed engine ----
     scale_point = None
-    if rank == 0 and world == 1 and not use_dist and args.scale == 1.0 and not args.no_scale_point:
+    if args.full and rank == 0 and world == 1 and not use_dist and args.scale == 1.0 and not args.no_scale_point:
         try:
             del sess
             torch.cuda.empty_cache()
@@ -362,9 +384,9 @@ def main():
         except Exception as e:        # the headline above must not depend on it
             scale_point = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    # ---- the other BASELINE configurations on this GPU, one child process each ----
+    # ---- --full: the other BASELINE configurations on this GPU, one child process each ----
     side = None
-    if rank == 0 and world == 1 and not use_dist and args.scale == 1.0 and not args.no_scale_point and not args.no_side_points:
+    if args.full and rank == 0 and world == 1 and not use_dist and args.scale == 1.0 and not args.no_scale_point and not args.no_side_points:
         side = side_points(args)
 
     if rank == 0:
@@ -377,7 +399,8 @@ def main():
                                                                                " (1 LastFM-sized user block per GPU)" if world > 1 else ""),
                           "parallelism": "row-block x%d + all-gather" % world if world > 1 else "single GPU",
                           "gen_seconds": round(t_gen, 1)},
-               "roofline": roofline, "cpu_baseline": cpu, "parity_vs_reference": parity, "scale_point": scale_point, "side_points": side}
+               "full": args.full, "roofline": roofline, "cpu_baseline": cpu, "parity_vs_reference": parity, "scale_point": scale_point,
+               "side_points": side}
         if args.scale != 1.0:
             out["config"]["INVALID_scaled_down"] = args.scale
         final_line = json.dumps(out)
@@ -570,7 +593,7 @@ def c4_run(args, rank, world, local_rank, steps, warmup):
                           "gen_seconds": round(t_gen, 1), "setup_seconds": round(t_setup, 1)},
                "roofline": roofline, "cpu_baseline": None}
         out["config"]["scaling_series"] = ("BASELINE.json configs[3] at N = 1, 2, 4, 8: every --gpus N > 1 line runs THIS workload; its N = 1 point "
-                                           "is the \"scale_point\" object of the --gpus 1 line (the same engine and collectives on one rank), which is "
+                                           "is the \"scale_point\" object of the --gpus 1 --full line (the same engine and collectives on one rank), which is "
                                            "what a per-N value is to be divided by -- not the headline of --gpus 1 (C2, double precision)")
         if args.scale != 1.0:
             out["config"]["INVALID_scaled_down"] = args.scale

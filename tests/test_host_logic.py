@@ -59,6 +59,10 @@ def test_bench_generator_and_bytes():
     assert np.array_equal(row, r2) and np.array_equal(val, v2)               # seeded
     p, i, v = bench.to_csr(row, col, val, 500)
     assert p[-1] == 6000 and (np.diff(p.astype(np.int64)) >= 0).all()
+    o = np.argsort(row, kind="stable")                                       # entries keep COO order inside a row
+    assert np.array_equal(i, col[o]) and np.array_equal(v, val[o])
+    q = np.random.default_rng(0).random(1001)
+    assert np.array_equal(bench.searchsorted(np.sort(q[:300]), q), np.searchsorted(np.sort(q[:300]), q))
     # 6.92 GB gather + 0.21 GB CSR per half-step at LastFM size
     b = bench.algorithmic_bytes(bench.NNZ, bench.M_USERS, bench.K)
     assert abs(bench.NNZ * bench.K * 8 / 1e9 - 6.92) < 0.01 and 7.3e9 < b < 7.6e9

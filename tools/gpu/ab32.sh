@@ -12,7 +12,7 @@ key = [k for k in d if k.startswith('bins')]
 print('c4shard $L', d.get('ms_per_iteration'), d.get('halfstep_ms'), {k: v['ms'] for k, v in d[key[0]].items()} if key else None)" | tee -a $O/lines.txt
 done; done
 for L in "$@"; do
-  CMFREC_HIP_LIBDIR=$R/cmfrec_amd/$L python $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python -c "
+  CMFREC_HIP_LIBDIR=$R/cmfrec_amd/$L python $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python -c "
 import sys, json
 l = [x for x in sys.stdin if x.startswith('{')]
 d = json.loads(l[-1]) if l else {}

@@ -12,7 +12,7 @@
 #   sideab <workload> <libdirA> <libdirB>   a side workload on two builds, alternating
 #   sideenv <workload> <VAR> <v1> <v2> ...  a side workload once per value of an environment switch, alternating
 #   final [nosuite]            the end-of-round set: suite, smoke, counter passes with the bins in line, kernel statistics of the
-#                              default and the in-line run, the default bench line, side workloads, the --force-dist launch paths on
+#                              default and the in-line run, the bench line with --full, side workloads, the --force-dist launch paths on
 #                              one rank, the suite again with poisoned LDS
 export TMPDIR=/tmp
 MODE=${1:-tests}; shift
@@ -20,7 +20,7 @@ TAG=${TAG:-$MODE}
 O=gpurun_out/$TAG; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 F='^RCCL\|^HIP ver\|^ROCm ver\|^Hostname\|^Librccl\|amdgpu.ids'
-B="python $R/bench.py --no-cpu-baseline --no-scale-point"
+B="python $R/bench.py --full --no-cpu-baseline --no-scale-point"
 cat > /tmp/line.py <<'PY'
 import sys, json
 tag = sys.argv[1]
@@ -46,9 +46,9 @@ ab)
   for w in c4shard c1; do for L in "$1" "$2"; do
     CMFREC_HIP_LIBDIR=$R/cmfrec_amd/$L $B --workload $w --steps 20 --warmup 3 2>/dev/null | python /tmp/line.py "$w $L" | tee -a $O/lines.txt
   done; done
-  # config 4 on one GPU (the scale point of the default line), per bin in line
+  # config 4 on one GPU (the scale point of the --full line), per bin in line
   for L in "$1" "$2"; do
-    CMFREC_HIP_LIBDIR=$R/cmfrec_amd/$L python $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python -c "
+    CMFREC_HIP_LIBDIR=$R/cmfrec_amd/$L python $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python -c "
 import sys, json
 l = [x for x in sys.stdin if x.startswith('{')]
 sp = (json.loads(l[-1]).get('scale_point') or {}) if l else {}
@@ -99,12 +99,12 @@ final)
   rm -rf $O/pmc_fetch $O/pmc_write $O/pmc_valu $O/pmc_busy $O/pmc_tcc $O/pmc_mfma $O/pmc_mfmai $O/pmc_lds
   for mode in default inline; do
     if [ $mode = inline ]; then export CMFREC_HIP_BINS_PAR=1; else unset CMFREC_HIP_BINS_PAR; fi
-    cd /tmp; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/trace_$mode -o c2 -- python $R/bench.py --no-cpu-baseline --no-scale-point > $R/$O/bench_under_rocprof_$mode.json 2>$R/$O/bench_under_rocprof_$mode.err; echo "trace $mode rc=$?"
+    cd "$TMPDIR"; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/trace_$mode -o c2 -- $B > $R/$O/bench_under_rocprof_$mode.json 2>$R/$O/bench_under_rocprof_$mode.err; echo "trace $mode rc=$?"
     cd $R; f=$(find $O/trace_$mode -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_$mode.csv
     rm -rf $O/trace_$mode
   done
   unset CMFREC_HIP_BINS_PAR
-  timeout -k 10 900 python bench.py > $O/bench.json 2>$O/bench.err; echo "bench rc=$?"; tail -1 $O/bench.json | cut -c1-1500
+  timeout -k 10 900 python bench.py --full > $O/bench.json 2>$O/bench.err; echo "bench rc=$?"; tail -1 $O/bench.json | cut -c1-1500
   rm -f $O/bench_side.jsonl
   for w in c1 c3 c4shard c5shard fit; do
     timeout -k 10 900 python bench.py --no-cpu-baseline --workload $w --steps 10 --warmup 3 2>/dev/null | tail -1 >> $O/bench_side.jsonl
