@@ -3,5 +3,6 @@ interface (fit_collective_*_als C ABI + CMF / CMF_implicit ``fit``)."""
 from .models import CMF, CMF_implicit  # noqa: F401
 from .session import AlsSession  # noqa: F401
 from . import ops  # noqa: F401
+from .rank import Ranker  # noqa: F401
 
-__all__ = ["CMF", "CMF_implicit", "AlsSession", "ops"]
+__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "ops"]

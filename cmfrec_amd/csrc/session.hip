@@ -849,9 +849,9 @@ static int launch_plain_lowrank(const DeviceInfo &dev, const CholCall &c, const 
     return 0;
 }
 
-static void init_device(DeviceInfo &dev, int device)
+void open_device(int device, int *device_id, int *num_cus, hipStream_t *stream)
 {
-    switches_mut().reload();           // the environment switches, once per session / operator call (device.hpp, Switches)
+    switches_mut().reload();           // the environment switches, once per session / operator call (device_base.hpp, Switches)
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0) {
@@ -860,11 +860,16 @@ static void init_device(DeviceInfo &dev, int device)
         throw HipError{4};
     }
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipGetDevice(&dev.device));
+    HIP_CHECK(hipGetDevice(device_id));
     hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev.device));
-    dev.num_cus = prop.multiProcessorCount;
-    HIP_CHECK(hipStreamCreateWithFlags(&dev.stream, hipStreamNonBlocking));
+    HIP_CHECK(hipGetDeviceProperties(&prop, *device_id));
+    *num_cus = prop.multiProcessorCount;
+    HIP_CHECK(hipStreamCreateWithFlags(stream, hipStreamNonBlocking));
+}
+
+static void init_device(DeviceInfo &dev, int device)
+{
+    open_device(device, &dev.device, &dev.num_cus, &dev.stream);
 }
 
 }  // namespace cmfhip
@@ -956,18 +961,6 @@ static void trim_events(std::vector<EventPair> &v)
     if (v.size() < CAP) return;
     for (size_t e = 0; e < CAP / 2; e++) { (void)hipEventDestroy(v[e].a); (void)hipEventDestroy(v[e].b); }
     v.erase(v.begin(), v.begin() + CAP / 2);
-}
-
-static int guarded(const std::function<int()> &f)
-{
-    try {
-        return f();
-    } catch (const HipError &e) {
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        g_last_error = "cmfrec_hip: host out of memory";
-        return 1;
-    }
 }
 
 extern "C" {
@@ -3084,48 +3077,7 @@ int cmfrec_hip_optimizeA_dense_full(real_t *A, size_t lda, const real_t *B, size
     });
 }
 
-int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
-                          const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
-                          int_t *out_ids, real_t *out_scores)
-{
-    return guarded([&]() {
-        if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids) {
-            g_last_error = "cmfrec_hip_topN_batch: invalid arguments";
-            return 2;
-        }
-        if (k > TOPN_KMAX || n_top > TOPN_NMAX || n_top > n) {
-            g_last_error = "cmfrec_hip_topN_batch: needs k <= 64 and n_top <= min(128, n)";
-            return 2;
-        }
-        DeviceInfo dev;
-        init_device(dev, -1);
-        DevBuf<real_t> dA, dB, dbias, dsc;
-        DevBuf<size_t> dep; DevBuf<int> dei, dids;
-        dA.upload(A, (size_t)nu * lda, dev.stream);
-        dB.upload(B, (size_t)n * ldb, dev.stream);
-        if (biasB) dbias.upload(biasB, (size_t)n, dev.stream);
-        if (excl_p) {
-            dep.upload(excl_p, (size_t)nu + 1, dev.stream);
-            dei.upload(excl_i, std::max<size_t>(excl_p[nu], 1), dev.stream);
-        }
-        dids.alloc((size_t)nu * n_top);
-        if (out_scores) dsc.alloc((size_t)nu * n_top);
-        TopnParams<real_t> P;
-        P.A = dA.ptr; P.lda = lda; P.nu = nu; P.B = dB.ptr; P.ldb = ldb; P.n = n; P.k = k;
-        P.biasB = biasB ? dbias.ptr : nullptr;
-        P.excl_p = excl_p ? dep.ptr : nullptr; P.excl_i = excl_p ? dei.ptr : nullptr;
-        P.n_top = n_top; P.out_ids = dids.ptr; P.out_scores = out_scores ? dsc.ptr : nullptr;
-        const size_t smem = topn_lds_bytes(sizeof(real_t));
-        HIP_CHECK(hipFuncSetAttribute((const void *)topn_kernel<real_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        const int tiles = (nu + TOPN_UT - 1) / TOPN_UT;
-        hipLaunchKernelGGL(topn_kernel<real_t>, dim3(std::min(tiles, dev.num_cus * 2)), dim3(TOPN_TH), smem, dev.stream, P);
-        HIP_CHECK(hipGetLastError());
-        dids.download(out_ids, (size_t)nu * n_top, dev.stream);
-        if (out_scores) dsc.download(out_scores, (size_t)nu * n_top, dev.stream);
-        HIP_CHECK(hipStreamSynchronize(dev.stream));
-        return 0;
-    });
-}
+// (cmfrec_hip_topN_batch and the ranking handle: topn_tu.hip)
 
 // ---- the reference's stand-alone entry points for the prediction matrices and the ranking, under their own names and with
 // ---- their own signatures (round 6; src/cmfrec.h:1922-1960, :2104-2127) ------------------------------------------------------

@@ -1,0 +1,245 @@
+// topn_tu.hip -- the ranking entry points: cmfrec_hip_ranker_* (the item factors stay on the device between calls) and
+// cmfrec_hip_topN_batch (one ranker for one call).  A translation unit of its own, like chol_wg_tu.hip: the wide kernel's
+// instantiations stay out of session.hip's compile.
+//
+// Routing: k <= TOPN_KMAX (64) launches topn_kernel, the kernel of every release so far; beyond that -- or for every k under
+// CMFREC_HIP_TOPN=wide, a cross-check and A/B switch -- topn_wide_kernel (topn_wide_kernels.hpp).
+#include <algorithm>
+#include "device_base.hpp"
+#include "topn_wide_kernels.hpp"
+
+using namespace cmfhip;
+
+struct cmfrec_hip_ranker {
+    struct Device { int device = 0, num_cus = 256; hipStream_t stream = nullptr; } dev;
+    int n = 0, k = 0;
+    size_t ldb = 0;                          // columns of the packed item matrix on the device: topnw_kp(k), columns [k, ldb) zero
+    bool has_bias = false;
+    DevBuf<real_t> B, bias;                  // uploaded once
+    DevBuf<real_t> A, sc;                    // per call; they grow on demand
+    DevBuf<size_t> ep;
+    DevBuf<int> ei, ids;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the ranking kernel of the last call
+    bool timed = false;
+    int last_users = 0, last_grid = 0;       // users per workgroup and workgroups of that launch
+    ~cmfrec_hip_ranker()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (dev.stream) (void)hipStreamDestroy(dev.stream);
+    }
+};
+
+namespace {
+
+constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
+
+// the calling thread's current device while a handle made on another one is used
+struct DeviceScope {
+    int prev = -1;
+    explicit DeviceScope(int device)
+    {
+        int cur = -1;
+        HIP_CHECK(hipGetDevice(&cur));
+        if (cur != device) { HIP_CHECK(hipSetDevice(device)); prev = cur; }
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// rows x cols values from a host matrix with leading dimension ld into a device matrix with leading dimension dld
+void upload_columns(real_t *dst, size_t dld, const real_t *src, size_t ld, size_t rows, size_t cols, hipStream_t st)
+{
+    if (ld == cols && dld == cols) HIP_CHECK(hipMemcpyAsync(dst, src, rows * cols * sizeof(real_t), hipMemcpyDefault, st));
+    else HIP_CHECK(hipMemcpy2DAsync(dst, dld * sizeof(real_t), src, ld * sizeof(real_t), cols * sizeof(real_t), rows, hipMemcpyDefault, st));
+}
+
+// User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
+// unless fewer finish the nu users in fewer or cheaper waves of workgroups.  A workgroup's time per item round is about
+// (nut + 1/2) -- its MFMAs and the item fetch they share -- times the workgroups that share its CU.
+// CMFREC_HIP_TOPN_TILES (test hook) asks for a number of tiles; it is clamped to what fits.
+int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu)
+{
+    const int forced = switches().topn_tiles;
+    int best = 1, best_bpc = 1;
+    double best_cost = 0;
+    for (int nut = 1; nut <= TOPNW_MAX_NUT; nut++) {
+        const size_t smem = topnw_lds_bytes(nut, k, n_top, sizeof(real_t));
+        if (smem > TOPNW_LDS_MAX) break;
+        const int bpc = (int)std::min<size_t>(TOPNW_LDS_MAX / smem, (size_t)(2048 / TOPNW_TH));
+        const long tiles = ((long)nu + 16 * nut - 1) / (16 * nut), slots = (long)num_cus * bpc;
+        const long share = std::min<long>(bpc, (tiles + num_cus - 1) / num_cus);
+        const double cost = (double)((tiles + slots - 1) / slots) * share * (nut + 0.5);
+        if (nut == 1 || (forced > 0 ? nut <= forced : cost <= best_cost)) { best = nut; best_bpc = bpc; best_cost = cost; }
+    }
+    *blocks_per_cu = best_bpc;
+    return best;
+}
+
+template <int NUT>
+int launch_wide(const cmfrec_hip_ranker::Device &dev, const TopnWideParams<real_t> &P, int blocks_per_cu)
+{
+    const size_t smem = topnw_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
+    HIP_CHECK(hipFuncSetAttribute((const void *)topn_wide_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
+    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
+    hipLaunchKernelGGL((topn_wide_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
+    return grid;
+}
+
+int check_n_top(const char *fn, int_t n_top, int_t n)
+{
+    if (n_top > TOPN_NMAX || n_top > n) {
+        g_last_error = std::string(fn) + ": " + LIMITS;
+        return 2;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+cmfrec_hip_ranker *cmfrec_hip_ranker_create(const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB, int device)
+{
+    cmfrec_hip_ranker *r = nullptr;
+    const int rc = guarded([&]() {
+        if (B == nullptr || n <= 0 || k <= 0 || ldb < (size_t)k) {
+            g_last_error = "cmfrec_hip_ranker_create: invalid arguments";
+            return 2;
+        }
+        if (k > TOPNW_KMAX) {
+            g_last_error = std::string("cmfrec_hip_ranker_create: ") + LIMITS;
+            return 2;
+        }
+        r = new cmfrec_hip_ranker();
+        open_device(device, &r->dev.device, &r->dev.num_cus, &r->dev.stream);
+        r->n = n; r->k = k; r->ldb = (size_t)topnw_kp(k, sizeof(real_t));
+        r->B.alloc((size_t)n * r->ldb);
+        if (r->ldb != (size_t)k) HIP_CHECK(hipMemsetAsync(r->B.ptr, 0, r->B.n * sizeof(real_t), r->dev.stream));
+        upload_columns(r->B.ptr, r->ldb, B, ldb, (size_t)n, (size_t)k, r->dev.stream);
+        r->has_bias = biasB != nullptr;
+        if (biasB) r->bias.upload(biasB, (size_t)n, r->dev.stream);
+        HIP_CHECK(hipEventCreate(&r->ev0));
+        HIP_CHECK(hipEventCreate(&r->ev1));
+        HIP_CHECK(hipStreamSynchronize(r->dev.stream));      // the caller's B may go away
+        return 0;
+    });
+    g_last_rc = rc;
+    if (rc != 0) {
+        delete r;
+        return nullptr;
+    }
+    return r;
+}
+
+int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t excl_p[], const int_t excl_i[],
+                           int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || n_top <= 0 || !A || !out_ids || lda < (size_t)r->k || (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
+            g_last_error = "cmfrec_hip_ranker_topN: invalid arguments";
+            return 2;
+        }
+        if (int rc = check_n_top("cmfrec_hip_ranker_topN", n_top, r->n)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        const int k = r->k;
+        r->A.alloc_at_least((size_t)nu * k);
+        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        if (excl_p) {
+            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
+            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
+            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
+        }
+        r->ids.alloc_at_least((size_t)nu * n_top);
+        if (out_scores) r->sc.alloc_at_least((size_t)nu * n_top);
+        HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+        if (k <= TOPN_KMAX && !switches().topn_wide) {
+            TopnParams<real_t> P;
+            P.A = r->A.ptr; P.lda = (size_t)k; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
+            P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+            P.excl_p = excl_p ? r->ep.ptr : nullptr; P.excl_i = excl_p ? r->ei.ptr : nullptr;
+            P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+            const size_t smem = topn_lds_bytes(sizeof(real_t));
+            HIP_CHECK(hipFuncSetAttribute((const void *)topn_kernel<real_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            const int tiles = (nu + TOPN_UT - 1) / TOPN_UT;
+            hipLaunchKernelGGL(topn_kernel<real_t>, dim3(std::min(tiles, dev.num_cus * 2)), dim3(TOPN_TH), smem, dev.stream, P);
+            r->last_users = TOPN_UT; r->last_grid = std::min(tiles, dev.num_cus * 2);
+        } else {
+            TopnWideParams<real_t> P;
+            P.A = r->A.ptr; P.lda = (size_t)k; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
+            P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+            P.excl_p = excl_p ? r->ep.ptr : nullptr; P.excl_i = excl_p ? r->ei.ptr : nullptr;
+            P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+            int bpc = 1;
+            const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
+            switch (nut) {
+            case 1: r->last_grid = launch_wide<1>(dev, P, bpc); break;
+            case 2: r->last_grid = launch_wide<2>(dev, P, bpc); break;
+            case 3: r->last_grid = launch_wide<3>(dev, P, bpc); break;
+            default: r->last_grid = launch_wide<4>(dev, P, bpc); break;
+            }
+            r->last_users = 16 * nut;
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
+        r->timed = true;
+        r->ids.download(out_ids, (size_t)nu * n_top, dev.stream);
+        if (out_scores) r->sc.download(out_scores, (size_t)nu * n_top, dev.stream);
+        HIP_CHECK(hipStreamSynchronize(dev.stream));
+        return 0;
+    });
+}
+
+int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms)
+{
+    return guarded([&]() {
+        if (r == nullptr || ms == nullptr || !r->timed) {
+            g_last_error = "cmfrec_hip_ranker_kernel_ms: no ranking call on this handle yet";
+            return 2;
+        }
+        HIP_CHECK(hipEventSynchronize(r->ev1));
+        float t = 0;
+        HIP_CHECK(hipEventElapsedTime(&t, r->ev0, r->ev1));
+        *ms = (double)t;
+        return 0;
+    });
+}
+
+int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups)
+{
+    if (r == nullptr || !r->timed) {
+        g_last_error = "cmfrec_hip_ranker_launch_shape: no ranking call on this handle yet";
+        return 2;
+    }
+    if (users_per_workgroup) *users_per_workgroup = r->last_users;
+    if (workgroups) *workgroups = r->last_grid;
+    return 0;
+}
+
+void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r)
+{
+    delete r;
+}
+
+int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                          const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                          int_t *out_ids, real_t *out_scores)
+{
+    if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids) {
+        g_last_error = "cmfrec_hip_topN_batch: invalid arguments";
+        return 2;
+    }
+    if (k > TOPNW_KMAX || n_top > TOPN_NMAX || n_top > n) {
+        g_last_error = std::string("cmfrec_hip_topN_batch: ") + LIMITS;
+        return 2;
+    }
+    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
+    if (r == nullptr) return g_last_rc;
+    const int rc = cmfrec_hip_ranker_topN(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
+    cmfrec_hip_ranker_destroy(r);
+    return rc;
+}
+
+}  // extern "C"

@@ -48,12 +48,10 @@ class _Base:
         return _lib.load(self.dtype_), _lib.real(self.dtype_)
 
 
-def _topN(self, users, n, exclude, biasB):
-    """Shared body of ``CMF.topN_batch`` / ``CMF_implicit.topN_batch``."""
-    from . import ops
+def _topN_inputs(self, users, exclude):
+    """(user ids, their factors, their exclusion lists) of a ranking call on a fitted model."""
     users = np.atleast_1d(np.asarray(users, np.int64))
     A = np.ascontiguousarray(self.A_[users][:, self.k_user:])
-    B = np.ascontiguousarray(self.B_[:, self.k_item:])
     excl = None
     if exclude is not None:                       # scipy CSR / (indptr, indices) over ALL users: take the asked rows
         ip, ix = (exclude.indptr, exclude.indices) if hasattr(exclude, "indptr") else exclude
@@ -62,7 +60,44 @@ def _topN(self, users, n, exclude, biasB):
         ep = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
         take = np.concatenate([np.arange(ip[u], ip[u + 1]) for u in users]) if lens.sum() else np.zeros(0, np.int64)
         excl = (ep, ix[take].astype(np.int32))
+    return users, A, excl
+
+
+def _topN(self, users, n, exclude, biasB):
+    """Shared body of ``CMF.topN_batch`` / ``CMF_implicit.topN_batch``."""
+    from . import ops
+    _, A, excl = _topN_inputs(self, users, exclude)
+    B = np.ascontiguousarray(self.B_[:, self.k_item:])
     return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl)
+
+
+class ModelRanker:
+    """What ``CMF.ranker()`` / ``CMF_implicit.ranker()`` return: the fitted model's item factors (and item bias) held on the
+    device by a ``cmfrec_amd.Ranker``; ``topN(users, n, exclude)`` takes user ids of the fitted model and returns what the model's
+    ``topN_batch`` returns.  The caller closes it (``close()`` or a ``with`` block); a refit needs a new one."""
+
+    def __init__(self, model, biasB):
+        from .rank import Ranker
+        self._model = model
+        self._ranker = Ranker(np.ascontiguousarray(model.B_[:, model.k_item:]),
+                              None if biasB is None else np.ascontiguousarray(biasB, model.B_.dtype))
+
+    def topN(self, users, n=10, exclude=None):
+        users, A, excl = _topN_inputs(self._model, users, exclude)
+        ids, sc = self._ranker.topN(A, n=n, exclude=excl)
+        return ids, self._model._finish_scores(users, sc)
+
+    def kernel_ms(self):
+        return self._ranker.kernel_ms()
+
+    def close(self):
+        self._ranker.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def _new_rows(X, n, dt):
@@ -238,6 +273,13 @@ class CMF_implicit(_Base):
         """Top-``n`` item ids and scores (A_u . B_i) for a batch of users, ranked on the GPU; ``exclude``: CSR of items
         to skip per user (e.g. the training matrix).  Batch form of the reference's ``topN`` (common.c:5127-5380)."""
         return _topN(self, users, n, exclude, None)
+
+    def _finish_scores(self, users, sc):
+        return sc
+
+    def ranker(self):
+        """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch."""
+        return ModelRanker(self, None)
 
     def predict(self, user, item):
         """A_u . B_i for paired user / item ids (reference predict_multiple, common.c:5066-5106)."""
@@ -448,11 +490,18 @@ class CMF(_Base):
         bias and the global mean do not change the order; the reference adds them to the scores, common.c:5339-5345,
         and so does this method).  ``exclude``: CSR of items to skip per user."""
         ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None)
-        users = np.atleast_1d(np.asarray(users, np.int64))
+        return ids, self._finish_scores(np.atleast_1d(np.asarray(users, np.int64)), sc)
+
+    def _finish_scores(self, users, sc):
         sc = sc + self.glob_mean_
         if self.user_bias:
             sc = sc + np.asarray(self.user_bias_)[users][:, None]
-        return ids, sc
+        return sc
+
+    def ranker(self):
+        """A ``ModelRanker`` over this model's item factors and item bias: upload them once, then ``.topN(users, n, exclude)``
+        per batch, with the scores of ``topN_batch``."""
+        return ModelRanker(self, self.item_bias_ if self.item_bias else None)
 
     def predict(self, user, item):
         """glob_mean + biasA[u] + biasB[i] + A_u . B_i (reference predict_multiple, common.c:5098-5106)."""

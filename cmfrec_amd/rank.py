@@ -1,0 +1,94 @@
+"""Ranking with the item side resident on the device: ``Ranker`` wraps the ``cmfrec_hip_ranker_*`` handle of
+include/cmfrec_hip.h.  ``ops.topN_batch`` uploads the item factors on every call; a ``Ranker`` uploads them once and
+ranks any number of user batches against them."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .ops import _sorted_exclude
+
+
+class Ranker:
+    """``Ranker(B, biasB=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype or None.
+    ``topN(A, n=10, exclude=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns the handle:
+    ``close()`` it, or use it as a context manager."""
+
+    def __init__(self, B, biasB=None, device=-1):
+        self.handle = None
+        B = np.asarray(B)
+        if B.ndim != 2:
+            raise ValueError("Ranker: B must be 2-D [items, factors], got %d-D" % B.ndim)
+        if B.dtype.type not in (np.float64, np.float32):
+            raise ValueError("Ranker: B must be float64 or float32, got %s" % B.dtype)
+        if B.shape[0] < 1 or B.shape[1] < 1:
+            raise ValueError("Ranker: B is empty")
+        if biasB is not None:
+            biasB = np.asarray(biasB)
+            if biasB.dtype != B.dtype:
+                raise ValueError("Ranker: biasB is %s, B is %s" % (biasB.dtype, B.dtype))
+            if biasB.shape != (B.shape[0],):
+                raise ValueError("Ranker: biasB must have one entry per item (%d), got shape %s" % (B.shape[0], biasB.shape))
+            biasB = np.ascontiguousarray(biasB)
+        B = np.ascontiguousarray(B)
+        self.dtype = B.dtype
+        self.n, self.k = B.shape
+        self.lib = _lib.load(B.dtype)
+        h = self.lib.cmfrec_hip_ranker_create(_lib.ptr(B), C.c_size_t(B.shape[1]), C.c_int(self.n), C.c_int(self.k),
+                                              _lib.ptr(biasB), C.c_int(device))
+        if not h:
+            _lib.check(self.lib.cmfrec_hip_last_error_code() or 4, self.lib, "Ranker")
+        self.handle = C.c_void_p(h)
+
+    def _live(self):
+        if not getattr(self, "handle", None):
+            raise RuntimeError("Ranker: the handle is closed")
+        return self.handle
+
+    def topN(self, A, n=10, exclude=None):
+        """(ids [nu, n] int32, scores [nu, n]) for every row of ``A``: score = A_u . B_i (+ biasB[i]), descending, ties by
+        lower id, -1 / -inf where fewer than ``n`` items remain; ``exclude`` = (indptr, indices) CSR over the rows of A."""
+        h = self._live()
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[1] != self.k:
+            raise ValueError("Ranker.topN: A must be [users, %d], got shape %s" % (self.k, A.shape))
+        if A.dtype != self.dtype:
+            raise ValueError("Ranker.topN: A is %s, the ranker's items are %s" % (A.dtype, self.dtype))
+        A = np.ascontiguousarray(A)
+        nu = A.shape[0]
+        n = int(n)
+        ids = np.empty((nu, n), np.int32); sc = np.empty((nu, n), self.dtype)
+        ep, ei = _sorted_exclude(exclude, nu)
+        rc = self.lib.cmfrec_hip_ranker_topN(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
+                                             _lib.ptr(ids), _lib.ptr(sc))
+        _lib.check(rc, self.lib, "Ranker.topN")
+        return ids, sc
+
+    def kernel_ms(self):
+        """HIP-event time (ms) of the ranking kernel of the most recent ``topN`` call."""
+        ms = C.c_double(0)
+        _lib.check(self.lib.cmfrec_hip_ranker_kernel_ms(self._live(), C.byref(ms)), self.lib, "Ranker.kernel_ms")
+        return ms.value
+
+    def launch_shape(self):
+        """(users per workgroup, workgroups) of that kernel launch: the items are streamed once per workgroup's users."""
+        u, g = C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.cmfrec_hip_ranker_launch_shape(self._live(), C.byref(u), C.byref(g)), self.lib, "Ranker.launch_shape")
+        return u.value, g.value
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.cmfrec_hip_ranker_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

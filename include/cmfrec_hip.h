@@ -530,10 +530,31 @@ void cmfrec_hip_session_reset_timers(cmfrec_hip_session *s);
  * pointers), items in the user's exclusion list (CSR over the nu users, each list sorted ascending; NULL = none)
  * are skipped, the n_top best item ids per user are returned in descending score (ties: lower id first), -1 where
  * fewer than n_top items remain.  out_scores (optional) holds the scores as defined above; the reference adds
- * glob_mean + biasA[u] afterwards, which does not change the order.  k <= 64, n_top <= 128. */
+ * glob_mean + biasA[u] afterwards, which does not change the order.  k <= 272 (every width the library fits),
+ * n_top <= min(128, n); beyond that return code 2.  k <= 64 runs the register-resident kernel, wider models the MFMA kernel
+ * (CMFREC_HIP_TOPN=wide: that one for every k).  One call = one ranker (below) made, used once and destroyed: B is uploaded
+ * on every call. */
 int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
                           const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
                           int_t *out_ids, real_t *out_scores);
+
+/* A ranking handle that keeps the item side on the device: ranking a user base in batches uploads B once, not once per batch.
+ * create: B [n, ldb], the k scored columns start at B (skip k_item by offsetting the pointer) and are uploaded packed; biasB
+ * optional; device < 0: the current device.  NULL on failure (cmfrec_hip_last_error / cmfrec_hip_last_error_code).
+ * topN: the semantics, limits and return codes of cmfrec_hip_topN_batch for nu users A [nu, lda]; uploads the users' factors
+ * and exclusion lists, ranks, downloads.  The handle's device buffers are reused from call to call and grow on demand; calls on
+ * one handle must not overlap.
+ * kernel_ms: HIP-event time of the ranking kernel of the most recent topN call (return code 2 before the first).
+ * launch_shape: how that kernel was launched -- users that share one pass over the items (16 for the register-resident kernel,
+ * 16 to 64 for the MFMA kernel, by what fits the LDS) and workgroups; the items are streamed once per 16..64 users. */
+typedef struct cmfrec_hip_ranker cmfrec_hip_ranker;
+cmfrec_hip_ranker *cmfrec_hip_ranker_create(const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB, int device);
+int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                           const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                           int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
+int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
+void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
 
 /* Replace precompute_collective_explicit / precompute_collective_implicit, /root/reference/src/cmfrec.h:1922-1960 (bodies
  * src/collective.c:10209-10485, :10487-10566): the matrices the prediction functions reuse, from factors the caller holds -- the
