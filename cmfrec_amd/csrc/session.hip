@@ -1688,46 +1688,214 @@ int cmfrec_hip_session_set_sideinfo_sparse(cmfrec_hip_session *s, int which, con
 }
 
 // ---- one half-step of the ALS loop on the local block -------------------------------------
+// What a half-step reads of the session by side, picked once: "self" = the matrix being updated (A when isA, B otherwise; its side
+// information U, C), "opp" = the fixed one.  The drivers below take their side-dependent values from here and pick none themselves.
+struct HalfStepSide {
+    const bool isA;
+    real_t *const self, *const opp;
+    const size_t ld_self, ld_opp;
+    const int k_side_self, k_side_opp;          // k_user / k_item
+    const int k_tot_opp;                        // columns of opp in front of its bias column
+    const real_t *const oppx;                   // opp + k_side_opp: the columns X refers to
+    const int p_self;                           // attributes of this side's side information
+    const int rows_self, rows_opp;              // rows of the two matrices (m / n)
+    const int rows_x_self, rows_x_opp;          // ... that X has (m_x / n_x where set): update_factor's Gramian and block systems
+    const int rows_u, begin;                    // rows with side information; first row of the local block
+    const SparseShard &X, &Us;                  // X by rows of self; sparse side information by rows of self
+    const real_t *const Cm, *const Um;          // C / D; U / I
+    const real_t *const Um_blk;                 // ... from the local block's first row
+    const real_t w;                             // w_user / w_item
+    const bool sparse_side;
+    const bool self_bias, opp_bias;
+    const real_t *const bias;                   // the opposing biases when that side has them (fused "X - bias", :8566-8570, :8750-8754)
+    // lam_unique[2] / [3] for A / B; the bias, when fitted, takes lam_unique[0] / [1] (collective.c:8649-8654, :8820-8825); the
+    // implicit model fits none
+    const real_t lam_self, lam_last_self;
+    const int kk, ks, kc, kt;                   // k + k_main; + the bias; k_side + k (the columns C has); k_side + ks
+    // NA_as_zero_X: the constant of the opposing biases and the mean exists; the mean when X is centred, else zero
+    const bool has_cst;
+    const real_t mean;
+    const real_t *const Fi;                     // the opposing side's implicit factors [rows_opp, kk], nullptr without implicit features
+    cmfrec_hip_session::GatherSegs &G;          // segments of the gather-sum over X
+    real_t *const uc;                           // U C of the block CG
+    BinTimers *const bins;
+    EigCache *const eig_mine, *const eig_next;  // eigenvectors of this side's w C^T C, and of the side whose half-step comes next ...
+    const real_t *const Cm_next;                // ... with what its prefetch reads of that side: D / C, q / p, k_item / k_user + k, w
+    const int p_next, kc_next;
+    const real_t w_next;
+    const bool sparse_side_next;
+
+    HalfStepSide(cmfrec_hip_session *s, bool isA_)
+        : isA(isA_), self(isA ? s->A.ptr : s->B.ptr), opp(isA ? s->B.ptr : s->A.ptr), ld_self(isA ? s->ldA : s->ldB),
+          ld_opp(isA ? s->ldB : s->ldA), k_side_self(isA ? s->mdl.k_user : s->mdl.k_item),
+          k_side_opp(isA ? s->mdl.k_item : s->mdl.k_user), k_tot_opp(isA ? s->k_totB : s->k_totA), oppx(opp + k_side_opp),
+          p_self(isA ? s->mdl.p : s->mdl.q), rows_self(isA ? s->mdl.m : s->mdl.n), rows_opp(isA ? s->mdl.n : s->mdl.m),
+          rows_x_self(isA ? (s->mdl.m_x > 0 ? s->mdl.m_x : s->mdl.m) : (s->mdl.n_x > 0 ? s->mdl.n_x : s->mdl.n)),
+          rows_x_opp(isA ? (s->mdl.n_x > 0 ? s->mdl.n_x : s->mdl.n) : (s->mdl.m_x > 0 ? s->mdl.m_x : s->mdl.m)),
+          rows_u(isA ? s->mdl.m_u : s->mdl.n_i), begin(isA ? s->mdl.row_begin : s->mdl.col_begin), X(isA ? s->Xr : s->Xc),
+          Us(isA ? s->Usr : s->Isr), Cm(isA ? s->C.ptr : s->D.ptr), Um(isA ? s->U.ptr : s->II.ptr),
+          Um_blk(Um != nullptr ? Um + (size_t)(s->side_local ? 0 : begin) * p_self : nullptr), w(isA ? s->mdl.w_user : s->mdl.w_item),
+          sparse_side(isA ? s->sparseU : s->sparseI), self_bias(isA ? s->mdl.user_bias : s->mdl.item_bias),
+          opp_bias(isA ? s->mdl.item_bias : s->mdl.user_bias), bias(opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr),
+          lam_self(s->lam6[isA ? 2 : 3]), lam_last_self((!s->mdl.implicit && self_bias) ? s->lam6[isA ? 0 : 1] : lam_self),
+          kk(s->mdl.k + s->mdl.k_main), ks(kk + (self_bias ? 1 : 0)), kc(k_side_self + s->mdl.k), kt(k_side_self + ks),
+          has_cst(opp_bias || s->naz_center), mean(s->naz_center ? s->naz_mean : (real_t)0),
+          Fi(s->implicit_feats ? (isA ? s->Bi.ptr : s->Ai.ptr) : nullptr), G(s->gsegs[isA ? 0 : 1]),
+          uc(isA ? s->ucA.ptr : s->ucB.ptr), bins(isA ? &s->binA : &s->binB), eig_mine(isA ? &s->eigA : &s->eigB),
+          eig_next(isA ? &s->eigB : &s->eigA), Cm_next(isA ? s->D.ptr : s->C.ptr), p_next(isA ? s->mdl.q : s->mdl.p),
+          kc_next(k_side_opp + s->mdl.k), w_next(isA ? s->mdl.w_item : s->mdl.w_user),
+          sparse_side_next(isA ? s->sparseI : s->sparseU)
+    {
+    }
+};
+
 // Explicit model: rows that exist only in the side information (beyond the shape of X) are fitted to it alone,
 //   a[:kc] = (C^T C + (lam / w) (p if scale_lam) I)^-1 C^T u     (optimizeA Case 1 on U[m_x:], collective.c:4967-5101)
 // their remaining unknowns are zero under Cholesky (A was zeroed) and left alone under CG.
-static int solve_sideinfo_only_rows(cmfrec_hip_session *s, bool isA, bool chol, int first, int count)
+static int solve_sideinfo_only_rows(cmfrec_hip_session *s, const HalfStepSide &v, bool chol, int first, int count)
 {
     if (count <= 0) return 0;
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
-    real_t *self = isA ? s->A.ptr : s->B.ptr;
-    const size_t ld_self = isA ? s->ldA : s->ldB;
-    const int begin = isA ? m.row_begin : m.col_begin;
-    const int p_self = isA ? m.p : m.q, kc = (isA ? m.k_user : m.k_item) + m.k;
-    const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-    const real_t *Um = isA ? s->U.ptr : s->II.ptr;
-    const real_t w = isA ? m.w_user : m.w_item;
+    const int p_self = v.p_self, kc = v.kc;
     const bool scale_lam = m.scale_lam || m.scale_lam_sideinfo;                                    // :7465
-    real_t *rows = self + (size_t)(begin + first) * ld_self;
-    if (chol) HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)count * ld_self * sizeof(real_t), dev.stream));
-    launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->betbe.ptr, (real_t)1,
-                (s->lam6[isA ? 2 : 3] / w) * (real_t)(scale_lam ? p_self : 1));                                   // common.c:2824-2832
-    launch_gemm<false>(dev, count, kc, p_self, (real_t)1, Um + (size_t)((s->side_local ? 0 : begin) + first) * p_self, (size_t)p_self, Cm,
-                       (size_t)kc, rows, ld_self);                                                 // common.c:2847-2855
-    CholCall c{rows, ld_self, nullptr, 0, kc, 0, nullptr, s->betbe.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
+    real_t *rows = v.self + (size_t)(v.begin + first) * v.ld_self;
+    if (chol) HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)count * v.ld_self * sizeof(real_t), dev.stream));
+    launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->betbe.ptr, (real_t)1,
+                (v.lam_self / v.w) * (real_t)(scale_lam ? p_self : 1));                                           // common.c:2824-2832
+    launch_gemm<false>(dev, count, kc, p_self, (real_t)1, v.Um_blk + (size_t)first * p_self, (size_t)p_self, v.Cm,
+                       (size_t)kc, rows, v.ld_self);                                               // common.c:2847-2855
+    CholCall c{rows, v.ld_self, nullptr, 0, kc, 0, nullptr, s->betbe.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
     return launch_chol(dev, c, nullptr, count);                                                    // common.c:2872-2875
 }
 
-// sum of the rows of F (Bi / Ai) at every row's observed positions, by the two-stage segmented gather-sum; result in s->grhs
-// [X.nrows, kk].  Returns false when the tables / widths do not allow it (the caller then gathers inside the row kernel).
-static bool launch_gsum(cmfrec_hip_session *s, bool isA, const SparseShard &X, const real_t *Fi, int kk)
+// sum of the rows of F (leading dimension ldf; Bi / Ai, or the factors themselves) at every row's observed positions, by the
+// two-stage segmented gather-sum; result in dst [rows, kk].  Returns false when the tables / widths do not allow it (the caller
+// then gathers inside the row kernel).
+static bool launch_gsum(cmfrec_hip_session *s, const HalfStepSide &v, const real_t *F, size_t ldf, int kk, real_t *dst, int rows)
 {
-    auto &G = s->gsegs[isA ? 0 : 1];
-    if (kk > 64 * GSUM_MAXC || s->grhs.ptr == nullptr) return false;
+    if (kk > 64 * GSUM_MAXC || dst == nullptr) return false;
     hipStream_t st = s->dev.stream;
-    if (G.nseg > 0)
-        hipLaunchKernelGGL(gather_sum_segments_kernel<real_t>, dim3((G.nseg + 3) / 4), dim3(256), 0, st, X.p.ptr, X.i.ptr, Fi, (size_t)kk, kk,
-                           G.seg_row.ptr, G.seg_off.ptr, G.nseg, s->gpartial.ptr);
-    hipLaunchKernelGGL(gather_sum_rows_kernel<real_t>, dim3((X.nrows + 3) / 4), dim3(256), 0, st, s->gpartial.ptr, G.row_first.ptr, X.nrows, kk,
-                       s->grhs.ptr, (size_t)kk);
+    if (v.G.nseg > 0)
+        hipLaunchKernelGGL(gather_sum_segments_kernel<real_t>, dim3((v.G.nseg + 3) / 4), dim3(256), 0, st, v.X.p.ptr, v.X.i.ptr, F, ldf, kk,
+                           v.G.seg_row.ptr, v.G.seg_off.ptr, v.G.nseg, s->gpartial.ptr);
+    hipLaunchKernelGGL(gather_sum_rows_kernel<real_t>, dim3((rows + 3) / 4), dim3(256), 0, st, s->gpartial.ptr, v.G.row_first.ptr, rows, kk,
+                       dst, (size_t)kk);
     HIP_CHECK(hipGetLastError());
     return true;
+}
+
+// ---- launch groups the half-steps share ----
+// the opposing matrix' bias column is fixed to 1 while this one's bias is fitted (collective.c:8538-8543, :8728-8732)
+static void fill_fixed_bias_column(cmfrec_hip_session *s, const HalfStepSide &v)
+{
+    if (!v.self_bias) return;
+    hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(v.rows_opp), dim3(256), 0, s->dev.stream, v.opp, v.ld_opp, v.rows_opp, v.k_tot_opp,
+                       (real_t)1);
+}
+
+// Bi^T Bi of the opposing implicit factors (rows of them) into s->bitbi [kk, kk]: times w_implicit when weighted; into_gram adds it
+// onto the first k + k_main unknowns of s->gram [ks, ks] (collective.c:1704-1707)
+static void launch_implicit_gram(cmfrec_hip_session *s, const HalfStepSide &v, int rows, bool weighted, bool into_gram)
+{
+    launch_gram(s->dev, s->gws, v.Fi, (size_t)v.kk, rows, v.kk, s->bitbi.ptr, weighted ? s->w_implicit : (real_t)1, (real_t)0);
+    if (into_gram)
+        hipLaunchKernelGGL(add_block_kernel<real_t>, grid1d((size_t)v.kk * v.kk), dim3(256), 0, s->dev.stream, s->bitbi.ptr, v.kk, (real_t)1,
+                           s->gram.ptr, v.ks, 0);
+}
+
+// w_i times the gather-sum (s->grhs) onto the columns behind k_side of the right-hand sides (:1757-1771)
+static void add_implicit_rhs(cmfrec_hip_session *s, const HalfStepSide &v, real_t *rhs, size_t ld)
+{
+    hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)v.X.nrows * v.kk), dim3(256), 0, s->dev.stream, rhs, ld, v.k_side_self,
+                       s->grhs.ptr, v.kk, s->w_implicit, (size_t)v.X.nrows);
+}
+
+// the implicit-features term of the lane <-> unknown CG kernel (it gathers Bi_j at the row's entries itself unless c.gsum is set)
+static void set_implicit_term(const cmfrec_hip_session *s, const HalfStepSide &v, CgCall &c)
+{
+    c.Bi = v.Fi; c.BiTBi = s->bitbi.ptr; c.ki = v.kk; c.w_imp = s->w_implicit;
+}
+
+// sparse side information: the row's attributes as the second gather source of the launch
+static void set_sparse_side(const HalfStepSide &v, CholCall &c)
+{
+    c.X2 = &v.Us; c.B2 = v.Cm; c.ldb2 = (size_t)v.kc; c.kc2 = v.kc; c.w2 = v.w;
+}
+static void set_sparse_side(const HalfStepSide &v, CgCall &c)
+{
+    c.X2 = &v.Us; c.C2 = v.Cm;
+}
+
+// ---- ... and the ones of the main matrix missing-as-zero ----
+static int naz_check_side_rows(int rows_u, int rows_self)
+{
+    if (rows_u == rows_self) return 0;
+    g_last_error = "cmfrec_hip: NA_as_zero_X with side information: side information on exactly the rows / columns of X";
+    return 2;
+}
+
+// sum of the opposing implicit factors at the row's observed positions into s->grhs
+static int naz_implicit_gsum(cmfrec_hip_session *s, const HalfStepSide &v)
+{
+    if (launch_gsum(s, v, v.Fi, (size_t)v.kk, v.kk, s->grhs.ptr, v.X.nrows)) return 0;
+    g_last_error = "cmfrec_hip: NA_as_zero_X with implicit features: k + k_main too wide for the gather-sum";
+    return 2;
+}
+
+// cst = - sum over ALL opposing rows of (bias + mean) x row into s->naz_vec [ks] (:3152-3157 / :5815-5821), added onto every row of
+// add_to [rows_self, ks] when that is given.  nullptr when there is neither an opposing bias nor centring.
+static const real_t *naz_constant(cmfrec_hip_session *s, const HalfStepSide &v, real_t *add_to = nullptr, size_t ld_add = 0)
+{
+    if (!v.has_cst) return nullptr;
+    hipStream_t st = s->dev.stream;
+    const int ks = v.ks, nb = (v.rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
+    s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
+    hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, v.oppx, v.ld_opp, v.rows_opp, ks, v.bias, v.mean,
+                       s->naz_part.ptr);
+    hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
+    if (add_to != nullptr)
+        hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)v.rows_self * ks), dim3(256), 0, st, add_to, ld_add, (size_t)v.rows_self, ks,
+                           s->naz_vec.ptr);
+    return s->naz_vec.ptr;
+}
+
+// sum_j x_j opp_j over every row's entries by the gather-only launch of the row Cholesky kernel (tgemm_sp_dense, :3145-3151 /
+// :5753-5762), x_j from values_override when given, added into dst, which the caller has zeroed
+static int naz_gather_rhs_into(cmfrec_hip_session *s, const HalfStepSide &v, real_t *dst, size_t ld, const real_t *values_override = nullptr)
+{
+    CholCall c{dst, ld, v.oppx, v.ld_opp, v.ks, 0, nullptr, s->gram.ptr, 0, 0, 0, v.lam_self, v.lam_last_self, false, false, false, CHOL_NAZ};
+    c.rhs_only = true; c.values_override = values_override;
+    return launch_chol(s->dev, c, &v.X);
+}
+
+// ... into s->naz_rhs [rows_self, ks], grown and zeroed here
+static int naz_gather_rhs(cmfrec_hip_session *s, const HalfStepSide &v, const real_t *values_override = nullptr)
+{
+    s->naz_rhs.alloc_at_least((size_t)v.rows_self * v.ks);
+    HIP_CHECK(hipMemsetAsync(s->naz_rhs.ptr, 0, (size_t)v.rows_self * v.ks * sizeof(real_t), s->dev.stream));
+    return naz_gather_rhs_into(s, v, s->naz_rhs.ptr, (size_t)v.ks, values_override);
+}
+
+// a zero array of at least nnz entries, in the place of the values for the CG kernels
+static const real_t *naz_zeros(cmfrec_hip_session *s, size_t nnz)
+{
+    nnz = std::max<size_t>(nnz, 1);
+    if (s->naz_zero.n < nnz) {
+        s->naz_zero.alloc(nnz);
+        HIP_CHECK(hipMemsetAsync(s->naz_zero.ptr, 0, nnz * sizeof(real_t), s->dev.stream));
+    }
+    return s->naz_zero.ptr;
+}
+
+// observation weights: per entry w_j - 1 into s->naz_g and the right-hand-side bracket w_j x_j - (w_j - 1)(mean + bias_j) into s->naz_xt
+static void naz_entry_transform(cmfrec_hip_session *s, const HalfStepSide &v)
+{
+    const size_t nnz = v.X.nnz;
+    s->naz_g.alloc_at_least(std::max<size_t>(nnz, 1)); s->naz_xt.alloc_at_least(std::max<size_t>(nnz, 1));
+    if (nnz > 0)
+        hipLaunchKernelGGL(naz_entry_transform_kernel<real_t>, grid1d(nnz), dim3(256), 0, s->dev.stream, v.X.v.ptr, v.X.w.ptr, v.X.i.ptr, nnz,
+                           v.bias, v.mean, s->naz_g.ptr, s->naz_xt.ptr);
 }
 
 // NA_as_zero_X on a side with SPARSE side information (missing = absent; round 5): no matrix is shared by the rows any more -- each
@@ -1738,121 +1906,66 @@ static bool launch_gsum(cmfrec_hip_session *s, bool isA, const SparseShard &X, c
 // on the two-source build of the row Cholesky kernel: B^T B embedded as the matrix every row starts from (Mfull), the entries of X
 // right-hand side only, the attributes as the second gather source with their rank-1 terms, the constant prefilled.  Closed
 // form only (the block CG with NA_as_zero_X, collective.c:2134-2903, is not restated).
-static int update_factor_naz_sparse_side(cmfrec_hip_session *s, bool isA, bool chol)
+static int update_factor_naz_sparse_side(cmfrec_hip_session *s, const HalfStepSide &v, bool chol)
 {
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
     hipStream_t st = dev.stream;
-    const int p_self = isA ? m.p : m.q, rows_u = isA ? m.m_u : m.n_i;
-    const int rows_self = isA ? m.m : m.n, rows_opp = isA ? m.n : m.m;
-    if (rows_u != rows_self) {
-        g_last_error = "cmfrec_hip: NA_as_zero_X with side information: side information on exactly the rows / columns of X";
-        return 2;
-    }
-    real_t *self = isA ? s->A.ptr : s->B.ptr;
-    real_t *opp = isA ? s->B.ptr : s->A.ptr;
-    const size_t ld_self = isA ? s->ldA : s->ldB, ld_opp = isA ? s->ldB : s->ldA;
-    const int k_side_self = isA ? m.k_user : m.k_item, k_side_opp = isA ? m.k_item : m.k_user;
-    const SparseShard &X = isA ? s->Xr : s->Xc;
-    const SparseShard &Us = isA ? s->Usr : s->Isr;
-    const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-    const real_t w = isA ? m.w_user : m.w_item;
-    const bool self_bias = isA ? m.user_bias : m.item_bias, opp_bias = isA ? m.item_bias : m.user_bias;
-    const real_t lam_self = s->lam6[isA ? 2 : 3];
-    const real_t lam_last_self = self_bias ? s->lam6[isA ? 0 : 1] : lam_self;
-    const int kk = m.k + m.k_main, ks = kk + (self_bias ? 1 : 0), kc = k_side_self + m.k, kt = k_side_self + ks;
-    const real_t *oppx = opp + k_side_opp;
-    if (self_bias)
-        hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_opp), dim3(256), 0, st, opp, ld_opp, rows_opp, isA ? s->k_totB : s->k_totA, (real_t)1);
-    launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, ks, s->gram.ptr, (real_t)1, (real_t)0);
+    if (int rc = naz_check_side_rows(v.rows_u, v.rows_self)) return rc;
+    const int ks = v.ks, kt = v.kt;
+    fill_fixed_bias_column(s, v);
+    launch_gram(dev, s->gws, v.oppx, v.ld_opp, v.rows_opp, ks, s->gram.ptr, (real_t)1, (real_t)0);
     // implicit features (round 6, fixture g37): w_i Bi^T Bi on the first k + k_main unknowns of the X block (collective.c:1704-1707;
     // the block CG keeps it apart, unweighted: :2301-2304, :2626-2629), w_i times the sum of the opposing implicit factors at the
     // row's observed positions in the right-hand side (:1757-1771)
-    const real_t *Fi = s->implicit_feats ? (isA ? s->Bi.ptr : s->Ai.ptr) : nullptr;
-    if (Fi != nullptr) {
-        launch_gram(dev, s->gws, Fi, (size_t)kk, rows_opp, kk, s->bitbi.ptr, chol ? s->w_implicit : (real_t)1, (real_t)0);
-        if (chol) {
-            hipLaunchKernelGGL(add_block_kernel<real_t>, grid1d((size_t)kk * kk), dim3(256), 0, st, s->bitbi.ptr, kk, (real_t)1, s->gram.ptr, ks, 0);
-            if (!launch_gsum(s, isA, X, Fi, kk)) {
-                g_last_error = "cmfrec_hip: NA_as_zero_X with implicit features: k + k_main too wide for the gather-sum";
-                return 2;
-            }
-        }
+    if (v.Fi != nullptr) {
+        launch_implicit_gram(s, v, v.rows_opp, chol, chol);
+        if (chol)
+            if (int rc = naz_implicit_gsum(s, v)) return rc;
     }
+    // mult_i = n: every cell of the row counts
+    const bool scaled = m.scale_lam || m.scale_lam_sideinfo;
+    auto fill_mult = [&]() {
+        if (!scaled) return;
+        s->naz_mult.alloc_at_least((size_t)v.rows_self);
+        hipLaunchKernelGGL(fill_kernel<real_t>, grid1d((size_t)v.rows_self), dim3(256), 0, st, s->naz_mult.ptr, (size_t)v.rows_self, (real_t)v.rows_opp);
+    };
     if (!chol) {
         // Block CG (round 6; collective_block_cg with NA_as_zero_X and u_vec_sp, collective.c:2134-2903): the X block of every row's
         // system is the shared B^T B (:2430-2445 first residual, :2700-2760 the products), its right-hand side sum_j x_j b_j + cst;
         // the row's attributes gather rows of C.  On the lane <-> unknown kernel: B^T B as its shared matrix (CgParams::gx), the
         // right-hand side of the X block as the per-row constant of the first residual, the entries of X with rank-1 weight zero.
-        s->naz_rhs.alloc_at_least((size_t)rows_self * ks);
-        HIP_CHECK(hipMemsetAsync(s->naz_rhs.ptr, 0, (size_t)rows_self * ks * sizeof(real_t), st));
-        {
-            CholCall cr{s->naz_rhs.ptr, (size_t)ks, oppx, ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, false, false, false, CHOL_NAZ};
-            cr.rhs_only = true;
-            int rc = launch_chol(dev, cr, &X);
-            if (rc) return rc;
-        }
-        if (opp_bias || s->naz_center) {
-            const int nb = (rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
-            s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
-            const real_t *bias = opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr;
-            hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, oppx, ld_opp, rows_opp, ks, bias,
-                               s->naz_center ? s->naz_mean : (real_t)0, s->naz_part.ptr);
-            hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
-            hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, (size_t)rows_self, ks,
-                               s->naz_vec.ptr);
-        }
-        const size_t nnz = std::max<size_t>(X.nnz, 1);
-        if (s->naz_zero.n < nnz) {
-            s->naz_zero.alloc(nnz);
-            HIP_CHECK(hipMemsetAsync(s->naz_zero.ptr, 0, nnz * sizeof(real_t), st));
-        }
-        const bool scaled_cg = m.scale_lam || m.scale_lam_sideinfo;
-        if (scaled_cg) {
-            s->naz_mult.alloc_at_least((size_t)rows_self);
-            hipLaunchKernelGGL(fill_kernel<real_t>, grid1d((size_t)rows_self), dim3(256), 0, st, s->naz_mult.ptr, (size_t)rows_self, (real_t)rows_opp);
-        }
+        if (int rc = naz_gather_rhs(s, v)) return rc;
+        naz_constant(s, v, s->naz_rhs.ptr, (size_t)ks);
+        const real_t *zeros = naz_zeros(s, v.X.nnz);
+        fill_mult();
         HIP_CHECK(hipGetLastError());
-        CgCall c{self, ld_self, oppx, ld_opp, ks, nullptr, nullptr, lam_self, lam_last_self, scaled_cg, false, m.max_cg_steps, false,
+        CgCall c{v.self, v.ld_self, v.oppx, v.ld_opp, ks, nullptr, nullptr, v.lam_self, v.lam_last_self, scaled, false, m.max_cg_steps, false,
                  (bool)m.precondition_cg};
-        c.koff = k_side_self; c.kc = kc; c.w_side = w; c.rows_with_u = rows_u; c.p_side = p_self;
-        c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo; c.X2 = &Us; c.C2 = Cm;
+        c.koff = v.k_side_self; c.kc = v.kc; c.w_side = v.w; c.rows_with_u = v.rows_u; c.p_side = v.p_self;
+        c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
+        set_sparse_side(v, c);
         c.Gx = s->gram.ptr; c.rconst_x = s->naz_rhs.ptr; c.ldr_x = (size_t)ks;
-        c.values_override = s->naz_zero.ptr; c.weights_override = s->naz_zero.ptr;
-        if (scaled_cg) c.wsum_override = s->naz_mult.ptr;
-        c.gx_all_rows = opp_bias || s->naz_center;         // rows with neither entries nor attributes: solved from the constant, zero without it
-        if (Fi != nullptr) { c.Bi = Fi; c.BiTBi = s->bitbi.ptr; c.ki = kk; c.w_imp = s->w_implicit; }     // (the kernel gathers Bi_j at the row's entries itself)
-        return launch_cg(dev, c, X);
+        c.values_override = zeros; c.weights_override = zeros;
+        if (scaled) c.wsum_override = s->naz_mult.ptr;
+        c.gx_all_rows = v.has_cst;                         // rows with neither entries nor attributes: solved from the constant, zero without it
+        if (v.Fi != nullptr) set_implicit_term(s, v, c);   // (the kernel gathers Bi_j at the row's entries itself)
+        return launch_cg(dev, c, v.X);
     }
     s->naz_M.alloc_at_least((size_t)kt * kt);
-    hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, s->gram.ptr, ks, k_side_self, (real_t)0, s->naz_M.ptr);
+    hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, s->gram.ptr, ks, v.k_side_self, (real_t)0, s->naz_M.ptr);
     // right-hand sides start from [0 ; cst]
-    HIP_CHECK(hipMemset2DAsync(self, ld_self * sizeof(real_t), 0, (size_t)kt * sizeof(real_t), (size_t)rows_self, st));
-    if (opp_bias || s->naz_center) {
-        const int nb = (rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
-        s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
-        const real_t *bias = opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr;
-        hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, oppx, ld_opp, rows_opp, ks, bias,
-                           s->naz_center ? s->naz_mean : (real_t)0, s->naz_part.ptr);
-        hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
-        hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, self + k_side_self, ld_self, (size_t)rows_self, ks,
-                           s->naz_vec.ptr);
-    }
-    if (Fi != nullptr)
-        hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)X.nrows * kk), dim3(256), 0, st, self, ld_self, k_side_self, s->grhs.ptr, kk,
-                           s->w_implicit, (size_t)X.nrows);
-    const bool scaled = m.scale_lam || m.scale_lam_sideinfo;
-    if (scaled) {
-        s->naz_mult.alloc_at_least((size_t)rows_self);
-        hipLaunchKernelGGL(fill_kernel<real_t>, grid1d((size_t)rows_self), dim3(256), 0, st, s->naz_mult.ptr, (size_t)rows_self, (real_t)rows_opp);
-    }
+    HIP_CHECK(hipMemset2DAsync(v.self, v.ld_self * sizeof(real_t), 0, (size_t)kt * sizeof(real_t), (size_t)v.rows_self, st));
+    naz_constant(s, v, v.self + v.k_side_self, v.ld_self);
+    if (v.Fi != nullptr) add_implicit_rhs(s, v, v.self, v.ld_self);
+    fill_mult();
     HIP_CHECK(hipGetLastError());
-    CholCall c{self, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, nullptr, kc, rows_u, p_self, lam_self, lam_last_self, scaled,
-               (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE, s->naz_M.ptr};
-    c.X2 = &Us; c.B2 = Cm; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w;
+    CholCall c{v.self, v.ld_self, v.oppx, v.ld_opp, kt, v.k_side_self, nullptr, nullptr, v.kc, v.rows_u, v.p_self, v.lam_self, v.lam_last_self,
+               scaled, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE, s->naz_M.ptr};
+    set_sparse_side(v, c);
     c.rhs_prefilled_all = true; c.x_rhs_only = true;
     if (scaled) c.mult_override = s->naz_mult.ptr;
-    return launch_chol(dev, c, &X);
+    return launch_chol(dev, c, &v.X);
 }
 
 // One half-step of the explicit model with the main matrix missing-as-zero (see cmfrec_hip_session::naz_X).
@@ -1861,14 +1974,12 @@ static int update_factor_naz_sparse_side(cmfrec_hip_session *s, bool isA, bool c
 // shares  blockdiag(0, B^T B) + w C^T C + lam mult I  (mult = n + p | n | 1, :4787-4799, :5700-5716), right-hand sides
 // X B + w U C + the bias / mean constant on the columns behind k_user (:5753-5770, :5815-5821), one factorisation (:5715) and
 // the substitutions of collective_closed_form_block's first branch (:1364-1460).
-static int update_factor_naz(cmfrec_hip_session *s, bool isA, bool chol)
+static int update_factor_naz(cmfrec_hip_session *s, const HalfStepSide &v, bool chol)
 {
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
     hipStream_t st = dev.stream;
-    const int p_self = isA ? m.p : m.q;
-    const int rows_u = isA ? m.m_u : m.n_i;
-    const int rows_self = isA ? m.m : m.n, rows_opp = isA ? m.n : m.m;
+    const int p_self = v.p_self, rows_self = v.rows_self, rows_opp = v.rows_opp;
     if (s->scale_bias_const || dev.nonneg_now || dev.l1_now != (real_t)0 ||
         dev.l1_last_now != (real_t)0 || m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n ||
         s->Xr.weighted() || s->side_local) {
@@ -1884,101 +1995,61 @@ static int update_factor_naz(cmfrec_hip_session *s, bool isA, bool chol)
     //  the same numbers bit for bit)
     // (round 6, fixture g37: with side information too -- dense: the shared block matrix takes w_i Bi^T Bi on its X block and the
     //  right-hand sides the gather-sum like below; sparse: update_factor_naz_sparse_side)
-    if (p_self > 0 && (isA ? s->sparseU : s->sparseI)) return update_factor_naz_sparse_side(s, isA, chol);
-    if (p_self > 0 && rows_u != rows_self) {
-        // (m > m_u takes optimizeA Case 3 for the rows beyond in the reference -- its build corrupts the heap there, so nothing
-        //  pins that branch)
-        g_last_error = "cmfrec_hip: NA_as_zero_X with side information: side information on exactly the rows / columns of X";
-        return 2;
-    }
+    if (p_self > 0 && v.sparse_side) return update_factor_naz_sparse_side(s, v, chol);
+    // (m > m_u takes optimizeA Case 3 for the rows beyond in the reference -- its build corrupts the heap there, so nothing
+    //  pins that branch)
+    if (p_self > 0)
+        if (int rc = naz_check_side_rows(v.rows_u, rows_self)) return rc;
     // (use_cg changes nothing here, like in Case 3: collective_closed_form_block takes the factorised block matrix before it looks
     //  at the solver, collective.c:1364-1460 -- the reference's fit with use_cg = true returns the closed-form numbers, g20)
     (void)chol;
-    if (p_self == 0 && (isA ? m.k_user : m.k_item) != 0) {
+    if (p_self == 0 && v.k_side_self != 0) {
         g_last_error = "cmfrec_hip: NA_as_zero_X: k_user / k_item without side information on that side";
         return 2;
     }
-    real_t *self = isA ? s->A.ptr : s->B.ptr;
-    real_t *opp = isA ? s->B.ptr : s->A.ptr;
-    const size_t ld_self = isA ? s->ldA : s->ldB, ld_opp = isA ? s->ldB : s->ldA;
-    const int k_side_self = isA ? m.k_user : m.k_item, k_side_opp = isA ? m.k_item : m.k_user;
-    const SparseShard &X = isA ? s->Xr : s->Xc;
-    const bool self_bias = isA ? m.user_bias : m.item_bias, opp_bias = isA ? m.item_bias : m.user_bias;
-    const real_t lam_self = s->lam6[isA ? 2 : 3];
-    const real_t lam_last_self = self_bias ? s->lam6[isA ? 0 : 1] : lam_self;
-    const int kk = m.k + m.k_main, ks = kk + (self_bias ? 1 : 0), kc = k_side_self + m.k, kt = k_side_self + ks;
-    const real_t *oppx = opp + k_side_opp;                        // the columns X refers to
-    if (self_bias) {                          // the opposing bias column is fixed to 1 (collective.c:8538-8543, :8728-8732)
-        hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_opp), dim3(256), 0, st, opp, ld_opp, rows_opp, isA ? s->k_totB : s->k_totA,
-                           (real_t)1);
-    }
+    const real_t lam_self = v.lam_self, lam_last_self = v.lam_last_self;
+    const int ks = v.ks, kc = v.kc, kt = v.kt;
+    fill_fixed_bias_column(s, v);
     // shared matrix: opp^T opp + diag(lam .. lam, lam_last), x rows_opp (+ p with side information on this side under
     // scale_lam_sideinfo) under scale_lam (common.c:3128-3138; collective.c:4787-4799)
     const real_t mult = (p_self > 0 && m.scale_lam_sideinfo) ? (real_t)(rows_opp + p_self)
                         : ((m.scale_lam || m.scale_lam_sideinfo) ? (real_t)rows_opp : (real_t)1);
-    launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, ks, s->gram.ptr, (real_t)1, lam_self * mult);
+    launch_gram(dev, s->gws, v.oppx, v.ld_opp, rows_opp, ks, s->gram.ptr, (real_t)1, lam_self * mult);
     if (lam_last_self != lam_self)
         hipLaunchKernelGGL(add_diag_kernel<real_t>, dim3(1), dim3(64), 0, st, s->gram.ptr, ks, ks - 1, ks, (lam_last_self - lam_self) * mult);
-    const real_t *Fi = s->implicit_feats ? (isA ? s->Bi.ptr : s->Ai.ptr) : nullptr;      // the opposing side's implicit factors [rows_opp, kk]
-    if (Fi != nullptr) {                                                                   // + w_i Bi^T Bi on the first k + k_main unknowns (:1704-1707)
-        launch_gram(dev, s->gws, Fi, (size_t)kk, rows_opp, kk, s->bitbi.ptr, s->w_implicit, (real_t)0);
-        hipLaunchKernelGGL(add_block_kernel<real_t>, grid1d((size_t)kk * kk), dim3(256), 0, st, s->bitbi.ptr, kk, (real_t)1, s->gram.ptr, ks, 0);
-    }
+    // + w_i Bi^T Bi on the first k + k_main unknowns (:1704-1707): weighted and added whatever the solver
+    if (v.Fi != nullptr) launch_implicit_gram(s, v, rows_opp, true, true);
     real_t *Msh = s->gram.ptr;                // the matrix the rows share, [kt, kt]
-    real_t *rhs_x = self;                     // where the row kernel leaves sum_j x_j opp_j: [rows, ks], ld
-    size_t ld_rhs = ld_self;
     if (p_self > 0) {
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const real_t w = isA ? m.w_user : m.w_item;
-        launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);            // :5658-5668
+        launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, v.w, (real_t)0);        // :5658-5668
         s->naz_M.alloc_at_least((size_t)kt * kt);
-        hipLaunchKernelGGL(naz_block_matrix_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, s->gram.ptr, ks, s->ctc.ptr, kc, k_side_self,
+        hipLaunchKernelGGL(naz_block_matrix_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, s->gram.ptr, ks, s->ctc.ptr, kc, v.k_side_self,
                            lam_self * mult, s->naz_M.ptr);
         Msh = s->naz_M.ptr;
-        s->naz_rhs.alloc_at_least((size_t)rows_self * ks);
-        rhs_x = s->naz_rhs.ptr; ld_rhs = (size_t)ks;
     }
-    // right-hand sides: sum_j x_j opp_j over the row's entries (tgemm_sp_dense, :3145-3151 / :5753-5762) ...
-    real_t *rhs = self;
-    const size_t ld_r = ld_self;
+    // right-hand sides: sum_j x_j opp_j over the row's entries (tgemm_sp_dense, :3145-3151 / :5753-5762), left by the row kernel in
+    // the rows of self themselves, with side information aside in naz_rhs [rows, ks] ...
+    real_t *rhs = v.self;
+    const size_t ld_r = v.ld_self;
     HIP_CHECK(hipMemset2DAsync(rhs, ld_r * sizeof(real_t), 0, (size_t)kt * sizeof(real_t), (size_t)rows_self, st));
-    if (p_self > 0) HIP_CHECK(hipMemsetAsync(rhs_x, 0, (size_t)rows_self * ks * sizeof(real_t), st));
-    CholCall c{rhs_x, ld_rhs, oppx, ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, false, false, false, CHOL_NAZ};
-    c.rhs_only = true;
-    int rc = launch_chol(dev, c, &X);
-    if (rc) return rc;
+    if (int rc = p_self > 0 ? naz_gather_rhs(s, v) : naz_gather_rhs_into(s, v, rhs, ld_r)) return rc;
     if (p_self > 0) {
         // ... w U C on the first k_side + k columns, the gathered part behind k_side
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const real_t *Um = isA ? s->U.ptr : s->II.ptr;
-        launch_gemm<false>(dev, rows_self, kc, p_self, isA ? m.w_user : m.w_item, Um, (size_t)p_self, Cm, (size_t)kc, rhs, ld_r);
-        hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, rhs, ld_r, k_side_self, rhs_x, ks,
+        launch_gemm<false>(dev, rows_self, kc, p_self, v.w, v.Um, (size_t)p_self, v.Cm, (size_t)kc, rhs, ld_r);
+        hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, rhs, ld_r, v.k_side_self, s->naz_rhs.ptr, ks,
                            (real_t)1, (size_t)rows_self);
     }
-    if (Fi != nullptr) {
+    if (v.Fi != nullptr) {
         // ... w_i times the sum of the opposing implicit factors at the row's observed positions (:1757-1771)
-        if (!launch_gsum(s, isA, X, Fi, kk)) {
-            g_last_error = "cmfrec_hip: NA_as_zero_X with implicit features: k + k_main too wide for the gather-sum";
-            return 2;
-        }
-        hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)X.nrows * kk), dim3(256), 0, st, rhs, ld_r, k_side_self, s->grhs.ptr, kk,
-                           s->w_implicit, (size_t)X.nrows);
+        if (int rc = naz_implicit_gsum(s, v)) return rc;
+        add_implicit_rhs(s, v, rhs, ld_r);
     }
     // ... plus the constant of the opposing biases and the mean (:3152-3157 / :5815-5821)
-    if (opp_bias || s->naz_center) {
-        const int nb = (rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
-        s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
-        const real_t *bias = opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr;
-        hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, oppx, ld_opp, rows_opp, ks, bias,
-                           s->naz_center ? s->naz_mean : (real_t)0, s->naz_part.ptr);
-        hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
-        hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, rhs + k_side_self, ld_r, (size_t)rows_self, ks,
-                           s->naz_vec.ptr);
-    }
+    naz_constant(s, v, rhs + v.k_side_self, ld_r);
     // one factorisation, all rows (with and without entries) through the triangular solves (:3171-3175 / :5715, :1455-1458)
     hipLaunchKernelGGL(potrf_upper_kernel<real_t>, dim3(1), dim3(256), 0, st, Msh, kt);
     HIP_CHECK(hipGetLastError());
-    launch_potrs_rows(dev, rows_self, kt, Msh, self, ld_self);
+    launch_potrs_rows(dev, rows_self, kt, Msh, v.self, v.ld_self);
     return 0;
 }
 
@@ -1988,7 +2059,7 @@ static int update_factor_naz(cmfrec_hip_session *s, bool isA, bool chol)
 //     rhs_i = [w U C ; sum_j (w_j x_j - (w_j - 1)(mean + bias_j)) b_j + cst]
 // on the row Cholesky kernel's collective mode: w C^T C for the rows with side information (all of them), blockdiag(0, B^T B) as the
 // matrix every row starts from, the entries' weight pairs as they are (entry_pairs), the right-hand sides prefilled.  Closed form.
-static int update_factor_naz_weighted_side(cmfrec_hip_session *s, bool isA, bool chol)
+static int update_factor_naz_weighted_side(cmfrec_hip_session *s, const HalfStepSide &v, bool chol)
 {
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
@@ -1996,132 +2067,69 @@ static int update_factor_naz_weighted_side(cmfrec_hip_session *s, bool isA, bool
     // has_side == false (round 6, fixture g39): no side information on this side, but implicit features -- the reference still takes its
     // collective route (collective.c:8612, :8783), whose rows without entries are zeroed unless the bias / mean constant exists
     // (:1258-1268); every row then counts as "with side information" of zero attributes
-    const int p_self = isA ? m.p : m.q;
+    const int p_self = v.p_self, rows_self = v.rows_self;
     const bool has_side = p_self > 0;
-    const int rows_self = isA ? m.m : m.n, rows_opp = isA ? m.n : m.m;
-    const int rows_u = has_side ? (isA ? m.m_u : m.n_i) : rows_self;
-    if (rows_u != rows_self) {
-        g_last_error = "cmfrec_hip: NA_as_zero_X with side information: side information on exactly the rows / columns of X";
-        return 2;
-    }
-    real_t *self = isA ? s->A.ptr : s->B.ptr;
-    real_t *opp = isA ? s->B.ptr : s->A.ptr;
-    const size_t ld_self = isA ? s->ldA : s->ldB, ld_opp = isA ? s->ldB : s->ldA;
-    const int k_side_self = isA ? m.k_user : m.k_item, k_side_opp = isA ? m.k_item : m.k_user;
-    const SparseShard &X = isA ? s->Xr : s->Xc;
-    const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-    const real_t *Um = isA ? s->U.ptr : s->II.ptr;
+    const int rows_u = has_side ? v.rows_u : rows_self;
+    if (int rc = naz_check_side_rows(rows_u, rows_self)) return rc;
     // sparse side information (missing = absent; round 6, fixture g36): the row's attributes as the second gather source instead of the
     // shared w C^T C / w U C (collective.c:1636-1653 / :2292-2298 beside the weight branches)
-    const bool sparse_side = has_side && (isA ? s->sparseU : s->sparseI);
-    const SparseShard &Us = isA ? s->Usr : s->Isr;
-    const real_t w = isA ? m.w_user : m.w_item;
-    const bool self_bias = isA ? m.user_bias : m.item_bias, opp_bias = isA ? m.item_bias : m.user_bias;
-    const real_t lam_self = s->lam6[isA ? 2 : 3];
-    const real_t lam_last_self = self_bias ? s->lam6[isA ? 0 : 1] : lam_self;
-    const int kk = m.k + m.k_main, ks = kk + (self_bias ? 1 : 0), kc = has_side ? k_side_self + m.k : 0, kt = k_side_self + ks;
-    const real_t *oppx = opp + k_side_opp;
-    if (self_bias)
-        hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_opp), dim3(256), 0, st, opp, ld_opp, rows_opp, isA ? s->k_totB : s->k_totA, (real_t)1);
-    launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, ks, s->gram.ptr, (real_t)1, (real_t)0);
+    const bool sparse_side = has_side && v.sparse_side;
+    const bool dense_side = has_side && !sparse_side;
+    const int ks = v.ks, kc = has_side ? v.kc : 0, kt = v.kt;
+    fill_fixed_bias_column(s, v);
+    launch_gram(dev, s->gws, v.oppx, v.ld_opp, v.rows_opp, ks, s->gram.ptr, (real_t)1, (real_t)0);
     // implicit features: w_i Bi^T Bi on the first k + k_main unknowns of the X block (closed form: inside the matrix every row starts
     // from; block CG: the kernel's own product with the unweighted matrix), w_i times the gather-sum of the opposing implicit factors in
     // the right-hand sides (closed form; the CG kernel gathers them itself)
-    const real_t *Fi = s->implicit_feats ? (isA ? s->Bi.ptr : s->Ai.ptr) : nullptr;
-    if (Fi != nullptr) {
-        launch_gram(dev, s->gws, Fi, (size_t)kk, rows_opp, kk, s->bitbi.ptr, chol ? s->w_implicit : (real_t)1, (real_t)0);
-        if (chol) {
-            hipLaunchKernelGGL(add_block_kernel<real_t>, grid1d((size_t)kk * kk), dim3(256), 0, st, s->bitbi.ptr, kk, (real_t)1, s->gram.ptr, ks, 0);
-            if (!launch_gsum(s, isA, X, Fi, kk)) {
-                g_last_error = "cmfrec_hip: NA_as_zero_X with implicit features: k + k_main too wide for the gather-sum";
-                return 2;
-            }
-        }
+    if (v.Fi != nullptr) {
+        launch_implicit_gram(s, v, v.rows_opp, chol, chol);
+        if (chol)
+            if (int rc = naz_implicit_gsum(s, v)) return rc;
     }
     s->naz_M.alloc_at_least((size_t)kt * kt);
-    hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, s->gram.ptr, ks, k_side_self, (real_t)0, s->naz_M.ptr);
-    const bool has_cst = opp_bias || s->naz_center;
-    const real_t *bias = opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr;
+    hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, s->gram.ptr, ks, v.k_side_self, (real_t)0, s->naz_M.ptr);
+    const bool scaled = m.scale_lam || m.scale_lam_sideinfo;
     if (!chol) {
         // Block CG (round 6; fixture g35).  The rows WITH entries: collective_block_cg with NA_as_zero_X and weights (collective.c:2446-2493
         // first residual, :2700-2760 products) -- the shared B^T B, the corrections (w_j - 1) b_j b_j^T of the row's entries, the dense
         // side-information block through C^T C and U C -- on the lane <-> unknown kernel (CgParams::gx).  The rows WITHOUT entries run
         // the same CG from their side information and the constant: the reference factorises the shared block matrix for them only
         // when the caller hands it the buffers of precompute_for_predictions (filled_BtB, :5702-5716), which this model does not offer.
-        real_t *uc = isA ? s->ucA.ptr : s->ucB.ptr;
-        if (has_side && !sparse_side) {
-            launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->ctc.ptr, (real_t)1, (real_t)0);                 // C^T C, unweighted
-            launch_gemm<false>(dev, rows_self, kc, p_self, (real_t)1, Um, (size_t)p_self, Cm, (size_t)kc, uc, (size_t)kc);   // U C
+        if (dense_side) {
+            launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, (real_t)1, (real_t)0);                 // C^T C, unweighted
+            launch_gemm<false>(dev, rows_self, kc, p_self, (real_t)1, v.Um, (size_t)p_self, v.Cm, (size_t)kc, v.uc, (size_t)kc);   // U C
         }
-        const size_t nnzc = X.nnz;
-        s->naz_g.alloc_at_least(std::max<size_t>(nnzc, 1)); s->naz_xt.alloc_at_least(std::max<size_t>(nnzc, 1));
-        if (nnzc > 0)
-            hipLaunchKernelGGL(naz_entry_transform_kernel<real_t>, grid1d(nnzc), dim3(256), 0, st, X.v.ptr, X.w.ptr, X.i.ptr, nnzc,
-                               has_cst ? bias : nullptr, s->naz_center ? s->naz_mean : (real_t)0, s->naz_g.ptr, s->naz_xt.ptr);
-        s->naz_rhs.alloc_at_least((size_t)rows_self * ks);
-        HIP_CHECK(hipMemsetAsync(s->naz_rhs.ptr, 0, (size_t)rows_self * ks * sizeof(real_t), st));
-        {
-            CholCall cr{s->naz_rhs.ptr, (size_t)ks, oppx, ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, false, false, false, CHOL_NAZ};
-            cr.rhs_only = true; cr.values_override = s->naz_xt.ptr;
-            int rc = launch_chol(dev, cr, &X);
-            if (rc) return rc;
-        }
-        if (has_cst) {
-            const int nb = (rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
-            s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
-            hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, oppx, ld_opp, rows_opp, ks, bias,
-                               s->naz_center ? s->naz_mean : (real_t)0, s->naz_part.ptr);
-            hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
-            hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, (size_t)rows_self, ks,
-                               s->naz_vec.ptr);
-        }
-        const size_t nz = std::max<size_t>(nnzc, 1);
-        if (s->naz_zero.n < nz) {
-            s->naz_zero.alloc(nz);
-            HIP_CHECK(hipMemsetAsync(s->naz_zero.ptr, 0, nz * sizeof(real_t), st));
-        }
+        naz_entry_transform(s, v);
+        if (int rc = naz_gather_rhs(s, v, s->naz_xt.ptr)) return rc;
+        naz_constant(s, v, s->naz_rhs.ptr, (size_t)ks);
+        const real_t *zeros = naz_zeros(s, v.X.nnz);
         HIP_CHECK(hipGetLastError());
-        const bool scaled_cg = m.scale_lam || m.scale_lam_sideinfo;
-        CgCall c{self, ld_self, oppx, ld_opp, ks, nullptr, nullptr, lam_self, lam_last_self, scaled_cg, false, m.max_cg_steps, false,
+        CgCall c{v.self, v.ld_self, v.oppx, v.ld_opp, ks, nullptr, nullptr, v.lam_self, v.lam_last_self, scaled, false, m.max_cg_steps, false,
                  (bool)m.precondition_cg};
-        c.koff = k_side_self; c.kc = kc; c.w_side = w; c.rows_with_u = rows_u; c.p_side = p_self;
-        if (sparse_side) { c.X2 = &Us; c.C2 = Cm; } else if (has_side) { c.CtC = s->ctc.ptr; c.UC = uc; }
-        if (Fi != nullptr) { c.Bi = Fi; c.BiTBi = s->bitbi.ptr; c.ki = kk; c.w_imp = s->w_implicit; }
+        c.koff = v.k_side_self; c.kc = kc; c.w_side = v.w; c.rows_with_u = rows_u; c.p_side = p_self;
+        if (sparse_side) set_sparse_side(v, c);
+        else if (has_side) { c.CtC = s->ctc.ptr; c.UC = v.uc; }
+        if (v.Fi != nullptr) set_implicit_term(s, v, c);
         c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
         c.Gx = s->gram.ptr; c.rconst_x = s->naz_rhs.ptr; c.ldr_x = (size_t)ks;
-        c.values_override = s->naz_zero.ptr; c.weights_override = s->naz_g.ptr;      // (the multipliers: X.wsum_naz, launch_cg)
-        c.gx_all_rows = has_cst;
-        return launch_cg(dev, c, X);
+        c.values_override = zeros; c.weights_override = s->naz_g.ptr;                // (the multipliers: X.wsum_naz, launch_cg)
+        c.gx_all_rows = v.has_cst;
+        return launch_cg(dev, c, v.X);
     }
-    if (has_side && !sparse_side) launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);
+    if (dense_side) launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, v.w, (real_t)0);
     // right-hand sides start from [w U C ; cst]  (sparse side information: [0 ; cst], the attributes are gathered by the row kernel)
-    HIP_CHECK(hipMemset2DAsync(self, ld_self * sizeof(real_t), 0, (size_t)kt * sizeof(real_t), (size_t)rows_self, st));
-    if (has_side && !sparse_side) launch_gemm<false>(dev, rows_self, kc, p_self, w, Um, (size_t)p_self, Cm, (size_t)kc, self, ld_self);
-    if (Fi != nullptr)
-        hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)X.nrows * kk), dim3(256), 0, st, self, ld_self, k_side_self, s->grhs.ptr, kk,
-                           s->w_implicit, (size_t)X.nrows);
-    if (has_cst) {
-        const int nb = (rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
-        s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
-        hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, oppx, ld_opp, rows_opp, ks, bias,
-                           s->naz_center ? s->naz_mean : (real_t)0, s->naz_part.ptr);
-        hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
-        hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, self + k_side_self, ld_self, (size_t)rows_self, ks,
-                           s->naz_vec.ptr);
-    }
-    const size_t nnz = X.nnz;
-    s->naz_g.alloc_at_least(std::max<size_t>(nnz, 1)); s->naz_xt.alloc_at_least(std::max<size_t>(nnz, 1));
-    if (nnz > 0)
-        hipLaunchKernelGGL(naz_entry_transform_kernel<real_t>, grid1d(nnz), dim3(256), 0, st, X.v.ptr, X.w.ptr, X.i.ptr, nnz,
-                           has_cst ? bias : nullptr, s->naz_center ? s->naz_mean : (real_t)0, s->naz_g.ptr, s->naz_xt.ptr);
+    HIP_CHECK(hipMemset2DAsync(v.self, v.ld_self * sizeof(real_t), 0, (size_t)kt * sizeof(real_t), (size_t)rows_self, st));
+    if (dense_side) launch_gemm<false>(dev, rows_self, kc, p_self, v.w, v.Um, (size_t)p_self, v.Cm, (size_t)kc, v.self, v.ld_self);
+    if (v.Fi != nullptr) add_implicit_rhs(s, v, v.self, v.ld_self);
+    naz_constant(s, v, v.self + v.k_side_self, v.ld_self);
+    naz_entry_transform(s, v);
     HIP_CHECK(hipGetLastError());
-    const bool scaled = m.scale_lam || m.scale_lam_sideinfo;
-    CholCall c{self, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, (sparse_side || !has_side) ? nullptr : s->ctc.ptr, kc, rows_u, p_self, lam_self, lam_last_self,
-               scaled, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE, s->naz_M.ptr};
+    CholCall c{v.self, v.ld_self, v.oppx, v.ld_opp, kt, v.k_side_self, nullptr, dense_side ? s->ctc.ptr : nullptr, kc, rows_u, p_self, v.lam_self,
+               v.lam_last_self, scaled, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE, s->naz_M.ptr};
     c.rhs_prefilled_all = true; c.entry_pairs = true; c.values_override = s->naz_xt.ptr; c.weights_override = s->naz_g.ptr;
-    if (sparse_side) { c.X2 = &Us; c.B2 = Cm; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w; }
-    if (scaled) c.mult_override = X.wsum_naz.ptr;        // sum of the row's weights + its absent entries (cmfrec_hip_session_set_NA_as_zero_X)
-    return launch_chol(dev, c, &X);
+    if (sparse_side) set_sparse_side(v, c);
+    if (scaled) c.mult_override = v.X.wsum_naz.ptr;      // sum of the row's weights + its absent entries (cmfrec_hip_session_set_NA_as_zero_X)
+    return launch_chol(dev, c, &v.X);
 }
 
 // The same half-step WITH observation weights and without side information (optimizeA Case 4 with NA_as_zero && weight,
@@ -2135,50 +2143,30 @@ static int update_factor_naz_weighted_side(cmfrec_hip_session *s, bool isA, bool
 // kernels of the explicit model with the shared matrix in LDS (GRAMX builds), weights w - 1 and zero values --
 //     r = rhs_i - M_i a,   Ap = M_i p
 // are the reference's :1321-1371 / :1391-1406 regrouped.  Rows without entries are solved when cst exists (:3270-3271).
-static int update_factor_naz_weighted(cmfrec_hip_session *s, bool isA, bool chol)
+static int update_factor_naz_weighted(cmfrec_hip_session *s, const HalfStepSide &v, bool chol)
 {
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
     hipStream_t st = dev.stream;
-    const int p_self = isA ? m.p : m.q;
     if (dev.nonneg_now || dev.l1_now != (real_t)0 || dev.l1_last_now != (real_t)0 || s->side_local) {
         g_last_error = "cmfrec_hip: NA_as_zero_X with observation weights: the model without nonneg / L1";
         return 2;
     }
-    if (p_self > 0 || s->implicit_feats) return update_factor_naz_weighted_side(s, isA, chol);
-    const int rows_self = isA ? m.m : m.n, rows_opp = isA ? m.n : m.m;
-    real_t *self = isA ? s->A.ptr : s->B.ptr;
-    real_t *opp = (isA ? s->B.ptr : s->A.ptr) + (isA ? m.k_item : m.k_user);      // the columns X refers to (the other side may carry k_item / k_user)
-    const size_t ld_self = isA ? s->ldA : s->ldB, ld_opp = isA ? s->ldB : s->ldA;
-    const SparseShard &X = isA ? s->Xr : s->Xc;
-    const bool self_bias = isA ? m.user_bias : m.item_bias, opp_bias = isA ? m.item_bias : m.user_bias;
-    const real_t lam_self = s->lam6[isA ? 2 : 3];
-    const real_t lam_last_self = self_bias ? s->lam6[isA ? 0 : 1] : lam_self;
-    const int ks = m.k + m.k_main + (self_bias ? 1 : 0);
+    if (v.p_self > 0 || s->implicit_feats) return update_factor_naz_weighted_side(s, v, chol);
+    const int rows_self = v.rows_self, ks = v.ks;
+    const real_t *opp = v.oppx;               // the columns X refers to (the other side may carry k_item / k_user)
+    const SparseShard &X = v.X;
+    const real_t lam_self = v.lam_self, lam_last_self = v.lam_last_self;
     if (!chol && ks > 64 && !m.precondition_cg) {
         g_last_error = "cmfrec_hip: NA_as_zero_X with observation weights under CG: at most 64 unknowns per row (the preconditioned solver takes more)";
         return 2;
     }
-    if (self_bias)                            // the opposing bias column is fixed to 1 (collective.c:8538-8543, :8728-8732)
-        hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_opp), dim3(256), 0, st, isA ? s->B.ptr : s->A.ptr, ld_opp, rows_opp,
-                           isA ? s->k_totB : s->k_totA, (real_t)1);
-    launch_gram(dev, s->gws, opp, ld_opp, rows_opp, ks, s->gram.ptr, (real_t)1, (real_t)0);       // :3233-3236, no diagonal
+    fill_fixed_bias_column(s, v);
+    launch_gram(dev, s->gws, opp, v.ld_opp, v.rows_opp, ks, s->gram.ptr, (real_t)1, (real_t)0);   // :3233-3236, no diagonal
     // cst (bias_BtX) and the per-entry pairs
-    const bool has_cst = opp_bias || s->naz_center;
-    const real_t *bias = opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr;
-    if (has_cst) {
-        const int nb = (rows_opp + COLSUM_ROWS - 1) / COLSUM_ROWS;
-        s->naz_part.alloc_at_least((size_t)nb * ks); s->naz_vec.alloc_at_least((size_t)ks);
-        hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb), dim3(256), 0, st, opp, ld_opp, rows_opp, ks, bias,
-                           s->naz_center ? s->naz_mean : (real_t)0, s->naz_part.ptr);
-        hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(ks), dim3(256), 0, st, s->naz_part.ptr, nb, ks, (real_t)-1, s->naz_vec.ptr);
-    }
-    const real_t *cst = has_cst ? s->naz_vec.ptr : nullptr;
-    const size_t nnz = X.nnz;
-    s->naz_g.alloc_at_least(std::max<size_t>(nnz, 1)); s->naz_xt.alloc_at_least(std::max<size_t>(nnz, 1));
-    if (nnz > 0)
-        hipLaunchKernelGGL(naz_entry_transform_kernel<real_t>, grid1d(nnz), dim3(256), 0, st, X.v.ptr, X.w.ptr, X.i.ptr, nnz,
-                           has_cst ? bias : nullptr, s->naz_center ? s->naz_mean : (real_t)0, s->naz_g.ptr, s->naz_xt.ptr);
+    const bool has_cst = v.has_cst;
+    const real_t *cst = naz_constant(s, v);
+    naz_entry_transform(s, v);
     HIP_CHECK(hipGetLastError());
     if (chol) {
         // right-hand sides start from cst (or zero), every row that is solved is overwritten
@@ -2186,35 +2174,24 @@ static int update_factor_naz_weighted(cmfrec_hip_session *s, bool isA, bool chol
         s->naz_rhs.alloc_at_least((size_t)rows_self * ks);
         hipLaunchKernelGGL(set_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, (size_t)rows_self, ks, cst);
         // (rows without entries and without cst keep their factors: the kernel solves into naz_rhs, copied back below for the solved rows)
-        CholCall c{s->naz_rhs.ptr, (size_t)ks, opp, ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, m.scale_lam != 0, false,
+        CholCall c{s->naz_rhs.ptr, (size_t)ks, opp, v.ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, m.scale_lam != 0, false,
                    s->scale_bias_const, CHOL_NAZ_W};
         c.values_override = s->naz_xt.ptr; c.weights_override = s->naz_g.ptr; c.rhs_prefilled_all = true; c.all_rows = has_cst;
         int rc = launch_chol(dev, c, &X);
         if (rc) return rc;
-        hipLaunchKernelGGL(copy_rows_by_order_kernel<real_t>, grid1d((size_t)nsolve * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, self, ld_self,
+        hipLaunchKernelGGL(copy_rows_by_order_kernel<real_t>, grid1d((size_t)nsolve * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, v.self, v.ld_self,
                            X.order.ptr, nsolve, ks);
         HIP_CHECK(hipGetLastError());
         return 0;
     }
     // CG: rhs_i by the gather-only launch (sum_j xt_j opp_j) + cst ...
-    s->naz_rhs.alloc_at_least((size_t)rows_self * ks);
-    HIP_CHECK(hipMemsetAsync(s->naz_rhs.ptr, 0, (size_t)rows_self * ks * sizeof(real_t), st));
-    {
-        CholCall c{s->naz_rhs.ptr, (size_t)ks, opp, ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, false, false, false, CHOL_NAZ};
-        c.rhs_only = true; c.values_override = s->naz_xt.ptr;
-        int rc = launch_chol(dev, c, &X);
-        if (rc) return rc;
-    }
+    if (int rc = naz_gather_rhs(s, v, s->naz_xt.ptr)) return rc;
     if (has_cst)
         hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, (size_t)rows_self, ks, cst);
     // ... then the tiled kernels: shared matrix in LDS, rank-1 weights w - 1, values zero
-    if (s->naz_zero.n < std::max<size_t>(nnz, 1)) {
-        s->naz_zero.alloc(std::max<size_t>(nnz, 1));
-        HIP_CHECK(hipMemsetAsync(s->naz_zero.ptr, 0, std::max<size_t>(nnz, 1) * sizeof(real_t), st));
-    }
-    CgCall c{self, ld_self, opp, ld_opp, ks, nullptr, nullptr, lam_self, lam_last_self, m.scale_lam != 0, s->scale_bias_const, m.max_cg_steps, false};
+    CgCall c{v.self, v.ld_self, opp, v.ld_opp, ks, nullptr, nullptr, lam_self, lam_last_self, m.scale_lam != 0, s->scale_bias_const, m.max_cg_steps, false};
     c.Gx = s->gram.ptr; c.rconst_x = s->naz_rhs.ptr; c.ldr_x = (size_t)ks;
-    c.values_override = s->naz_zero.ptr; c.weights_override = s->naz_g.ptr;
+    c.values_override = naz_zeros(s, X.nnz); c.weights_override = s->naz_g.ptr;
     // precondition_cg (round 6; factors_explicit_pcg_NA_as_zero_weighted, common.c:1443-1613): the lane <-> unknown kernel with the
     // shared matrix, its diagonal in the Jacobi preconditioner, the rows without entries in the same launch when the constant exists
     c.precond = m.precondition_cg != 0; c.gx_all_rows = c.precond && has_cst;
@@ -2222,7 +2199,7 @@ static int update_factor_naz_weighted(cmfrec_hip_session *s, bool isA, bool chol
     if (rc) return rc;
     if (!c.precond && has_cst && X.nrows > X.n_nonempty) {
         const int cnt = X.nrows - X.n_nonempty;
-        hipLaunchKernelGGL(cg_shared_matrix_rows_kernel<real_t>, dim3((cnt + 3) / 4), dim3(256), 0, st, self, ld_self, X.order.ptr + X.n_nonempty, cnt, ks,
+        hipLaunchKernelGGL(cg_shared_matrix_rows_kernel<real_t>, dim3((cnt + 3) / 4), dim3(256), 0, st, v.self, v.ld_self, X.order.ptr + X.n_nonempty, cnt, ks,
                            s->gram.ptr, cst, lam_self, lam_last_self, m.scale_lam ? X.wsum_naz.ptr : nullptr, s->scale_bias_const ? 1 : 0, m.max_cg_steps);
         HIP_CHECK(hipGetLastError());
     }
@@ -2231,290 +2208,217 @@ static int update_factor_naz_weighted(cmfrec_hip_session *s, bool isA, bool chol
 
 static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = -1)
 {
-    if (s->naz_X && !s->mdl.implicit && s->Xr.weighted()) return update_factor_naz_weighted(s, isA, chol);
-    if (s->naz_X && !s->mdl.implicit) return update_factor_naz(s, isA, chol);
+    // "self" = matrix being updated, "opp" = the fixed one
+    const HalfStepSide v(s, isA);
+    if (s->naz_X && !s->mdl.implicit && s->Xr.weighted()) return update_factor_naz_weighted(s, v, chol);
+    if (s->naz_X && !s->mdl.implicit) return update_factor_naz(s, v, chol);
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
     hipStream_t st = dev.stream;
-    // "self" = matrix being updated, "opp" = the fixed one
-    real_t *self = isA ? s->A.ptr : s->B.ptr;
-    real_t *opp = isA ? s->B.ptr : s->A.ptr;
-    const size_t ld_self = isA ? s->ldA : s->ldB, ld_opp = isA ? s->ldB : s->ldA;
-    const int rows_opp = isA ? (m.n_x > 0 ? m.n_x : m.n) : (m.m_x > 0 ? m.m_x : m.m);   // rows of the opposing matrix that X refers to (the Gramian's rows)
-    const int k_side_self = isA ? m.k_user : m.k_item, k_side_opp = isA ? m.k_item : m.k_user;
-    const int begin = isA ? m.row_begin : m.col_begin;
-    const SparseShard &X = (part >= 0) ? *s->XrParts[part] : (isA ? s->Xr : s->Xc);
-    const bool self_bias = isA ? m.user_bias : m.item_bias;
-    const bool opp_bias = isA ? m.item_bias : m.user_bias;
-    const int p_self = isA ? m.p : m.q;
-    // lam_unique[2] / [3] for A / B; the bias, when fitted, takes lam_unique[0] / [1] (collective.c:8649-8654, :8820-8825)
+    const size_t ld_self = v.ld_self, ld_opp = v.ld_opp;
+    const int rows_opp = v.rows_x_opp;        // rows of the opposing matrix that X refers to (the Gramian's rows)
+    const int k_side_self = v.k_side_self, p_self = v.p_self, begin = v.begin;
+    const real_t *oppx = v.oppx;
+    const SparseShard &X = (part >= 0) ? *s->XrParts[part] : v.X;
     const bool sbc = s->scale_bias_const && !m.implicit;      // rows without side information: common.c:679-723
-    const real_t lam_self = s->lam6[isA ? 2 : 3];
-    const real_t lam_last_self = (!m.implicit && self_bias) ? s->lam6[isA ? 0 : 1] : lam_self;
-    real_t *self_blk = self + (size_t)(begin + (part >= 0 ? s->partBegin[part] : 0)) * ld_self;
+    const real_t lam_self = v.lam_self, lam_last_self = v.lam_last_self;
+    real_t *self_blk = v.self + (size_t)(begin + (part >= 0 ? s->partBegin[part] : 0)) * ld_self;
     if (part >= 0 && (!isA || p_self > 0)) {
         g_last_error = "cmfrec_hip: row parts are only built for A-steps without side information";
         return 2;
     }
-    const int kk = m.k + m.k_main;
-    const int rows_x_self = isA ? (m.m_x > 0 ? m.m_x : m.m) : (m.n_x > 0 ? m.n_x : m.n);          // rows of this matrix X has
+    const int kk = v.kk, kc = v.kc, rows_u = v.rows_u;
+    const int rows_x_self = v.rows_x_self;                    // rows of this matrix X has
+    const real_t w = v.w;
+    const bool scale_lam = m.scale_lam || m.scale_lam_sideinfo;                                     // :7465
 
-    const bool sparse_side = isA ? s->sparseU : s->sparseI;
-    if (p_self > 0 && sparse_side) {
+    // the X block of a block-CG system: the implicit model's Gramian, or the explicit model's fixed bias column and fused "X - bias"
+    auto block_cg_call = [&](bool scale_bias_const) {
+        const real_t *bias_sub_cg = nullptr;
+        int kx = kk;
+        if (m.implicit) {
+            launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, (real_t)0);
+        } else {
+            fill_fixed_bias_column(s, v);
+            HIP_CHECK(hipGetLastError());
+            kx = v.ks;
+            bias_sub_cg = v.bias;
+        }
+        CgCall c{self_blk, ld_self, oppx, ld_opp, kx, bias_sub_cg, m.implicit ? s->gram.ptr : nullptr, lam_self, lam_last_self, scale_lam,
+                 scale_bias_const, m.max_cg_steps, (bool)m.implicit, (bool)m.precondition_cg};
+        c.koff = k_side_self; c.kc = kc; c.w_side = w; c.p_side = p_self; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
+        return c;
+    };
+    // ... and its implicit-features term (collective.c:2301-2304, :2624-2643, :2862-2868; round 6: with u_vec_sp too): the unweighted
+    // Bi^T Bi apart, the right-hand-side term by the gather-sum where the tables allow it
+    auto add_implicit_term_cg = [&](CgCall &c) {
+        if (v.Fi == nullptr || m.implicit) return;
+        launch_implicit_gram(s, v, rows_opp, false, false);
+        set_implicit_term(s, v, c);
+        if (part < 0 && launch_gsum(s, v, v.Fi, (size_t)kk, kk, s->grhs.ptr, X.nrows)) c.gsum = s->grhs.ptr;
+    };
+
+    if (p_self > 0 && v.sparse_side) {
         // sparse side information (missing = absent): the row's attributes are a second gather source of the same
         // Cholesky launch (collective.c:1636-1653, :1719-1731 / :2003-2021) or of the lane <-> unknown CG kernel
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const SparseShard &Us = isA ? s->Usr : s->Isr;
-        const int rows_u = isA ? m.m_u : m.n_i;
-        const int kc = k_side_self + m.k;
-        const real_t w = isA ? m.w_user : m.w_item;
         if (!chol) {
             // block CG / PCG with the attributes as a second gathered term (collective_block_cg u_vec_sp branches,
             // collective.c:2292-2298, :2609-2621, :2847-2860; implicit: :2993-2999 ff.), generic kernel
-            const real_t *bias_sub_cg = nullptr;
-            int kx = kk;
-            if (m.implicit) {
-                launch_gram(dev, s->gws, opp + k_side_opp, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, (real_t)0);
-            } else {
-                if (self_bias) {
-                    const int rows_fill = isA ? m.n : m.m;
-                    hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_fill), dim3(256), 0, st, opp, ld_opp, rows_fill,
-                                       isA ? s->k_totB : s->k_totA, (real_t)1);
-                    kx += 1;
-                }
-                if (opp_bias) bias_sub_cg = isA ? s->biasB.ptr : s->biasA.ptr;
-            }
-            CgCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, kx, bias_sub_cg, m.implicit ? s->gram.ptr : nullptr,
-                     lam_self, lam_last_self, (bool)(m.scale_lam || m.scale_lam_sideinfo), false, m.max_cg_steps, (bool)m.implicit,
-                     (bool)m.precondition_cg};
-            c.koff = k_side_self; c.kc = kc; c.w_side = w; c.rows_with_u = rows_u; c.p_side = p_self;
-            c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo; c.X2 = &Us; c.C2 = Cm;
-            if (s->implicit_feats && !m.implicit) {             // collective.c:2301-2304, :2624-2643, :2862-2868 (round 6: with u_vec_sp too)
-                const real_t *Fc = isA ? s->Bi.ptr : s->Ai.ptr;
-                launch_gram(dev, s->gws, Fc, (size_t)kk, rows_opp, kk, s->bitbi.ptr, (real_t)1, (real_t)0);
-                c.Bi = Fc; c.BiTBi = s->bitbi.ptr; c.ki = kk; c.w_imp = s->w_implicit;
-                if (part < 0 && launch_gsum(s, isA, X, Fc, kk)) c.gsum = s->grhs.ptr;
-            }
+            CgCall c = block_cg_call(false);          // (scale_bias_const: not with sparse side information)
+            c.rows_with_u = rows_u;
+            set_sparse_side(v, c);
+            add_implicit_term_cg(c);
             return launch_cg_any(dev, c, X, nullptr);
         }
         if (m.implicit) {
             if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :6018-6019
             const int kt = k_side_self + kk;
-            launch_gram(dev, s->gws, opp + k_side_opp, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, lam_self);
+            launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, lam_self);
             hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d(kt * kt), dim3(256), 0, st, s->gram.ptr, kk, k_side_self, lam_self,
                                s->betbe.ptr);
-            CholCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, kt, k_side_self, nullptr, nullptr, kc, rows_u, p_self, lam_self,
+            CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, nullptr, kc, rows_u, p_self, lam_self,
                        lam_last_self, false, false, false, CHOL_COLLECTIVE_IMPLICIT, s->betbe.ptr};
-            c.X2 = &Us; c.B2 = Cm; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w;
+            set_sparse_side(v, c);
             return launch_chol(dev, c, &X);
         }
         // (the explicit model's closed form: below, after the implicit-features term it may carry)
     }
+    // rows of the local block with side information, and those of them that X has (explicit model: rows beyond X are not part of
+    // the block system, solve_sideinfo_only_rows)
+    const int local_u = std::max(0, std::min(rows_u - begin, X.nrows));
+    const int local_x = std::max(0, std::min(rows_x_self - begin, X.nrows));
     if (p_self > 0 && !chol) {
         // block CG on the collective system, dense full side information: collective_block_cg (explicit,
         // collective.c:2134-2903) / collective_block_cg_implicit (:2905-3303), prefer_CtC branch
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const real_t *Um = isA ? s->U.ptr : s->II.ptr;
-        const int rows_u = isA ? m.m_u : m.n_i;
-        const int kc = k_side_self + m.k;
-        const real_t w = isA ? m.w_user : m.w_item;
-        const int local_u = std::max(0, std::min(rows_u - begin, X.nrows));
-        real_t *uc = isA ? s->ucA.ptr : s->ucB.ptr;
-        launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->ctc.ptr, (real_t)1, (real_t)0);   // C^T C, unweighted
-        launch_gemm<false>(dev, local_u, kc, p_self, (real_t)1, Um + (size_t)(s->side_local ? 0 : begin) * p_self, (size_t)p_self, Cm, (size_t)kc,
-                           uc, (size_t)kc);                                                        // U C
-        const real_t *bias_sub_cg = nullptr;
-        int kx = kk;
-        if (m.implicit) {
-            launch_gram(dev, s->gws, opp + k_side_opp, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, (real_t)0);
-        } else {
-            if (self_bias) {
-                const int rows_fill = isA ? m.n : m.m;
-                hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_fill), dim3(256), 0, st, opp, ld_opp, rows_fill,
-                                   isA ? s->k_totB : s->k_totA, (real_t)1);
-                HIP_CHECK(hipGetLastError());
-                kx += 1;
-            }
-            if (opp_bias) bias_sub_cg = isA ? s->biasB.ptr : s->biasA.ptr;
-        }
-        CgCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, kx, bias_sub_cg, m.implicit ? s->gram.ptr : nullptr,
-                 lam_self, lam_last_self, (bool)(m.scale_lam || m.scale_lam_sideinfo), sbc, m.max_cg_steps, (bool)m.implicit,
-                 (bool)m.precondition_cg};
-        // explicit model: rows beyond X are not part of the block system (solve_sideinfo_only_rows)
-        const int local_x = std::max(0, std::min(rows_x_self - begin, X.nrows));
+        launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, (real_t)1, (real_t)0);   // C^T C, unweighted
+        launch_gemm<false>(dev, local_u, kc, p_self, (real_t)1, v.Um_blk, (size_t)p_self, v.Cm, (size_t)kc, v.uc, (size_t)kc);   // U C
+        CgCall c = block_cg_call(sbc);
         const int local_u_main = m.implicit ? local_u : std::min(local_u, local_x);
-        c.koff = k_side_self; c.kc = kc; c.CtC = s->ctc.ptr; c.UC = uc; c.w_side = w; c.rows_with_u = local_u_main;
-        c.p_side = p_self; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
-        if (s->implicit_feats && !m.implicit) {                 // collective.c:2301-2304, :2624-2643, :2862-2868
-            const real_t *Fi = isA ? s->Bi.ptr : s->Ai.ptr;
-            launch_gram(dev, s->gws, Fi, (size_t)kk, rows_opp, kk, s->bitbi.ptr, (real_t)1, (real_t)0);
-            c.Bi = Fi; c.BiTBi = s->bitbi.ptr; c.ki = kk; c.w_imp = s->w_implicit;
-            if (part < 0 && launch_gsum(s, isA, X, Fi, kk)) c.gsum = s->grhs.ptr;
-        }
+        c.CtC = s->ctc.ptr; c.UC = v.uc; c.rows_with_u = local_u_main;
+        add_implicit_term_cg(c);
         int rc = launch_cg_any(dev, c, X, nullptr);
         if (rc) return rc;
-        return solve_sideinfo_only_rows(s, isA, false, local_u_main, local_u - local_u_main);
+        return solve_sideinfo_only_rows(s, v, false, local_u_main, local_u - local_u_main);
     }
     if (m.implicit && p_self > 0) {
         // optimizeA_collective_implicit, Cholesky, dense full side information (collective.c:5971-6244)
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const real_t *Um = isA ? s->U.ptr : s->II.ptr;
-        const int rows_u = isA ? m.m_u : m.n_i;
-        const int kc = k_side_self + m.k, kt = k_side_self + kk;
-        const real_t w = isA ? m.w_user : m.w_item;
-        launch_gram(dev, s->gws, opp + k_side_opp, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, lam_self);     // :6056-6061
+        const int kt = k_side_self + kk;
+        launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, lam_self);     // :6056-6061
         hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d(kt * kt), dim3(256), 0, st, s->gram.ptr, kk, k_side_self, lam_self,
                            s->betbe.ptr);                                                           // :6121-6135
-        launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);            // :6138-6160
+        launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);          // :6138-6160
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :6018-6019
-        const int local_u = std::max(0, std::min(rows_u - begin, X.nrows));
-        launch_gemm<false>(dev, local_u, kc, p_self, w, Um + (size_t)(s->side_local ? 0 : begin) * p_self, (size_t)p_self, Cm, (size_t)kc,
-                           self_blk, ld_self);                                                      // :6163-6168
-        CholCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, kt, k_side_self, nullptr, s->ctc.ptr, kc, local_u,
+        launch_gemm<false>(dev, local_u, kc, p_self, w, v.Um_blk, (size_t)p_self, v.Cm, (size_t)kc, self_blk, ld_self);   // :6163-6168
+        CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, s->ctc.ptr, kc, local_u,
                    p_self, lam_self, lam_last_self, false, false, false, CHOL_COLLECTIVE_IMPLICIT, s->betbe.ptr};
         return launch_chol(dev, c, &X);
     }
     if (m.implicit) {
         // optimizeA_implicit, common.c:3305-3421 (the Gramian once per half-step: parts > 0 reuse it)
         if (part <= 0)
-            launch_gram(dev, s->gws, opp + k_side_opp, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, chol ? lam_self : (real_t)0);
+            launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, chol ? lam_self : (real_t)0);
         if (chol) {
             if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st)); // :3334
-            CholCall c{self_blk + k_side_self, ld_self, opp + k_side_opp, ld_opp, kk, 0, nullptr,
+            CholCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, kk, 0, nullptr,
                        s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, false, false, false, CHOL_IMPLICIT};
             return launch_chol(dev, c, &X);
         }
-        CgCall c{self_blk + k_side_self, ld_self, opp + k_side_opp, ld_opp, kk, nullptr, s->gram.ptr,
+        CgCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, kk, nullptr, s->gram.ptr,
                  lam_self, lam_last_self, false, false, m.max_cg_steps, true, (bool)m.precondition_cg};
-        return launch_cg_any(dev, c, X, isA ? &s->binA : &s->binB);
+        return launch_cg_any(dev, c, X, v.bins);
     }
 
     // ---- explicit ----
     // the opposing matrix' bias column is fixed to 1 while this one's bias is fitted (collective.c:8538-8543, :8728-8732)
-    if (self_bias) {
-        const int rows_fill = isA ? m.n : m.m;
-        hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(rows_fill), dim3(256), 0, st, opp, ld_opp, rows_fill,
-                           isA ? s->k_totB : s->k_totA, (real_t)1);
-        HIP_CHECK(hipGetLastError());
-    }
-    const real_t *bias_sub = nullptr;
-    if (opp_bias) bias_sub = isA ? s->biasB.ptr : s->biasA.ptr;             // fused "X - bias" (:8566-8570, :8750-8754)
-    const int ksolve = kk + (self_bias ? 1 : 0);
+    fill_fixed_bias_column(s, v);
+    HIP_CHECK(hipGetLastError());
+    const real_t *bias_sub = v.bias;                                        // fused "X - bias" (:8566-8570, :8750-8754)
+    const int ksolve = v.ks, kt = v.kt;
     // implicit features: w_i Bi^T Bi joins the X block of every row's matrix (collective.c:1704-1707) and
     // w_i sum_{j observed} Bi_j its right-hand side (:1757-1771).  The second gather source of the Cholesky launch reads
     // the same sparsity pattern with unit values from Bi, right-hand side only.
-    const real_t *Fi = nullptr;
-    if (s->implicit_feats && chol) {
-        Fi = isA ? s->Bi.ptr : s->Ai.ptr;
-        const int kt_i = k_side_self + ksolve;
-        launch_gram(dev, s->gws, Fi, (size_t)kk, rows_opp, kk, s->bitbi.ptr, s->w_implicit, (real_t)0);
-        hipLaunchKernelGGL(embed_block_kernel<real_t>, grid1d(kt_i * kt_i), dim3(256), 0, st, s->bitbi.ptr, kk, k_side_self,
-                           kt_i, s->bitbi_full.ptr);
+    const real_t *Fi = chol ? v.Fi : nullptr;
+    if (Fi != nullptr) {
+        launch_implicit_gram(s, v, rows_opp, true, false);
+        hipLaunchKernelGGL(embed_block_kernel<real_t>, grid1d(kt * kt), dim3(256), 0, st, s->bitbi.ptr, kk, k_side_self,
+                           kt, s->bitbi_full.ptr);
         HIP_CHECK(hipGetLastError());
     }
     auto add_implicit_term = [&](CholCall &c) {
         if (Fi == nullptr) return;
         c.Mfull = s->bitbi_full.ptr;
-        auto &G = s->gsegs[isA ? 0 : 1];
-        if (kk <= 64 * GSUM_MAXC && part < 0) {
+        if (part < 0 && launch_gsum(s, v, Fi, (size_t)kk, kk, s->grhs.ptr, X.nrows)) {
             // the right-hand-side term by the segmented gather-sum, added to the (zeroed / w U C) rows the launch then starts
             // from: the row kernel gathers X only (first version: Bi as a second gather source of the same launch, c3 +
             // implicit features A-step 34.4 ms, B-step 20.5 ms)
-            if (G.nseg > 0)
-                hipLaunchKernelGGL(gather_sum_segments_kernel<real_t>, dim3((G.nseg + 3) / 4), dim3(256), 0, st, X.p.ptr, X.i.ptr, Fi,
-                                   (size_t)kk, kk, G.seg_row.ptr, G.seg_off.ptr, G.nseg, s->gpartial.ptr);
-            hipLaunchKernelGGL(gather_sum_rows_kernel<real_t>, dim3((X.nrows + 3) / 4), dim3(256), 0, st, s->gpartial.ptr,
-                               G.row_first.ptr, X.nrows, kk, s->grhs.ptr, (size_t)kk);
-            hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)X.nrows * kk), dim3(256), 0, st, self_blk, ld_self,
-                               k_side_self, s->grhs.ptr, kk, s->w_implicit, (size_t)X.nrows);
+            add_implicit_rhs(s, v, self_blk, ld_self);
             c.rhs_prefilled_all = true;
             return;
         }
         c.X2 = &X; c.values2 = s->ones.ptr; c.B2 = Fi; c.ldb2 = (size_t)kk; c.kc2 = kk; c.koff2 = k_side_self;
         c.w2 = s->w_implicit; c.w2_syr_zero = true; c.rows2 = X.nrows;
     };
-    if (p_self > 0 && sparse_side) {
+    if (p_self > 0 && v.sparse_side) {
         // sparse side information, closed form: the row's attributes as the second gather source (collective.c:1636-1653, :1719-1731);
         // round 6: together with the implicit-features term (its right-hand side by the segmented gather-sum)
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const SparseShard &Us = isA ? s->Usr : s->Isr;
-        const int rows_u = isA ? m.m_u : m.n_i;
-        const int kc = k_side_self + m.k, kt = k_side_self + ksolve;
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
-        CholCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, kt, k_side_self, bias_sub, nullptr, kc, rows_u, p_self, lam_self,
-                   lam_last_self, (bool)(m.scale_lam || m.scale_lam_sideinfo), (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE};
+        CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, bias_sub, nullptr, kc, rows_u, p_self, lam_self,
+                   lam_last_self, scale_lam, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE};
         add_implicit_term(c);
         if (c.X2 != nullptr) {
             g_last_error = "cmfrec_hip: implicit features with sparse side information: k + k_main beyond the gather-sum's width";
             return 2;
         }
-        c.X2 = &Us; c.B2 = Cm; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = isA ? m.w_user : m.w_item;
+        set_sparse_side(v, c);
         return launch_chol(dev, c, &X);
     }
     if (p_self > 0) {
         // optimizeA_collective general branch, Cholesky (collective.c:5566-5968)
-        const real_t *Cm = isA ? s->C.ptr : s->D.ptr;
-        const real_t *Um = isA ? s->U.ptr : s->II.ptr;
-        const int rows_u = isA ? m.m_u : m.n_i;
-        const int kc = k_side_self + m.k, kt = k_side_self + ksolve;
-        const real_t w = isA ? m.w_user : m.w_item;
-        launch_gram(dev, s->gws, Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);            // :5658-5668
+        launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);          // :5658-5668
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
-        const int local_u = std::max(0, std::min(rows_u - begin, X.nrows));
-        launch_gemm<false>(dev, local_u, kc, p_self, w, Um + (size_t)(s->side_local ? 0 : begin) * p_self, (size_t)p_self, Cm, (size_t)kc,
-                           self_blk, ld_self);                                                      // :5768-5773
-        const int local_x = std::max(0, std::min(rows_x_self - begin, X.nrows));
+        launch_gemm<false>(dev, local_u, kc, p_self, w, v.Um_blk, (size_t)p_self, v.Cm, (size_t)kc, self_blk, ld_self);   // :5768-5773
         const int local_u_main = std::min(local_u, local_x);              // rows beyond X: solve_sideinfo_only_rows
-        CholCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, kt, k_side_self, bias_sub, s->ctc.ptr, kc, local_u_main,
-                   p_self, lam_self, lam_last_self, (bool)(m.scale_lam || m.scale_lam_sideinfo), (bool)m.scale_lam_sideinfo, sbc,
-                   CHOL_COLLECTIVE};
+        CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, bias_sub, s->ctc.ptr, kc, local_u_main,
+                   p_self, lam_self, lam_last_self, scale_lam, (bool)m.scale_lam_sideinfo, sbc, CHOL_COLLECTIVE};
         add_implicit_term(c);
         // rows with few entries against many unknowns: low-rank path (lowrank_kernels.hpp)
         if (Fi == nullptr && !sbc && local_u_main == X.nrows && part < 0) {
             // the other side's w D^T D, if its next half-step will want the eigenvectors and they are not there yet: decomposed
             // behind this side's (EigCache)
-            EigCache *mine = isA ? &s->eigA : &s->eigB, *next = isA ? &s->eigB : &s->eigA;
-            const int p_next = isA ? m.q : m.p, kc_next = (isA ? m.k_item : m.k_user) + m.k;
-            if (next->wanted && !next->fresh && p_next > 0 && !(isA ? s->sparseI : s->sparseU)) {
-                next->M.alloc_at_least((size_t)kc_next * kc_next);
-                launch_gram(dev, s->gws, isA ? s->D.ptr : s->C.ptr, (size_t)kc_next, p_next, kc_next, next->M.ptr, isA ? m.w_item : m.w_user,
-                            (real_t)0);
+            EigCache *next = v.eig_next;
+            if (next->wanted && !next->fresh && v.p_next > 0 && !v.sparse_side_next) {
+                next->M.alloc_at_least((size_t)v.kc_next * v.kc_next);
+                launch_gram(dev, s->gws, v.Cm_next, (size_t)v.kc_next, v.p_next, v.kc_next, next->M.ptr, v.w_next, (real_t)0);
             } else {
                 next = nullptr;
             }
-            const int rc_lr = launch_collective_lowrank(dev, s->lr, c, X, Cm, Um + (size_t)(s->side_local ? 0 : begin) * p_self, p_self, w, m.k,
-                                                        isA ? m.n : m.m, mine, next, kc_next);
+            const int rc_lr = launch_collective_lowrank(dev, s->lr, c, X, v.Cm, v.Um_blk, p_self, w, m.k, v.rows_opp, v.eig_mine, next,
+                                                        v.kc_next);
             if (rc_lr >= 0) return rc_lr;
         }
         int rc = launch_chol(dev, c, &X);
         if (rc) return rc;
-        return solve_sideinfo_only_rows(s, isA, true, local_u_main, local_u - local_u_main);
+        return solve_sideinfo_only_rows(s, v, true, local_u_main, local_u - local_u_main);
     }
-    const bool scale_lam = m.scale_lam || m.scale_lam_sideinfo;                                     // :7465
     if (Fi != nullptr) {
         // without side information on this side the reference still takes optimizeA_collective (collective.c:8612, :8783)
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
-        CholCall c{self_blk, ld_self, opp + k_side_opp, ld_opp, ksolve, 0, bias_sub, nullptr, 0, 0, 0,
+        CholCall c{self_blk, ld_self, oppx, ld_opp, ksolve, 0, bias_sub, nullptr, 0, 0, 0,
                    lam_self, lam_last_self, scale_lam, false, false, CHOL_COLLECTIVE};
         add_implicit_term(c);
         return launch_chol(dev, c, &X);
     }
     if (chol) {
-        CholCall c{self_blk + k_side_self, ld_self, opp + k_side_opp, ld_opp, ksolve, 0, bias_sub, nullptr, 0, 0, 0,
+        CholCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, ksolve, 0, bias_sub, nullptr, 0, 0, 0,
                    lam_self, lam_last_self, scale_lam, false, sbc, CHOL_EXPLICIT};
         return launch_chol(dev, c, &X);
     }
-    CgCall c{self_blk + k_side_self, ld_self, opp + k_side_opp, ld_opp, ksolve, bias_sub, nullptr,
+    CgCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, ksolve, bias_sub, nullptr,
              lam_self, lam_last_self, scale_lam, sbc, m.max_cg_steps, false, (bool)m.precondition_cg};
-    if (s->implicit_feats) {
-        // block CG with the implicit-features term (collective_block_cg without side information on this side,
-        // collective.c:2624-2643, :2862-2868): generic kernel; rows without entries are zeroed (:1258-1268)
-        const real_t *Fc = isA ? s->Bi.ptr : s->Ai.ptr;
-        launch_gram(dev, s->gws, Fc, (size_t)kk, rows_opp, kk, s->bitbi.ptr, (real_t)1, (real_t)0);
-        c.Bi = Fc; c.BiTBi = s->bitbi.ptr; c.ki = kk; c.w_imp = s->w_implicit;
-        if (part < 0 && launch_gsum(s, isA, X, Fc, kk)) c.gsum = s->grhs.ptr;
-    }
-    return launch_cg_any(dev, c, X, isA ? &s->binA : &s->binB);
+    // block CG with the implicit-features term (collective_block_cg without side information on this side,
+    // collective.c:2624-2643, :2862-2868): generic kernel; rows without entries are zeroed (:1258-1268)
+    add_implicit_term_cg(c);
+    return launch_cg_any(dev, c, X, v.bins);
 }
 
 // Ai / Bi update: optimizeA Case 3 on the binary indicator of X (collective.c:8448-8534; common.c:3116-3205): one
@@ -2523,14 +2427,15 @@ static int update_implicit_feats(cmfrec_hip_session *s, bool isAi)
 {
     const cmfrec_hip_model &m = s->mdl;
     const DeviceInfo &dev = s->dev;
-    const int kk = m.k + m.k_main;
+    const HalfStepSide v(s, isAi);
+    const int kk = v.kk;
     real_t *self = isAi ? s->Ai.ptr : s->Bi.ptr;
-    const real_t *F = isAi ? s->B.ptr + m.k_item : s->A.ptr + m.k_user;      // B_bias + k_item / A_bias + k_user
-    const size_t ldf = isAi ? s->ldB : s->ldA;
-    const int rows_f = isAi ? m.n : m.m, rows_self = isAi ? m.m : m.n;
-    const SparseShard &X = isAi ? s->Xr : s->Xc;
+    const real_t *F = v.oppx;                                                // B_bias + k_item / A_bias + k_user
+    const size_t ldf = v.ld_opp;
+    const int rows_f = v.rows_opp, rows_self = v.rows_self;
+    const SparseShard &X = v.X;
     const bool scale_lam = m.scale_lam || m.scale_lam_sideinfo;
-    const real_t lam = (s->lam6[isAi ? 2 : 3] / s->w_implicit) * (scale_lam ? (real_t)rows_f : (real_t)1);   // :8469, :8510
+    const real_t lam = (v.lam_self / s->w_implicit) * (scale_lam ? (real_t)rows_f : (real_t)1);   // :8469, :8510
     launch_gram(dev, s->gws, F, ldf, rows_f, kk, s->gram.ptr, (real_t)1, lam);
     HIP_CHECK(hipMemsetAsync(self, 0, (size_t)rows_self * kk * sizeof(real_t), dev.stream));
     CholCall c{self, (size_t)kk, F, ldf, kk, 0, nullptr, s->gram.ptr, 0, 0, 0, lam, lam, false, false, false, CHOL_NAZ};
@@ -2541,15 +2446,7 @@ static int update_implicit_feats(cmfrec_hip_session *s, bool isAi)
     // matrix factorised once per row -- c1 + implicit features 8 ms for Bi + Ai)
     // ... first by the row kernel itself (rhs_only, still the path of wider systems), whose staging loop made the longest
     // row the critical path (Bi at the C1 shape 4.5 ms); now a two-stage segmented gather-sum
-    auto &G = s->gsegs[isAi ? 0 : 1];
-    if (kk <= 64 * GSUM_MAXC) {
-        if (G.nseg > 0)
-            hipLaunchKernelGGL(gather_sum_segments_kernel<real_t>, dim3((G.nseg + 3) / 4), dim3(256), 0, dev.stream, X.p.ptr, X.i.ptr, F, ldf,
-                               kk, G.seg_row.ptr, G.seg_off.ptr, G.nseg, s->gpartial.ptr);
-        hipLaunchKernelGGL(gather_sum_rows_kernel<real_t>, dim3((rows_self + 3) / 4), dim3(256), 0, dev.stream, s->gpartial.ptr,
-                           G.row_first.ptr, rows_self, kk, self, (size_t)kk);
-        HIP_CHECK(hipGetLastError());
-    } else {
+    if (!launch_gsum(s, v, F, ldf, kk, self, rows_self)) {
         c.rhs_only = true;
         int rc = launch_chol(dev, c, &X);
         if (rc) return rc;
