@@ -138,15 +138,19 @@ struct DenseNanSide {
 // rank-one correction (collective.c:8354-8386, common.c:3116-3205), the full w C^T C block plus a constant -w C^T colmeans on
 // every right-hand side (collective.c:1277-1457, :5790-5800, :5823-5836; block CG: :2292-2298) -- and agrees with the dense
 // route on the zero-filled matrix to 1e-15, closed form and CG, both models (tests/test_oracle_vs_ref.py).  So that is what the
-// fit runs: the triplets are scattered into a [rows of X, cols] matrix here and take the dense path, GEMMs and all.  Cost: rows x
-// cols numbers of host and device memory instead of the triplets.  More rows of side information than X has: refused (the
-// reference treats the rows beyond X differently from its dense branch, nothing pins them).
+// fit runs, in one of two forms.  Up to CMFREC_HIP_ZEROFILL_MAX_GB the triplets are scattered into a [rows of X, cols] matrix here
+// and take the dense path, GEMMs and all; cost: rows x cols numbers of host and device memory instead of the triplets.  Beyond it
+// (single device) the triplets themselves go to the session (SparseZerosSide below, cmfrec_hip_session_set_sideinfo_sparse_zeros):
+// the same dense path with its two products by that matrix taken as sparse products plus the column means' rank-one term.  More
+// rows of side information than X has: refused (the reference treats the rows beyond X differently from its dense branch,
+// nothing pins them).
 struct ZeroFilledSide {
     std::vector<real_t> dense;
-    // Size limit of the zero-filled matrix: it exists three times (here, as the centred copy, on the device), so it is refused
-    // -- a controlled "not implemented at this size", not a bad_alloc / hipErrorOutOfMemory late in the fit -- beyond
+    // Size limit of the zero-filled matrix: it exists three times (here, as the centred copy, on the device).  Beyond
     // CMFREC_HIP_ZEROFILL_MAX_GB (default 8 GB per copy; realistic sparse side information of 1e6..1e7 rows x 1e3..1e4 columns
-    // is 8e9..8e11 bytes and belongs on the sparse kernels with the -w C^T colmeans constant, which this route does not build).
+    // is 8e9..8e11 bytes) build() returns 3 and the fit takes the sparse form; a multi-device fit, whose row-block shards need
+    // the dense matrix, answers with a controlled "not implemented at this size" instead of a bad_alloc / hipErrorOutOfMemory
+    // late in the fit.  Read per fit: a tiny value sends any problem down the sparse form (tests, tools/bench_side_zeros.py).
     static double max_bytes()
     {
         const char *e = getenv("CMFREC_HIP_ZEROFILL_MAX_GB");
@@ -167,6 +171,33 @@ struct ZeroFilledSide {
         }
         return 0;
     }
+};
+// ... the sparse form: the triplets as they came (validated; positions given twice add up in the products as they do in the
+// scatter above) and the column means over ALL rows of X, summed in double -- what center_cols computes of the zero-filled matrix.
+struct SparseZerosSide {
+    bool on = false;
+    const int_t *row = nullptr, *col = nullptr;
+    const real_t *val = nullptr;
+    size_t nnz = 0;
+    std::vector<real_t> means;           // empty: the caller asked for no centring (no colmeans output)
+    // 0 ok, 1 triplets missing / out of range, 4 NaN among the values
+    int take(int_t rows_x, int_t rows_side, int_t cols, const int_t *r, const int_t *c, const real_t *v, size_t n, real_t *means_out)
+    {
+        if (!r || !c || !v || cols <= 0) return 1;
+        std::vector<double> sum((size_t)cols, 0.0);
+        for (size_t e = 0; e < n; e++) {
+            if (r[e] < 0 || r[e] >= rows_side || c[e] < 0 || c[e] >= cols) return 1;
+            if (std::isnan(v[e])) return 4;
+            sum[(size_t)c[e]] += (double)v[e];
+        }
+        if (means_out != nullptr) {
+            means.resize((size_t)cols);
+            for (int_t j = 0; j < cols; j++) means_out[j] = means[(size_t)j] = (real_t)(sum[(size_t)j] / (double)rows_x);
+        }
+        row = r; col = c; val = v; nnz = n; on = true;
+        return 0;
+    }
+    const real_t *colmeans() const { return means.empty() ? nullptr : means.data(); }
 };
 // ... with one exception the reference makes: a row with neither an entry of X nor an entry of the side information is not solved
 // but set to zero, bias included (collective_closed_form_block, collective.c:1262-1271; _implicit: :1876-1884).  The list of
@@ -698,31 +729,40 @@ int_t fit_collective_implicit_als(
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
     if (k_main && nnz == 0) return fail(verbose, "Cannot pass 'k_main' without X data.");
     if (nnz == 0) return fail(verbose, "cmfrec_hip: the implicit model needs at least one entry of X.");
-    // sparse side information whose absent entries are zeros -> the dense route on the zero-filled matrix (ZeroFilledSide)
+    // sparse side information whose absent entries are zeros -> the dense route on the zero-filled matrix (ZeroFilledSide), or, past
+    // its size limit on a single device, the same route on the triplets (SparseZerosSide)
     ZeroFilledSide zfU, zfI;
+    SparseZerosSide szU, szI;
+    const bool sparse_zeros_ok = !sharded_fit_wanted(devices_from_env());
     const bool naz_U = NA_as_zero_U && U == nullptr && nnz_U > 0, naz_I = NA_as_zero_I && II == nullptr && nnz_I > 0;
     std::vector<int_t> zero_rows_A, zero_rows_B;
     if (naz_U) {
         zero_rows_A = rows_without_data(m, ixA, nnz, U_row, nnz_U);
-        const int e = zfU.build(m, m_u, p, U_row, U_col, U_sp, nnz_U);
+        int e = zfU.build(m, m_u, p, U_row, U_col, U_sp, nnz_U);
+        if (e == 3 && sparse_zeros_ok && (e = szU.take(m, m_u, p, U_row, U_col, U_sp, nnz_U, U_colmeans)) == 4)
+            return fail(verbose, "cmfrec_hip: NA_as_zero_U beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of U is not implemented.");
         if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_U with more rows of U than X is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_U runs on the zero-filled dense matrix (rows of X x p), which is larger than "
+                                    : e == 3 ? "cmfrec_hip: NA_as_zero_U on several devices runs on the zero-filled dense matrix (rows of X x p), which is larger than "
                                                "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
                                              : "cmfrec_hip: U index out of range.");
-        U = zfU.dense.data(); m_u = m; nnz_U = 0; U_row = U_col = nullptr; U_sp = nullptr;
+        if (!szU.on) U = zfU.dense.data();
+        m_u = m; nnz_U = 0; U_row = U_col = nullptr; U_sp = nullptr;
     }
     if (naz_I) {
         zero_rows_B = rows_without_data(n, ixB, nnz, I_row, nnz_I);
-        const int e = zfI.build(n, n_i, q, I_row, I_col, I_sp, nnz_I);
+        int e = zfI.build(n, n_i, q, I_row, I_col, I_sp, nnz_I);
+        if (e == 3 && sparse_zeros_ok && (e = szI.take(n, n_i, q, I_row, I_col, I_sp, nnz_I, I_colmeans)) == 4)
+            return fail(verbose, "cmfrec_hip: NA_as_zero_I beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of I is not implemented.");
         if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_I with more rows of I than X has columns is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_I runs on the zero-filled dense matrix (columns of X x q), which is larger than "
+                                    : e == 3 ? "cmfrec_hip: NA_as_zero_I on several devices runs on the zero-filled dense matrix (columns of X x q), which is larger than "
                                                "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
                                              : "cmfrec_hip: I index out of range.");
-        II = zfI.dense.data(); n_i = n; nnz_I = 0; I_row = I_col = nullptr; I_sp = nullptr;
+        if (!szI.on) II = zfI.dense.data();
+        n_i = n; nnz_I = 0; I_row = I_col = nullptr; I_sp = nullptr;
     }
     // dense side information with NaN -> the sparse route on its centred present entries
     DenseNanSide nanU, nanI;
-    const bool hadU = (U != nullptr);
+    const bool hadU = (U != nullptr) || szU.on;
     bool nan_side = false;
     if (U && m_u > 0 && p > 0 && nanU.convert(U, m_u, p, U_colmeans)) {
         U = nullptr; U_row = nanU.row.data(); U_col = nanU.col.data(); U_sp = nanU.val.data(); nnz_U = nanU.val.size(); nan_side = true;
@@ -744,8 +784,8 @@ int_t fit_collective_implicit_als(
     const bool spU = (U == nullptr && nnz_U > 0), spI = (II == nullptr && nnz_I > 0);
     if ((spU && (m_u > m || !U_row || !U_col || !U_sp)) || (spI && (n_i > n || !I_row || !I_col || !I_sp)))
         return fail(verbose, "cmfrec_hip: sparse side information must be COO triplets with rows inside X.");
-    if (U == nullptr && !spU) { m_u = 0; p = 0; }
-    if (II == nullptr && !spI) { n_i = 0; q = 0; }
+    if (U == nullptr && !spU && !szU.on) { m_u = 0; p = 0; }
+    if (II == nullptr && !spI && !szI.on) { n_i = 0; q = 0; }
     for (size_t e = 0; spU && e < nnz_U; e++)
         if (U_row[e] < 0 || U_row[e] >= m_u || U_col[e] < 0 || U_col[e] >= p) return fail(verbose, "cmfrec_hip: U index out of range.");
     for (size_t e = 0; spI && e < nnz_I; e++)
@@ -804,12 +844,12 @@ int_t fit_collective_implicit_als(
     const int k_totA = k_user + k + k_main, k_totB = k_item + k + k_main;
     const int_t m_max = std::max(m, m_u), n_max = std::max(n, n_i);     // rows of A / B (collective.c:9437-9440)
     if (reset_values) {                                                  // :9750-9774
-        const bool fill_B = (II != nullptr || spI);
+        const bool fill_B = (II != nullptr || spI || szI.on);
         cmfrng::random_parallel<real_t>(A, (size_t)m_max * k_totA, fill_B ? B : nullptr, fill_B ? (size_t)n_max * k_totB : 0, seed, false);
         if (use_cg) {
             if (!fill_B) memset(B, 0, (size_t)n_max * k_totB * sizeof(real_t));
-            if (U || spU) memset(C, 0, (size_t)p * (k_user + k) * sizeof(real_t));
-            if (II || spI) memset(D, 0, (size_t)q * (k_item + k) * sizeof(real_t));
+            if (U || spU || szU.on) memset(C, 0, (size_t)p * (k_user + k) * sizeof(real_t));
+            if (II || spI || szI.on) memset(D, 0, (size_t)q * (k_item + k) * sizeof(real_t));
         }
         // Cholesky: start values that are never read (the C / D / B steps run first) are left as passed, like the reference
     }
@@ -828,7 +868,7 @@ int_t fit_collective_implicit_als(
     // Sharded: the plain model and the one with DENSE side information (C / D by partial sums + all-reduce, multi_sideinfo_step),
     // all solvers, constraints and penalties; sparse side information and side information beyond the shape of X keep to the
     // first listed device.
-    const bool multi_ok = sharded_fit_wanted(devs) && !spU && !spI && m_u <= m && n_i <= n && m >= (int_t)devs.size() &&
+    const bool multi_ok = sharded_fit_wanted(devs) && !spU && !spI && !szU.on && !szI.on && m_u <= m && n_i <= n && m >= (int_t)devs.size() &&
                           n >= (int_t)devs.size() && zero_rows_A.empty() && zero_rows_B.empty();
     if (devs.size() > 1 && !multi_ok && verbose)
         printf("cmfrec_hip: CMFREC_HIP_DEVICES lists %d devices; this configuration (sparse side information / side information beyond X) "
@@ -870,6 +910,8 @@ int_t fit_collective_implicit_als(
     if (!rc && !zero_rows_A.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'A', zero_rows_A.data(), (int)zero_rows_A.size());
     if (!rc && !zero_rows_B.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'B', zero_rows_B.data(), (int)zero_rows_B.size());
     if (!rc) rc = cmfrec_hip_session_set_sideinfo(s, U ? Uc.data() : nullptr, II ? Ic.data() : nullptr);
+    if (!rc && szU.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'U', szU.row, szU.col, szU.val, szU.nnz, szU.colmeans());
+    if (!rc && szI.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'I', szI.row, szI.col, szI.val, szI.nnz, szI.colmeans());
     if (!rc && spU) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'U', U_row, U_col, U_sp, nnz_U);
     if (!rc && spI) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'I', I_row, I_col, I_sp, nnz_I);
     // dense side information with NaN: the per-attribute rules of the dense C / D update (DenseNanSide::rules)
@@ -936,27 +978,36 @@ int_t fit_collective_explicit_als(
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
     if (k_main && Xfull == nullptr && nnz == 0) return fail(verbose, "Cannot pass 'k_main' without X data.");
-    // sparse side information whose absent entries are zeros -> the dense route on the zero-filled matrix (ZeroFilledSide)
+    // sparse side information whose absent entries are zeros -> the dense route on the zero-filled matrix (ZeroFilledSide), or, past
+    // its size limit on a single device, the same route on the triplets (SparseZerosSide)
     ZeroFilledSide zfU, zfI;
+    SparseZerosSide szU, szI;
+    const bool sparse_zeros_ok = !sharded_fit_wanted(devices_from_env());
     const bool naz_U = NA_as_zero_U && U == nullptr && nnz_U > 0, naz_I = NA_as_zero_I && II == nullptr && nnz_I > 0;
     std::vector<int_t> zero_rows_A, zero_rows_B;
     if (naz_U) {
         zero_rows_A = rows_without_data(m, ixA, nnz, U_row, nnz_U);
-        const int e = zfU.build(m, m_u, p, U_row, U_col, U_sp, nnz_U);
+        int e = zfU.build(m, m_u, p, U_row, U_col, U_sp, nnz_U);
+        if (e == 3 && sparse_zeros_ok && (e = szU.take(m, m_u, p, U_row, U_col, U_sp, nnz_U, U_colmeans)) == 4)
+            return fail(verbose, "cmfrec_hip: NA_as_zero_U beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of U is not implemented.");
         if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_U with more rows of U than X is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_U runs on the zero-filled dense matrix (rows of X x p), which is larger than "
+                                    : e == 3 ? "cmfrec_hip: NA_as_zero_U on several devices runs on the zero-filled dense matrix (rows of X x p), which is larger than "
                                                "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
                                              : "cmfrec_hip: U index out of range.");
-        U = zfU.dense.data(); m_u = m; nnz_U = 0; U_row = U_col = nullptr; U_sp = nullptr;
+        if (!szU.on) U = zfU.dense.data();
+        m_u = m; nnz_U = 0; U_row = U_col = nullptr; U_sp = nullptr;
     }
     if (naz_I) {
         zero_rows_B = rows_without_data(n, ixB, nnz, I_row, nnz_I);
-        const int e = zfI.build(n, n_i, q, I_row, I_col, I_sp, nnz_I);
+        int e = zfI.build(n, n_i, q, I_row, I_col, I_sp, nnz_I);
+        if (e == 3 && sparse_zeros_ok && (e = szI.take(n, n_i, q, I_row, I_col, I_sp, nnz_I, I_colmeans)) == 4)
+            return fail(verbose, "cmfrec_hip: NA_as_zero_I beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of I is not implemented.");
         if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_I with more rows of I than X has columns is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_I runs on the zero-filled dense matrix (columns of X x q), which is larger than "
+                                    : e == 3 ? "cmfrec_hip: NA_as_zero_I on several devices runs on the zero-filled dense matrix (columns of X x q), which is larger than "
                                                "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
                                              : "cmfrec_hip: I index out of range.");
-        II = zfI.dense.data(); n_i = n; nnz_I = 0; I_row = I_col = nullptr; I_sp = nullptr;
+        if (!szI.on) II = zfI.dense.data();
+        n_i = n; nnz_I = 0; I_row = I_col = nullptr; I_sp = nullptr;
     }
     // Dense X: the rows of the present entries go through the same row kernels as a sparse X (a row's system is the sum over
     // its present entries either way: factors_closed_form, common.c:762-1075; factors_explicit_cg_dense, :1615-1749).  What the
@@ -979,7 +1030,7 @@ int_t fit_collective_explicit_als(
     // information is dense or missing-as-zero (:5121-5130), the solver asked for otherwise.  The side without side information keeps
     // optimizeA's rules above.  Side information on exactly the rows / columns of X (the rows beyond it would take optimizeA's dense
     // cases on a sub-block, :4832-5099), complete (no NaN), no weights.
-    const bool dense_side_A = Xfull && (U != nullptr || nnz_U > 0), dense_side_B = Xfull && (II != nullptr || nnz_I > 0);
+    const bool dense_side_A = Xfull && (U != nullptr || nnz_U > 0 || szU.on), dense_side_B = Xfull && (II != nullptr || nnz_I > 0 || szI.on);
     const bool had_dense_X = Xfull != nullptr;
     if (Xfull) {
         if (add_implicit_features || NA_as_zero_X)
@@ -1050,7 +1101,7 @@ int_t fit_collective_explicit_als(
         return fail(verbose, "cmfrec_hip: NA_as_zero_X is implemented for the model without nonneg / L1 and scale_bias_const.");
     // the matrices for predictions (round 5): for the model without side information -- B_plus_bias, BtB, TransBtBinvBt as ever, plus
     // BtXbias, the constant every new row's right-hand side receives (collective.c:8938-8986)
-    if (NA_as_zero_X && precompute_for_predictions && (U || II || nnz_U || nnz_I || add_implicit_features))
+    if (NA_as_zero_X && precompute_for_predictions && (U || II || nnz_U || nnz_I || szU.on || szI.on || add_implicit_features))
         return fail(verbose, "cmfrec_hip: NA_as_zero_X with precompute_for_predictions: the model without side information and implicit features.");
     // ... with implicit features (round 5): the model without side information and weights, closed form (optimizeA_collective's
     // general branch on a matrix all rows share, collective.c:8612 / :8783 -> :1534-1846)
@@ -1089,7 +1140,7 @@ int_t fit_collective_explicit_als(
     }
     // dense side information with NaN -> the sparse route on its centred present entries
     DenseNanSide nanU, nanI;
-    const bool hadU = (U != nullptr);
+    const bool hadU = (U != nullptr) || szU.on;
     bool nan_side = false;
     if (U && m_u > 0 && p > 0 && nanU.convert(U, m_u, p, U_colmeans)) {
         U = nullptr; U_row = nanU.row.data(); U_col = nanU.col.data(); U_sp = nanU.val.data(); nnz_U = nanU.val.size(); nan_side = true;
@@ -1160,8 +1211,8 @@ int_t fit_collective_explicit_als(
                    (scale_bias_const && scale_lam && (user_bias || item_bias))))
         return fail(verbose, "cmfrec_hip: observation weights together with NaN side information / scale_lam_sideinfo / "
                              "scale_bias_const are not implemented.");
-    if (U == nullptr && !spU) { m_u = 0; p = 0; }
-    if (II == nullptr && !spI) { n_i = 0; q = 0; }
+    if (U == nullptr && !spU && !szU.on) { m_u = 0; p = 0; }
+    if (II == nullptr && !spI && !szI.on) { n_i = 0; q = 0; }
     if (m <= 0 || n <= 0 || nnz == 0) return fail(verbose, "cmfrec_hip: invalid dimensions.");
     for (size_t e = 0; e < nnz; e++)
         if (ixA[e] < 0 || ixA[e] >= m || ixB[e] < 0 || ixB[e] >= n) return fail(verbose, "cmfrec_hip: X index out of range.");
@@ -1197,8 +1248,8 @@ int_t fit_collective_explicit_als(
             }
             return (real_t)wmean;
         };
-        if (user_bias) { *scaling_biasA = mean_count(ixA, m, U ? p : 0, m_u); lam6[0] *= *scaling_biasA; l16[0] *= *scaling_biasA; }
-        if (item_bias) { *scaling_biasB = mean_count(ixB, n, II ? q : 0, n_i); lam6[1] *= *scaling_biasB; l16[1] *= *scaling_biasB; }
+        if (user_bias) { *scaling_biasA = mean_count(ixA, m, (U || szU.on) ? p : 0, m_u); lam6[0] *= *scaling_biasA; l16[0] *= *scaling_biasA; }
+        if (item_bias) { *scaling_biasB = mean_count(ixB, n, (II || szI.on) ? q : 0, n_i); lam6[1] *= *scaling_biasB; l16[1] *= *scaling_biasB; }
     }
     const int k_totA = k_user + k + k_main, k_totB = k_item + k + k_main;
     const int_t m_max = std::max(m, m_u), n_max = std::max(n, n_i);      // rows of A / B (collective.c:7332-7335)
@@ -1285,7 +1336,7 @@ int_t fit_collective_explicit_als(
     tm.lap("side info centring");
     // ---- factor start values, collective.c:8241-8274 ----
     if (reset_values) {
-        const bool fill_B = (II != nullptr || spI || add_implicit_features);
+        const bool fill_B = (II != nullptr || spI || szI.on || add_implicit_features);
         cmfrng::random_parallel<real_t>(A, (size_t)m_max * k_totA, fill_B ? B : nullptr, fill_B ? (size_t)n_max * k_totB : 0, seed, true);
         if (nonneg) {                                                     // :8256-8263: non-negative start values
             for (size_t e = 0; e < (size_t)m_max * k_totA; e++) A[e] = std::fabs(A[e]);
@@ -1293,8 +1344,8 @@ int_t fit_collective_explicit_als(
         }
         if (use_cg) {
             if (!fill_B) memset(B, 0, (size_t)n_max * k_totB * sizeof(real_t));
-            if (U || spU) memset(C, 0, (size_t)p * (k_user + k) * sizeof(real_t));
-            if (II || spI) memset(D, 0, (size_t)q * (k_item + k) * sizeof(real_t));
+            if (U || spU || szU.on) memset(C, 0, (size_t)p * (k_user + k) * sizeof(real_t));
+            if (II || spI || szI.on) memset(D, 0, (size_t)q * (k_item + k) * sizeof(real_t));
         }
     }
 
@@ -1322,7 +1373,7 @@ int_t fit_collective_explicit_als(
     // sweeps alternate over all rows and all columns, common.c:4410-4909), then handed to every shard.
     // (a dense X keeps to one device: its half-steps follow the reference's per-half-step choice of solver, dense_chol_A / _B,
     // and its empty rows are zeroed afterwards -- neither is part of multi_loop)
-    const bool multi_ok = sharded_fit_wanted(devs) && !spU && !spI && m_u <= m && n_i <= n && !add_implicit_features && !NA_as_zero_X &&
+    const bool multi_ok = sharded_fit_wanted(devs) && !spU && !spI && !szU.on && !szI.on && m_u <= m && n_i <= n && !add_implicit_features && !NA_as_zero_X &&
                           !weight && dx.na_row.empty() && m >= (int_t)devs.size() && n >= (int_t)devs.size() && zero_rows_A.empty() &&
                           zero_rows_B.empty();
     if (devs.size() > 1 && !multi_ok && verbose)
@@ -1396,6 +1447,8 @@ int_t fit_collective_explicit_als(
     if (!rc && !zero_rows_A.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'A', zero_rows_A.data(), (int)zero_rows_A.size());
     if (!rc && !zero_rows_B.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'B', zero_rows_B.data(), (int)zero_rows_B.size());
     if (!rc) rc = cmfrec_hip_session_set_sideinfo(s, U ? Uc.data() : nullptr, II ? Ic.data() : nullptr);
+    if (!rc && szU.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'U', szU.row, szU.col, szU.val, szU.nnz, szU.colmeans());
+    if (!rc && szI.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'I', szI.row, szI.col, szI.val, szI.nnz, szI.colmeans());
     if (!rc && spU) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'U', U_row, U_col, U_sp, nnz_U);
     if (!rc && spI) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'I', I_row, I_col, I_sp, nnz_I);
     // dense side information with NaN: the per-attribute rules of the dense C / D update (DenseNanSide::rules)

@@ -12,6 +12,7 @@
 #include "lowrank_kernels.hpp"
 #include "eig_kernels.hpp"
 #include "gram_cg_wide_kernels.hpp"
+#include "side_zeros_kernels.hpp"
 #include <dlfcn.h>
 #include <functional>
 #include <memory>
@@ -673,6 +674,36 @@ static void issue_eig(DeviceInfo &d, EigCache &E, const real_t *Minit, int kc, h
     HIP_CHECK(hipEventRecord(E.ev, d.eig_stream()));
 }
 
+// Side information as the half-steps multiply by it: the dense matrix (from the operand's first row), or the sparse matrix whose
+// absent entries are zeros, centred by its column means (side_zeros_kernels.hpp).  No kernel reads U element by element: every
+// use is one of the two products below, so the solvers downstream see the same operands either way.
+struct SideOperand {
+    const real_t *dense = nullptr;
+    SideZeros *zeros = nullptr;
+    int first = 0;                              // the operand's first row within `zeros`
+    SideOperand from_row(int r, int p) const
+    {
+        SideOperand o = *this;
+        if (o.dense != nullptr) o.dense += (size_t)r * p;
+        o.first += r;
+        return o;
+    }
+};
+// out[count, kc] = alpha U[:count, :] M,  M [p, kc]
+static void side_times(const DeviceInfo &dev, const SideOperand &u, int count, int kc, int p, real_t alpha, const real_t *M, real_t *out,
+                       size_t ldo)
+{
+    if (u.zeros != nullptr) sz_times(dev, *u.zeros, u.first, count, kc, alpha, M, (size_t)kc, out, ldo);
+    else launch_gemm<false>(dev, count, kc, p, alpha, u.dense, (size_t)p, M, (size_t)kc, out, ldo);
+}
+// out[p, kc] = U[:rows, :]^T F[:rows, :kc]   (sparse-as-zeros: all its rows)
+static void side_transposed_times(const DeviceInfo &dev, const SideOperand &u, int rows, int kc, int p, const real_t *F, size_t ldF,
+                                  real_t *out, size_t ldo)
+{
+    if (u.zeros != nullptr) sz_transposed_times(dev, *u.zeros, kc, F, ldF, out, ldo);
+    else launch_gemm<true>(dev, p, kc, rows, (real_t)1, u.dense, (size_t)p, F, ldF, out, ldo);
+}
+
 // Collective Cholesky half-step (mode CHOL_COLLECTIVE, dense side information on every row of the block) with the rows of
 // few entries solved by the low-rank update of a diagonalised shared matrix instead of a k_t^3 / 3 factorisation per row
 // (config 5's users: 20 entries against k_t = 257 unknowns).  c: the call as launch_chol would take it (right-hand sides
@@ -682,7 +713,7 @@ static void issue_eig(DeviceInfo &d, EigCache &E, const real_t *Minit, int kc, h
 // mine: this side's cache (NULL: the scratch's own, never fresh); next / kc_next: the other side's cache with its matrix in
 // next->M, decomposed behind this one for the half-step that follows (NULL: nothing to prefetch).
 static int launch_collective_lowrank(const DeviceInfo &dev, LowRankScratch &S, CholCall c, const SparseShard &X, const real_t *Cm,
-                                     const real_t *Um, int p_self, real_t w, int k, int rows_b, EigCache *mine = nullptr,
+                                     const SideOperand &Um, int p_self, real_t w, int k, int rows_b, EigCache *mine = nullptr,
                                      EigCache *next = nullptr, int kc_next = 0)
 {
     const int lr_sw = switches().lowrank;       // CMFREC_HIP_LOWRANK: 0 / 1 force the path off / on
@@ -743,7 +774,7 @@ static int launch_collective_lowrank(const DeviceInfo &dev, LowRankScratch &S, C
     if (kt > kc)
         hipLaunchKernelGGL(copy_cols_kernel<real_t>, grid1d((size_t)rows_b * (kt - kc)), dim3(256), 0, st, S.Bt.ptr, ldbt, kc, c.B, c.ldb, k,
                            kt - kc, (size_t)rows_b);
-    launch_gemm<false>(dev, X.nrows, kc, p_self, w, Um, (size_t)p_self, S.Ct.ptr, (size_t)kc, S.R.ptr, (size_t)kc);
+    side_times(dev, Um, X.nrows, kc, p_self, w, S.Ct.ptr, S.R.ptr, (size_t)kc);
     LrParams<real_t> L;
     L.A = c.A; L.lda = c.lda; L.pre = S.R.ptr; L.ldpre = (size_t)kc;
     L.Tc = S.T.ptr; L.ldt = (size_t)kc; L.pos0 = n_full;
@@ -886,6 +917,16 @@ struct cmfrec_hip_session {
     // sparse side information (missing = absent): CSR by user / item for the factor updates, CSC by attribute for C / D
     SparseShard Usr, Usc, Isr, Isc;
     bool sparseU = false, sparseI = false;
+    // sparse side information whose ABSENT ENTRIES ARE ZEROS (cmfrec_hip_session_set_sideinfo_sparse_zeros): the same two shards and
+    // the column means, standing in for the dense U / II in every product (SideOperand)
+    SideZeros zerosU, zerosI;
+    SideOperand side_operand(bool isU)
+    {
+        SideOperand o;
+        SideZeros &z = isU ? zerosU : zerosI;
+        if (z.on()) o.zeros = &z; else o.dense = isU ? U.ptr : II.ptr;
+        return o;
+    }
     // non-negativity constraints (solve_nonneg instead of the Cholesky solve; they switch the CG off for that matrix)
     bool nonneg = false, nonneg_C = false, nonneg_D = false;
     int max_cd_steps = 100;
@@ -1359,8 +1400,8 @@ int cmfrec_hip_session_set_sideinfo(cmfrec_hip_session *s, const real_t *U, cons
     return guarded([&]() {
         HIP_CHECK(hipSetDevice(s->dev.device));
         const cmfrec_hip_model &m = s->mdl;
-        if (U && m.p > 0) s->U.upload(U, (size_t)m.m_u * m.p, s->dev.stream);
-        if (II && m.q > 0) s->II.upload(II, (size_t)m.n_i * m.q, s->dev.stream);
+        if (U && m.p > 0) { s->U.upload(U, (size_t)m.m_u * m.p, s->dev.stream); s->zerosU.clear(); }
+        if (II && m.q > 0) { s->II.upload(II, (size_t)m.n_i * m.q, s->dev.stream); s->zerosI.clear(); }
         HIP_CHECK(hipStreamSynchronize(s->dev.stream));
         return 0;
     });
@@ -1376,6 +1417,7 @@ int cmfrec_hip_session_set_sideinfo_local(cmfrec_hip_session *s, const real_t *U
         if (U_local && m.p > 0 && ru > 0) s->U.upload(U_local, (size_t)ru * m.p, s->dev.stream);
         if (I_local && m.q > 0 && ri > 0) s->II.upload(I_local, (size_t)ri * m.q, s->dev.stream);
         s->side_local = true;
+        s->zerosU.clear(); s->zerosI.clear();          // (a row block runs on the dense matrix alone)
         HIP_CHECK(hipStreamSynchronize(s->dev.stream));
         return 0;
     });
@@ -1393,7 +1435,7 @@ int cmfrec_hip_session_sideinfo_partial(cmfrec_hip_session *s, int which)
         const DeviceInfo &dev = s->dev;
         const bool isC = (which == 'C');
         const int p = isC ? m.p : m.q;
-        if ((which != 'C' && which != 'D') || p <= 0 || (isC ? s->sparseU : s->sparseI)) {
+        if ((which != 'C' && which != 'D') || p <= 0 || (isC ? s->sparseU : s->sparseI) || (isC ? s->zerosU : s->zerosI).on()) {
             g_last_error = "cmfrec_hip_session_sideinfo_partial: dense side information on that side is required";
             return 2;
         }
@@ -1422,7 +1464,7 @@ int cmfrec_hip_session_sideinfo_finish(cmfrec_hip_session *s, int which)
         const DeviceInfo &dev = s->dev;
         const bool isC = (which == 'C');
         const int p = isC ? m.p : m.q;
-        if ((which != 'C' && which != 'D') || p <= 0 || (isC ? s->sparseU : s->sparseI)) {
+        if ((which != 'C' && which != 'D') || p <= 0 || (isC ? s->sparseU : s->sparseI) || (isC ? s->zerosU : s->zerosI).on()) {
             g_last_error = "cmfrec_hip_session_sideinfo_finish: dense side information on that side is required";
             return 2;
         }
@@ -1683,6 +1725,108 @@ int cmfrec_hip_session_set_sideinfo_sparse(cmfrec_hip_session *s, int which, con
         shard_from_coo(isU ? s->Usc : s->Isc, cols, rows, dc.ptr, dr.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, s->dev.stream);
         HIP_CHECK(hipStreamSynchronize(s->dev.stream));
         (isU ? s->sparseU : s->sparseI) = true;
+        (isU ? s->zerosU : s->zerosI).clear();          // (the shards just rebuilt were that form's)
+        return 0;
+    });
+}
+
+// Sparse side information whose ABSENT ENTRIES ARE ZEROS (NA_as_zero_U / _I) on every row of the factor matrix: the session keeps
+// the triplets in both orientations and the column means, and every product with the dense centred matrix U - 1 colmeans^T --
+// right-hand sides, block CG, low-rank rows, the C / D update -- is taken on them (side_times / side_transposed_times,
+// side_zeros_kernels.hpp).  The solvers downstream see the same operands as with cmfrec_hip_session_set_sideinfo on the
+// zero-filled centred matrix.  Whole-matrix sessions with m_u = m (n_i = n); row-block shards keep to the dense matrix.
+int cmfrec_hip_session_set_sideinfo_sparse_zeros(cmfrec_hip_session *s, int which, const int_t *row, const int_t *col,
+                                                 const real_t *val, size_t nnz, const real_t *colmeans)
+{
+    return guarded([&]() {
+        HIP_CHECK(hipSetDevice(s->dev.device));
+        const cmfrec_hip_model &m = s->mdl;
+        const bool isU = (which == 'U');
+        const int rows = isU ? m.m_u : m.n_i, cols = isU ? m.p : m.q;
+        if ((which != 'U' && which != 'I') || rows <= 0 || cols <= 0 || nnz == 0 || !row || !col || !val) {
+            g_last_error = "cmfrec_hip_session_set_sideinfo_sparse_zeros: needs 'U' / 'I', the model's m_u, p / n_i, q and entries";
+            return 2;
+        }
+        if (m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n || s->side_local || !s->XrParts.empty()) {
+            g_last_error = "cmfrec_hip_session_set_sideinfo_sparse_zeros: row-block shards (local side information, parts of A, partial "
+                           "C / D sums) need the dense matrix: cmfrec_hip_session_set_sideinfo_local";
+            return 2;
+        }
+        if (rows != (isU ? m.m : m.n)) {
+            g_last_error = "cmfrec_hip_session_set_sideinfo_sparse_zeros: the side information must cover every row of the factor matrix "
+                           "(m_u = m / n_i = n): rows without entries are rows of zeros";
+            return 2;
+        }
+        if (cols > 0 && (isU ? m.k_user : m.k_item) + m.k > SZ_MAX_WIDTH) {
+            g_last_error = "cmfrec_hip_session_set_sideinfo_sparse_zeros: at most 320 factors shared with the side information";
+            return 2;
+        }
+        for (size_t e = 0; e < nnz; e++)
+            if (row[e] < 0 || row[e] >= rows || col[e] < 0 || col[e] >= cols) {
+                g_last_error = "cmfrec_hip_session_set_sideinfo_sparse_zeros: index out of range";
+                return 2;
+            }
+        DevBuf<int> dr, dc; DevBuf<real_t> dv;
+        dr.upload(row, nnz, s->dev.stream); dc.upload(col, nnz, s->dev.stream); dv.upload(val, nnz, s->dev.stream);
+        SparseShard &by_row = isU ? s->Usr : s->Isr, &by_col = isU ? s->Usc : s->Isc;
+        shard_from_coo(by_row, rows, cols, dr.ptr, dc.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, s->dev.stream);
+        shard_from_coo(by_col, cols, rows, dc.ptr, dr.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, s->dev.stream);
+        (isU ? s->zerosU : s->zerosI).build(&by_row, &by_col, colmeans, s->dev.stream);
+        (isU ? s->sparseU : s->sparseI) = false;
+        (isU ? s->U : s->II).release();
+        (isU ? s->eigA : s->eigB).fresh = false;
+        HIP_CHECK(hipStreamSynchronize(s->dev.stream));
+        return 0;
+    });
+}
+
+// The two products of that form alone, host buffers in and out (what the session's helpers launch, for callers who want the
+// products and for the tests): U~ = U_sparse - 1 colmeans^T over `rows` rows and p attributes,
+//     UM  [count, kc] = alpha (U~ M)[first : first + count, :]      when M [p, kc] is given
+//     UtF [p, kc]     = U~^T F[:, :kc]                               when F [rows, ldF] is given
+int cmfrec_hip_side_zeros_products(int_t rows, int_t p, int_t kc, const int_t *row, const int_t *col, const real_t *val, size_t nnz,
+                                   const real_t *colmeans, const real_t *M, real_t alpha, int_t first, int_t count, real_t *UM,
+                                   const real_t *F, size_t ldF, real_t *UtF)
+{
+    return guarded([&]() {
+        if (rows <= 0 || p <= 0 || kc <= 0 || kc > SZ_MAX_WIDTH || nnz == 0 || !row || !col || !val || (M != nullptr && UM == nullptr) ||
+            (F != nullptr && (UtF == nullptr || ldF < (size_t)kc)) || (M != nullptr && (first < 0 || count < 0 || first > rows - count))) {
+            g_last_error = "cmfrec_hip_side_zeros_products: invalid sizes (kc <= 320, rows first .. first + count inside the matrix, ldF >= kc)";
+            return 2;
+        }
+        for (size_t e = 0; e < nnz; e++)
+            if (row[e] < 0 || row[e] >= rows || col[e] < 0 || col[e] >= p) {
+                g_last_error = "cmfrec_hip_side_zeros_products: index out of range";
+                return 2;
+            }
+        DeviceInfo dev;
+        init_device(dev, -1);
+        hipStream_t st = dev.stream;
+        DevBuf<int> dr, dc; DevBuf<real_t> dv;
+        dr.upload(row, nnz, st); dc.upload(col, nnz, st); dv.upload(val, nnz, st);
+        SparseShard by_row, by_col;
+        SideZeros Z;
+        shard_from_coo(by_row, rows, p, dr.ptr, dc.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, st);
+        shard_from_coo(by_col, p, rows, dc.ptr, dr.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, st);
+        Z.build(&by_row, &by_col, colmeans, st);
+        SideOperand u;
+        u.zeros = &Z;
+        if (M != nullptr && count > 0) {
+            DevBuf<real_t> dM, dO;
+            dM.upload(M, (size_t)p * kc, st);
+            dO.alloc((size_t)count * kc);
+            side_times(dev, u.from_row(first, p), count, kc, p, alpha, dM.ptr, dO.ptr, (size_t)kc);
+            dO.download(UM, (size_t)count * kc, st);
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+        if (F != nullptr) {
+            DevBuf<real_t> dF, dO;
+            dF.upload(F, (size_t)rows * ldF, st);
+            dO.alloc((size_t)p * kc);
+            side_transposed_times(dev, u, rows, kc, p, dF.ptr, ldF, dO.ptr, (size_t)kc);
+            dO.download(UtF, (size_t)p * kc, st);
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
         return 0;
     });
 }
@@ -1702,8 +1846,8 @@ struct HalfStepSide {
     const int rows_x_self, rows_x_opp;          // ... that X has (m_x / n_x where set): update_factor's Gramian and block systems
     const int rows_u, begin;                    // rows with side information; first row of the local block
     const SparseShard &X, &Us;                  // X by rows of self; sparse side information by rows of self
-    const real_t *const Cm, *const Um;          // C / D; U / I
-    const real_t *const Um_blk;                 // ... from the local block's first row
+    const real_t *const Cm;                     // C / D
+    const SideOperand Um, Um_blk;               // U / I (dense, or sparse with zeros); ... from the local block's first row
     const real_t w;                             // w_user / w_item
     const bool sparse_side;
     const bool self_bias, opp_bias;
@@ -1733,8 +1877,8 @@ struct HalfStepSide {
           rows_x_self(isA ? (s->mdl.m_x > 0 ? s->mdl.m_x : s->mdl.m) : (s->mdl.n_x > 0 ? s->mdl.n_x : s->mdl.n)),
           rows_x_opp(isA ? (s->mdl.n_x > 0 ? s->mdl.n_x : s->mdl.n) : (s->mdl.m_x > 0 ? s->mdl.m_x : s->mdl.m)),
           rows_u(isA ? s->mdl.m_u : s->mdl.n_i), begin(isA ? s->mdl.row_begin : s->mdl.col_begin), X(isA ? s->Xr : s->Xc),
-          Us(isA ? s->Usr : s->Isr), Cm(isA ? s->C.ptr : s->D.ptr), Um(isA ? s->U.ptr : s->II.ptr),
-          Um_blk(Um != nullptr ? Um + (size_t)(s->side_local ? 0 : begin) * p_self : nullptr), w(isA ? s->mdl.w_user : s->mdl.w_item),
+          Us(isA ? s->Usr : s->Isr), Cm(isA ? s->C.ptr : s->D.ptr), Um(s->side_operand(isA)),
+          Um_blk(Um.from_row(s->side_local ? 0 : begin, p_self)), w(isA ? s->mdl.w_user : s->mdl.w_item),
           sparse_side(isA ? s->sparseU : s->sparseI), self_bias(isA ? s->mdl.user_bias : s->mdl.item_bias),
           opp_bias(isA ? s->mdl.item_bias : s->mdl.user_bias), bias(opp_bias ? (isA ? s->biasB.ptr : s->biasA.ptr) : nullptr),
           lam_self(s->lam6[isA ? 2 : 3]), lam_last_self((!s->mdl.implicit && self_bias) ? s->lam6[isA ? 0 : 1] : lam_self),
@@ -1763,8 +1907,7 @@ static int solve_sideinfo_only_rows(cmfrec_hip_session *s, const HalfStepSide &v
     if (chol) HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)count * v.ld_self * sizeof(real_t), dev.stream));
     launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->betbe.ptr, (real_t)1,
                 (v.lam_self / v.w) * (real_t)(scale_lam ? p_self : 1));                                           // common.c:2824-2832
-    launch_gemm<false>(dev, count, kc, p_self, (real_t)1, v.Um_blk + (size_t)first * p_self, (size_t)p_self, v.Cm,
-                       (size_t)kc, rows, v.ld_self);                                               // common.c:2847-2855
+    side_times(dev, v.Um_blk.from_row(first, p_self), count, kc, p_self, (real_t)1, v.Cm, rows, v.ld_self);   // common.c:2847-2855
     CholCall c{rows, v.ld_self, nullptr, 0, kc, 0, nullptr, s->betbe.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
     return launch_chol(dev, c, nullptr, count);                                                    // common.c:2872-2875
 }
@@ -2035,7 +2178,7 @@ static int update_factor_naz(cmfrec_hip_session *s, const HalfStepSide &v, bool 
     if (int rc = p_self > 0 ? naz_gather_rhs(s, v) : naz_gather_rhs_into(s, v, rhs, ld_r)) return rc;
     if (p_self > 0) {
         // ... w U C on the first k_side + k columns, the gathered part behind k_side
-        launch_gemm<false>(dev, rows_self, kc, p_self, v.w, v.Um, (size_t)p_self, v.Cm, (size_t)kc, rhs, ld_r);
+        side_times(dev, v.Um, rows_self, kc, p_self, v.w, v.Cm, rhs, ld_r);
         hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, rhs, ld_r, v.k_side_self, s->naz_rhs.ptr, ks,
                            (real_t)1, (size_t)rows_self);
     }
@@ -2097,7 +2240,7 @@ static int update_factor_naz_weighted_side(cmfrec_hip_session *s, const HalfStep
         // when the caller hands it the buffers of precompute_for_predictions (filled_BtB, :5702-5716), which this model does not offer.
         if (dense_side) {
             launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, (real_t)1, (real_t)0);                 // C^T C, unweighted
-            launch_gemm<false>(dev, rows_self, kc, p_self, (real_t)1, v.Um, (size_t)p_self, v.Cm, (size_t)kc, v.uc, (size_t)kc);   // U C
+            side_times(dev, v.Um, rows_self, kc, p_self, (real_t)1, v.Cm, v.uc, (size_t)kc);   // U C
         }
         naz_entry_transform(s, v);
         if (int rc = naz_gather_rhs(s, v, s->naz_xt.ptr)) return rc;
@@ -2119,7 +2262,7 @@ static int update_factor_naz_weighted_side(cmfrec_hip_session *s, const HalfStep
     if (dense_side) launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, v.w, (real_t)0);
     // right-hand sides start from [w U C ; cst]  (sparse side information: [0 ; cst], the attributes are gathered by the row kernel)
     HIP_CHECK(hipMemset2DAsync(v.self, v.ld_self * sizeof(real_t), 0, (size_t)kt * sizeof(real_t), (size_t)rows_self, st));
-    if (dense_side) launch_gemm<false>(dev, rows_self, kc, p_self, v.w, v.Um, (size_t)p_self, v.Cm, (size_t)kc, v.self, v.ld_self);
+    if (dense_side) side_times(dev, v.Um, rows_self, kc, p_self, v.w, v.Cm, v.self, v.ld_self);
     if (v.Fi != nullptr) add_implicit_rhs(s, v, v.self, v.ld_self);
     naz_constant(s, v, v.self + v.k_side_self, v.ld_self);
     naz_entry_transform(s, v);
@@ -2291,7 +2434,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
         // block CG on the collective system, dense full side information: collective_block_cg (explicit,
         // collective.c:2134-2903) / collective_block_cg_implicit (:2905-3303), prefer_CtC branch
         launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, (real_t)1, (real_t)0);   // C^T C, unweighted
-        launch_gemm<false>(dev, local_u, kc, p_self, (real_t)1, v.Um_blk, (size_t)p_self, v.Cm, (size_t)kc, v.uc, (size_t)kc);   // U C
+        side_times(dev, v.Um_blk, local_u, kc, p_self, (real_t)1, v.Cm, v.uc, (size_t)kc);   // U C
         CgCall c = block_cg_call(sbc);
         const int local_u_main = m.implicit ? local_u : std::min(local_u, local_x);
         c.CtC = s->ctc.ptr; c.UC = v.uc; c.rows_with_u = local_u_main;
@@ -2308,7 +2451,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
                            s->betbe.ptr);                                                           // :6121-6135
         launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);          // :6138-6160
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :6018-6019
-        launch_gemm<false>(dev, local_u, kc, p_self, w, v.Um_blk, (size_t)p_self, v.Cm, (size_t)kc, self_blk, ld_self);   // :6163-6168
+        side_times(dev, v.Um_blk, local_u, kc, p_self, w, v.Cm, self_blk, ld_self);   // :6163-6168
         CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, s->ctc.ptr, kc, local_u,
                    p_self, lam_self, lam_last_self, false, false, false, CHOL_COLLECTIVE_IMPLICIT, s->betbe.ptr};
         return launch_chol(dev, c, &X);
@@ -2376,7 +2519,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
         // optimizeA_collective general branch, Cholesky (collective.c:5566-5968)
         launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);          // :5658-5668
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
-        launch_gemm<false>(dev, local_u, kc, p_self, w, v.Um_blk, (size_t)p_self, v.Cm, (size_t)kc, self_blk, ld_self);   // :5768-5773
+        side_times(dev, v.Um_blk, local_u, kc, p_self, w, v.Cm, self_blk, ld_self);   // :5768-5773
         const int local_u_main = std::min(local_u, local_x);              // rows beyond X: solve_sideinfo_only_rows
         CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, bias_sub, s->ctc.ptr, kc, local_u_main,
                    p_self, lam_self, lam_last_self, scale_lam, (bool)m.scale_lam_sideinfo, sbc, CHOL_COLLECTIVE};
@@ -2468,7 +2611,7 @@ static int update_sideinfo(cmfrec_hip_session *s, bool isC, bool chol, int cg_st
     const int rows_u = isC ? m.m_u : m.n_i;
     const int kc = (isC ? m.k_user : m.k_item) + m.k;
     real_t *Cm = isC ? s->C.ptr : s->D.ptr;
-    const real_t *Um = isC ? s->U.ptr : s->II.ptr;
+    const SideOperand Um = s->side_operand(isC);
     const real_t *F = isC ? s->A.ptr : s->B.ptr;
     const size_t ldF = isC ? s->ldA : s->ldB;
     const real_t w = isC ? m.w_user : m.w_item;
@@ -2488,7 +2631,7 @@ static int update_sideinfo(cmfrec_hip_session *s, bool isC, bool chol, int cg_st
     }
     real_t diag = scale_lam ? lam * (real_t)rows_u : lam;                                          // common.c:2832
     launch_gram(dev, s->gws, F, ldF, rows_u, kc, s->gram.ptr, (real_t)1, diag);                    // common.c:2824
-    launch_gemm<true>(dev, p, kc, rows_u, (real_t)1, Um, (size_t)p, F, ldF, Cm, (size_t)kc);       // common.c:2852-2855
+    side_transposed_times(dev, Um, rows_u, kc, p, F, ldF, Cm, (size_t)kc);                         // common.c:2852-2855
     CholCall c{Cm, (size_t)kc, nullptr, 0, kc, 0, nullptr, s->gram.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
     return launch_chol(dev, c, nullptr, p);                                                        // common.c:2872-2875
 }
@@ -3303,7 +3446,7 @@ int cmfrec_hip_optimizeA_collective(real_t *A, size_t lda, const real_t *B, size
         CholCall c{dA.ptr, lda, dB.ptr + k_item, ldb, kt, k_user, bias_sub ? dbias.ptr : nullptr, dG.ptr, kc, m_u, p,
                    lam, lam_last, (bool)(scale_lam || scale_lam_sideinfo), scale_lam_sideinfo, false, CHOL_COLLECTIVE};
         LowRankScratch lrs;
-        int rc = (m_u >= m) ? launch_collective_lowrank(dev, lrs, c, X, dC.ptr, dU.ptr, p, w_user, k, n) : -1;
+        int rc = (m_u >= m) ? launch_collective_lowrank(dev, lrs, c, X, dC.ptr, SideOperand{dU.ptr}, p, w_user, k, n) : -1;
         if (rc < 0) rc = launch_chol(dev, c, &X);
         dA.download(A, (size_t)m * lda, dev.stream);
         HIP_CHECK(hipStreamSynchronize(dev.stream));

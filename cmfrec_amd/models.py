@@ -155,7 +155,8 @@ class CMF_implicit(_Base):
                  precondition_cg=False, finalize_chol=False, random_state=1, verbose=False,
                  produce_dicts=False, handle_interrupt=True, nthreads=-1, n_jobs=None):
         # sparse side information whose absent entries are zeros (not missing): cmfrec/__init__.py:4688-4690.  The C library
-        # runs it as the zero-filled dense matrix it denotes (fit.hip, ZeroFilledSide)
+        # runs it as the zero-filled dense matrix it denotes (fit.hip, ZeroFilledSide), or on the triplets where that matrix would
+        # be too large (SparseZerosSide)
         self.NA_as_zero_user = bool(NA_as_zero_user); self.NA_as_zero_item = bool(NA_as_zero_item)
         self.k = int(k); self.alpha = float(alpha); self.use_cg = bool(use_cg)
         self.lambda_, self._lam6 = _penalty(lambda_, "lambda_")
@@ -303,7 +304,8 @@ class CMF(_Base):
         if method != "als":
             raise NotImplementedError("only method='als' is implemented in cmfrec_amd")
         # sparse side information whose absent entries are zeros (not missing): cmfrec/__init__.py:2903-2905.  The C library
-        # runs it as the zero-filled dense matrix it denotes (fit.hip, ZeroFilledSide)
+        # runs it as the zero-filled dense matrix it denotes (fit.hip, ZeroFilledSide), or on the triplets where that matrix would
+        # be too large (SparseZerosSide)
         self.NA_as_zero_user = bool(NA_as_zero_user); self.NA_as_zero_item = bool(NA_as_zero_item)
         # NA_as_zero (absent entries of a sparse X are zeros): without side information or with dense complete / sparse side
         # information on exactly the rows / columns of X, closed form or CG, with add_implicit_features too; the matrices for

@@ -122,6 +122,50 @@ def optimizeA_collective_sparse(A, B, Cm, csr, U_csr, lam, w_user=1.0, lam_last=
     _lib.check(rc, lib, "optimizeA_collective_sparse")
 
 
+def side_zeros_products(rows, p, row, col, val, colmeans=None, M=None, alpha=1.0, first=0, count=None, F=None, kc=None):
+    """The two products of sparse side information whose absent entries are zeros, U~ = U_sparse - 1 colmeans^T ([rows, p], COO
+    triplets, duplicates add up), as the session takes them: returns (UM, UtF) with
+    UM [count, kc] = alpha (U~ M)[first : first + count] for M [p, kc], and UtF [p, kc] = U~^T F[:, :kc] for F [rows, ldF]
+    (each None when its input is).  ``kc`` defaults to the columns of M, else of F.  Bitwise reproducible."""
+    given = M if M is not None else F
+    if given is None:
+        raise ValueError("pass M, F or both")
+    dtype = np.asarray(given).dtype
+    if dtype.type not in (np.float64, np.float32):
+        raise TypeError("M / F must be float64 or float32")
+    lib, R = _lib.load(dtype), _lib.real(dtype)
+    r = np.ascontiguousarray(row, np.int32); c = np.ascontiguousarray(col, np.int32); v = np.ascontiguousarray(val, dtype)
+    if not (len(r) == len(c) == len(v)):
+        raise ValueError("row, col and val must have one entry per triplet")
+    mu = None if colmeans is None else np.ascontiguousarray(colmeans, dtype)
+    if mu is not None and len(mu) != p:
+        raise ValueError("colmeans must have one entry per attribute")
+    UM = UtF = None
+    ldF = 0
+    if M is not None:
+        M = np.ascontiguousarray(M, dtype)
+        if M.ndim != 2 or M.shape[0] != p:
+            raise ValueError("M must be [p, kc]")
+        kc = M.shape[1] if kc is None else kc
+        if kc != M.shape[1]:
+            raise ValueError("kc must be the columns of M")
+        count = rows - first if count is None else count
+        UM = np.empty((count, kc), dtype)
+    if F is not None:
+        F = np.ascontiguousarray(F, dtype)
+        if F.ndim != 2 or F.shape[0] != rows:
+            raise ValueError("F must be [rows, ldF]")
+        ldF = F.shape[1]
+        kc = ldF if kc is None else kc
+        UtF = np.empty((p, kc), dtype)
+    rc = lib.cmfrec_hip_side_zeros_products(C.c_int(rows), C.c_int(p), C.c_int(kc), _lib.ptr(r), _lib.ptr(c), _lib.ptr(v),
+                                            C.c_size_t(len(v)), _lib.ptr(mu), _lib.ptr(M), R(alpha), C.c_int(first),
+                                            C.c_int(0 if count is None else count), _lib.ptr(UM), _lib.ptr(F), C.c_size_t(ldF),
+                                            _lib.ptr(UtF))
+    _lib.check(rc, lib, "side_zeros_products")
+    return UM, UtF
+
+
 def _sorted_exclude(exclude, nu):
     """(indptr uint64, indices int32) of the per-user exclusion lists, each list ascending (the kernels binary-search it);
     (None, None) without lists."""

@@ -196,6 +196,21 @@ class AlsSession:
         _lib.check(self.lib.cmfrec_hip_session_set_sideinfo(self.handle, *[_lib.ptr(a) for a in keep]), self.lib,
                    "set_sideinfo")
 
+    def set_sideinfo_sparse_zeros(self, which, row, col, val, colmeans=None):
+        """Sparse side information whose absent entries are zeros (``which`` = 'U' / 'I'; NA_as_zero_U / _I): COO triplets over
+        all m / n rows, duplicates add up; ``colmeans`` = the column means over all rows, subtracted from every cell (None:
+        none).  Same results as ``set_sideinfo`` on the zero-filled centred matrix, work and memory proportional to the triplets.
+        Whole-matrix sessions created with m_u = m (n_i = n)."""
+        keep = [self._c(row, np.int32), self._c(col, np.int32), self._c(val), self._c(colmeans)]
+        if not (len(keep[0]) == len(keep[1]) == len(keep[2])):
+            raise ValueError("row, col and val must have one entry per triplet")
+        ncol = self.model.p if which == "U" else self.model.q
+        if keep[3] is not None and len(keep[3]) != ncol:
+            raise ValueError("colmeans must have one entry per attribute (%d)" % ncol)
+        _lib.check(self.lib.cmfrec_hip_session_set_sideinfo_sparse_zeros(
+            self.handle, C.c_int(ord(which)), _lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]), C.c_size_t(len(keep[2])),
+            _lib.ptr(keep[3])), self.lib, "set_sideinfo_sparse_zeros")
+
     def set_sideinfo_local(self, U=None, II=None):
         """Row-block shards: only the block's rows of the (centred) side information -- U rows [row_begin, min(row_end, m_u)),
         I rows [col_begin, min(col_end, n_i)).  Arrays on the host, or contiguous torch tensors of the session's dtype that

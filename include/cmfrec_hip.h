@@ -49,7 +49,9 @@ extern "C" {
  * within X's; collective.c:1849-2131 / :2905-3303 with u_vec_sp); nonneg / nonneg_C / nonneg_D with max_cd_steps
  * (solve_nonneg, common.c:2131-2179; k_t <= 140 / 199), l1_lam (solve_elasticnet, :2228-2294) and the per-matrix
  * lam_unique / l1_lam_unique (entries 2..5: A, B, C, D; :9793-9809, :9855-10016); dense U / II with NaN (= missing) under the
- * plain Cholesky solver; precompute_for_predictions.  Anything else returns 2. */
+ * plain Cholesky solver; precompute_for_predictions; NA_as_zero_U / NA_as_zero_I (sparse U / I whose absent entries are zeros,
+ * on the rows / columns of X): the dense route on the zero-filled matrix up to CMFREC_HIP_ZEROFILL_MAX_GB (default 8 GB), on the
+ * triplets themselves beyond it (single device; cmfrec_hip_session_set_sideinfo_sparse_zeros).  Anything else returns 2. */
 int_t fit_collective_implicit_als(
     real_t *A, real_t *B,
     real_t *C, real_t *D,
@@ -94,7 +96,9 @@ int_t fit_collective_implicit_als(
  * outputs); observation weights (weight, one per entry of X; src/common.c:1098-1291, :679-723); NA_as_zero_X on sparse X for
  * the model without side information (optimizeA Case 3, src/common.c:3118-3205; src/collective.c:8573-8600); dense X
  * (Xfull [m, n], NaN = missing, weight [m, n]) for the model without side information, with the reference's choice of solver
- * per half-step (optimizeA Cases 1-2, src/common.c:2787-3116).  Not built: NA_as_zero_U / NA_as_zero_I.  Anything else
+ * per half-step (optimizeA Cases 1-2, src/common.c:2787-3116); NA_as_zero_U / NA_as_zero_I (sparse U / I whose absent entries
+ * are zeros, on the rows / columns of X): the dense route on the zero-filled matrix up to CMFREC_HIP_ZEROFILL_MAX_GB (default
+ * 8 GB), on the triplets themselves beyond it (single device; cmfrec_hip_session_set_sideinfo_sparse_zeros).  Anything else
  * returns 2. */
 int_t fit_collective_explicit_als(
     real_t *biasA, real_t *biasB,
@@ -469,6 +473,23 @@ int cmfrec_hip_session_set_l1(cmfrec_hip_session *s, real_t l1_lam, int max_cd_s
  * source of the row kernel; CG / PCG: a second gathered term of the block CG (generic kernel).  m_u <= rows of X. */
 int cmfrec_hip_session_set_sideinfo_sparse(cmfrec_hip_session *s, int which, const int_t *row, const int_t *col,
                                            const real_t *val, size_t nnz);
+/* SPARSE side information whose ABSENT ENTRIES ARE ZEROS (NA_as_zero_U / NA_as_zero_I), on every row of the factor matrix
+ * (the model's m_u = m / n_i = n; rows without triplets are rows of zeros).  colmeans [p] / [q]: the column means over ALL
+ * rows, subtracted from every cell, absent ones included (NULL: none).  The session then behaves as after
+ * cmfrec_hip_session_set_sideinfo on the zero-filled, centred dense matrix -- every solver and option of dense side
+ * information -- but keeps the triplets alone: the products with that matrix run as sparse products plus a rank-one
+ * correction (side_zeros_kernels.hpp), work and memory proportional to nnz.  Triplets that repeat a position add up.
+ * Returns 2 on a row-block shard (local side information, parts of A, cmfrec_hip_session_sideinfo_partial): those keep to
+ * the dense matrix. */
+int cmfrec_hip_session_set_sideinfo_sparse_zeros(cmfrec_hip_session *s, int which /* 'U' | 'I' */, const int_t *row,
+                                                 const int_t *col, const real_t *val, size_t nnz, const real_t *colmeans);
+/* The two products of that form alone, host buffers: U~ = U_sparse - 1 colmeans^T of `rows` rows and p attributes,
+ *   UM  [count, kc] = alpha (U~ M)[first : first + count, :]   when M [p, kc] is given (else NULL),
+ *   UtF [p, kc]     = U~^T F[:, :kc]                            when F [rows, ldF] is given (else NULL).
+ * kc <= 320.  Bitwise reproducible: no floating-point atomics, every sum in a fixed order. */
+int cmfrec_hip_side_zeros_products(int_t rows, int_t p, int_t kc, const int_t *row, const int_t *col, const real_t *val,
+                                   size_t nnz, const real_t *colmeans, const real_t *M, real_t alpha, int_t first,
+                                   int_t count, real_t *UM, const real_t *F, size_t ldF, real_t *UtF);
 
 /* One update of the local block, asynchronous on the session stream. which: 'A','B','C','D'.
  * use_cholesky != 0 forces the Cholesky solver for this call (finalize_chol). */
