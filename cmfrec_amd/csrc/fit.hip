@@ -1584,10 +1584,12 @@ int_t fit_collective_explicit_als(
 
 // ---- factors of new rows (the step after the path) -----------------------------------------------------
 // Same positional signatures as the reference (src/cmfrec.h:2004-2071).  Supported: sparse X (COO or CSR, missing = not
-// observed), dense U without NaN, L1 penalties, non-negativity; no binary side information / weights / implicit features /
-// NA_as_zero.  Anything else returns 2 with a message on stderr.  The precomputed matrices of the reference's
+// observed) or dense X (Xfull, NaN = not observed; compacted on the device), observation weights in either form, implicit
+// features (Bi), dense U without NaN or sparse U, L1 penalties, non-negativity; no binary side information / NA_as_zero.
+// Anything else returns 2 with a message on stderr.  The precomputed matrices of the reference's
 // signature are optional accelerators there; here the small Gramians are rebuilt on the device from B and C (BtB of the
-// implicit model and TransCtCinvCt are used when given, because they decide the result: collective.c:11270-11280, :3380).
+// implicit model, TransCtCinvCt, TransBtBinvBt and BiTBi are used when given, because they decide the result:
+// collective.c:11270-11280, :3380, common.c:736-758, collective.c:1704-1707).
 static int unsupported_multiple(const char *what)
 {
     fprintf(stderr, "cmfrec_hip: factors_collective_*_multiple: %s is not supported by the HIP build\n", what);
@@ -1622,34 +1624,56 @@ int_t factors_collective_explicit_multiple(
     real_t *TransCtCinvCt, real_t *CtCw, real_t *CtUbias, real_t *B_plus_bias,
     int nthreads)
 {
-    (void)m_ubin; (void)pbin; (void)Cb; (void)w_implicit;
-    (void)BtB; (void)TransBtBinvBt; (void)BtXbias; (void)BeTBeChol; (void)BiTBi; (void)CtCw; (void)CtUbias; (void)B_plus_bias;
+    (void)m_ubin; (void)pbin; (void)Cb;
+    (void)BtB; (void)BtXbias; (void)BeTBeChol; (void)CtCw; (void)CtUbias; (void)B_plus_bias;
     (void)nthreads;
     if (NA_as_zero_U || NA_as_zero_X) return unsupported_multiple("NA_as_zero");
     const bool spU = (U == nullptr && (nnz_U || U_csr_p));
     if (Ub) return unsupported_multiple("binary side information");
-    if (Xfull) return unsupported_multiple("dense X");
-    if (weight) return unsupported_multiple("observation weights");
-    if (Bi || add_implicit_features) return unsupported_multiple("implicit features");
+    if (Xfull && (nnz || Xcsr_p)) return unsupported_multiple("X both as a dense and as a sparse matrix");
+    if (add_implicit_features && !Bi) return unsupported_multiple("add_implicit_features without Bi");
+    if (!add_implicit_features) { Bi = nullptr; BiTBi = nullptr; }
     if (U == nullptr && !spU) { m_u = 0; }
     if (std::max(m, m_u) <= 0) return 0;
+    if (m <= 0) { Xfull = nullptr; weight = nullptr; }
     if (U) for (size_t e = 0; e < (size_t)m_u * (size_t)p; e++) if (std::isnan(U[e])) return unsupported_multiple("missing values in U");
+    const bool side = U != nullptr || spU;
+    // The block solver's weighted right-hand side of sparse X is the NA_as_zero one, w x - (w - 1)(glob_mean + biasB), applied
+    // to values that preprocess_vec has centred already (collective.c:1743-1753): with a mean or item biases the reference's
+    // rows are not the solution of the weighted model.  Not restated.
+    if (weight && !Xfull && (side || Bi) && (glob_mean != 0 || biasB))
+        return unsupported_multiple("observation weights of sparse X together with glob_mean / biasB and side information or implicit "
+                                    "features (the reference's right-hand side is not the weighted model's, collective.c:1743-1753)");
+    // A dense row of NaN with side information reaches the side-information-only solution through collective_factors_warm,
+    // which has centred u already and hands it on with the column means: they are subtracted twice (:3616, :3662-3677, :3337).
+    if (Xfull && U && U_colmeans && !Bi)
+        for (int_t r = 0; r < std::min(m, m_u); r++) {
+            int_t c = 0;
+            while (c < n && std::isnan(Xfull[(size_t)r * (size_t)n + c])) c++;
+            if (c == n)
+                return unsupported_multiple("a dense row of X without any observation together with U and U_colmeans (the reference "
+                                            "centres that row's side information twice, collective.c:3616, :3337)");
+        }
     // factors_collective_explicit_single, collective.c:10611-10630
     real_t lam_bias = lam, l1_lam_bias = l1_lam;
     if (lam_unique) { lam_bias = lam_unique[biasA ? 0 : 2]; lam = lam_unique[2]; }
     if (l1_lam_unique) { l1_lam_bias = l1_lam_unique[biasA ? 0 : 2]; l1_lam = l1_lam_unique[2]; }
     if (!biasA) scale_bias_const = false;
     if ((scale_lam || scale_lam_sideinfo) && scale_bias_const) { lam_bias *= scaling_biasA; l1_lam_bias *= scaling_biasA; }
+    // BiTBi carries the w_implicit of the call (batch driver, :11016-11020), the right-hand side the rescaled one (:3706-3714)
+    const real_t w_implicit_gram = w_implicit;
     if (w_main != 1) {                                                          // collective_factors_warm, :3694-3713
-        w_user /= w_main; lam /= w_main; lam_bias /= w_main; l1_lam /= w_main; l1_lam_bias /= w_main;
+        w_user /= w_main; w_implicit /= w_main; lam /= w_main; lam_bias /= w_main; l1_lam /= w_main; l1_lam_bias /= w_main;
     }
     const bool l1on = l1_lam != 0 || (biasA && l1_lam_bias != 0);
     if (l1on && nonneg) return unsupported_multiple("L1 regularisation together with non-negativity");
     // rows without side information and without a bias: the reference passes scale_lam where factors_closed_form
-    // expects scale_bias_const (:3789-3799), so the last factor keeps the unscaled lam
-    if (!biasA) scale_bias_const = scale_lam || scale_lam_sideinfo;
-    // preprocess_vec, :6337-6388: x -= biasB[col] + glob_mean.  The mean goes here, the bias is fused into the gather.
-    const size_t nz = Xcsr_p ? Xcsr_p[m] : nnz;
+    // expects scale_bias_const (:3789-3799), so the last factor keeps the unscaled lam (not with implicit features: those
+    // rows go through the block solver, :3759-3760)
+    if (!biasA && !Bi) scale_bias_const = scale_lam || scale_lam_sideinfo;
+    // preprocess_vec, :6337-6388: x -= biasB[col] + glob_mean.  The mean goes here (dense X: on the device), the bias is fused
+    // into the gather.
+    const size_t nz = Xfull ? 0 : (Xcsr_p ? Xcsr_p[m] : nnz);
     const real_t *vals = Xcsr_p ? Xcsr : X;
     std::vector<real_t> shifted;
     if (glob_mean != 0 && nz) {
@@ -1657,13 +1681,19 @@ int_t factors_collective_explicit_multiple(
         for (size_t e = 0; e < nz; e++) shifted[e] -= glob_mean;
         vals = shifted.data();
     }
-    const int_t n_rows_B = include_all_X ? std::max(n, n_max) : n;
-    // (TransCtCinvCt: not with non-negativity or an L1 penalty, collective.c:3378)
-    int rc = cmfrec_hip_factors_multiple_l1(A, biasA, m, m_u, (U || spU) ? p : 0, U, U_colmeans, ixA, ixB, Xcsr_p ? nullptr : vals, nnz,
-                                            Xcsr_p, Xcsr_i, Xcsr_p ? vals : nullptr, B, n_rows_B, C, biasB, k, k_user, k_item,
-                                            k_main, lam, lam_bias, lam, w_user, false, scale_lam, scale_lam_sideinfo,
-                                            scale_bias_const, nullptr, (nonneg || l1on) ? nullptr : TransCtCinvCt, U_row, U_col,
-                                            U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, nonneg, l1_lam, l1_lam_bias);
+    // B's rows: with dense X or implicit features the n columns of Xfull / rows of Bi bound the item indices
+    const int_t n_rows_B = (include_all_X && !Xfull && !Bi) ? std::max(n, n_max) : n;
+    // TransBtBinvBt: complete dense rows of the model without side information (common.c:736-758, n_BtB == n)
+    const bool use_TB = TransBtBinvBt && Xfull && !weight && !nonneg && !l1on && !side && !Bi && (!include_all_X || n_max <= n);
+    // (TransCtCinvCt: not with non-negativity or an L1 penalty, collective.c:3378; a dense row of NaN reaches the side-information-only
+    //  solution through collective_factors_warm, which does not hand the matrix on, :3662-3677)
+    int rc = cmfrec_hip_factors_multiple_ex(A, biasA, m, m_u, side ? p : 0, U, U_colmeans, ixA, ixB, (Xcsr_p || Xfull) ? nullptr : vals,
+                                            Xfull ? 0 : nnz, Xcsr_p, Xcsr_i, Xcsr_p ? vals : nullptr, B, n_rows_B, C, biasB, k, k_user,
+                                            k_item, k_main, lam, lam_bias, lam, w_user, false, scale_lam, scale_lam_sideinfo,
+                                            scale_bias_const, nullptr, (nonneg || l1on || Xfull) ? nullptr : TransCtCinvCt, U_row, U_col,
+                                            U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, nonneg, l1_lam, l1_lam_bias,
+                                            Xfull ? nullptr : weight, Xfull, Xfull ? weight : nullptr, glob_mean, Bi, w_implicit,
+                                            w_implicit_gram, BiTBi, use_TB ? TransBtBinvBt : nullptr);
     if (rc == 2) fprintf(stderr, "%s\n", cmfrec_hip_last_error());
     return rc > 3 ? 1 : rc;
 }

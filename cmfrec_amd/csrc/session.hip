@@ -7,6 +7,7 @@
 // the small k x k work matrices -- all resident in HBM for the whole fit.
 #include "device.hpp"
 #include "coo_device.hpp"
+#include "dense_rows_device.hpp"
 #include "chol_wave_kernels.hpp"
 #include "gramk_kernels.hpp"
 #include "lowrank_kernels.hpp"
@@ -15,6 +16,7 @@
 #include "side_zeros_kernels.hpp"
 #include <dlfcn.h>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <new>
 
@@ -3509,6 +3511,18 @@ int cmfrec_hip_optimizeA_collective_sparse(real_t *A, size_t lda, const real_t *
     });
 }
 
+// what cmfrec_hip_factors_multiple_ex adds to the arguments of cmfrec_hip_factors_multiple_l1 (include/cmfrec_hip.h)
+struct NewRowsExtra {
+    const real_t *weight = nullptr;            // sparse X: one per entry, in the order of the triplets / of Xcsr
+    const real_t *Xfull = nullptr;             // [m_x, n], NaN = not observed
+    const real_t *weight_full = nullptr;       // [m_x, n], read where Xfull is present
+    real_t glob_mean_full = 0;                 // subtracted from the present entries of Xfull on the device
+    const real_t *Bi = nullptr;                // [n, k + k_main]
+    real_t w_implicit = 1, w_implicit_gram = 1;
+    const real_t *BiTBi_pre = nullptr;         // [k + k_main]^2, w_implicit_gram included
+    const real_t *TransBtBinvBt_pre = nullptr; // [n, k + k_main (+ 1 with a bias)]
+};
+
 // Factors of rows that were not part of the fit, all of them in one pass (the step after the path):
 // factors_collective_explicit_multiple (collective.c:10865-11174) / factors_collective_implicit_multiple
 // (:11176-11340) restricted to sparse X (COO or CSR, values already transformed: minus the global mean, times
@@ -3536,9 +3550,24 @@ static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u,
                                  const real_t *BtB_pre, const real_t *TransCtCinvCt_pre,
                                  const int_t U_row[], const int_t U_col[], const real_t *U_sp, size_t nnz_U,
                                  const size_t U_csr_p[], const int_t U_csr_i[], const real_t *U_csr, bool nonneg,
-                                 real_t l1_lam, real_t l1_lam_bias)
+                                 real_t l1_lam, real_t l1_lam_bias, const NewRowsExtra &ex)
 {
     return guarded([&]() {
+        const real_t *weight = ex.weight, *Xfull = ex.Xfull, *weight_full = ex.weight_full, *Bi = ex.Bi;
+        if (implicit && (weight || Xfull || weight_full || Bi)) {
+            g_last_error = "cmfrec_hip_factors_multiple: observation weights, dense X and implicit features belong to the explicit model";
+            return 2;
+        }
+        if (Xfull && (nnz > 0 || Xcsr_p)) {
+            g_last_error = "cmfrec_hip_factors_multiple: X given both as a dense and as a sparse matrix";
+            return 2;
+        }
+        if ((weight_full && !Xfull) || (weight && Xfull)) {
+            g_last_error = "cmfrec_hip_factors_multiple: the weights must have the form of X (weight with sparse X, weight_full with Xfull)";
+            return 2;
+        }
+        if (Xfull) { nnz = 0; ixA = nullptr; ixB = nullptr; X = nullptr; weight = nullptr; }
+        if (m_x <= 0 || (!Xfull && !Xcsr_p && nnz == 0)) weight = nullptr;
         // sparse side information (COO or CSR over m_u rows, missing = absent): second gather source of the row kernel
         const bool spU = (U == nullptr && p > 0 && ((nnz_U > 0 && U_row && U_col && U_sp) || U_csr_p));
         const int m_max = std::max(m_x, (p > 0 && (U || spU)) ? m_u : 0);
@@ -3558,6 +3587,8 @@ static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u,
         // fit.hip): a row id outside [0, m_x) or an item id outside [0, n) would corrupt device memory silently
         {
             auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_factors_multiple: ") + what; return 2; };
+            if (Bi && ((size_t)k + (size_t)k_main == 0)) return bad("implicit features without factors");
+            if (ex.BiTBi_pre && !Bi) return bad("BiTBi without Bi");
             if (Xcsr_p) {
                 const size_t nz = Xcsr_p[m_x];
                 for (int r = 0; r < m_x; r++) if (Xcsr_p[r] > Xcsr_p[r + 1]) return bad("Xcsr_p is not non-decreasing");
@@ -3607,19 +3638,90 @@ static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u,
         if (biasB) dbias.upload(biasB, (size_t)n, st);
         dA.alloc((size_t)m_max * ldA);
         HIP_CHECK(hipMemsetAsync(dA.ptr, 0, dA.n * sizeof(real_t), st));
-        if (Xcsr_p) {
-            std::vector<size_t> pp((size_t)m_max + 1);
-            for (int r = 0; r <= m_max; r++) pp[r] = Xcsr_p[std::min(r, m_x)];
-            shard_from_csr(Xs, m_max, pp.data(), Xcsr_i, Xcsr, n, st);
-        } else if (nnz == 0) {
+        auto empty_shard = [&]() {
             std::vector<size_t> pp((size_t)m_max + 1, 0);
             shard_from_csr(Xs, m_max, pp.data(), nullptr, nullptr, n, st);
+        };
+        // dense X: the block is compacted on the device into the triplets of its present entries (dense_rows_device.hpp), in
+        // blocks of rows so that its device copy (and the weights') stays within a budget; with TransBtBinvBt and nothing that
+        // changes the row systems, the rows without a missing entry are  x^T TransBtBinvBt  (common.c:736-758)
+        DevBuf<int> dmiss;
+        DevBuf<real_t> dTB, dTBout;
+        const int kT = kk + ub;
+        const bool use_TB = Xfull != nullptr && ex.TransBtBinvBt_pre != nullptr && !weight_full && !nonneg && !l1on && p == 0 && !Bi;
+        if (Xfull) {
+            const size_t per_row = (size_t)n * sizeof(real_t) * (weight_full ? 2 : 1);
+            long long block_rows = (long long)std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_row, 1));
+            if (switches().newrows_block_rows > 0) block_rows = switches().newrows_block_rows;     // test hook
+            block_rows = std::min<long long>(block_rows, m_x);
+            dmiss.alloc((size_t)m_x);
+            if (use_TB) { dTB.upload(ex.TransBtBinvBt_pre, (size_t)n * kT, st); dTBout.alloc((size_t)m_x * kT); }
+            DevBuf<real_t> dXb, dWb;
+            std::vector<std::unique_ptr<DenseRowsCoo>> parts;
+            size_t total = 0;
+            for (long long r0 = 0; r0 < m_x; r0 += block_rows) {
+                const int rows = (int)std::min<long long>(block_rows, m_x - r0);
+                dXb.upload(Xfull + (size_t)r0 * n, (size_t)rows * n, st);
+                if (weight_full) dWb.upload(weight_full + (size_t)r0 * n, (size_t)rows * n, st);
+                parts.emplace_back(new DenseRowsCoo);
+                dense_rows_to_coo(dXb.ptr, weight_full ? dWb.ptr : nullptr, rows, n, (int)r0, ex.glob_mean_full, dmiss.ptr + r0,
+                                  *parts.back(), st);
+                total += parts.back()->nnz;
+                if (use_TB) {
+                    hipLaunchKernelGGL(dense_rows_center_kernel<real_t>, grid1d(std::min<size_t>((size_t)rows * n, (size_t)1 << 22)), dim3(256), 0,
+                                       st, dXb.ptr, (size_t)rows, n, ex.glob_mean_full, biasB ? dbias.ptr : nullptr, dmiss.ptr + r0);
+                    HIP_CHECK(hipGetLastError());
+                    launch_gemm<false>(dev, rows, kT, n, (real_t)1, dXb.ptr, (size_t)n, dTB.ptr, (size_t)kT, dTBout.ptr + (size_t)r0 * kT,
+                                       (size_t)kT);
+                    HIP_CHECK(hipStreamSynchronize(st));
+                }
+            }
+            if (total == 0) empty_shard();
+            else if (parts.size() == 1) {
+                DenseRowsCoo &c = *parts[0];
+                shard_from_coo(Xs, m_max, n, c.row.ptr, c.col.ptr, c.val.ptr, total, (real_t)0, (real_t)1, st, weight_full ? c.wt.ptr : nullptr);
+                HIP_CHECK(hipStreamSynchronize(st));
+            } else {
+                DenseRowsCoo all;
+                all.row.alloc(total); all.col.alloc(total); all.val.alloc(total);
+                if (weight_full) all.wt.alloc(total);
+                size_t at = 0;
+                for (auto &c : parts) {
+                    if (c->nnz == 0) continue;
+                    HIP_CHECK(hipMemcpyAsync(all.row.ptr + at, c->row.ptr, c->nnz * sizeof(int), hipMemcpyDeviceToDevice, st));
+                    HIP_CHECK(hipMemcpyAsync(all.col.ptr + at, c->col.ptr, c->nnz * sizeof(int), hipMemcpyDeviceToDevice, st));
+                    HIP_CHECK(hipMemcpyAsync(all.val.ptr + at, c->val.ptr, c->nnz * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+                    if (weight_full) HIP_CHECK(hipMemcpyAsync(all.wt.ptr + at, c->wt.ptr, c->nnz * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+                    at += c->nnz;
+                }
+                HIP_CHECK(hipStreamSynchronize(st));
+                parts.clear();
+                shard_from_coo(Xs, m_max, n, all.row.ptr, all.col.ptr, all.val.ptr, total, (real_t)0, (real_t)1, st, weight_full ? all.wt.ptr : nullptr);
+                HIP_CHECK(hipStreamSynchronize(st));
+            }
+        } else if (Xcsr_p) {
+            std::vector<size_t> pp((size_t)m_max + 1);
+            for (int r = 0; r <= m_max; r++) pp[r] = Xcsr_p[std::min(r, m_x)];
+            shard_from_csr(Xs, m_max, pp.data(), Xcsr_i, Xcsr, n, st, Xcsr_p[m_x] > 0 ? weight : nullptr);
+        } else if (nnz == 0) {
+            empty_shard();
         } else {
-            DevBuf<int> dr, dc; DevBuf<real_t> dv;
+            DevBuf<int> dr, dc; DevBuf<real_t> dv, dw;
             dr.upload(ixA, std::max<size_t>(nnz, 1), st); dc.upload(ixB, std::max<size_t>(nnz, 1), st);
             dv.upload(X, std::max<size_t>(nnz, 1), st);
-            shard_from_coo(Xs, m_max, n, dr.ptr, dc.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, st);
+            if (weight) dw.upload(weight, nnz, st);
+            shard_from_coo(Xs, m_max, n, dr.ptr, dc.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, st, weight ? dw.ptr : nullptr);
             HIP_CHECK(hipStreamSynchronize(st));
+        }
+        // implicit features: w_i Bi^T Bi joins the X block of every row's matrix (collective.c:1704-1707), w_i sum_{j observed} Bi_j
+        // its right-hand side (:1757-1771); the matrix term carries the weight of the batch driver (:11016-11020), the right-hand
+        // side the one the row function rescales by w_main (:3706-3714)
+        DevBuf<real_t> dBi, dBiG, dBiFull;
+        if (Bi) {
+            dBi.upload(Bi, (size_t)n * kk, st);
+            dBiG.alloc((size_t)kk * kk);
+            if (ex.BiTBi_pre) dBiG.upload(ex.BiTBi_pre, dBiG.n, st);
+            else launch_gram(dev, gws, dBi.ptr, (size_t)kk, n, kk, dBiG.ptr, ex.w_implicit_gram, (real_t)0);
         }
         SparseShard Us;
         if (spU) {
@@ -3673,6 +3775,37 @@ static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u,
                            CHOL_COLLECTIVE_IMPLICIT, dM.ptr};
                 rc = launch_chol(dev, c, &Xs);
             }
+        } else if (Bi) {
+            // with implicit features every row goes through the block solver, the model without side information included
+            // (collective.c:3759-3760), and a row without observations is not a "cold" row (:3655-3659): one launch.  Rows that
+            // the kernel treats as rows with side information take the block solver's rules for the last unknown's lambda
+            // and the L1 penalty (:1349-1354); that is every row except those beyond a dense U.
+            const bool all_u = p == 0 || spU || m_u >= m_max;
+            bool sbc = scale_bias_const;
+            if (!all_u) {
+                if (l1on && scale_bias_const && (scale_lam || scale_lam_sideinfo)) {
+                    g_last_error = "cmfrec_hip_factors_multiple: implicit features with an L1 penalty, scale_bias_const and dense side "
+                                   "information for fewer rows than the batch is not supported";
+                    return 2;
+                }
+                sbc = false;
+            }
+            if (p > 0 && !spU) {
+                launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, dCtC.ptr, w_user, (real_t)0);
+                launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
+            }
+            if (Xs.nnz > 0)
+                hipLaunchKernelGGL(implicit_rhs_rows_kernel<real_t>, grid1d((size_t)m_max * 64), dim3(256), 0, st, Xs.p.ptr, Xs.i.ptr, dBi.ptr, kk,
+                                   ex.w_implicit, m_max, dA.ptr, ldA, k_user);
+            dBiFull.alloc((size_t)kt * kt);
+            hipLaunchKernelGGL(embed_block_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, dBiG.ptr, kk, k_user, kt, dBiFull.ptr);
+            HIP_CHECK(hipGetLastError());
+            CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, (p > 0 && !spU) ? dCtC.ptr : nullptr, p > 0 ? kc : 0,
+                       all_u ? m_max : m_u, p, lam, lam_bias, (bool)(scale_lam || scale_lam_sideinfo),
+                       (bool)(scale_lam_sideinfo && !spU), sbc, CHOL_COLLECTIVE};
+            c.Mfull = dBiFull.ptr; c.rhs_prefilled_all = true;
+            if (spU) { c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user; c.rows2 = m_u; }
+            rc = launch_chol(dev, c, &Xs);
         } else if (p == 0) {
             CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk + ub, 0, bias_sub, nullptr, 0, 0, 0, lam, lam_bias,
                        (bool)(scale_lam || scale_lam_sideinfo), false, scale_bias_const, CHOL_EXPLICIT};
@@ -3718,6 +3851,16 @@ static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u,
         }
         HIP_CHECK(hipGetLastError());
         if (rc) return rc;
+        if (!implicit && Xs.weighted() && (scale_lam || scale_lam_sideinfo)) {
+            hipLaunchKernelGGL(zero_weightless_rows_kernel<real_t>, dim3(m_max), dim3(64), 0, st, Xs.p.ptr, Xs.wsum.ptr, m_max, p > 0 ? m_u : 0,
+                               std::numeric_limits<real_t>::epsilon(), dA.ptr, ldA, kt);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (use_TB) {
+            hipLaunchKernelGGL(dense_rows_select_complete_kernel<real_t>, grid1d(std::min<size_t>((size_t)m_x * kT, (size_t)1 << 22)), dim3(256), 0, st,
+                               dA.ptr, ldA, k_user, dTBout.ptr, kT, dmiss.ptr, (size_t)m_x);
+            HIP_CHECK(hipGetLastError());
+        }
         HIP_CHECK(hipMemcpy2DAsync(A, (size_t)ktA * sizeof(real_t), dA.ptr, ldA * sizeof(real_t), (size_t)ktA * sizeof(real_t),
                                    (size_t)m_max, hipMemcpyDeviceToHost, st));
         if (ub) {
@@ -3745,7 +3888,7 @@ int cmfrec_hip_factors_multiple(real_t *A, real_t *biasA, int_t m_x, int_t m_u, 
     return factors_multiple_impl(A, biasA, m_x, m_u, p, U, U_colmeans, ixA, ixB, X, nnz, Xcsr_p, Xcsr_i, Xcsr, B, n, C, biasB, k,
                                  k_user, k_item, k_main, lam, lam_bias, lam_x, w_user, implicit, scale_lam, scale_lam_sideinfo,
                                  scale_bias_const, BtB_pre, TransCtCinvCt_pre, U_row, U_col, U_sp, nnz_U, U_csr_p, U_csr_i, U_csr,
-                                 nonneg, (real_t)0, (real_t)0);
+                                 nonneg, (real_t)0, (real_t)0, NewRowsExtra());
 }
 
 int cmfrec_hip_factors_multiple_l1(real_t *A, real_t *biasA, int_t m_x, int_t m_u, int_t p, const real_t *U,
@@ -3762,7 +3905,31 @@ int cmfrec_hip_factors_multiple_l1(real_t *A, real_t *biasA, int_t m_x, int_t m_
     return factors_multiple_impl(A, biasA, m_x, m_u, p, U, U_colmeans, ixA, ixB, X, nnz, Xcsr_p, Xcsr_i, Xcsr, B, n, C, biasB, k,
                                  k_user, k_item, k_main, lam, lam_bias, lam_x, w_user, implicit, scale_lam, scale_lam_sideinfo,
                                  scale_bias_const, BtB_pre, TransCtCinvCt_pre, U_row, U_col, U_sp, nnz_U, U_csr_p, U_csr_i, U_csr,
-                                 nonneg, l1_lam, l1_lam_bias);
+                                 nonneg, l1_lam, l1_lam_bias, NewRowsExtra());
+}
+
+int cmfrec_hip_factors_multiple_ex(real_t *A, real_t *biasA, int_t m_x, int_t m_u, int_t p, const real_t *U,
+                                   const real_t *U_colmeans, const int_t ixA[], const int_t ixB[], const real_t *X,
+                                   size_t nnz, const size_t Xcsr_p[], const int_t Xcsr_i[], const real_t *Xcsr,
+                                   const real_t *B, int_t n, const real_t *C, const real_t *biasB, int_t k, int_t k_user,
+                                   int_t k_item, int_t k_main, real_t lam, real_t lam_bias, real_t lam_x, real_t w_user,
+                                   bool implicit, bool scale_lam, bool scale_lam_sideinfo, bool scale_bias_const,
+                                   const real_t *BtB_pre, const real_t *TransCtCinvCt_pre,
+                                   const int_t U_row[], const int_t U_col[], const real_t *U_sp, size_t nnz_U,
+                                   const size_t U_csr_p[], const int_t U_csr_i[], const real_t *U_csr, bool nonneg,
+                                   real_t l1_lam, real_t l1_lam_bias,
+                                   const real_t *weight, const real_t *Xfull, const real_t *weight_full, real_t glob_mean_full,
+                                   const real_t *Bi, real_t w_implicit, real_t w_implicit_gram, const real_t *BiTBi_pre,
+                                   const real_t *TransBtBinvBt_pre)
+{
+    NewRowsExtra ex;
+    ex.weight = weight; ex.Xfull = Xfull; ex.weight_full = weight_full; ex.glob_mean_full = glob_mean_full;
+    ex.Bi = Bi; ex.w_implicit = w_implicit; ex.w_implicit_gram = w_implicit_gram; ex.BiTBi_pre = BiTBi_pre;
+    ex.TransBtBinvBt_pre = TransBtBinvBt_pre;
+    return factors_multiple_impl(A, biasA, m_x, m_u, p, U, U_colmeans, ixA, ixB, X, nnz, Xcsr_p, Xcsr_i, Xcsr, B, n, C, biasB, k,
+                                 k_user, k_item, k_main, lam, lam_bias, lam_x, w_user, implicit, scale_lam, scale_lam_sideinfo,
+                                 scale_bias_const, BtB_pre, TransCtCinvCt_pre, U_row, U_col, U_sp, nnz_U, U_csr_p, U_csr_i, U_csr,
+                                 nonneg, l1_lam, l1_lam_bias, ex);
 }
 
 }  // extern "C"
@@ -3881,6 +4048,65 @@ extern "C" int cmfrec_hip_gemm_probe(int M, int N, int K, int transa, int reps, 
         double mx = 0, df = 0;
         for (size_t e = 0; e < h1.size(); e++) { mx = std::max(mx, std::fabs((double)h2[e])); df = std::max(df, std::fabs((double)h1[e] - (double)h2[e])); }
         if (max_rel_diff) *max_rel_diff = df / std::max(mx, 1e-300);
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        return 0;
+    });
+}
+
+// Timing probe of the dense batch's compaction (tools/microbench/dense_rows_probe.py): a seeded [rows, n] block with the given
+// fraction of present entries, the count pass and the scan + write pass timed with device events over `reps` runs after one
+// warm-up run each (milliseconds per run); nnz: present entries found.
+extern "C" int cmfrec_hip_dense_rows_probe(int rows, int n, double present, int reps, double *ms_count, double *ms_write, size_t *nnz)
+{
+    return guarded([&]() {
+        if (rows <= 0 || n <= 0 || reps <= 0) { g_last_error = "cmfrec_hip_dense_rows_probe: rows, n, reps > 0"; return 2; }
+        DeviceInfo dev;
+        init_device(dev, -1);
+        hipStream_t st = dev.stream;
+        std::vector<real_t> h((size_t)rows * n);
+        unsigned long long x = 88172645463325252ull;
+        const real_t nan = std::numeric_limits<real_t>::quiet_NaN();
+        for (auto &v : h) {
+            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+            const double u = (double)(x >> 11) / 9007199254740992.0;
+            v = (u < present) ? (real_t)(1.0 + 4.0 * u) : nan;
+        }
+        DevBuf<real_t> dX; DevBuf<int> dmiss; DevBuf<unsigned> cnt;
+        dX.upload(h.data(), h.size(), st); dmiss.alloc((size_t)rows); cnt.alloc((size_t)rows + 1);
+        hipEvent_t e0, e1;
+        HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+        const dim3 grid((unsigned)((rows + DENSE_ROWS_WAVES - 1) / DENSE_ROWS_WAVES)), block(64 * DENSE_ROWS_WAVES);
+        float t = 0;
+        for (int r = 0; r < reps + 1; r++) {
+            if (r == 1) HIP_CHECK(hipEventRecord(e0, st));
+            hipLaunchKernelGGL(dense_rows_count_kernel<real_t>, grid, block, 0, st, dX.ptr, rows, n, cnt.ptr, dmiss.ptr);
+        }
+        HIP_CHECK(hipEventRecord(e1, st)); HIP_CHECK(hipEventSynchronize(e1));
+        HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+        if (ms_count) *ms_count = (double)t / reps;
+        DenseRowsCoo out;
+        dense_rows_to_coo(dX.ptr, nullptr, rows, n, 0, (real_t)0, dmiss.ptr, out, st);          // the triplets' buffers (and one whole conversion)
+        DevBuf<size_t> off; off.alloc((size_t)rows + 1);
+        {
+            auto in = rocprim::make_transform_iterator(cnt.ptr, u32_to_size());
+            DevBuf<unsigned char> tmp; size_t bytes = 0;
+            HIP_CHECK(hipMemsetAsync(cnt.ptr + rows, 0, sizeof(unsigned), st));
+            HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, off.ptr, (size_t)0, (size_t)rows + 1, rocprim::plus<size_t>(), st));
+            tmp.alloc(bytes + 16);
+            HIP_CHECK(rocprim::exclusive_scan(tmp.ptr, bytes, in, off.ptr, (size_t)0, (size_t)rows + 1, rocprim::plus<size_t>(), st));
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+        for (int r = 0; r < reps + 1; r++) {
+            if (r == 1) HIP_CHECK(hipEventRecord(e0, st));
+            if (out.nnz)
+                hipLaunchKernelGGL(dense_rows_write_kernel<real_t>, grid, block, 0, st, dX.ptr, (const real_t *)nullptr, rows, n, 0, (real_t)0, off.ptr,
+                                   out.row.ptr, out.col.ptr, out.val.ptr, (real_t *)nullptr);
+        }
+        HIP_CHECK(hipEventRecord(e1, st)); HIP_CHECK(hipEventSynchronize(e1));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+        if (ms_write) *ms_write = (double)t / reps;
+        if (nnz) *nnz = out.nnz;
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         return 0;
     });

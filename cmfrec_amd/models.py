@@ -121,6 +121,43 @@ def _new_rows(X, n, dt):
             np.ascontiguousarray(val, dt), int(m_x))
 
 
+def _new_rows_weights(X, W, row, col, dt):
+    """Observation weights of new rows in the form of ``X``: an array [m_x, n] for a dense ``X``; for a triplet an array (nnz,)
+    or a triplet with the same (row, col); for a SciPy sparse ``X`` a sparse matrix with the same pattern.  Returns the
+    weights in the order of ``X``'s entries."""
+    if W is None:
+        return None
+    if isinstance(X, np.ndarray):
+        W = np.ascontiguousarray(W, dt)
+        if W.shape != X.shape:
+            raise ValueError("'W' must have the shape of 'X'.")
+        return W
+    if isinstance(X, tuple):
+        if isinstance(W, tuple):
+            wr, wc, wv = W
+            if len(wr) != len(row) or not (np.array_equal(wr, row) and np.array_equal(wc, col)):
+                raise ValueError("'W' must have the same non-missing entries as 'X'.")
+        else:
+            wv = np.asarray(W).reshape(-1)
+        if len(wv) != len(row):
+            raise ValueError("'W' must have the same number of entries as 'X'.")
+        return np.ascontiguousarray(wv, dt)
+    if isinstance(W, (np.ndarray, tuple)) or not hasattr(W, "tocoo"):
+        raise ValueError("'W' must be a sparse matrix like 'X'.")
+    Wc = W.tocoo()
+    if Wc.shape != X.shape or Wc.nnz != len(row):
+        raise ValueError("'W' must have the same non-missing entries as 'X'.")
+    ncol = int(X.shape[1])
+    kx = row.astype(np.int64) * ncol + col
+    kw = Wc.row.astype(np.int64) * ncol + Wc.col
+    ox, ow = np.argsort(kx, kind="stable"), np.argsort(kw, kind="stable")
+    if not np.array_equal(kx[ox], kw[ow]):
+        raise ValueError("'W' must have the same non-missing entries as 'X'.")
+    wv = np.empty(len(row), dt)
+    wv[ox] = Wc.data[ow]
+    return wv
+
+
 def _side_info(M, dt):
     """Side information for fit(): dense array -> (array, None); SciPy sparse matrix -> (None, (row, col, val, rows, cols))."""
     if M is None:
@@ -445,26 +482,39 @@ class CMF(_Base):
         self.is_fitted_ = True
         return self
 
-    def factors_multiple(self, X=None, U=None, return_bias=False):
-        """Factors (and bias) of new users from their ratings ``X`` [m_x, n] (sparse) and / or dense attributes ``U``
-        [m_u, p] (reference ``CMF.factors_multiple``, cmfrec/__init__.py:3706; C function
-        factors_collective_explicit_multiple).  Returns ``A`` [max(m_x, m_u), k_user+k+k_main], or ``(A, bias)``."""
+    def factors_multiple(self, X=None, U=None, W=None, return_bias=False):
+        """Factors (and bias) of new users from their ratings ``X`` [m_x, n] and / or dense attributes ``U`` [m_u, p]
+        (reference ``CMF.factors_multiple``, cmfrec/__init__.py:3706; C function factors_collective_explicit_multiple).
+        ``X``: a SciPy sparse matrix, a (row, col, val) triplet, or a dense array with NaN for the missing entries.  ``W``:
+        observation weights in the form of ``X`` (a sparse ``W`` must have ``X``'s pattern).  A model fitted with
+        ``add_implicit_features`` uses its ``Bi_``.  Returns ``A`` [max(m_x, m_u), k_user+k+k_main], or ``(A, bias)``."""
         if X is None and U is None:
             raise ValueError("Must pass at least one of 'X', 'U'.")
         lam6 = None if self._lam6 is None else np.ascontiguousarray(self._lam6, self.dtype_)
         l16 = None if self._l16 is None else np.ascontiguousarray(self._l16, self.dtype_)
-        if self.add_implicit_features:
-            raise NotImplementedError("factors_multiple with add_implicit_features is not implemented in cmfrec_amd")
         lib, R = self._lib()
         dt = self.dtype_
         n = self.B_.shape[0]
-        row, col, val, m_x = _new_rows(X, n, dt)
+        Xfull = None
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2 or X.shape[1] != n:
+                raise ValueError("a dense 'X' must be a 2-D array with one column per item of the model")
+            Xfull = np.ascontiguousarray(X, dt)
+            row = col = np.zeros(0, np.int32); val = np.zeros(0, dt); m_x = Xfull.shape[0]
+        else:
+            row, col, val, m_x = _new_rows(X, n, dt)
+        if W is not None and X is None:
+            raise ValueError("'W' needs 'X'.")
+        Wv = _new_rows_weights(X, W, row, col, dt)
         Uc = None if (U is None or not self.C_.shape[0]) else np.ascontiguousarray(U, dt)
         m_u, p = (0, 0) if Uc is None else Uc.shape
         mm = max(m_x, m_u)
         A = np.empty((mm, self.k_user + self.k + self.k_main), dt)
         biasA = np.empty(mm, dt) if self.user_bias else None
         has = lambda M: M is not None and M.shape[0] > 0
+        imp = self.add_implicit_features
+        Bi = np.ascontiguousarray(self.Bi_, dt) if imp else None
+        TBt = getattr(self, "_TransBtBinvBt", None)
         rc = lib.factors_collective_explicit_multiple(
             _lib.ptr(A), _lib.ptr(biasA), C.c_int(m_x), _lib.ptr(Uc), C.c_int(m_u), C.c_int(p),
             C.c_bool(False), C.c_bool(False), C.c_bool(self.nonneg),
@@ -472,14 +522,15 @@ class CMF(_Base):
             _lib.ptr(self.C_) if p else None, None, R(self.glob_mean_),
             _lib.ptr(self.item_bias_) if self.item_bias else None,
             _lib.ptr(self._U_colmeans) if (p and len(self._U_colmeans)) else None,
-            _lib.ptr(val), _lib.ptr(row), _lib.ptr(col), C.c_size_t(len(val)), None, None, None,
-            None, C.c_int(n), None, _lib.ptr(self.B_), None, C.c_bool(False),
+            _lib.ptr(val) if Xfull is None else None, _lib.ptr(row) if Xfull is None else None,
+            _lib.ptr(col) if Xfull is None else None, C.c_size_t(len(val)), None, None, None,
+            _lib.ptr(Xfull), C.c_int(n), _lib.ptr(Wv), _lib.ptr(self.B_), _lib.ptr(Bi), C.c_bool(imp),
             C.c_int(self.k), C.c_int(self.k_user), C.c_int(self.k_item), C.c_int(self.k_main),
             R(self.lambda_), _lib.ptr(lam6), R(self.l1_lambda), _lib.ptr(l16), C.c_bool(self.scale_lam), C.c_bool(self.scale_lam_sideinfo),
             C.c_bool(self.scale_bias_const), R(self._scaling_biasA if self.scale_bias_const else 1.), R(self.w_main), R(self.w_user),
             R(self.w_implicit),
             C.c_int(n), C.c_bool(True),
-            None, None, None, None, None,
+            None, _lib.ptr(TBt) if has(TBt) else None, None, None, None,
             _lib.ptr(self._TransCtCinvCt) if (p and has(self._TransCtCinvCt)) else None, None, None, None,
             C.c_int(self.nthreads))
         _lib.check(rc, lib, "factors_collective_explicit_multiple")

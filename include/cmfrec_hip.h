@@ -234,6 +234,35 @@ int cmfrec_hip_factors_multiple_l1(
     /* L1 penalty of the row systems / of the bias unknown, after the w_main rescaling (solve_elasticnet,
      * /root/reference/src/common.c:2228-2294; collective.c:3571-3931); TransCtCinvCt_pre must be NULL */
     real_t l1_lam, real_t l1_lam_bias);
+/* The same with the remaining inputs of the explicit model's new rows (implicit: they must be NULL):
+ * weight: observation weights of sparse X, one per entry in the order of the triplets / of Xcsr; every entry's rank-1 term
+ *   and right-hand side are weighted, and under scale_lam the row's lambda multiplier is the sum of its weights
+ *   (src/common.c:693-715; a row whose sum is below the type's epsilon comes out as zeros).
+ * Xfull [m_x, n], NaN = not observed, instead of the sparse forms (both: return 2), weight_full [m_x, n] its weights, read
+ *   only where Xfull is present.  The block is compacted on the device into the triplets of its present entries
+ *   (dense_rows_device.hpp), glob_mean_full subtracted there, in blocks of rows of at most 1 GB; a row solves on its present
+ *   entries, a row of NaN is a row without observations.
+ * Bi [n, k+k_main]: implicit features.  Every row system gets BiTBi on the X block and w_implicit * sum_{j observed} Bi_j
+ *   on the right-hand side (src/collective.c:1704-1707, :1757-1771), rows without observations included (no "cold"
+ *   solution).  BiTBi_pre replaces w_implicit_gram * Bi^T Bi, built on the device otherwise -- two weights because the
+ *   reference's batch driver builds the matrix before the row function divides w_implicit by w_main (:11016-11020, :3706-3714).
+ * TransBtBinvBt_pre [n, k+k_main (+1 with biasA)]: without weights, nonneg, L1, side information and Bi the rows of Xfull
+ *   without a NaN are (x - glob_mean_full - biasB)^T TransBtBinvBt (src/common.c:736-758), whatever lambda it was built with. */
+int cmfrec_hip_factors_multiple_ex(
+    real_t *A, real_t *biasA, int_t m_x, int_t m_u, int_t p, const real_t *U, const real_t *U_colmeans,
+    const int_t ixA[], const int_t ixB[], const real_t *X, size_t nnz,
+    const size_t Xcsr_p[], const int_t Xcsr_i[], const real_t *Xcsr,
+    const real_t *B, int_t n, const real_t *C, const real_t *biasB,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t lam_bias, real_t lam_x, real_t w_user,
+    bool implicit, bool scale_lam, bool scale_lam_sideinfo, bool scale_bias_const,
+    const real_t *BtB_pre, const real_t *TransCtCinvCt_pre,
+    const int_t U_row[], const int_t U_col[], const real_t *U_sp, size_t nnz_U,
+    const size_t U_csr_p[], const int_t U_csr_i[], const real_t *U_csr,
+    bool nonneg, real_t l1_lam, real_t l1_lam_bias,
+    const real_t *weight, const real_t *Xfull, const real_t *weight_full, real_t glob_mean_full,
+    const real_t *Bi, real_t w_implicit, real_t w_implicit_gram, const real_t *BiTBi_pre,
+    const real_t *TransBtBinvBt_pre);
 
 /* Replace factors_collective_explicit_multiple / factors_collective_implicit_multiple,
  * /root/reference/src/cmfrec.h:2004-2047 and :2048-2071 (bodies src/collective.c:10865-11174, :11176-11340): same
@@ -241,9 +270,16 @@ int cmfrec_hip_factors_multiple_l1(
  * (COO or CSR), dense U without NaN (rows beyond m get the side-information-only solution, rows beyond m_u the plain
  * one), user bias, lam_unique, scale_lam / scale_lam_sideinfo / scale_bias_const, w_main / w_user, alpha and
  * apply_log_transf; sparse side information (COO or CSR; not together with scale_lam_sideinfo in the explicit
- * version).  NA_as_zero, L1, weights, dense X, binary side information and implicit features return 2; nonneg is
- * supported (solve_nonneg on every row system).  Of the precomputed matrices only BtB (implicit) and TransCtCinvCt (explicit) are read -- the
- * ones that change the result; the others are rebuilt on the device from B and C.
+ * version); nonneg (solve_nonneg on every row system) and L1 penalties (not both).  The explicit version also takes
+ * Xfull [m, n] with NaN = missing instead of the sparse forms (both: 2), weight (per triplet, in the order of Xcsr, or
+ * [m, n] with Xfull) and Bi with add_implicit_features (BiTBi read when given, else w_implicit Bi^T Bi built on the
+ * device; the right-hand side carries w_implicit / w_main, as in the reference) -- see cmfrec_hip_factors_multiple_ex.
+ * Returned with 2: NA_as_zero_X / _U, binary side information, NaN in U, and the combinations in which the reference's
+ * own rows are not the solution of the model: weights of a sparse X with side information or
+ * implicit features together with glob_mean / biasB; a dense row without observations together with U and U_colmeans.
+ * Of the precomputed matrices BtB (implicit), TransCtCinvCt, TransBtBinvBt (complete dense rows of the model without
+ * side information) and BiTBi are read -- the ones that change the result; the others (BtB of the explicit model
+ * among them) are rebuilt on the device from B and C.
  * Two details of the reference that are kept: (1) without a precomputed BtB the implicit version puts the lam of the
  * call, *not* lam / w_main, on the diagonal of the X block (collective.c:11270-11280) while the k_user block gets
  * lam / w_main; (2) the side-information-only solution of the explicit version under scale_lam_sideinfo scales lam by
@@ -651,6 +687,10 @@ int cmfrec_hip_selftest_lanes(void);
    the library's own MFMA kernel and of rocBLAS (loaded at run time if it is there; -1 and a plain reference kernel otherwise),
    largest difference of the two results relative to the largest entry */
 int cmfrec_hip_gemm_probe(int M, int N, int K, int transa, int reps, double *ms_own, double *ms_rocblas, double *max_rel_diff);
+/* timing probe of the compaction of a dense batch of new rows (dense_rows_device.hpp) on a seeded [rows, n] block with the given
+   fraction of present entries: device-event milliseconds per run of the count kernel and of the write kernel over `reps` runs
+   after a warm-up run each; nnz: the present entries found */
+int cmfrec_hip_dense_rows_probe(int rows, int n, double present, int reps, double *ms_count, double *ms_write, size_t *nnz);
 /* The symmetric eigen-decomposition the low-rank row path runs once per half-step on w C^T C (replaces what the reference gets
  * from a k_t x k_t dposv per row, src/collective.c:1823, for rows of few entries): A [n, n] symmetric (2 <= n <= 320) ->
  * Q [n, n] with Q[i][c] = component i of eigenvector c, lam [n] clamped at zero.  method 0: Householder tridiagonalisation +
