@@ -371,6 +371,39 @@ struct PassAcc<float> {
     }
 };
 
+// The next row's gather in the registers the last CG step frees (an A/B build): in the peeled final step of a resident
+// row, slot t of the tile is dead once its S products of the second tile product have issued, and the next row's indices are
+// already in registers -- so the S loads of the next row's slot t go out right there and land while this row finishes (the Gramian
+// product, the reductions, the exchange, the quotient, the update).  Same loads, only earlier.
+// Default 0 -- the gather is issued at the top of the row; the peeled final step is in both builds.  The row kernels fill their
+// register budgets with the tile dying at the end of the row (168 of 168, 238-256 of 256); carried through the row's tail and
+// the next row's head the tile meets what used its registers there, and every double-precision k = 50 instantiation spills
+// (88-372 bytes per lane, the arriving slots first: a wait per load).  make OUTDIR=../lib_early EXTRA=-DCMF_CG_EARLY_GATHER=1.
+#ifndef CMF_CG_EARLY_GATHER
+#define CMF_CG_EARLY_GATHER 0
+#endif
+// what a tile product calls after the second product's last use of slot t (tag: std::integral_constant<int, t>): nothing, or the
+// loads of the next row's slot t
+struct NoAfter {
+    template <typename TAG> __device__ __forceinline__ void operator()(TAG) const {}
+};
+// The accumulators of a tile product pinned where they stand: without it the compiler sinks the products of slot t below the
+// next row's loads (nothing there reads them), the old slot stays live and the new one is spilled as it arrives.
+template <int S, typename ACC>
+__device__ __forceinline__ void pin_acc(ACC &out)
+{
+#pragma unroll
+    for (int s = 0; s < S; s++) asm volatile("" : "+v"(out.v[s]));
+}
+// the S loads of one slot of a register tile from the row `it` of the opposing factors (base: B + ll in bytes, see load_tile)
+template <int TS, typename T, int S, typename TILE>
+__device__ __forceinline__ void load_tile_slot(TILE &tile, const char *base, unsigned ldb_bytes, unsigned it, int col_last)
+{
+    const T *rp = reinterpret_cast<const T *>(base + (unsigned long long)it * ldb_bytes);
+#pragma unroll
+    for (int s = 0; s < S; s++) tile.set(TS, s, rp[(s < S - 1) ? 8 * s : col_last]);
+}
+
 // Branch-free (like load_tile4 below): slots past the end of the tile re-read the row of the tile's first entry (their
 // weight w_j is forced to zero by `valid`), factor columns past k re-read column k-1 (their vrep / Gramian entries are
 // zero and the result lanes >= k are cleared).  One v_mad_u64_u32 per gathered row forms its address.
@@ -434,9 +467,9 @@ __device__ __forceinline__ T entry_weight(const CgParams<T> &P, size_t pos)
 
 // INIT (round 6): the pass accumulators are DEFINED by this call (first products as multiplications) instead of cleared beforehand and
 // accumulated into -- the S (double) / S (packed single) clearing moves per pass go; the unused slots S .. 7 are cleared here.
-template <int S, bool IMPLICIT, int MODE, int NT = 8, bool INIT = false>
+template <int S, bool IMPLICIT, int MODE, int NT = 8, bool INIT = false, typename AFTER = NoAfter>
 __device__ __forceinline__ void tile_pass_f32(const RegTile<float, S> &tile, const float (&vrep)[S], float x, bool valid,
-                                          PassAcc<float> &out, int lane, float g = 1.f)
+                                          PassAcc<float> &out, int lane, float g = 1.f, AFTER after = AFTER())
 {
     static_assert(NT % 2 == 0, "single precision: the entries of a lane group travel in pairs");
     float c[8];
@@ -453,11 +486,24 @@ __device__ __forceinline__ void tile_pass_f32(const RegTile<float, S> &tile, con
     wts[0] = lanes::bcast8<0>(w); wts[1] = lanes::bcast8<1>(w); wts[2] = lanes::bcast8<2>(w); wts[3] = lanes::bcast8<3>(w);
     if (NT > 4) { wts[4] = lanes::bcast8<4>(w); wts[5] = lanes::bcast8<5>(w); }
     if (NT > 6) { wts[6] = lanes::bcast8<6>(w); wts[7] = lanes::bcast8<7>(w); }
+    if constexpr (std::is_same<AFTER, NoAfter>::value) {
 #pragma unroll
     for (int q = 0; q < NT / 2; q++) {
         const f32x2 w2 = f32x2{wts[2 * q], wts[2 * q + 1]};
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] = (INIT && q == 0) ? w2 * tile.v[q][s] : out.v[s] + w2 * tile.v[q][s];
+    }
+    } else {
+        // (the pair q of slots is dead behind its S packed products)
+        static_for<0, NT / 2>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            const f32x2 w2 = f32x2{wts[2 * q], wts[2 * q + 1]};
+#pragma unroll
+            for (int s = 0; s < S; s++) out.v[s] = (INIT && q == 0) ? w2 * tile.v[q][s] : out.v[s] + w2 * tile.v[q][s];
+            pin_acc<S>(out);
+            after(std::integral_constant<int, 2 * q>{});
+            after(std::integral_constant<int, 2 * q + 1>{});
+        });
     }
     if constexpr (INIT) {
 #pragma unroll
@@ -465,12 +511,12 @@ __device__ __forceinline__ void tile_pass_f32(const RegTile<float, S> &tile, con
     }
 }
 
-template <typename T, int S, bool IMPLICIT, int MODE, int NT = 8, bool INIT = false>
+template <typename T, int S, bool IMPLICIT, int MODE, int NT = 8, bool INIT = false, typename AFTER = NoAfter>
 __device__ __forceinline__ void tile_pass(const RegTile<T, S> &tile, const T (&vrep)[S], T x, bool valid,
-                                          PassAcc<T> &out, int lane, T g = T(1))
+                                          PassAcc<T> &out, int lane, T g = T(1), AFTER after = AFTER())
 {
     if constexpr (std::is_same<T, float>::value) {
-        tile_pass_f32<S, IMPLICIT, MODE, NT, INIT>(tile, vrep, x, valid, out, lane, g);
+        tile_pass_f32<S, IMPLICIT, MODE, NT, INIT, AFTER>(tile, vrep, x, valid, out, lane, g, after);
     } else {
     T c[8];
 #pragma unroll
@@ -488,10 +534,20 @@ __device__ __forceinline__ void tile_pass(const RegTile<T, S> &tile, const T (&v
     if (NT > 5) wts[5] = lanes::bcast8<5>(w);
     if (NT > 6) wts[6] = lanes::bcast8<6>(w);
     if (NT > 7) wts[7] = lanes::bcast8<7>(w);
+    if constexpr (std::is_same<AFTER, NoAfter>::value) {
 #pragma unroll
     for (int t = 0; t < NT; t++) {
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] = (INIT && t == 0) ? wts[t] * tile.v[t][s] : out.v[s] + wts[t] * tile.v[t][s];
+    }
+    } else {
+        static_for<0, NT>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+#pragma unroll
+            for (int s = 0; s < S; s++) out.v[s] = (INIT && t == 0) ? wts[t] * tile.v[t][s] : out.v[s] + wts[t] * tile.v[t][s];
+            pin_acc<S>(out);
+            after(tc);
+        });
     }
     if constexpr (INIT) {
 #pragma unroll
@@ -704,6 +760,50 @@ cg_rows_kernel(const CgParams<T> P)
     RowDesc dnxt = load_desc(rnxt);
     Pre pcur = load_pre(dcur);
     int pend = issue_claim();      // the position after rnn; lands while this row is solved
+    // The wavefront's tile(s) are carried from row to row (CMF_CG_EARLY_GATHER): the gather of row i + 1 is issued inside the final
+    // CG step of row i, slot by slot into the registers that step has just released (behind the step loop where the row left it
+    // early or is not resident; in front of the row loop for the team's first row).  The next row's tile size is not this
+    // row's: the slot loop is bounded by the wave-uniform number of slots the next row has (none: no next row, or no entries of
+    // it for this wavefront), NT_MAX what a row of this launch can have at most.
+    constexpr bool EARLY = CMF_CG_EARLY_GATHER != 0;
+    constexpr int NT_MAX = (NTSEL == 1) ? CG_NT_LOW : 8;
+    RegTile<T, S> tile_c;
+    RegTile<T, (NRES == 2) ? S : 1> tile2_c;     // second resident tile (entries (wr + W) * TL ...)
+    const char *const gbase = reinterpret_cast<const char *>(P.B + (lane & 7));
+    const unsigned gldb = (unsigned)(P.ldb * sizeof(T));
+    const int gcol_last = min((lane & 7) + 8 * (S - 1), k - 1) - (lane & 7);
+    // slot t of a tile of the row whose tile has `nt` entries per lane group, `cnt` entries in all and the lane's index `idx`
+    // (the addresses of load_tile; nt = 0: nothing to load)
+    auto gather_slot = [&](auto &tl_, auto tc, int idx_, int first_idx_, int nt_, int cnt_) {
+        constexpr int t = decltype(tc)::value;
+        if constexpr (t < NT_MAX) {
+            if (t < nt_) {
+                const unsigned it_ = (unsigned)((((lane >> 3) * nt_ + t) < cnt_) ? lanes::bcast8<t>(idx_) : first_idx_);
+                load_tile_slot<t, T, S>(tl_, gbase, gldb, it_, gcol_last);
+            }
+        }
+    };
+    // what this wavefront gathers for the row (d, q): slots per tile (0: none) and entries of its first and second tile
+    struct Want { int nt0, cnt0, nt1, cnt1; };
+    auto want_of = [&](const RowDesc &d) -> Want {
+        Want w_;
+        const int nt = nt_of(d.nnz), tl = 8 * nt;
+        w_.cnt0 = min(tl, d.nnz - wr * tl);
+        w_.nt0 = (w_.cnt0 > 0 && !CMF_DBG(P, 1)) ? nt : 0;
+        w_.cnt1 = (NRES == 2) ? min(tl, d.nnz - (wr + W) * tl) : 0;
+        w_.nt1 = (w_.cnt1 > 0 && !CMF_DBG(P, 1)) ? nt : 0;
+        return w_;
+    };
+    auto gather_row = [&](const RowDesc &d, const Pre &q) {
+        const Want w_ = want_of(d);
+        const int f0 = __builtin_amdgcn_readfirstlane(q.idx);
+        static_for<0, NT_MAX>([&](auto tc) { gather_slot(tile_c, tc, q.idx, f0, w_.nt0, w_.cnt0); });
+        if constexpr (NRES == 2) {
+            const int f1 = __builtin_amdgcn_readfirstlane(q.idx2);
+            static_for<0, NT_MAX>([&](auto tc) { gather_slot(tile2_c, tc, q.idx2, f1, w_.nt1, w_.cnt1); });
+        }
+    };
+    if constexpr (EARLY) gather_row(dcur, pcur);
 #ifdef CMF_CG_TICKS
     unsigned long long tk_wait = 0, tk_pass = 0, tk_rows = 0;
     const unsigned long long tk_begin = CMF_TICK();
@@ -737,8 +837,12 @@ cg_rows_kernel(const CgParams<T> P)
         T *arow = P.A + (size_t)row * P.lda;
         T a_d = pcur.a;
 
-        // first tile of this wave: gather now (critical path), then start the next row's loads
-        RegTile<T, S> tile;
+        // first tile of this wave: in flight since the previous row (or gathered now -- critical path), then start the next row's loads
+        // (the late build keeps its tiles local to the row: carried registers stay live in the slots a row does not use)
+        RegTile<T, S> tile_r;
+        RegTile<T, (NRES == 2) ? S : 1> tile2_r;
+        auto &tile = [&]() -> RegTile<T, S> & { if constexpr (EARLY) return tile_c; else return tile_r; }();
+        auto &tile2 = [&]() -> RegTile<T, (NRES == 2) ? S : 1> & { if constexpr (EARLY) return tile2_c; else return tile2_r; }();
         const int ent = (lane >> 3) * NT + (lane & 7);     // this lane's entry of the tile (lanes with (lane & 7) >= NT: none)
         const bool lane_has = (NT == 8) || (lane & 7) < NT;
         const int cnt0 = min(TL, nnz - wr * TL);
@@ -746,13 +850,12 @@ cg_rows_kernel(const CgParams<T> P)
         const T g_res = pcur.g;
         bool valid_res = lane_has && ent < cnt0;
         if (CMF_DBG(P, 1)) dbg_fill_tile<8, S>(tile, (T)(pcur.idx & 3) * (T)0.001);
-        else if (cnt0 > 0) load_tile<T, S, NT>(tile, P.B, P.ldb, k, pcur.idx, cnt0, lane);
-        RegTile<T, (NRES == 2) ? S : 1> tile2;       // second resident tile (entries (wr + W) * TL ...)
+        else if (!EARLY && cnt0 > 0) load_tile<T, S, NT>(tile, P.B, P.ldb, k, pcur.idx, cnt0, lane);
         const int cnt1 = (NRES == 2) ? min(TL, nnz - (wr + W) * TL) : 0;
         const T x2_res = pcur.x2, g2_res = pcur.g2;
         const bool valid2_res = lane_has && ent < cnt1;
         if constexpr (NRES == 2) {
-            if (cnt1 > 0 && !CMF_DBG(P, 1)) load_tile<T, S, NT>(tile2, P.B, P.ldb, k, pcur.idx2, cnt1, lane);
+            if (!EARLY && cnt1 > 0 && !CMF_DBG(P, 1)) load_tile<T, S, NT>(tile2, P.B, P.ldb, k, pcur.idx2, cnt1, lane);
         }
         dnn = load_desc(rnn);
         pnxt = load_pre(dnxt);
@@ -763,8 +866,10 @@ cg_rows_kernel(const CgParams<T> P)
         tk_wait += tk1 - tk0;
 #endif
 
-        auto run_pass = [&](T vdist, auto mode_tag, bool first) -> T {
+        // FIN: the pass of the peeled final step -- the tile registers are not read after it
+        auto run_pass = [&](T vdist, auto mode_tag, bool first, auto fin_tag) -> T {
             constexpr int MODE = decltype(mode_tag)::value;
+            constexpr bool FIN = decltype(fin_tag)::value && EARLY;
             // keep the staged Gramian in LDS: without this the compiler hoists its 8*S loads per
             // lane out of the pass / row loops and pins 16*S VGPRs (occupancy 2 -> 1 wave/SIMD)
             asm volatile("" ::: "memory");
@@ -774,6 +879,40 @@ cg_rows_kernel(const CgParams<T> P)
             else replicate<T, S>(vdist, vrep, lane);
             PassAcc<T> acc;
             acc.zero();
+            if constexpr (FIN) {
+                if (NT < 8 || NRES == 2 || resident) {
+                    // the next row's slots follow this row's last use of theirs; a wavefront without entries of this row has
+                    // nothing to wait for
+                    const Want nx = want_of(dnxt);
+                    const int f0 = __builtin_amdgcn_readfirstlane(pnxt.idx);
+                    auto after0 = [&](auto tc) { gather_slot(tile, tc, pnxt.idx, f0, nx.nt0, nx.cnt0); };
+                    if (cnt0 > 0 && !CMF_DBG(P, 4)) {
+                        tile_pass<T, S, IMPLICIT, MODE, NT>(tile, vrep, x_res, valid_res, acc, lane, g_res, after0);
+                        static_for<NT, NT_MAX>(after0);
+                    } else static_for<0, NT_MAX>(after0);
+                    if constexpr (NRES == 2) {
+                        const int f1 = __builtin_amdgcn_readfirstlane(pnxt.idx2);
+                        auto after1 = [&](auto tc) { gather_slot(tile2, tc, pnxt.idx2, f1, nx.nt1, nx.cnt1); };
+                        if (cnt1 > 0 && !CMF_DBG(P, 4)) {
+                            tile_pass<T, S, IMPLICIT, MODE, NT>(tile2, vrep, x2_res, valid2_res, acc, lane, g2_res, after1);
+                            static_for<NT, NT_MAX>(after1);
+                        } else static_for<0, NT_MAX>(after1);
+                    }
+                } else {
+                for (int tl = wr; tl < ntiles; tl += W) {       // (not resident: NT = 8, every tile is gathered for this pass)
+                    const int cnt = min(TL, nnz - tl * TL);
+                    const bool valid = lane_has && ent < cnt;
+                    const size_t pos = st + (size_t)tl * TL + ent;
+                    int my_idx = valid ? P.indices[pos] : 0;
+                    T x = valid ? P.values[pos] : T(0);
+                    const T g = valid ? entry_weight<T, IMPLICIT>(P, pos) : T(1);
+                    if (!IMPLICIT && P.bias_sub != nullptr && valid) x -= P.bias_sub[my_idx];
+                    if (!CMF_DBG(P, 1)) load_tile<T, S, NT>(tile, P.B, P.ldb, k, my_idx, cnt, lane);
+                    if (!CMF_DBG(P, 4)) tile_pass<T, S, IMPLICIT, MODE, NT>(tile, vrep, x, valid, acc, lane, g);
+                }
+                gather_row(dnxt, pnxt);       // (behind the last pass over the row's tiles)
+                }
+            } else
             if constexpr (NRES == 2) {
                 // both tiles of the wave are resident: the launch holds rows of at most 2 * W * 64 = 1024 entries (the host
                 // keeps the split-row boundary at or below that in single precision)
@@ -824,7 +963,7 @@ cg_rows_kernel(const CgParams<T> P)
         };
 
         // ---- residual (common.c:1932-1943 / :1112-1139) ----
-        T r_d = run_pass(a_d, std::integral_constant<int, 0>{}, true);
+        T r_d = run_pass(a_d, std::integral_constant<int, 0>{}, true, std::false_type{});
         r_d -= lam * a_d;
         if (!IMPLICIT && lam != lam_last && lane == k - 1) r_d -= (lam_last - lam) * a_d;
         if (GRAMX && P.rconst != nullptr && lane < k) r_d += P.rconst[(size_t)row * P.ldr + lane];
@@ -834,13 +973,18 @@ cg_rows_kernel(const CgParams<T> P)
         // r_old / r_new are bit-identical on every wave of the team (same LDS partials summed in
         // the same order), so the data-dependent exits below are uniform over the workgroup.
         bool done = (r_old <= (T)1e-12);            // common.c:1952 / :1147
-        for (int step = 0; step < P.max_cg_steps && !done; step++) {
-            T Ap_d = run_pass(p_d, std::integral_constant<int, 1>{}, false);
+        // max_cg_steps - 1 full steps, then the final one peeled: only a_d += alpha p_d of it is ever read -- the residual update,
+        // its wave sum, the comparison, the second quotient and the new direction (one dependent chain) are left out
+        // (the late build leaves the step loop behind the final step's update instead of repeating the pass's code behind the loop:
+        //  the same instructions executed, and the register allocation of the kernels as it was)
+        for (int step = 0; step < P.max_cg_steps - (EARLY ? 1 : 0) && !done; step++) {
+            T Ap_d = run_pass(p_d, std::integral_constant<int, 1>{}, false, std::false_type{});
             Ap_d += lam * p_d;
             if (!IMPLICIT && lam != lam_last && lane == k - 1) Ap_d += (lam_last - lam) * p_d;
             if (lane >= k) Ap_d = T(0);
             T alpha = CMF_DBG(P, 8) ? T(0.001) : cg_div(r_old, wave_sum(Ap_d * p_d));
             a_d += alpha * p_d;
+            if (!EARLY && step == P.max_cg_steps - 1) break;
             r_d -= alpha * Ap_d;
             T r_new = CMF_DBG(P, 8) ? T(0.5) : wave_sum(r_d * r_d);
             if (r_new <= (T)1e-8) done = true;      // common.c:1979 / :1180
@@ -849,10 +993,18 @@ cg_rows_kernel(const CgParams<T> P)
                 r_old = r_new;
             }
         }
-        if (wr == 0 && lane < k) arow[lane] = a_d;
+        if (EARLY && P.max_cg_steps > 0 && !done) {
+            T Ap_d = run_pass(p_d, std::integral_constant<int, 1>{}, false, std::true_type{});
+            Ap_d += lam * p_d;
+            if (!IMPLICIT && lam != lam_last && lane == k - 1) Ap_d += (lam_last - lam) * p_d;
+            if (lane >= k) Ap_d = T(0);
+            const T alpha = CMF_DBG(P, 8) ? T(0.001) : cg_div(r_old, wave_sum(Ap_d * p_d));
+            a_d += alpha * p_d;
+        } else if constexpr (EARLY) gather_row(dnxt, pnxt);      // (the row left the step loop early: the next row's gather starts here)
 #ifdef CMF_CG_TICKS
         tk_pass += CMF_TICK() - tk1; tk_rows += (wr == 0);
 #endif
+        if (wr == 0 && lane < k) arow[lane] = a_d;
     };
     for (; rix < P.nrows; it++) {
         const int nt = nt_of(dcur.nnz);      // uniform over the team
@@ -949,9 +1101,9 @@ __device__ __forceinline__ T treduce4_low(const T (&v)[4], int lane)
 }
 
 // (TILE: a RegTile4, or a RegTile whose first four entries per lane group are used -- the mixed launch of the pair kernel)
-template <int S, bool IMPLICIT, int MODE, typename TILE, bool INIT = false>
+template <int S, bool IMPLICIT, int MODE, typename TILE, bool INIT = false, typename AFTER = NoAfter>
 __device__ __forceinline__ void tile_pass4_f32(const TILE &tile, const float (&vrep)[S], float x, bool valid,
-                                           PassAcc<float> &out, int lane, float g = 1.f)
+                                           PassAcc<float> &out, int lane, float g = 1.f, AFTER after = AFTER())
 {
     float c[4];
 #pragma unroll
@@ -965,11 +1117,23 @@ __device__ __forceinline__ void tile_pass4_f32(const TILE &tile, const float (&v
     const float w = pass_weight<float, IMPLICIT, MODE>(coef, x, valid, g);
     float wts[4];
     wts[0] = lanes::bcast8<0>(w); wts[1] = lanes::bcast8<2>(w); wts[2] = lanes::bcast8<4>(w); wts[3] = lanes::bcast8<6>(w);
+    if constexpr (std::is_same<AFTER, NoAfter>::value) {
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         const f32x2 w2 = f32x2{wts[2 * q], wts[2 * q + 1]};
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] = (INIT && q == 0) ? w2 * tile.v[q][s] : out.v[s] + w2 * tile.v[q][s];
+    }
+    } else {
+        static_for<0, 2>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            const f32x2 w2 = f32x2{wts[2 * q], wts[2 * q + 1]};
+#pragma unroll
+            for (int s = 0; s < S; s++) out.v[s] = (INIT && q == 0) ? w2 * tile.v[q][s] : out.v[s] + w2 * tile.v[q][s];
+            pin_acc<S>(out);
+            after(std::integral_constant<int, 2 * q>{});
+            after(std::integral_constant<int, 2 * q + 1>{});
+        });
     }
     if constexpr (INIT) {
 #pragma unroll
@@ -977,12 +1141,12 @@ __device__ __forceinline__ void tile_pass4_f32(const TILE &tile, const float (&v
     }
 }
 
-template <typename T, int S, bool IMPLICIT, int MODE, typename TILE, bool INIT = false>
+template <typename T, int S, bool IMPLICIT, int MODE, typename TILE, bool INIT = false, typename AFTER = NoAfter>
 __device__ __forceinline__ void tile_pass4(const TILE &tile, const T (&vrep)[S], T x, bool valid,
-                                           PassAcc<T> &out, int lane, T g = T(1))
+                                           PassAcc<T> &out, int lane, T g = T(1), AFTER after = AFTER())
 {
     if constexpr (std::is_same<T, float>::value) {
-        tile_pass4_f32<S, IMPLICIT, MODE, TILE, INIT>(tile, vrep, x, valid, out, lane, g);
+        tile_pass4_f32<S, IMPLICIT, MODE, TILE, INIT, AFTER>(tile, vrep, x, valid, out, lane, g, after);
     } else {
     T c[4];
 #pragma unroll
@@ -996,10 +1160,20 @@ __device__ __forceinline__ void tile_pass4(const TILE &tile, const T (&vrep)[S],
     const T w = pass_weight<T, IMPLICIT, MODE>(coef, x, valid, g);
     T wts[4];
     wts[0] = lanes::bcast8<0>(w); wts[1] = lanes::bcast8<2>(w); wts[2] = lanes::bcast8<4>(w); wts[3] = lanes::bcast8<6>(w);
+    if constexpr (std::is_same<AFTER, NoAfter>::value) {
 #pragma unroll
     for (int t = 0; t < 4; t++) {
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] = (INIT && t == 0) ? wts[t] * tile.v[t][s] : out.v[s] + wts[t] * tile.v[t][s];
+    }
+    } else {
+        static_for<0, 4>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+#pragma unroll
+            for (int s = 0; s < S; s++) out.v[s] = (INIT && t == 0) ? wts[t] * tile.v[t][s] : out.v[s] + wts[t] * tile.v[t][s];
+            pin_acc<S>(out);
+            after(tc);
+        });
     }
     if constexpr (INIT) {
 #pragma unroll
@@ -1054,9 +1228,9 @@ __device__ __forceinline__ T treduce2_low(const T (&v)[2], int lane)
     return u + lanes::xor1(u);          // lanes 4t .. 4t+3 hold the total of v[t]
 }
 
-template <typename T, int S, bool IMPLICIT, int MODE, typename TILE, bool INIT = false>
+template <typename T, int S, bool IMPLICIT, int MODE, typename TILE, bool INIT = false, typename AFTER = NoAfter>
 __device__ __forceinline__ void tile_pass2(const TILE &tile, const T (&vrep)[S], T x, bool valid,
-                                           PassAcc<T> &out, int lane, T g = T(1))
+                                           PassAcc<T> &out, int lane, T g = T(1), AFTER after = AFTER())
 {
     T c[2];
     if constexpr (std::is_same<T, float>::value) {
@@ -1080,6 +1254,9 @@ __device__ __forceinline__ void tile_pass2(const TILE &tile, const T (&vrep)[S],
         const f32x2 w2 = f32x2{w0, w1};
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] = INIT ? w2 * tile.pair0(s) : out.v[s] + w2 * tile.pair0(s);
+        if constexpr (!std::is_same<AFTER, NoAfter>::value) pin_acc<S>(out);
+        after(std::integral_constant<int, 0>{});
+        after(std::integral_constant<int, 1>{});
         if constexpr (INIT) {
 #pragma unroll
             for (int s = S; s < 8; s++) out.v[s] = f32x2{0.f, 0.f};
@@ -1087,8 +1264,12 @@ __device__ __forceinline__ void tile_pass2(const TILE &tile, const T (&vrep)[S],
     } else {
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] = INIT ? w0 * tile.get(0, s) : out.v[s] + w0 * tile.get(0, s);
+        if constexpr (!std::is_same<AFTER, NoAfter>::value) pin_acc<S>(out);
+        after(std::integral_constant<int, 0>{});
 #pragma unroll
         for (int s = 0; s < S; s++) out.v[s] += w1 * tile.get(1, s);
+        if constexpr (!std::is_same<AFTER, NoAfter>::value) pin_acc<S>(out);
+        after(std::integral_constant<int, 1>{});
         if constexpr (INIT) {
 #pragma unroll
             for (int s = S; s < 8; s++) out.v[s] = T(0);
@@ -1247,9 +1428,41 @@ cg_rows_tiny_kernel(const CgParams<T> P)
         if constexpr (NE != 2) load_tile4<T, S>(t_, Bm_, ldb_, k_, idx_, cnt_, lane_);
         else load_tile2<T, S>(t_, Bm_, ldb_, k_, idx_, cnt_, lane_);
     };
-    // CG on one register-resident 32-nnz tile (same arithmetic as cg_rows_kernel)
-    auto solve = [&](const RowDesc &d, const Pre &pr, const Tile &tile, auto short_tag) {
+    // The next row's gather into the single tile buffer of the dynamically scheduled loop (CMF_CG_EARLY_GATHER, see cg_rows_kernel):
+    // slot t of the row (d, q) -- of its 32-slot tile (four entries per lane group, index in the lanes 2t, 2t+1 of the group) or its
+    // 16-slot tile (two, lanes 4t .. 4t+3); which one is uniform over the wavefront.  Rows without entries load nothing.
+    constexpr bool EARLY = CMF_CG_EARLY_GATHER != 0 && CMF_TINY_WAVES_PER_SIMD >= 3;
+    constexpr int NE_MAX = (NE == 2) ? 2 : 4;
+    const char *const gbase = reinterpret_cast<const char *>(P.B + (lane & 7));
+    const unsigned gldb = (unsigned)(P.ldb * sizeof(T));
+    const int gcol_last = min((lane & 7) + 8 * (S - 1), k - 1) - (lane & 7);
+    auto gather_slot = [&](Tile &tl_, auto tc, int idx_, int first_idx_, int ne_, int cnt_) {
+        constexpr int t = decltype(tc)::value;
+        if constexpr (t < NE_MAX) {
+            if (t < ne_) {
+                int its;
+                if constexpr (NE == 2) its = lanes::bcast8<(4 * t) & 7>(idx_);
+                else if constexpr (!MIX || t != 1) its = lanes::bcast8<(t == 0) ? 0 : (t == 2) ? 4 : (t == 3) ? 6 : 2>(idx_);
+                else its = (ne_ == 2) ? lanes::bcast8<4>(idx_) : lanes::bcast8<2>(idx_);
+                const unsigned it_ = (unsigned)((((lane >> 3) * ne_ + t) < cnt_) ? its : first_idx_);
+                load_tile_slot<t, T, S>(tl_, gbase, gldb, it_, gcol_last);
+            }
+        }
+    };
+    auto slots_of = [&](const RowDesc &d) -> int {
+        if (d.nnz <= 0 || CMF_DBG(P, 1)) return 0;
+        return (NE == 2 || short_row(d.nnz)) ? 2 : 4;
+    };
+    auto gather_row = [&](Tile &tl_, const RowDesc &d, const Pre &q) {
+        const int ne_ = slots_of(d);
+        const int f0 = __builtin_amdgcn_readfirstlane(q.idx);
+        static_for<0, NE_MAX>([&](auto tc) { gather_slot(tl_, tc, q.idx, f0, ne_, d.nnz); });
+    };
+    // CG on one register-resident 32-nnz tile (same arithmetic as cg_rows_kernel); next_tag: the tile is the loop's single buffer, and
+    // the gather of the row (dn, pn) is issued into it -- in the peeled final step, or behind the step loop when the row left it early
+    auto solve = [&](const RowDesc &d, const Pre &pr, Tile &tile, auto short_tag, auto next_tag, const RowDesc &dn, const Pre &pn) {
         constexpr bool T2 = NE == 2 || decltype(short_tag)::value;      // 16-slot tile (the first two entries of a RegTile4 in the mixed launch)
+        constexpr bool NEXT = decltype(next_tag)::value && EARLY;
         const int nnz = d.nnz;
         T lam = P.lam, lam_last = P.lam_last;
         if (GRAMX && P.kc > 0) {
@@ -1265,17 +1478,30 @@ cg_rows_tiny_kernel(const CgParams<T> P)
         }
         const bool valid = (T2 ? (lane >> 2) : (lane >> 1)) < nnz;
         T a_d = pr.a;
-        auto run_pass = [&](T vdist, auto mode_tag) -> T {
+        auto run_pass = [&](T vdist, auto mode_tag, auto fin_tag) -> T {
             constexpr int MODE = decltype(mode_tag)::value;
+            constexpr bool FIN = decltype(fin_tag)::value && NEXT;      // the pass of the peeled final step: the tile is not read after it
             asm volatile("" ::: "memory");
             T vrep[S];
             T gw[8];
             if constexpr (PV) pass_vector_lds<T, S, GR>(vdist, vrep, gw, lane, &s_pv[tid >> 6][0]);
             else replicate<T, S>(vdist, vrep, lane);
             PassAcc<T> acc;
+            if constexpr (FIN) {
+                const int ne_ = slots_of(dn);
+                const int f0 = __builtin_amdgcn_readfirstlane(pn.idx);
+                auto after = [&](auto tc) { gather_slot(tile, tc, pn.idx, f0, ne_, dn.nnz); };
+                if (!CMF_DBG(P, 4)) {
+                    if constexpr (!T2) tile_pass4<T, S, IMPLICIT, MODE, Tile, true>(tile, vrep, pr.x, valid, acc, lane, pr.g, after);
+                    else {
+                        tile_pass2<T, S, IMPLICIT, MODE, Tile, true>(tile, vrep, pr.x, valid, acc, lane, pr.g, after);
+                        static_for<2, NE_MAX>(after);       // (the slots this row's 16-slot tile did not use)
+                    }
+                } else { acc.zero(); static_for<0, NE_MAX>(after); }
+            } else
             if (!CMF_DBG(P, 4)) {          // (the accumulators are defined by the tile pass itself: no clearing moves)
-                if constexpr (!T2) tile_pass4<T, S, IMPLICIT, MODE, decltype(tile), true>(tile, vrep, pr.x, valid, acc, lane, pr.g);
-                else tile_pass2<T, S, IMPLICIT, MODE, decltype(tile), true>(tile, vrep, pr.x, valid, acc, lane, pr.g);
+                if constexpr (!T2) tile_pass4<T, S, IMPLICIT, MODE, Tile, true>(tile, vrep, pr.x, valid, acc, lane, pr.g);
+                else tile_pass2<T, S, IMPLICIT, MODE, Tile, true>(tile, vrep, pr.x, valid, acc, lane, pr.g);
             } else acc.zero();
             if constexpr (GREG) {
                 if (!CMF_DBG(P, 2)) {
@@ -1288,7 +1514,7 @@ cg_rows_tiny_kernel(const CgParams<T> P)
             acc.close(out);
             return treduce8_high<T>(out, lane);
         };
-        T r_d = run_pass(a_d, std::integral_constant<int, 0>{});
+        T r_d = run_pass(a_d, std::integral_constant<int, 0>{}, std::false_type{});
         r_d -= lam * a_d;
         if (!IMPLICIT && lam != lam_last && lane == k - 1) r_d -= (lam_last - lam) * a_d;
         if (GRAMX && P.rconst != nullptr && lane < k) r_d += P.rconst[(size_t)d.row * P.ldr + lane];
@@ -1296,13 +1522,15 @@ cg_rows_tiny_kernel(const CgParams<T> P)
         T p_d = r_d;
         T r_old = wave_sum(r_d * r_d);
         bool done = (r_old <= (T)1e-12);
-        for (int step = 0; step < P.max_cg_steps && !done; step++) {
-            T Ap_d = run_pass(p_d, std::integral_constant<int, 1>{});
+        // (the final step is peeled as in cg_rows_kernel: only a_d += alpha p_d of it is read)
+        for (int step = 0; step < P.max_cg_steps - (NEXT ? 1 : 0) && !done; step++) {
+            T Ap_d = run_pass(p_d, std::integral_constant<int, 1>{}, std::false_type{});
             Ap_d += lam * p_d;
             if (!IMPLICIT && lam != lam_last && lane == k - 1) Ap_d += (lam_last - lam) * p_d;
             if (lane >= k) Ap_d = T(0);
             T alpha = cg_div(r_old, wave_sum(Ap_d * p_d));
             a_d += alpha * p_d;
+            if (!NEXT && step == P.max_cg_steps - 1) break;
             r_d -= alpha * Ap_d;
             T r_new = wave_sum(r_d * r_d);
             if (r_new <= (T)1e-8) done = true;
@@ -1311,6 +1539,14 @@ cg_rows_tiny_kernel(const CgParams<T> P)
                 r_old = r_new;
             }
         }
+        if (NEXT && P.max_cg_steps > 0 && !done) {
+            T Ap_d = run_pass(p_d, std::integral_constant<int, 1>{}, std::true_type{});
+            Ap_d += lam * p_d;
+            if (!IMPLICIT && lam != lam_last && lane == k - 1) Ap_d += (lam_last - lam) * p_d;
+            if (lane >= k) Ap_d = T(0);
+            const T alpha = cg_div(r_old, wave_sum(Ap_d * p_d));
+            a_d += alpha * p_d;
+        } else if constexpr (NEXT) gather_row(tile, dn, pn);      // (the row left the step loop early)
         if (lane < k) P.A[(size_t)d.row * P.lda + lane] = a_d;
     };
 
@@ -1333,10 +1569,13 @@ cg_rows_tiny_kernel(const CgParams<T> P)
         Pre p0 = load_pre(d0);
         Tile tA;
         int pend = issue_claim();
+        if constexpr (EARLY) gather_row(tA, d0, p0);
         while (rix < P.nrows) {
             const bool shrt = short_row(d0.nnz);
             if (CMF_DBG(P, 1)) {
                 dbg_fill_tile<(NE == 2) ? 2 : 4, S>(tA, (T)(p0.idx & 3) * (T)0.001);
+            } else if constexpr (EARLY) {
+                // (in flight since the previous row)
             } else if constexpr (MIX) {
                 if (shrt) load_tile2<T, S>(tA, P.B, P.ldb, k, p0.idx, d0.nnz, lane);
                 else load_tile_ne(tA, P.B, P.ldb, k, p0.idx, d0.nnz, lane);
@@ -1344,9 +1583,9 @@ cg_rows_tiny_kernel(const CgParams<T> P)
             RowDesc d2 = load_desc(rnn);
             Pre p1 = load_pre(d1);
             if constexpr (MIX) {
-                if (shrt) solve(d0, p0, tA, std::true_type{});
-                else solve(d0, p0, tA, std::false_type{});
-            } else solve(d0, p0, tA, std::false_type{});
+                if (shrt) solve(d0, p0, tA, std::true_type{}, std::true_type{}, d1, p1);
+                else solve(d0, p0, tA, std::false_type{}, std::true_type{}, d1, p1);
+            } else solve(d0, p0, tA, std::false_type{}, std::true_type{}, d1, p1);
             const int r3 = cbase + CG_NCOUNTERS * __builtin_amdgcn_readfirstlane(pend);
             d0 = d1; p0 = p1; d1 = d2;
             rix = rnxt; rnxt = rnn; rnn = r3;
@@ -1365,14 +1604,14 @@ cg_rows_tiny_kernel(const CgParams<T> P)
         if (d1.nnz > 0) load_tile_ne(tB, P.B, P.ldb, k, p1.idx, d1.nnz, lane);
         RowDesc d3 = load_desc(rix + 3 * nwaves);
         Pre p2 = load_pre(d2);
-        solve(d0, p0, tA, std::false_type{});
+        solve(d0, p0, tA, std::false_type{}, std::false_type{}, d1, p1);
         rix += nwaves;
         if (rix >= P.nrows) break;
         // row i+1 : buffer B, row i+2: gather into buffer A
         if (d2.nnz > 0) load_tile_ne(tA, P.B, P.ldb, k, p2.idx, d2.nnz, lane);
         RowDesc d4 = load_desc(rix + 3 * nwaves);
         Pre p3 = load_pre(d3);
-        solve(d1, p1, tB, std::false_type{});
+        solve(d1, p1, tB, std::false_type{}, std::false_type{}, d2, p2);
         rix += nwaves;
         d0 = d2; p0 = p2; d1 = d3; p1 = p3; d2 = d4;
     }

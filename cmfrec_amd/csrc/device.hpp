@@ -511,6 +511,52 @@ inline void poison_lds(hipStream_t st, int num_cus)
     HIP_CHECK(hipGetLastError());
 }
 
+// CMFREC_HIP_CG_TEAMS (test hook): a launch of the dynamically scheduled row kernels with fewer teams than rows AND fewer than
+// CG_NCOUNTERS.  The kernels hand out the positions nteams + j + CG_NCOUNTERS c from counter j = team mod CG_NCOUNTERS, which
+// reaches every position only when all counters are in use (or no row is left to claim: what an uncapped launch guarantees).  So
+// the capped launch gets its own descriptor array with the rows, in their order, at the positions its teams do reach -- 0 ..
+// nteams-1, then nteams + j + CG_NCOUNTERS c for j < nteams -- and whatever at the others, which no team reads; the kernels stay as
+// they are.  Host round trip and a synchronise behind the launch (release): a test hook, not a path of a fit.
+struct CappedDesc {
+    RowDesc *dev = nullptr;
+    int nrows = 0;
+    void build(const RowDesc *desc_dev, int count, int nteams, hipStream_t st)
+    {
+        std::vector<RowDesc> h((size_t)count);
+        HIP_CHECK(hipMemcpyAsync(h.data(), desc_dev, (size_t)count * sizeof(RowDesc), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        const int per_round = nteams;                       // positions reached per round of CG_NCOUNTERS
+        const int rest = count - nteams;                    // rows beyond every team's first
+        const int last = nteams + ((rest - 1) / per_round) * CG_NCOUNTERS + (rest - 1) % per_round;
+        nrows = last + 1;
+        RowDesc none; none.row = 0; none.nnz = 0; none.st = 0;
+        std::vector<RowDesc> out((size_t)nrows, none);
+        for (int i = 0; i < count; i++) {
+            const int pos = (i < nteams) ? i : nteams + ((i - nteams) / per_round) * CG_NCOUNTERS + (i - nteams) % per_round;
+            out[(size_t)pos] = h[(size_t)i];
+        }
+        HIP_CHECK(hipMalloc((void **)&dev, (size_t)nrows * sizeof(RowDesc)));
+        HIP_CHECK(hipMemcpyAsync(dev, out.data(), (size_t)nrows * sizeof(RowDesc), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));                // (`out` leaves scope)
+    }
+    void release(hipStream_t st)
+    {
+        if (dev == nullptr) return;
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipFree(dev));
+        dev = nullptr;
+    }
+};
+// the grid of such a launch and whether it needs the array above (teams per workgroup: RPB, or the tiny kernel's four wavefronts)
+inline bool cg_teams_cap(int &grid, int teams_per_block, int count)
+{
+    const int cap = switches().cg_teams;
+    if (cap <= 0) return false;
+    grid = std::min(grid, (cap + teams_per_block - 1) / teams_per_block);
+    const int nteams = grid * teams_per_block;
+    return nteams < CG_NCOUNTERS && nteams < count;
+}
+
 template <int S, bool IMPLICIT, int W, int RPB, bool GRAMX = false, int NRES_ = 0, int NTSEL = 0>
 inline void launch_cg_bin(const DeviceInfo &dev, CgParams<real_t> P, int first, int count, BinTimers *tm, int bin, hipStream_t st, int counter_set = -1)
 {
@@ -541,8 +587,15 @@ inline void launch_cg_bin(const DeviceInfo &dev, CgParams<real_t> P, int first, 
     }
     int teams_needed = (count + RPB - 1) / RPB;
     int grid = std::min(teams_needed, dev.num_cus * blocks_per_cu);
+    CappedDesc capped;
+    if (cg_teams_cap(grid, RPB, count)) {
+        capped.build(P.desc, count, grid * RPB, st);
+        P.desc = capped.dev;
+        P.nrows = capped.nrows;
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), smem, st, P);
     HIP_CHECK(hipGetLastError());
+    capped.release(st);
     if (tm) {
         HIP_CHECK(hipEventRecord(ev.b, st));
         tm->ev[bin].push_back(ev);
@@ -584,8 +637,15 @@ inline void launch_cg_tiny(const DeviceInfo &dev, CgParams<real_t> P, int first,
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, smem));
             blocks_per_cu = std::max(1, nb);
         }
-        const int grid = std::min((count + 3) / 4, dev.num_cus * blocks_per_cu);
+        int grid = std::min((count + 3) / 4, dev.num_cus * blocks_per_cu);
+        CappedDesc capped;
+        if (cg_teams_cap(grid, 4, count)) {
+            capped.build(P1.desc, count, grid * 4, st);
+            P1.desc = capped.dev;
+            P1.nrows = capped.nrows;
+        }
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, P1);
+        capped.release(st);
     }
     HIP_CHECK(hipGetLastError());
     if (tm) {

@@ -68,6 +68,7 @@ struct Switches {
     bool eig_jacobi = false;        // CMFREC_HIP_EIG=jacobi: the one-workgroup Jacobi kernel instead of tridiagonalisation + QL (cross-check)
     int debug_skip = 0;             // CMFREC_HIP_CG_SKIP / _CHOL_SKIP / _WAVE_SKIP (timing builds only: -DCMF_CG_DEBUG / -DCMF_CHOL_DEBUG)
     bool debug_ticks = false;       // CMFREC_HIP_GRAM_TICKS / _CHOL_TICKS (timing builds only)
+    int cg_teams = 0;               // CMFREC_HIP_CG_TEAMS: at most that many teams (rounded up to whole workgroups) in a launch of the dynamically scheduled CG row kernels, so that a small problem gives a team several rows (test hook; 0: by occupancy)
     int newrows_block_rows = 0;     // CMFREC_HIP_NEWROWS_BLOCK_ROWS: rows per device block of a dense batch of new rows (test hook; 0: by the 1 GB budget)
     void reload()
     {
@@ -93,6 +94,7 @@ struct Switches {
         v = str("CMFREC_HIP_EIG"); eig_jacobi = v && strcmp(v, "jacobi") == 0;
         debug_skip = num("CMFREC_HIP_CG_SKIP", num("CMFREC_HIP_CHOL_SKIP", num("CMFREC_HIP_WAVE_SKIP", 0)));
         debug_ticks = str("CMFREC_HIP_GRAM_TICKS") != nullptr || str("CMFREC_HIP_CHOL_TICKS") != nullptr;
+        cg_teams = num("CMFREC_HIP_CG_TEAMS", 0);
         newrows_block_rows = num("CMFREC_HIP_NEWROWS_BLOCK_ROWS", 0);
     }
 };

@@ -466,15 +466,24 @@ gram_cg_kernel(const CgParams<T> P, const GramParams<T> Gp)
             T p = r;
             T r_old = lanes::wave_sum(r * r);
             if (r_old > (T)1e-12) {           // :1952 / :1147
-                for (int step = 0; step < P.max_cg_steps; step++) {
+                // (the final step is peeled as in cg_rows_kernel: only a += alpha p of it is read)
+                bool done = false;
+                for (int step = 0; step < P.max_cg_steps - 1 && !done; step++) {
                     const T Mp = mul(p);
                     const T Ap = live ? Mp : T(0);
                     const T alpha = cg_div(r_old, lanes::wave_sum(Ap * p));
                     a += alpha * p; r -= alpha * Ap;
                     const T r_new = lanes::wave_sum(r * r);
-                    if (r_new <= (T)1e-8) break;              // :1979 / :1180
-                    p = p * cg_div(r_new, r_old) + r;
-                    r_old = r_new;
+                    if (r_new <= (T)1e-8) done = true;        // :1979 / :1180
+                    else {
+                        p = p * cg_div(r_new, r_old) + r;
+                        r_old = r_new;
+                    }
+                }
+                if (P.max_cg_steps > 0 && !done) {
+                    const T Mp = mul(p);
+                    const T Ap = live ? Mp : T(0);
+                    a += cg_div(r_old, lanes::wave_sum(Ap * p)) * p;
                 }
             }
             if (live) arow[lane] = a;
