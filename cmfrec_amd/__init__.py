@@ -4,5 +4,6 @@ from .models import CMF, CMF_implicit  # noqa: F401
 from .session import AlsSession  # noqa: F401
 from . import ops  # noqa: F401
 from .rank import Ranker  # noqa: F401
+from .new_users import NewUsers  # noqa: F401
 
-__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "ops"]
+__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "NewUsers", "ops"]

@@ -33,12 +33,46 @@ class ModelF(C.Structure):
         [(n, C.c_int32) for n in ("row_begin", "row_end", "col_begin", "col_end", "m_x", "n_x")]
 
 
+def _newrows_model_fields(real):
+    return [(n, C.c_int32) for n in (
+        "implicit", "n", "n_max", "include_all_X", "p", "user_bias", "add_implicit_features", "k", "k_user", "k_item", "k_main",
+        "scale_lam", "scale_lam_sideinfo", "scale_bias_const", "nonneg", "apply_log_transf")] + \
+        [(n, real) for n in ("glob_mean", "lam", "l1_lam", "scaling_biasA", "w_main", "w_user", "w_implicit", "alpha",
+                             "w_main_multiplier")] + \
+        [(n, C.c_void_p) for n in ("B", "C", "U_colmeans", "biasB", "Bi", "lam_unique", "l1_lam_unique", "BtB", "TransBtBinvBt",
+                                   "BiTBi", "TransCtCinvCt")]
+
+
+class NewRowsModel(C.Structure):
+    """``cmfrec_hip_newrows_model`` (include/cmfrec_hip.h), double precision."""
+    _fields_ = _newrows_model_fields(C.c_double)
+
+
+class NewRowsModelF(C.Structure):
+    _fields_ = _newrows_model_fields(C.c_float)
+
+
+class NewRowsBatch(C.Structure):
+    """``cmfrec_hip_newrows_batch``: pointers and counts only, the same layout in both precisions."""
+    _fields_ = [("m", C.c_int32), ("m_u", C.c_int32), ("U", C.c_void_p),
+                ("U_row", C.c_void_p), ("U_col", C.c_void_p), ("U_sp", C.c_void_p), ("nnz_U", C.c_size_t),
+                ("U_csr_p", C.c_void_p), ("U_csr_i", C.c_void_p), ("U_csr", C.c_void_p),
+                ("X", C.c_void_p), ("ixA", C.c_void_p), ("ixB", C.c_void_p), ("nnz", C.c_size_t),
+                ("Xcsr_p", C.c_void_p), ("Xcsr_i", C.c_void_p), ("Xcsr", C.c_void_p),
+                ("Xfull", C.c_void_p), ("weight", C.c_void_p)]
+
+
+def newrows_model_mirror(dtype):
+    return NewRowsModel if np.dtype(dtype) == np.float64 else NewRowsModelF
+
+
 EXPORTED = [
     "fit_collective_implicit_als", "fit_collective_explicit_als",
     "factors_collective_explicit_multiple", "factors_collective_implicit_multiple", "cmfrec_hip_factors_multiple", "cmfrec_hip_factors_multiple_l1", "cmfrec_hip_factors_multiple_ex",
     "cmfrec_hip_optimizeA_implicit", "cmfrec_hip_optimizeA_explicit", "cmfrec_hip_optimizeA_explicit_weighted",
     "cmfrec_hip_optimizeA_dense_full", "cmfrec_hip_optimizeA_collective", "cmfrec_hip_optimizeA_collective_sparse", "cmfrec_hip_topN_batch",
     "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
+    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
     "cmfrec_hip_session_set_sideinfo", "cmfrec_hip_session_set_sideinfo_local", "cmfrec_hip_session_sideinfo_partial", "cmfrec_hip_session_sideinfo_finish", "cmfrec_hip_session_set_nonneg", "cmfrec_hip_session_set_l1", "cmfrec_hip_session_set_lam_unique", "cmfrec_hip_session_set_scale_bias_const", "cmfrec_hip_session_set_NA_as_zero_X", "cmfrec_hip_session_set_zero_rows", "cmfrec_hip_session_set_closed_form_rows", "cmfrec_hip_session_set_lambda_multipliers", "cmfrec_hip_session_set_implicit_features", "cmfrec_hip_session_get_implicit_features", "cmfrec_hip_session_set_sideinfo_sparse", "cmfrec_hip_session_set_sideinfo_sparse_zeros", "cmfrec_hip_side_zeros_products", "cmfrec_hip_session_update", "cmfrec_hip_session_iterate",
@@ -84,6 +118,15 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_session_create.restype = C.c_void_p
     lib.cmfrec_hip_ranker_create.restype = C.c_void_p
     lib.cmfrec_hip_ranker_destroy.restype = None
+    nrm = newrows_model_mirror(dtype)
+    lib.cmfrec_hip_newrows_create.restype = C.c_void_p
+    lib.cmfrec_hip_newrows_create.argtypes = [C.POINTER(nrm), C.c_int]
+    lib.cmfrec_hip_newrows_factors.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p]
+    lib.cmfrec_hip_newrows_topN.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cmfrec_hip_newrows_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.cmfrec_hip_newrows_destroy.restype = None
+    lib.cmfrec_hip_newrows_destroy.argtypes = [C.c_void_p]
     lib.cmfrec_hip_session_device_ptr.restype = C.c_void_p
     lib.cmfrec_hip_session_stream.restype = C.c_void_p
     assert lib.cmfrec_hip_sizeof_real() == np.dtype(dtype).itemsize
@@ -91,6 +134,9 @@ def load(dtype=np.float64):
     if lib.cmfrec_hip_sizeof_model() != C.sizeof(mirror):
         raise RuntimeError("cmfrec_amd: the ctypes mirror of cmfrec_hip_model (%d bytes) does not match the library (%d)"
                            % (C.sizeof(mirror), lib.cmfrec_hip_sizeof_model()))
+    if lib.cmfrec_hip_sizeof_newrows_model() != C.sizeof(nrm):
+        raise RuntimeError("cmfrec_amd: the ctypes mirror of cmfrec_hip_newrows_model (%d bytes) does not match the library (%d)"
+                           % (C.sizeof(nrm), lib.cmfrec_hip_sizeof_newrows_model()))
     _cache[dtype] = lib
     return lib
 

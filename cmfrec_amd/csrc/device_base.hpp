@@ -143,6 +143,18 @@ struct DevBuf {
     }
 };
 
+// the calling thread's current device while a handle made on another one is used
+struct DeviceScope {
+    int prev = -1;
+    explicit DeviceScope(int device)
+    {
+        int cur = -1;
+        HIP_CHECK(hipGetDevice(&cur));
+        if (cur != device) { HIP_CHECK(hipSetDevice(device)); prev = cur; }
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 // reloads the switches, selects `device` (< 0: the current one), reports it and its CU count, creates a stream (session.hip)
 void open_device(int device, int *device_id, int *num_cus, hipStream_t *stream);
 

@@ -31,6 +31,7 @@
 #include "../../include/cmfrec_hip.h"
 #include "rng_host.hpp"
 #include "exchange_plan.hpp"
+#include "newrows.hpp"
 
 namespace {
 
@@ -1592,8 +1593,285 @@ int_t fit_collective_explicit_als(
 // collective.c:11270-11280, :3380, common.c:736-758, collective.c:1704-1707).
 static int unsupported_multiple(const char *what)
 {
-    fprintf(stderr, "cmfrec_hip: factors_collective_*_multiple: %s is not supported by the HIP build\n", what);
+    cmfhip::g_last_error = std::string("factors_collective_*_multiple: ") + what + " is not supported by the HIP build";
+    fprintf(stderr, "cmfrec_hip: %s\n", cmfhip::g_last_error.c_str());
     return 2;
+}
+
+}  // extern "C"
+
+// ---- the handle: a model of new rows resident on the device (cmfrec_hip_newrows_*, include/cmfrec_hip.h) ---------------------
+// The rescaling rules of the two drop-in functions live here once: newrows_model_side is their model half (create), newrows_batch_side
+// their batch half (factors / topN); the drop-in functions themselves are create, factors, destroy.
+struct cmfrec_hip_newrows {
+    cmfrec_hip_newrows_model mdl;              // the scalars; its pointers are cleared after create
+    cmfhip::NewRowsState *state = nullptr;
+    cmfrec_hip_ranker *ranker = nullptr;       // made by the first topN call
+    bool has_C = false, has_biasB = false, has_Bi = false, has_means = false;
+    int_t n_sparse = 0;                        // rows of B a sparse batch may index (n_max with include_all_X), n: a dense one
+    bool called = false, ranked = false;       // a solve on this handle; the last call ranked
+    ~cmfrec_hip_newrows()
+    {
+        if (ranker) cmfrec_hip_ranker_destroy(ranker);
+        cmfhip::newrows_state_destroy(state);
+    }
+};
+
+namespace {
+
+// Model half of factors_collective_explicit_multiple (factors_collective_explicit_single, collective.c:10611-10630;
+// collective_factors_warm, :3694-3713) and of factors_collective_implicit_multiple (collective_factors_warm_implicit, :4000-4004).
+int newrows_model_side(const cmfrec_hip_newrows_model &m, cmfhip::NewRowsModelArgs &M, int_t *n_sparse)
+{
+    const bool side = m.C != nullptr && m.p > 0;
+    M.B = m.B; M.C = side ? m.C : nullptr; M.p = side ? m.p : 0; M.U_colmeans = side ? m.U_colmeans : nullptr;
+    M.k = m.k; M.k_user = m.k_user; M.k_item = m.k_item; M.k_main = m.k_main;
+    M.nonneg = m.nonneg != 0;
+    if (m.implicit) {
+        // L1 penalty: rows with observations keep the l1_lam of the call (collective_factors_warm_implicit rescales lam and w_user by
+        // w_main only, :4000-4004).
+        // With side information the reference's own result is not finite (its elastic-net sweeps diverge on the block system of
+        // collective_closed_form_block_implicit: +-inf in most rows of a seeded problem, tests/golden_cases.py) -- refused.
+        if (m.l1_lam != 0 && side)
+            return unsupported_multiple("L1 regularisation together with side information (the reference's result is not finite)");
+        if (m.l1_lam != 0 && m.nonneg) return unsupported_multiple("L1 regularisation together with non-negativity");
+        // BtB as the reference builds it when none is passed: + the lam of the call, before the w_main rescaling
+        // (collective.c:11270-11280; not built for a single row without BeTBeChol either, where the row function does the same)
+        real_t lam = m.lam, w_user = m.w_user;
+        M.lam_x = lam;
+        const real_t wm = m.w_main * m.w_main_multiplier;                       // collective_factors_warm_implicit, :4000-4004
+        if (wm != 1) { lam /= wm; w_user /= wm; }
+        M.implicit = true; M.n = m.n; *n_sparse = m.n;
+        M.lam = lam; M.lam_bias = lam; M.w_user = w_user; M.l1_lam = m.l1_lam; M.l1_lam_bias = m.l1_lam;
+        M.BtB_pre = m.BtB;
+        return 0;
+    }
+    const bool Bi = m.add_implicit_features != 0;
+    if (Bi && !m.Bi) return unsupported_multiple("add_implicit_features without Bi");
+    const bool ub = m.user_bias != 0;
+    // factors_collective_explicit_single, collective.c:10611-10630
+    real_t lam = m.lam, l1_lam = m.l1_lam, lam_bias = m.lam, l1_lam_bias = m.l1_lam, w_user = m.w_user, w_implicit = m.w_implicit;
+    bool scale_bias_const = m.scale_bias_const != 0;
+    const bool scale_any = m.scale_lam || m.scale_lam_sideinfo;
+    if (m.lam_unique) { lam_bias = m.lam_unique[ub ? 0 : 2]; lam = m.lam_unique[2]; }
+    if (m.l1_lam_unique) { l1_lam_bias = m.l1_lam_unique[ub ? 0 : 2]; l1_lam = m.l1_lam_unique[2]; }
+    if (!ub) scale_bias_const = false;
+    if (scale_any && scale_bias_const) { lam_bias *= m.scaling_biasA; l1_lam_bias *= m.scaling_biasA; }
+    // BiTBi carries the w_implicit of the call (batch driver, :11016-11020), the right-hand side the rescaled one (:3706-3714)
+    const real_t w_implicit_gram = w_implicit;
+    if (m.w_main != 1) {                                                        // collective_factors_warm, :3694-3713
+        w_user /= m.w_main; w_implicit /= m.w_main; lam /= m.w_main; lam_bias /= m.w_main; l1_lam /= m.w_main; l1_lam_bias /= m.w_main;
+    }
+    const bool l1on = l1_lam != 0 || (ub && l1_lam_bias != 0);
+    if (l1on && m.nonneg) return unsupported_multiple("L1 regularisation together with non-negativity");
+    // rows without side information and without a bias: the reference passes scale_lam where factors_closed_form
+    // expects scale_bias_const (:3789-3799), so the last factor keeps the unscaled lam (not with implicit features: those
+    // rows go through the block solver, :3759-3760)
+    if (!ub && !Bi) scale_bias_const = scale_any;
+    // B's rows: with dense X or implicit features the n columns of Xfull / rows of Bi bound the item indices
+    const bool more = m.include_all_X && m.n_max > m.n;
+    *n_sparse = (more && !Bi) ? m.n_max : m.n;
+    M.n = more ? m.n_max : m.n;
+    M.biasB = m.biasB; M.user_bias = ub;
+    M.lam = lam; M.lam_bias = lam_bias; M.lam_x = lam; M.w_user = w_user;
+    M.scale_lam = m.scale_lam != 0; M.scale_lam_sideinfo = m.scale_lam_sideinfo != 0; M.scale_bias_const = scale_bias_const;
+    M.l1_lam = l1_lam; M.l1_lam_bias = l1_lam_bias;
+    // (TransCtCinvCt: not with non-negativity or an L1 penalty, collective.c:3378)
+    M.TransCtCinvCt_pre = (m.nonneg || l1on || !side) ? nullptr : m.TransCtCinvCt;
+    if (Bi) { M.Bi = m.Bi; M.n_Bi = m.n; M.w_implicit = w_implicit; M.w_implicit_gram = w_implicit_gram; M.BiTBi_pre = m.BiTBi; }
+    // TransBtBinvBt: complete dense rows of the model without side information (common.c:736-758, n_BtB == n); the batch decides
+    // the rest (no weights, no side information in it)
+    if (m.TransBtBinvBt && !m.nonneg && !l1on && !Bi && !more) { M.TransBtBinvBt_pre = m.TransBtBinvBt; M.n_TB = m.n; }
+    return 0;
+}
+
+// Batch half: the refusals that depend on the batch, preprocess_vec's shift by the global mean (:6337-6388; dense X: on the
+// device, the item bias: inside the gather) or the implicit model's log / alpha (:10802-10810, :4006-4016).  `vals` holds the
+// transformed values while the batch runs.  1: a batch without rows (nothing to do), 0: run it, 2: refused.
+int newrows_batch_side(const cmfrec_hip_newrows &h, const cmfrec_hip_newrows_batch &b, cmfhip::NewRowsBatchArgs &bt, std::vector<real_t> &vals_tmp)
+{
+    const cmfrec_hip_newrows_model &m = h.mdl;
+    int_t mx = b.m, m_u = b.m_u;
+    const real_t *U = h.has_C ? b.U : nullptr, *Xfull = b.Xfull, *weight = b.weight;
+    const bool spU = h.has_C && (b.U == nullptr && (b.nnz_U || b.U_csr_p));
+    if (Xfull && (b.nnz || b.Xcsr_p)) return unsupported_multiple("X both as a dense and as a sparse matrix");
+    if (m.implicit && (Xfull || weight)) {
+        cmfhip::g_last_error = "cmfrec_hip_factors_multiple: observation weights, dense X and implicit features belong to the explicit model";
+        return 2;
+    }
+    if (!h.has_C && m.p > 0 && (b.U || b.nnz_U || b.U_csr_p)) {             // side information for a model without C
+        cmfhip::g_last_error = "cmfrec_hip_factors_multiple: invalid arguments";
+        return 2;
+    }
+    if (U == nullptr && !spU) m_u = 0;
+    if (std::max(mx, m_u) <= 0) return 1;                                       // rows out: max(m, m_u), collective.c:11210
+    if (mx <= 0) { Xfull = nullptr; weight = nullptr; }
+    if (U) for (size_t e = 0; e < (size_t)m_u * (size_t)m.p; e++) if (std::isnan(U[e])) return unsupported_multiple("missing values in U");
+    const bool side = U != nullptr || spU;
+    if (!m.implicit) {
+        // The block solver's weighted right-hand side of sparse X is the NA_as_zero one, w x - (w - 1)(glob_mean + biasB), applied
+        // to values that preprocess_vec has centred already (collective.c:1743-1753): with a mean or item biases the reference's
+        // rows are not the solution of the weighted model.  Not restated.
+        if (weight && !Xfull && (side || h.has_Bi) && (m.glob_mean != 0 || h.has_biasB))
+            return unsupported_multiple("observation weights of sparse X together with glob_mean / biasB and side information or implicit "
+                                        "features (the reference's right-hand side is not the weighted model's, collective.c:1743-1753)");
+        // A dense row of NaN with side information reaches the side-information-only solution through collective_factors_warm,
+        // which has centred u already and hands it on with the column means: they are subtracted twice (:3616, :3662-3677, :3337).
+        if (Xfull && U && h.has_means && !h.has_Bi)
+            for (int_t r = 0; r < std::min(mx, m_u); r++) {
+                int_t c = 0;
+                while (c < m.n && std::isnan(Xfull[(size_t)r * (size_t)m.n + c])) c++;
+                if (c == m.n)
+                    return unsupported_multiple("a dense row of X without any observation together with U and U_colmeans (the reference "
+                                                "centres that row's side information twice, collective.c:3616, :3337)");
+            }
+    }
+    const size_t nz = Xfull ? 0 : (b.Xcsr_p ? b.Xcsr_p[mx > 0 ? mx : 0] : b.nnz);
+    const real_t *vals = b.Xcsr_p ? b.Xcsr : b.X;
+    if (m.implicit) {
+        if ((m.apply_log_transf || m.alpha != 1) && nz) {
+            vals_tmp.assign(vals, vals + nz);
+            if (m.apply_log_transf) for (size_t e = 0; e < nz; e++) vals_tmp[e] = std::log(vals_tmp[e]);   // :10802-10810
+            if (m.alpha != 1) for (size_t e = 0; e < nz; e++) vals_tmp[e] *= m.alpha;                      // :4006-4016
+            vals = vals_tmp.data();
+        }
+    } else if (m.glob_mean != 0 && nz) {
+        vals_tmp.assign(vals, vals + nz);
+        for (size_t e = 0; e < nz; e++) vals_tmp[e] -= m.glob_mean;
+        vals = vals_tmp.data();
+    }
+    bt.m_x = mx; bt.m_u = m_u; bt.n = Xfull ? m.n : h.n_sparse;
+    bt.U = U;
+    if (spU) {
+        bt.U_row = b.U_row; bt.U_col = b.U_col; bt.U_sp = b.U_sp; bt.nnz_U = b.nnz_U;
+        bt.U_csr_p = b.U_csr_p; bt.U_csr_i = b.U_csr_i; bt.U_csr = b.U_csr;
+    }
+    bt.ixA = b.ixA; bt.ixB = b.ixB; bt.X = (b.Xcsr_p || Xfull) ? nullptr : vals; bt.nnz = Xfull ? 0 : b.nnz;
+    bt.Xcsr_p = b.Xcsr_p; bt.Xcsr_i = b.Xcsr_i; bt.Xcsr = b.Xcsr_p ? vals : nullptr;
+    bt.weight = Xfull ? nullptr : weight; bt.Xfull = Xfull; bt.weight_full = Xfull ? weight : nullptr;
+    bt.glob_mean_full = m.glob_mean;
+    // (a dense row of NaN reaches the side-information-only solution through collective_factors_warm, which does not hand
+    //  TransCtCinvCt on, :3662-3677)
+    bt.allow_TransCtCinvCt = Xfull == nullptr;
+    return 0;
+}
+
+// the raw return code of the batch run (0 .. 4)
+int newrows_solve(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *A, real_t *biasA, bool *empty)
+{
+    *empty = false;
+    if (h == nullptr || batch == nullptr || h->state == nullptr) {
+        cmfhip::g_last_error = "cmfrec_hip_newrows: invalid arguments";
+        return 2;
+    }
+    return cmfhip::guarded([&]() {
+        cmfhip::NewRowsBatchArgs bt;
+        std::vector<real_t> vals_tmp;
+        const int brc = newrows_batch_side(*h, *batch, bt, vals_tmp);
+        if (brc == 1) { *empty = true; return 0; }
+        if (brc) return brc;
+        h->ranked = false;
+        const int rc = cmfhip::newrows_state_run(h->state, bt, A, biasA);
+        if (rc == 0) h->called = true;
+        return rc;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmfrec_hip_sizeof_newrows_model(void) { return (int)sizeof(cmfrec_hip_newrows_model); }
+
+cmfrec_hip_newrows *cmfrec_hip_newrows_create(const cmfrec_hip_newrows_model *model, int device)
+{
+    cmfrec_hip_newrows *h = nullptr;
+    const int rc = cmfhip::guarded([&]() {
+        if (model == nullptr) {
+            cmfhip::g_last_error = "cmfrec_hip_newrows_create: invalid arguments";
+            return 2;
+        }
+        cmfhip::NewRowsModelArgs M;
+        int_t n_sparse = 0;
+        if (int mrc = newrows_model_side(*model, M, &n_sparse)) return mrc;
+        h = new cmfrec_hip_newrows();
+        h->mdl = *model;
+        h->n_sparse = n_sparse;
+        h->has_C = M.C != nullptr; h->has_biasB = M.biasB != nullptr; h->has_Bi = M.Bi != nullptr; h->has_means = M.U_colmeans != nullptr;
+        int src = 0;
+        h->state = cmfhip::newrows_state_create(M, device, &src);
+        if (h->state == nullptr) return src ? src : 4;
+        cmfrec_hip_newrows_model &m = h->mdl;
+        m.B = m.C = m.U_colmeans = m.biasB = m.Bi = m.lam_unique = m.l1_lam_unique = m.BtB = m.TransBtBinvBt = m.BiTBi = m.TransCtCinvCt = nullptr;
+        return 0;
+    });
+    cmfhip::g_last_rc = rc;
+    if (rc != 0) {
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+
+int cmfrec_hip_newrows_factors(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *A, real_t *biasA)
+{
+    bool empty = false;
+    if (h != nullptr && batch != nullptr && A == nullptr && std::max(batch->m, batch->m_u) > 0) {
+        cmfhip::g_last_error = "cmfrec_hip_newrows_factors: invalid arguments";
+        return 2;
+    }
+    const int rc = newrows_solve(h, batch, A, biasA, &empty);
+    return rc > 3 ? 1 : rc;
+}
+
+int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, int exclude_seen,
+                            const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                            int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA)
+{
+    const char *fn = "cmfrec_hip_newrows_topN";
+    if (h == nullptr || batch == nullptr || h->state == nullptr || n_top <= 0 || out_ids == nullptr) {
+        cmfhip::g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    const int_t kr = h->mdl.k + h->mdl.k_main;
+    if (int rc = cmfhip::ranker_check_limits(fn, kr, n_top, cmfhip::newrows_state_view(h->state).n)) return rc;
+    bool empty = false;
+    if (int rc = newrows_solve(h, batch, A, biasA, &empty)) return rc;
+    if (empty) return 0;
+    const int rc = cmfhip::guarded([&]() {
+        const cmfhip::NewRowsView v = cmfhip::newrows_state_view(h->state);
+        if (h->ranker == nullptr) {
+            h->ranker = cmfhip::ranker_create_from_device(v.dB + h->mdl.k_item, v.ldB, v.n, kr, v.dbiasB, v.device);
+            if (h->ranker == nullptr) return cmfhip::g_last_rc ? cmfhip::g_last_rc : 4;
+        }
+        const size_t *dp = nullptr;
+        const int *di = nullptr;
+        if (int erc = cmfhip::newrows_state_exclusions(h->state, exclude_seen != 0, excl_p, excl_i, &dp, &di)) return erc;
+        return cmfhip::ranker_topN_device(h->ranker, fn, v.dA + h->mdl.k_user, v.ldA, v.rows, dp, di, n_top, out_ids, out_scores);
+    });
+    if (rc == 0) h->ranked = true;
+    return rc;
+}
+
+int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms)
+{
+    if (h == nullptr || h->state == nullptr || !h->called) {
+        cmfhip::g_last_error = "cmfrec_hip_newrows_kernel_ms: no call on this handle yet";
+        return 2;
+    }
+    return cmfhip::guarded([&]() {
+        double s = 0, r = 0;
+        if (int rc = cmfhip::newrows_state_solve_ms(h->state, &s)) return rc;
+        if (h->ranked) { if (int rc = cmfrec_hip_ranker_kernel_ms(h->ranker, &r)) return rc; }
+        if (solve_ms) *solve_ms = s;
+        if (rank_ms) *rank_ms = r;
+        return 0;
+    });
+}
+
+void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h)
+{
+    delete h;
 }
 
 int_t factors_collective_explicit_multiple(
@@ -1632,68 +1910,39 @@ int_t factors_collective_explicit_multiple(
     if (Ub) return unsupported_multiple("binary side information");
     if (Xfull && (nnz || Xcsr_p)) return unsupported_multiple("X both as a dense and as a sparse matrix");
     if (add_implicit_features && !Bi) return unsupported_multiple("add_implicit_features without Bi");
-    if (!add_implicit_features) { Bi = nullptr; BiTBi = nullptr; }
     if (U == nullptr && !spU) { m_u = 0; }
     if (std::max(m, m_u) <= 0) return 0;
     if (m <= 0) { Xfull = nullptr; weight = nullptr; }
-    if (U) for (size_t e = 0; e < (size_t)m_u * (size_t)p; e++) if (std::isnan(U[e])) return unsupported_multiple("missing values in U");
     const bool side = U != nullptr || spU;
-    // The block solver's weighted right-hand side of sparse X is the NA_as_zero one, w x - (w - 1)(glob_mean + biasB), applied
-    // to values that preprocess_vec has centred already (collective.c:1743-1753): with a mean or item biases the reference's
-    // rows are not the solution of the weighted model.  Not restated.
-    if (weight && !Xfull && (side || Bi) && (glob_mean != 0 || biasB))
-        return unsupported_multiple("observation weights of sparse X together with glob_mean / biasB and side information or implicit "
-                                    "features (the reference's right-hand side is not the weighted model's, collective.c:1743-1753)");
-    // A dense row of NaN with side information reaches the side-information-only solution through collective_factors_warm,
-    // which has centred u already and hands it on with the column means: they are subtracted twice (:3616, :3662-3677, :3337).
-    if (Xfull && U && U_colmeans && !Bi)
-        for (int_t r = 0; r < std::min(m, m_u); r++) {
-            int_t c = 0;
-            while (c < n && std::isnan(Xfull[(size_t)r * (size_t)n + c])) c++;
-            if (c == n)
-                return unsupported_multiple("a dense row of X without any observation together with U and U_colmeans (the reference "
-                                            "centres that row's side information twice, collective.c:3616, :3337)");
-        }
-    // factors_collective_explicit_single, collective.c:10611-10630
-    real_t lam_bias = lam, l1_lam_bias = l1_lam;
-    if (lam_unique) { lam_bias = lam_unique[biasA ? 0 : 2]; lam = lam_unique[2]; }
-    if (l1_lam_unique) { l1_lam_bias = l1_lam_unique[biasA ? 0 : 2]; l1_lam = l1_lam_unique[2]; }
-    if (!biasA) scale_bias_const = false;
-    if ((scale_lam || scale_lam_sideinfo) && scale_bias_const) { lam_bias *= scaling_biasA; l1_lam_bias *= scaling_biasA; }
-    // BiTBi carries the w_implicit of the call (batch driver, :11016-11020), the right-hand side the rescaled one (:3706-3714)
-    const real_t w_implicit_gram = w_implicit;
-    if (w_main != 1) {                                                          // collective_factors_warm, :3694-3713
-        w_user /= w_main; w_implicit /= w_main; lam /= w_main; lam_bias /= w_main; l1_lam /= w_main; l1_lam_bias /= w_main;
+    // the model as this batch sees it: side information only where the batch has some, a bias unknown where biasA is asked for
+    cmfrec_hip_newrows_model mdl;
+    memset(&mdl, 0, sizeof mdl);
+    mdl.n = n; mdl.n_max = n_max; mdl.include_all_X = include_all_X; mdl.p = side ? p : 0;
+    mdl.user_bias = biasA != nullptr; mdl.add_implicit_features = add_implicit_features;
+    mdl.k = k; mdl.k_user = k_user; mdl.k_item = k_item; mdl.k_main = k_main;
+    mdl.scale_lam = scale_lam; mdl.scale_lam_sideinfo = scale_lam_sideinfo; mdl.scale_bias_const = scale_bias_const;
+    mdl.nonneg = nonneg;
+    mdl.glob_mean = glob_mean; mdl.lam = lam; mdl.l1_lam = l1_lam; mdl.scaling_biasA = scaling_biasA;
+    mdl.w_main = w_main; mdl.w_user = w_user; mdl.w_implicit = w_implicit; mdl.alpha = 1; mdl.w_main_multiplier = 1;
+    mdl.B = B; mdl.C = side ? C : nullptr; mdl.U_colmeans = U_colmeans; mdl.biasB = biasB; mdl.Bi = add_implicit_features ? Bi : nullptr;
+    mdl.lam_unique = lam_unique; mdl.l1_lam_unique = l1_lam_unique;
+    mdl.TransBtBinvBt = (Xfull && !side && !weight) ? TransBtBinvBt : nullptr; mdl.BiTBi = add_implicit_features ? BiTBi : nullptr;
+    mdl.TransCtCinvCt = TransCtCinvCt;
+    cmfrec_hip_newrows_batch bt;
+    memset(&bt, 0, sizeof bt);
+    bt.m = m; bt.m_u = m_u; bt.U = U;
+    bt.U_row = U_row; bt.U_col = U_col; bt.U_sp = U_sp; bt.nnz_U = nnz_U; bt.U_csr_p = U_csr_p; bt.U_csr_i = U_csr_i; bt.U_csr = U_csr;
+    bt.X = X; bt.ixA = ixA; bt.ixB = ixB; bt.nnz = nnz; bt.Xcsr_p = Xcsr_p; bt.Xcsr_i = Xcsr_i; bt.Xcsr = Xcsr;
+    bt.Xfull = Xfull; bt.weight = weight;
+    cmfrec_hip_newrows *h = cmfrec_hip_newrows_create(&mdl, -1);
+    if (h == nullptr) {
+        const int ec = cmfrec_hip_last_error_code();
+        if (ec == 2) fprintf(stderr, "%s\n", cmfrec_hip_last_error());
+        return ec > 3 ? 1 : (ec ? ec : 1);
     }
-    const bool l1on = l1_lam != 0 || (biasA && l1_lam_bias != 0);
-    if (l1on && nonneg) return unsupported_multiple("L1 regularisation together with non-negativity");
-    // rows without side information and without a bias: the reference passes scale_lam where factors_closed_form
-    // expects scale_bias_const (:3789-3799), so the last factor keeps the unscaled lam (not with implicit features: those
-    // rows go through the block solver, :3759-3760)
-    if (!biasA && !Bi) scale_bias_const = scale_lam || scale_lam_sideinfo;
-    // preprocess_vec, :6337-6388: x -= biasB[col] + glob_mean.  The mean goes here (dense X: on the device), the bias is fused
-    // into the gather.
-    const size_t nz = Xfull ? 0 : (Xcsr_p ? Xcsr_p[m] : nnz);
-    const real_t *vals = Xcsr_p ? Xcsr : X;
-    std::vector<real_t> shifted;
-    if (glob_mean != 0 && nz) {
-        shifted.assign(vals, vals + nz);
-        for (size_t e = 0; e < nz; e++) shifted[e] -= glob_mean;
-        vals = shifted.data();
-    }
-    // B's rows: with dense X or implicit features the n columns of Xfull / rows of Bi bound the item indices
-    const int_t n_rows_B = (include_all_X && !Xfull && !Bi) ? std::max(n, n_max) : n;
-    // TransBtBinvBt: complete dense rows of the model without side information (common.c:736-758, n_BtB == n)
-    const bool use_TB = TransBtBinvBt && Xfull && !weight && !nonneg && !l1on && !side && !Bi && (!include_all_X || n_max <= n);
-    // (TransCtCinvCt: not with non-negativity or an L1 penalty, collective.c:3378; a dense row of NaN reaches the side-information-only
-    //  solution through collective_factors_warm, which does not hand the matrix on, :3662-3677)
-    int rc = cmfrec_hip_factors_multiple_ex(A, biasA, m, m_u, side ? p : 0, U, U_colmeans, ixA, ixB, (Xcsr_p || Xfull) ? nullptr : vals,
-                                            Xfull ? 0 : nnz, Xcsr_p, Xcsr_i, Xcsr_p ? vals : nullptr, B, n_rows_B, C, biasB, k, k_user,
-                                            k_item, k_main, lam, lam_bias, lam, w_user, false, scale_lam, scale_lam_sideinfo,
-                                            scale_bias_const, nullptr, (nonneg || l1on || Xfull) ? nullptr : TransCtCinvCt, U_row, U_col,
-                                            U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, nonneg, l1_lam, l1_lam_bias,
-                                            Xfull ? nullptr : weight, Xfull, Xfull ? weight : nullptr, glob_mean, Bi, w_implicit,
-                                            w_implicit_gram, BiTBi, use_TB ? TransBtBinvBt : nullptr);
+    bool empty = false;
+    const int rc = newrows_solve(h, &bt, A, biasA, &empty);
+    cmfrec_hip_newrows_destroy(h);
     if (rc == 2) fprintf(stderr, "%s\n", cmfrec_hip_last_error());
     return rc > 3 ? 1 : rc;
 }
@@ -1717,39 +1966,41 @@ int_t factors_collective_implicit_multiple(
     real_t *BeTBe, real_t *BtB, real_t *BeTBeChol, real_t *CtUbias,
     int nthreads)
 {
-    (void)BeTBe; (void)CtUbias; (void)nthreads;
+    // a precomputed BeTBeChol without BtB means the caller's BtB is unknown: rebuild (equal for consistent inputs)
+    (void)BeTBe; (void)BeTBeChol; (void)CtUbias; (void)nthreads;
     if (NA_as_zero_U) return unsupported_multiple("NA_as_zero");
     const bool spU = (U == nullptr && (nnz_U || U_csr_p));
     if (U == nullptr && !spU) m_u = 0;
-    // L1 penalty: rows with observations keep the l1_lam of the call (collective_factors_warm_implicit rescales lam and w_user by
-    // w_main only, :4000-4004).
-    // With side information the reference's own result is not finite (its elastic-net sweeps diverge on the block system of
-    // collective_closed_form_block_implicit: +-inf in most rows of a seeded problem, tests/golden_cases.py) -- refused.
-    if (l1_lam != 0 && (U || spU))
-        return unsupported_multiple("L1 regularisation together with side information (the reference's result is not finite)");
-    if (l1_lam != 0 && nonneg) return unsupported_multiple("L1 regularisation together with non-negativity");
-    if (std::max(m, m_u) <= 0) return 0;                                        // rows out: max(m, m_u), collective.c:11210
-    if (U) for (size_t e = 0; e < (size_t)m_u * (size_t)p; e++) if (std::isnan(U[e])) return unsupported_multiple("missing values in U");
-    // BtB as the reference builds it when none is passed: + the lam of the call, before the w_main rescaling
-    // (collective.c:11270-11280; not built for a single row without BeTBeChol either, where the row function does the same)
-    const real_t lam_x = lam;
-    real_t wm = w_main * w_main_multiplier;                                     // collective_factors_warm_implicit, :4000-4004
-    if (wm != 1) { lam /= wm; w_user /= wm; }
-    const size_t nz = Xcsr_p ? Xcsr_p[m] : nnz;
-    const real_t *vals = Xcsr_p ? Xcsr : X;
-    std::vector<real_t> scaled;
-    if ((apply_log_transf || alpha != 1) && nz) {
-        scaled.assign(vals, vals + nz);
-        if (apply_log_transf) for (size_t e = 0; e < nz; e++) scaled[e] = std::log(scaled[e]);   // :10802-10810
-        if (alpha != 1) for (size_t e = 0; e < nz; e++) scaled[e] *= alpha;                      // :4006-4016
-        vals = scaled.data();
+    const bool side = U != nullptr || spU;
+    cmfrec_hip_newrows_model mdl;
+    memset(&mdl, 0, sizeof mdl);
+    mdl.implicit = 1;
+    mdl.n = n; mdl.n_max = n; mdl.p = side ? p : 0;
+    mdl.k = k; mdl.k_user = k_user; mdl.k_item = k_item; mdl.k_main = k_main;
+    mdl.nonneg = nonneg; mdl.apply_log_transf = apply_log_transf;
+    mdl.lam = lam; mdl.l1_lam = l1_lam; mdl.scaling_biasA = 1; mdl.w_main = w_main; mdl.w_user = w_user; mdl.w_implicit = 1;
+    mdl.alpha = alpha; mdl.w_main_multiplier = w_main_multiplier;
+    mdl.B = B; mdl.C = side ? C : nullptr; mdl.U_colmeans = U_colmeans; mdl.BtB = BtB;
+    // the model-side refusals come first, as they always have; then a batch without rows is no work
+    {
+        cmfhip::NewRowsModelArgs M;
+        int_t ns = 0;
+        if (int mrc = newrows_model_side(mdl, M, &ns)) return mrc;
     }
-    // a precomputed BeTBeChol without BtB means the caller's BtB is unknown: rebuild (equal for consistent inputs)
-    (void)BeTBeChol;
-    int rc = cmfrec_hip_factors_multiple_l1(A, nullptr, m, m_u, (U || spU) ? p : 0, U, U_colmeans, ixA, ixB, Xcsr_p ? nullptr : vals, nnz,
-                                            Xcsr_p, Xcsr_i, Xcsr_p ? vals : nullptr, B, n, C, nullptr, k, k_user, k_item, k_main,
-                                            lam, lam, BtB ? lam : lam_x, w_user, true, false, false, false, BtB, nullptr,
-                                            U_row, U_col, U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, nonneg, l1_lam, l1_lam);
+    if (std::max(m, m_u) <= 0) return 0;                                        // rows out: max(m, m_u), collective.c:11210
+    cmfrec_hip_newrows_batch bt;
+    memset(&bt, 0, sizeof bt);
+    bt.m = m; bt.m_u = m_u; bt.U = U;
+    bt.U_row = U_row; bt.U_col = U_col; bt.U_sp = U_sp; bt.nnz_U = nnz_U; bt.U_csr_p = U_csr_p; bt.U_csr_i = U_csr_i; bt.U_csr = U_csr;
+    bt.X = X; bt.ixA = ixA; bt.ixB = ixB; bt.nnz = nnz; bt.Xcsr_p = Xcsr_p; bt.Xcsr_i = Xcsr_i; bt.Xcsr = Xcsr;
+    cmfrec_hip_newrows *h = cmfrec_hip_newrows_create(&mdl, -1);
+    if (h == nullptr) {
+        const int ec = cmfrec_hip_last_error_code();
+        return ec > 3 ? 1 : (ec ? ec : 1);
+    }
+    bool empty = false;
+    const int rc = newrows_solve(h, &bt, A, nullptr, &empty);
+    cmfrec_hip_newrows_destroy(h);
     return rc > 3 ? 1 : rc;
 }
 

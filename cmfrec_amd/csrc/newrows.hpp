@@ -1,0 +1,77 @@
+// newrows.hpp -- what the three units behind the new-rows handle share (cmfrec_hip_newrows_*, include/cmfrec_hip.h): the
+// device-resident model of a batch of new rows and its batch run (session.hip), the ranking of device factors against device
+// items (topn_tu.hip), the C entry points and the rescaling rules of the two drop-in functions (fit.hip).  No kernels.
+#pragma once
+#include "device_base.hpp"
+
+struct cmfrec_hip_ranker;
+
+namespace cmfhip {
+
+// The model side of cmfrec_hip_factors_multiple_ex's arguments (the rescaling of the drop-in functions applied): what does not
+// change from batch to batch.
+struct NewRowsModelArgs {
+    const real_t *B = nullptr;                 // [n, k_item + k + k_main]
+    int_t n = 0;
+    const real_t *C = nullptr;                 // [p, k_user + k], null: no side information in any batch
+    int_t p = 0;
+    const real_t *U_colmeans = nullptr;
+    const real_t *biasB = nullptr;
+    int_t k = 0, k_user = 0, k_item = 0, k_main = 0;
+    bool user_bias = false;                    // a bias unknown in every row system (the one-shot calls: biasA given)
+    real_t lam = 0, lam_bias = 0, lam_x = 0, w_user = 1;
+    bool implicit = false, scale_lam = false, scale_lam_sideinfo = false, scale_bias_const = false;
+    const real_t *BtB_pre = nullptr, *TransCtCinvCt_pre = nullptr;
+    bool nonneg = false;
+    real_t l1_lam = 0, l1_lam_bias = 0;
+    const real_t *Bi = nullptr;                // [n_Bi, k + k_main]
+    int_t n_Bi = 0;
+    real_t w_implicit = 1, w_implicit_gram = 1;
+    const real_t *BiTBi_pre = nullptr;
+    const real_t *TransBtBinvBt_pre = nullptr; // [n_TB, k + k_main (+ 1)]
+    int_t n_TB = 0;
+};
+
+// The batch side: everything that depends on X, U, the weights or Xfull.
+struct NewRowsBatchArgs {
+    int_t m_x = 0, m_u = 0;
+    int_t n = 0;                               // items of this batch: bound of X's indices, columns of Xfull (<= the model's n)
+    const real_t *U = nullptr;                 // [m_u, p]
+    const int_t *U_row = nullptr, *U_col = nullptr; const real_t *U_sp = nullptr; size_t nnz_U = 0;
+    const size_t *U_csr_p = nullptr; const int_t *U_csr_i = nullptr; const real_t *U_csr = nullptr;
+    const int_t *ixA = nullptr, *ixB = nullptr; const real_t *X = nullptr; size_t nnz = 0;
+    const size_t *Xcsr_p = nullptr; const int_t *Xcsr_i = nullptr; const real_t *Xcsr = nullptr;
+    const real_t *weight = nullptr, *Xfull = nullptr, *weight_full = nullptr;
+    real_t glob_mean_full = 0;
+    bool allow_TransCtCinvCt = true;           // the drop-in functions do not hand that matrix on with a dense X
+};
+
+struct NewRowsState;
+
+// session.hip.  create / run report through g_last_error and the ABI's return codes; both throw HipError on a HIP failure
+// (call them inside guarded()).  run leaves the factors on the device ([rows, ldA], the bias in the last column) and downloads
+// them where A / biasA are given.
+NewRowsState *newrows_state_create(const NewRowsModelArgs &M, int device, int *rc);
+void newrows_state_destroy(NewRowsState *s);
+int newrows_state_run(NewRowsState *s, const NewRowsBatchArgs &bt, real_t *A, real_t *biasA);
+struct NewRowsView {
+    int device = 0;
+    const real_t *dA = nullptr; size_t ldA = 0; int rows = 0;     // factors of the last batch
+    const real_t *dB = nullptr; size_t ldB = 0; int n = 0;        // the resident items (all columns), their bias or null
+    const real_t *dbiasB = nullptr;
+};
+NewRowsView newrows_state_view(const NewRowsState *s);
+// Exclusion lists of the last batch's rows for the ranking kernels, on the device: the items of each row's own X (seen), the
+// caller's lists (host CSR over the rows, each sorted), or their union; every list sorted ascending.  Both null: *dp = null.
+int newrows_state_exclusions(NewRowsState *s, bool seen, const size_t *excl_p, const int_t *excl_i, const size_t **dp, const int **di);
+int newrows_state_solve_ms(NewRowsState *s, double *ms);
+
+// topn_tu.hip: a ranker over items that are on the device already (packed copy, ldb = topnw_kp(k)), and a ranking call on
+// device factors with device exclusion lists -- cmfrec_hip_ranker_topN without its uploads.  The caller has synchronised the
+// stream that wrote dA / the lists.
+cmfrec_hip_ranker *ranker_create_from_device(const real_t *dB, size_t ldb, int_t n, int_t k, const real_t *dbiasB, int device);
+int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p,
+                       const int *dexcl_i, int_t n_top, int_t *out_ids, real_t *out_scores);
+int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n);
+
+}  // namespace cmfhip

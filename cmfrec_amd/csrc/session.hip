@@ -14,6 +14,7 @@
 #include "eig_kernels.hpp"
 #include "gram_cg_wide_kernels.hpp"
 #include "side_zeros_kernels.hpp"
+#include "newrows.hpp"
 #include <dlfcn.h>
 #include <functional>
 #include <limits>
@@ -3541,6 +3542,524 @@ struct NewRowsExtra {
 // l1_lam / l1_lam_bias: the L1 penalty of the row systems and of the bias unknown (solve_elasticnet instead of the Cholesky
 // substitution, common.c:2228-2294; collective_factors_warm / _cold hand them down like lam / lam_bias, collective.c:3571-3931,
 // :3321-3400), already divided by w_main.  Rows that only have side information take l1_lam / w_user (:3395).
+// The work is split in two (newrows.hpp): NewRowsState holds what belongs to the model -- the device copies of B (with its ones
+// column), biasB, C, the column means, Bi, the Gramians and the precomputed matrices, the stream and the workspaces -- and is
+// built once; newrows_state_run does what depends on the batch and leaves the factors on the device.  The three one-shot entry
+// points below are "state made, one batch, state destroyed"; the handle of fit.hip (cmfrec_hip_newrows_*) keeps the state.
+}  // extern "C"
+
+namespace cmfhip {
+
+struct NewRowsState {
+    DeviceInfo dev;                            // (first: its stream outlives the buffers below)
+    GramWorkspace gws;
+    NewRowsModelArgs M;                        // the scalars; the host pointers are not read after create
+    int ub = 0, kc = 0, kk = 0, kt = 0, ktA = 0, kT = 0;
+    size_t ldB = 0, ldA = 0;
+    bool l1on = false, have_C = false, have_means = false, have_Bi = false, have_T = false, have_TB = false;
+    // model side, built once (w_user C^T C and the matrix of the rows without observations: on the first batch that needs them)
+    DevBuf<real_t> dB, dbias, dC, dmeans, dG, dM, dCtC, dMcold, dT, dTB, dBi, dBiG, dBiFull;
+    bool ctc_built = false, cold_built = false;
+    // batch side: reused from call to call, grown on demand (the shards are rebuilt: their layout belongs to the batch)
+    DevBuf<real_t> dA, dU, dcold, dTBout, dba, dXb, dWb;
+    DevBuf<int> dmiss;
+    std::unique_ptr<SparseShard> Xs, Us;
+    int rows = 0;                              // rows of the last batch, 0: none yet
+    // exclusion lists of the last batch's rows for the ranking kernels (newrows_state_exclusions)
+    DevBuf<size_t> ep, ep_in;
+    DevBuf<int> ei, ei_in;
+    DevBuf<unsigned char> sort_tmp;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the solve phase of the last batch
+    bool timed = false;
+    ~NewRowsState()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+// the three refusals about the form of X and its weights, in front of everything else (a batch without rows included)
+static int newrows_form_check(bool implicit, bool Bi, const NewRowsBatchArgs &bt)
+{
+    auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_factors_multiple: ") + what; return 2; };
+    if (implicit && (bt.weight || bt.Xfull || bt.weight_full || Bi)) return bad("observation weights, dense X and implicit features belong to the explicit model");
+    if (bt.Xfull && (bt.nnz > 0 || bt.Xcsr_p)) return bad("X given both as a dense and as a sparse matrix");
+    if ((bt.weight_full && !bt.Xfull) || (bt.weight && bt.Xfull)) return bad("the weights must have the form of X (weight with sparse X, weight_full with Xfull)");
+    return 0;
+}
+
+NewRowsState *newrows_state_create(const NewRowsModelArgs &M, int device, int *rc)
+{
+    auto bad = [&](const char *what) -> NewRowsState * {
+        g_last_error = std::string("cmfrec_hip_factors_multiple: ") + what;
+        *rc = 2;
+        return nullptr;
+    };
+    *rc = 0;
+    if (M.implicit && M.Bi) return bad("observation weights, dense X and implicit features belong to the explicit model");
+    if (!M.B || M.n <= 0 || M.k < 0 || M.k_user < 0 || M.k_item < 0 || M.k_main < 0 || M.p < 0 || (M.implicit && M.user_bias))
+        return bad("invalid arguments");
+    if (M.Bi && ((size_t)M.k + (size_t)M.k_main == 0)) return bad("implicit features without factors");
+    if (M.BiTBi_pre && !M.Bi) return bad("BiTBi without Bi");
+    const bool l1on = M.l1_lam != (real_t)0 || (M.user_bias && M.l1_lam_bias != (real_t)0);
+    if (l1on && M.TransCtCinvCt_pre) return bad("TransCtCinvCt cannot be used with an L1 penalty (collective.c:3378)");
+    std::unique_ptr<NewRowsState> sp(new NewRowsState);
+    NewRowsState &S = *sp;
+    S.M = M;
+    init_device(S.dev, device);
+    DeviceInfo &dev = S.dev;
+    hipStream_t st = dev.stream;
+    const int ub = S.ub = M.user_bias ? 1 : 0;
+    // non-negative factors: every row system goes through solve_nonneg with the reference's sweep limit for new rows, 10 x the
+    // number of unknowns (collective.c:3401, :3800-3931, :4041-4054)
+    dev.nonneg_now = M.nonneg;
+    dev.max_cd_steps = 10 * (M.k_user + M.k + M.k_main + ub);
+    S.l1on = l1on;
+    dev.l1_now = M.l1_lam;
+    dev.l1_last_now = ub ? M.l1_lam_bias : M.l1_lam;
+    dev.l1_scale = 1;
+    const int kc = S.kc = M.k_user + M.k, kk = S.kk = M.k + M.k_main, kt = S.kt = M.k_user + kk + ub, ktA = S.ktA = M.k_user + kk;
+    S.kT = kk + ub;
+    const size_t ldb_host = (size_t)(M.k_item + kk), ldB = S.ldB = ldb_host + ub;
+    S.ldA = (size_t)kt;
+    const int n = M.n;
+    S.dB.alloc((size_t)n * ldB);
+    HIP_CHECK(hipMemcpy2DAsync(S.dB.ptr, ldB * sizeof(real_t), M.B, ldb_host * sizeof(real_t), ldb_host * sizeof(real_t),
+                               (size_t)n, hipMemcpyHostToDevice, st));
+    if (ub) hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(n), dim3(256), 0, st, S.dB.ptr, ldB, n, (int)ldb_host, (real_t)1);
+    if (M.biasB) S.dbias.upload(M.biasB, (size_t)n, st);
+    // implicit features: w_i Bi^T Bi joins the X block of every row's matrix (collective.c:1704-1707), w_i sum_{j observed} Bi_j
+    // its right-hand side (:1757-1771); the matrix term carries the weight of the batch driver (:11016-11020), the right-hand
+    // side the one the row function rescales by w_main (:3706-3714)
+    if (M.Bi) {
+        if (M.n_Bi <= 0 || M.n_Bi > n) return bad("invalid arguments");
+        S.have_Bi = true;
+        S.dBi.upload(M.Bi, (size_t)M.n_Bi * kk, st);
+        S.dBiG.alloc((size_t)kk * kk);
+        if (M.BiTBi_pre) S.dBiG.upload(M.BiTBi_pre, S.dBiG.n, st);
+        else launch_gram(dev, S.gws, S.dBi.ptr, (size_t)kk, M.n_Bi, kk, S.dBiG.ptr, M.w_implicit_gram, (real_t)0);
+        S.dBiFull.alloc((size_t)kt * kt);
+        hipLaunchKernelGGL(embed_block_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, S.dBiG.ptr, kk, M.k_user, kt, S.dBiFull.ptr);
+    }
+    if (M.C && M.p > 0) {
+        S.have_C = true;
+        S.dC.upload(M.C, (size_t)M.p * kc, st);
+        if (M.U_colmeans) { S.have_means = true; S.dmeans.upload(M.U_colmeans, (size_t)M.p, st); }
+        if (M.TransCtCinvCt_pre) { S.have_T = true; S.dT.upload(M.TransCtCinvCt_pre, (size_t)M.p * kc, st); }
+    }
+    if (M.implicit) {
+        S.dG.alloc((size_t)kk * kk);
+        if (M.BtB_pre) S.dG.upload(M.BtB_pre, (size_t)kk * kk, st);
+        else launch_gram(dev, S.gws, S.dB.ptr + M.k_item, ldB, n, kk, S.dG.ptr, (real_t)1, M.lam_x);
+        if (S.have_C) {
+            S.dM.alloc((size_t)ktA * ktA);
+            hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)ktA * ktA), dim3(256), 0, st, S.dG.ptr, kk, M.k_user, M.lam,
+                               S.dM.ptr);
+        }
+    }
+    if (M.TransBtBinvBt_pre && M.n_TB > 0) { S.have_TB = true; S.dTB.upload(M.TransBtBinvBt_pre, (size_t)M.n_TB * S.kT, st); }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventCreate(&S.ev0));
+    HIP_CHECK(hipEventCreate(&S.ev1));
+    HIP_CHECK(hipStreamSynchronize(st));       // the caller's matrices may go away
+    S.M.B = S.M.C = S.M.U_colmeans = S.M.biasB = S.M.BtB_pre = S.M.TransCtCinvCt_pre = S.M.Bi = S.M.BiTBi_pre = S.M.TransBtBinvBt_pre = nullptr;
+    return sp.release();
+}
+
+void newrows_state_destroy(NewRowsState *s)
+{
+    if (s == nullptr) return;
+    int cur = -1;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != s->dev.device && hipSetDevice(s->dev.device) == hipSuccess;
+    delete s;
+    if (sw) (void)hipSetDevice(cur);
+}
+
+NewRowsView newrows_state_view(const NewRowsState *s)
+{
+    NewRowsView v;
+    v.device = s->dev.device;
+    v.dA = s->dA.ptr; v.ldA = s->ldA; v.rows = s->rows;
+    v.dB = s->dB.ptr; v.ldB = s->ldB; v.n = s->M.n;
+    v.dbiasB = s->dbias.ptr;
+    return v;
+}
+
+int newrows_state_solve_ms(NewRowsState *s, double *ms)
+{
+    if (!s->timed) return 2;
+    DeviceScope scope(s->dev.device);
+    HIP_CHECK(hipEventSynchronize(s->ev1));
+    float t = 0;
+    HIP_CHECK(hipEventElapsedTime(&t, s->ev0, s->ev1));
+    *ms = (double)t;
+    return 0;
+}
+
+int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, real_t *biasA)
+{
+    NewRowsState &S = *sp;
+    const NewRowsModelArgs &M = S.M;
+    auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_factors_multiple: ") + what; return 2; };
+    const bool implicit = M.implicit, nonneg = M.nonneg, scale_lam = M.scale_lam, scale_lam_sideinfo = M.scale_lam_sideinfo,
+               scale_bias_const = M.scale_bias_const, l1on = S.l1on, Bi = S.have_Bi;
+    const real_t lam = M.lam, lam_bias = M.lam_bias, w_user = M.w_user, l1_lam = M.l1_lam, l1_lam_bias = M.l1_lam_bias;
+    const int k_user = M.k_user, n = bt.n;
+    const real_t *weight = bt.weight, *Xfull = bt.Xfull, *weight_full = bt.weight_full, *U = bt.U, *X = bt.X;
+    const int_t *ixA = bt.ixA, *ixB = bt.ixB;
+    const size_t *Xcsr_p = bt.Xcsr_p, *U_csr_p = bt.U_csr_p;
+    size_t nnz = bt.nnz;
+    int m_x = bt.m_x, m_u = bt.m_u, p = M.p;
+    S.rows = 0;
+    if (int frc = newrows_form_check(implicit, false, bt)) return frc;
+    if (Xfull) { nnz = 0; ixA = nullptr; ixB = nullptr; X = nullptr; weight = nullptr; }
+    if (m_x <= 0 || (!Xfull && !Xcsr_p && nnz == 0)) weight = nullptr;
+    // sparse side information (COO or CSR over m_u rows, missing = absent): second gather source of the row kernel
+    const bool spU = (U == nullptr && p > 0 && ((bt.nnz_U > 0 && bt.U_row && bt.U_col && bt.U_sp) || U_csr_p));
+    const int m_max = std::max(m_x, (p > 0 && (U || spU)) ? m_u : 0);
+    if (m_max <= 0) return 0;
+    if (n <= 0 || n > M.n || (Bi && n > M.n_Bi) || (p > 0 && (U || spU) && !S.have_C) || (nnz > 0 && !Xcsr_p && (!ixA || !ixB || !X)))
+        return bad("invalid arguments");
+    if (spU && !implicit && scale_lam_sideinfo)
+        return bad("sparse side information with scale_lam_sideinfo is not supported "
+                   "(the reference scales the rows without observations differently, collective.c:3397-3411)");
+    if (!(p > 0 && (U || spU))) { p = 0; m_u = 0; }
+    // index validation on the host, before anything reaches the device (the fit entry points do the same,
+    // fit.hip): a row id outside [0, m_x) or an item id outside [0, n) would corrupt device memory silently
+    if (Xcsr_p) {
+        const size_t nz = Xcsr_p[m_x];
+        for (int r = 0; r < m_x; r++) if (Xcsr_p[r] > Xcsr_p[r + 1]) return bad("Xcsr_p is not non-decreasing");
+        if (nz > 0 && (!bt.Xcsr_i || !bt.Xcsr)) return bad("Xcsr_i / Xcsr missing");
+        for (size_t e = 0; e < nz; e++) if (bt.Xcsr_i[e] < 0 || bt.Xcsr_i[e] >= n) return bad("item index of X outside [0, n)");
+    } else {
+        for (size_t e = 0; e < nnz; e++)
+            if (ixA[e] < 0 || ixA[e] >= m_x || ixB[e] < 0 || ixB[e] >= n) return bad("row / item index of X outside [0, m_x) x [0, n)");
+    }
+    if (spU) {
+        if (U_csr_p) {
+            const size_t nz = U_csr_p[m_u];
+            for (int r = 0; r < m_u; r++) if (U_csr_p[r] > U_csr_p[r + 1]) return bad("U_csr_p is not non-decreasing");
+            if (nz > 0 && (!bt.U_csr_i || !bt.U_csr)) return bad("U_csr_i / U_csr missing");
+            for (size_t e = 0; e < nz; e++) if (bt.U_csr_i[e] < 0 || bt.U_csr_i[e] >= p) return bad("attribute index of U outside [0, p)");
+        } else {
+            for (size_t e = 0; e < bt.nnz_U; e++)
+                if (bt.U_row[e] < 0 || bt.U_row[e] >= m_u || bt.U_col[e] < 0 || bt.U_col[e] >= p) return bad("row / attribute index of U outside [0, m_u) x [0, p)");
+        }
+    }
+    DeviceScope scope(S.dev.device);
+    switches_mut().reload();
+    DeviceInfo &dev = S.dev;
+    GramWorkspace &gws = S.gws;
+    hipStream_t st = dev.stream;
+    const int ub = S.ub, kc = S.kc, kk = S.kk, kt = S.kt, ktA = S.ktA, kT = S.kT;
+    const size_t ldB = S.ldB, ldA = S.ldA;
+    DevBuf<real_t> &dA = S.dA, &dC = S.dC, &dU = S.dU;
+    S.Xs.reset(new SparseShard);
+    S.Us.reset(new SparseShard);
+    SparseShard &Xs = *S.Xs, &Us = *S.Us;
+    HIP_CHECK(hipEventRecord(S.ev0, st));
+    dA.alloc_at_least((size_t)m_max * ldA);
+    HIP_CHECK(hipMemsetAsync(dA.ptr, 0, (size_t)m_max * ldA * sizeof(real_t), st));
+    auto empty_shard = [&]() {
+        std::vector<size_t> pp((size_t)m_max + 1, 0);
+        shard_from_csr(Xs, m_max, pp.data(), nullptr, nullptr, n, st);
+    };
+    // dense X: the block is compacted on the device into the triplets of its present entries (dense_rows_device.hpp), in
+    // blocks of rows so that its device copy (and the weights') stays within a budget; with TransBtBinvBt and nothing that
+    // changes the row systems, the rows without a missing entry are  x^T TransBtBinvBt  (common.c:736-758)
+    const bool use_TB = Xfull != nullptr && S.have_TB && n == M.n_TB && !weight_full && !nonneg && !l1on && p == 0 && !Bi;
+    if (Xfull) {
+        const size_t per_row = (size_t)n * sizeof(real_t) * (weight_full ? 2 : 1);
+        long long block_rows = (long long)std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_row, 1));
+        if (switches().newrows_block_rows > 0) block_rows = switches().newrows_block_rows;     // test hook
+        block_rows = std::min<long long>(block_rows, m_x);
+        S.dmiss.alloc_at_least((size_t)m_x);
+        if (use_TB) S.dTBout.alloc_at_least((size_t)m_x * kT);
+        DevBuf<real_t> &dXb = S.dXb, &dWb = S.dWb;
+        std::vector<std::unique_ptr<DenseRowsCoo>> parts;
+        size_t total = 0;
+        for (long long r0 = 0; r0 < m_x; r0 += block_rows) {
+            const int rows = (int)std::min<long long>(block_rows, m_x - r0);
+            dXb.upload(Xfull + (size_t)r0 * n, (size_t)rows * n, st);
+            if (weight_full) dWb.upload(weight_full + (size_t)r0 * n, (size_t)rows * n, st);
+            parts.emplace_back(new DenseRowsCoo);
+            dense_rows_to_coo(dXb.ptr, weight_full ? dWb.ptr : nullptr, rows, n, (int)r0, bt.glob_mean_full, S.dmiss.ptr + r0,
+                              *parts.back(), st);
+            total += parts.back()->nnz;
+            if (use_TB) {
+                hipLaunchKernelGGL(dense_rows_center_kernel<real_t>, grid1d(std::min<size_t>((size_t)rows * n, (size_t)1 << 22)), dim3(256), 0,
+                                   st, dXb.ptr, (size_t)rows, n, bt.glob_mean_full, S.dbias.ptr, S.dmiss.ptr + r0);
+                HIP_CHECK(hipGetLastError());
+                launch_gemm<false>(dev, rows, kT, n, (real_t)1, dXb.ptr, (size_t)n, S.dTB.ptr, (size_t)kT, S.dTBout.ptr + (size_t)r0 * kT,
+                                   (size_t)kT);
+                HIP_CHECK(hipStreamSynchronize(st));
+            }
+        }
+        if (total == 0) empty_shard();
+        else if (parts.size() == 1) {
+            DenseRowsCoo &c = *parts[0];
+            shard_from_coo(Xs, m_max, n, c.row.ptr, c.col.ptr, c.val.ptr, total, (real_t)0, (real_t)1, st, weight_full ? c.wt.ptr : nullptr);
+            HIP_CHECK(hipStreamSynchronize(st));
+        } else {
+            DenseRowsCoo all;
+            all.row.alloc(total); all.col.alloc(total); all.val.alloc(total);
+            if (weight_full) all.wt.alloc(total);
+            size_t at = 0;
+            for (auto &c : parts) {
+                if (c->nnz == 0) continue;
+                HIP_CHECK(hipMemcpyAsync(all.row.ptr + at, c->row.ptr, c->nnz * sizeof(int), hipMemcpyDeviceToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(all.col.ptr + at, c->col.ptr, c->nnz * sizeof(int), hipMemcpyDeviceToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(all.val.ptr + at, c->val.ptr, c->nnz * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+                if (weight_full) HIP_CHECK(hipMemcpyAsync(all.wt.ptr + at, c->wt.ptr, c->nnz * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+                at += c->nnz;
+            }
+            HIP_CHECK(hipStreamSynchronize(st));
+            parts.clear();
+            shard_from_coo(Xs, m_max, n, all.row.ptr, all.col.ptr, all.val.ptr, total, (real_t)0, (real_t)1, st, weight_full ? all.wt.ptr : nullptr);
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+    } else if (Xcsr_p) {
+        std::vector<size_t> pp((size_t)m_max + 1);
+        for (int r = 0; r <= m_max; r++) pp[r] = Xcsr_p[std::min(r, m_x)];
+        shard_from_csr(Xs, m_max, pp.data(), bt.Xcsr_i, bt.Xcsr, n, st, Xcsr_p[m_x] > 0 ? weight : nullptr);
+    } else if (nnz == 0) {
+        empty_shard();
+    } else {
+        DevBuf<int> dr, dc; DevBuf<real_t> dv, dw;
+        dr.upload(ixA, std::max<size_t>(nnz, 1), st); dc.upload(ixB, std::max<size_t>(nnz, 1), st);
+        dv.upload(X, std::max<size_t>(nnz, 1), st);
+        if (weight) dw.upload(weight, nnz, st);
+        shard_from_coo(Xs, m_max, n, dr.ptr, dc.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, st, weight ? dw.ptr : nullptr);
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (spU) {
+        if (U_csr_p) {
+            std::vector<size_t> up((size_t)m_max + 1);
+            for (int r = 0; r <= m_max; r++) up[r] = U_csr_p[std::min(r, m_u)];
+            shard_from_csr(Us, m_max, up.data(), bt.U_csr_i, bt.U_csr, p, st);
+        } else {
+            DevBuf<int> dr, dc; DevBuf<real_t> dv;
+            dr.upload(bt.U_row, bt.nnz_U, st); dc.upload(bt.U_col, bt.nnz_U, st); dv.upload(bt.U_sp, bt.nnz_U, st);
+            shard_from_coo(Us, m_max, p, dr.ptr, dc.ptr, dv.ptr, bt.nnz_U, (real_t)0, (real_t)1, st);
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+    } else if (p > 0) {
+        dU.upload(U, (size_t)m_u * p, st);
+        if (S.have_means)
+            hipLaunchKernelGGL(sub_colmeans_kernel<real_t>, grid1d((size_t)m_u * p), dim3(256), 0, st, dU.ptr, (size_t)m_u, p,
+                               S.dmeans.ptr);
+    }
+    // w_user C^T C of the rows with dense side information: the model's, built by the first batch that has such rows
+    auto ensure_CtC = [&]() {
+        if (S.ctc_built) return;
+        S.dCtC.alloc((size_t)kc * kc);
+        launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, S.dCtC.ptr, w_user, (real_t)0);
+        S.ctc_built = true;
+    };
+    const real_t *opp = S.dB.ptr + M.k_item;
+    const real_t *bias_sub = S.dbias.ptr;
+    int rc = 0;
+    if (implicit) {
+        if (p == 0) {
+            CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk, 0, nullptr, S.dG.ptr, 0, 0, 0, lam, lam, false, false, false,
+                       CHOL_IMPLICIT};
+            rc = launch_chol(dev, c, &Xs);
+        } else if (spU) {
+            CholCall c{dA.ptr, ldA, opp, ldB, ktA, k_user, nullptr, nullptr, kc, m_u, p, lam, lam, false, false, false,
+                       CHOL_COLLECTIVE_IMPLICIT, S.dM.ptr};
+            c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
+            rc = launch_chol(dev, c, &Xs);
+        } else {
+            ensure_CtC();
+            launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
+            CholCall c{dA.ptr, ldA, opp, ldB, ktA, k_user, nullptr, S.dCtC.ptr, kc, m_u, p, lam, lam, false, false, false,
+                       CHOL_COLLECTIVE_IMPLICIT, S.dM.ptr};
+            rc = launch_chol(dev, c, &Xs);
+        }
+    } else if (Bi) {
+        // with implicit features every row goes through the block solver, the model without side information included
+        // (collective.c:3759-3760), and a row without observations is not a "cold" row (:3655-3659): one launch.  Rows that
+        // the kernel treats as rows with side information take the block solver's rules for the last unknown's lambda
+        // and the L1 penalty (:1349-1354); that is every row except those beyond a dense U.
+        const bool all_u = p == 0 || spU || m_u >= m_max;
+        bool sbc = scale_bias_const;
+        if (!all_u) {
+            if (l1on && scale_bias_const && (scale_lam || scale_lam_sideinfo))
+                return bad("implicit features with an L1 penalty, scale_bias_const and dense side "
+                           "information for fewer rows than the batch is not supported");
+            sbc = false;
+        }
+        if (p > 0 && !spU) {
+            ensure_CtC();
+            launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
+        }
+        if (Xs.nnz > 0)
+            hipLaunchKernelGGL(implicit_rhs_rows_kernel<real_t>, grid1d((size_t)m_max * 64), dim3(256), 0, st, Xs.p.ptr, Xs.i.ptr, S.dBi.ptr, kk,
+                               M.w_implicit, m_max, dA.ptr, ldA, k_user);
+        HIP_CHECK(hipGetLastError());
+        CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, (p > 0 && !spU) ? S.dCtC.ptr : nullptr, p > 0 ? kc : 0,
+                   all_u ? m_max : m_u, p, lam, lam_bias, (bool)(scale_lam || scale_lam_sideinfo),
+                   (bool)(scale_lam_sideinfo && !spU), sbc, CHOL_COLLECTIVE};
+        c.Mfull = S.dBiFull.ptr; c.rhs_prefilled_all = true;
+        if (spU) { c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user; c.rows2 = m_u; }
+        rc = launch_chol(dev, c, &Xs);
+    } else if (p == 0) {
+        CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk + ub, 0, bias_sub, nullptr, 0, 0, 0, lam, lam_bias,
+                   (bool)(scale_lam || scale_lam_sideinfo), false, scale_bias_const, CHOL_EXPLICIT};
+        rc = launch_chol(dev, c, &Xs);
+    } else if (spU) {
+        // rows with attributes but no observations come out of the same launch: without scale_lam_sideinfo the
+        // "cold" solution (collective.c:3309-3440 with u_vec_sp) is the block system with an empty X part
+        CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, nullptr, kc, m_u, p, lam, lam_bias, scale_lam, false,
+                   scale_bias_const, CHOL_COLLECTIVE};
+        c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
+        rc = launch_chol(dev, c, &Xs);
+    } else {
+        ensure_CtC();
+        launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
+        CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, S.dCtC.ptr, kc, m_u, p, lam, lam_bias,
+                   (bool)(scale_lam || scale_lam_sideinfo), scale_lam_sideinfo, scale_bias_const, CHOL_COLLECTIVE};
+        rc = launch_chol(dev, c, &Xs);
+        if (rc == 0) {
+            // cold rows
+            S.dcold.alloc_at_least((size_t)m_u * kc);
+            if (S.have_T && bt.allow_TransCtCinvCt) {
+                launch_gemm<false>(dev, m_u, kc, p, (real_t)1, dU.ptr, (size_t)p, S.dT.ptr, (size_t)kc, S.dcold.ptr, (size_t)kc);
+            } else {
+                const real_t lc = lam / w_user;
+                if (!S.cold_built) {
+                    S.dMcold.alloc((size_t)kc * kc);
+                    launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, S.dMcold.ptr, (real_t)1, scale_lam_sideinfo ? lc * (real_t)p : lc);
+                    if (scale_lam_sideinfo)
+                        hipLaunchKernelGGL(add_diag_kernel<real_t>, dim3(1), dim3(64), 0, st, S.dMcold.ptr, kc, kc - 1, kc,
+                                           lc - lc * (real_t)p);
+                    S.cold_built = true;
+                }
+                launch_gemm<false>(dev, m_u, kc, p, (real_t)1, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, S.dcold.ptr, (size_t)kc);
+                CholCall cc{S.dcold.ptr, (size_t)kc, nullptr, 0, kc, 0, nullptr, S.dMcold.ptr, 0, 0, 0, 0, 0, false, false, false,
+                            CHOL_PREFILLED};
+                // factors_closed_form on C with l1_lam / w_user, scaled by p like lam except on the last unknown (collective.c:3385-3400)
+                dev.l1_last_now = l1_lam / w_user;
+                dev.l1_now = scale_lam_sideinfo ? dev.l1_last_now * (real_t)p : dev.l1_last_now;
+                rc = launch_chol(dev, cc, nullptr, m_u);
+                dev.l1_now = l1_lam; dev.l1_last_now = ub ? l1_lam_bias : l1_lam;
+            }
+            hipLaunchKernelGGL(cold_select_kernel<real_t>, dim3(m_u), dim3(64), 0, st, dA.ptr, ldA, kt, kc, S.dcold.ptr,
+                               Xs.p.ptr, m_u);
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+    if (rc) return rc;
+    if (!implicit && Xs.weighted() && (scale_lam || scale_lam_sideinfo)) {
+        hipLaunchKernelGGL(zero_weightless_rows_kernel<real_t>, dim3(m_max), dim3(64), 0, st, Xs.p.ptr, Xs.wsum.ptr, m_max, p > 0 ? m_u : 0,
+                           std::numeric_limits<real_t>::epsilon(), dA.ptr, ldA, kt);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (use_TB) {
+        hipLaunchKernelGGL(dense_rows_select_complete_kernel<real_t>, grid1d(std::min<size_t>((size_t)m_x * kT, (size_t)1 << 22)), dim3(256), 0, st,
+                           dA.ptr, ldA, k_user, S.dTBout.ptr, kT, S.dmiss.ptr, (size_t)m_x);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(S.ev1, st));
+    S.timed = true;
+    S.rows = m_max;
+    // the factors stay on the device (dA, the bias in its last column); the copies to the host are the caller's choice
+    if (A)
+        HIP_CHECK(hipMemcpy2DAsync(A, (size_t)ktA * sizeof(real_t), dA.ptr, ldA * sizeof(real_t), (size_t)ktA * sizeof(real_t),
+                                   (size_t)m_max, hipMemcpyDeviceToHost, st));
+    if (ub && biasA) {
+        S.dba.alloc_at_least((size_t)m_max);
+        hipLaunchKernelGGL(col_extract_kernel<real_t>, grid1d(m_max), dim3(256), 0, st, dA.ptr, ldA, m_max, ktA, S.dba.ptr);
+        S.dba.download(biasA, (size_t)m_max, st);
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---- exclusion lists of the last batch's rows ---------------------------------------------------
+// row pointers of the union: the row's own entries, then the caller's list
+__global__ void seen_union_ptr_kernel(const size_t *__restrict__ xp, const size_t *__restrict__ lp, int rows, size_t *__restrict__ out)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r <= rows) out[r] = xp[r] + lp[r];
+}
+
+// one wavefront per row: the item ids of the row's entries, then those of the caller's list
+__global__ void __launch_bounds__(64)
+seen_union_fill_kernel(const size_t *__restrict__ xp, const int *__restrict__ xi, const size_t *__restrict__ lp,
+                       const int *__restrict__ li, const size_t *__restrict__ op, int rows, int *__restrict__ out)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const size_t x0 = xp[r], nx = xp[r + 1] - x0, l0 = lp[r], nl = lp[r + 1] - l0, o0 = op[r];
+    for (size_t e = threadIdx.x; e < nx; e += 64) out[o0 + e] = xi[x0 + e];
+    for (size_t e = threadIdx.x; e < nl; e += 64) out[o0 + nx + e] = li[l0 + e];
+}
+
+int newrows_state_exclusions(NewRowsState *sp, bool seen, const size_t *excl_p, const int_t *excl_i, const size_t **dp, const int **di)
+{
+    NewRowsState &S = *sp;
+    *dp = nullptr; *di = nullptr;
+    const int rows = S.rows;
+    if (rows <= 0 || (!seen && !excl_p)) return 0;
+    auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_newrows_topN: ") + what; return 2; };
+    const int n = S.M.n;
+    size_t nl = 0;
+    if (excl_p) {
+        nl = excl_p[rows];
+        if (nl > 0 && !excl_i) return bad("invalid arguments");
+        for (int r = 0; r < rows; r++) if (excl_p[r] > excl_p[r + 1]) return bad("excl_p is not non-decreasing");
+    }
+    DeviceScope scope(S.dev.device);
+    hipStream_t st = S.dev.stream;
+    if (!seen) {                                   // the caller's lists as they are (sorted by contract, like the ranker's)
+        S.ep.upload(excl_p, (size_t)rows + 1, st);
+        S.ei.alloc_at_least(std::max<size_t>(nl, 1));
+        if (nl > 0) S.ei.upload(excl_i, nl, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        *dp = S.ep.ptr; *di = S.ei.ptr;
+        return 0;
+    }
+    // The shard keeps a row's entries in the order of the triplets (that order fixes the sums of the row's system); the ranking
+    // kernels search a sorted list.  So: a second CSR of item ids -- the shard's row pointers (or theirs plus the lists'), the ids
+    // copied (or concatenated), each row's ids sorted by a segmented radix sort.  An id in both lists stays twice: the search
+    // is a lower bound.
+    const SparseShard &Xs = *S.Xs;
+    const size_t total = Xs.nnz + nl;
+    if (total >= ((size_t)1 << 31)) return bad("more than 2^31 excluded entries in one batch");
+    const size_t *ptr = Xs.p.ptr;
+    const int *keys_in = Xs.i.ptr;
+    if (nl > 0) {
+        S.ep_in.upload(excl_p, (size_t)rows + 1, st);
+        S.ei_in.alloc_at_least(total);
+        DevBuf<int> dl;
+        dl.upload(excl_i, nl, st);
+        S.ep.alloc_at_least((size_t)rows + 1);
+        hipLaunchKernelGGL(seen_union_ptr_kernel, grid1d((size_t)rows + 1), dim3(256), 0, st, Xs.p.ptr, S.ep_in.ptr, rows, S.ep.ptr);
+        hipLaunchKernelGGL(seen_union_fill_kernel, dim3(rows), dim3(64), 0, st, Xs.p.ptr, Xs.i.ptr, S.ep_in.ptr, dl.ptr, S.ep.ptr, rows,
+                           S.ei_in.ptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));       // dl goes away
+        ptr = S.ep.ptr; keys_in = S.ei_in.ptr;
+    }
+    S.ei.alloc_at_least(std::max<size_t>(total, 1));
+    if (total > 0) {
+        unsigned bits = 1;
+        while (bits < 32 && (1ull << bits) < (unsigned long long)n) bits++;
+        size_t bytes = 0;
+        HIP_CHECK(rocprim::segmented_radix_sort_keys(nullptr, bytes, keys_in, S.ei.ptr, (unsigned)total, (unsigned)rows, ptr, ptr + 1, 0u, bits, st));
+        S.sort_tmp.alloc_at_least(bytes + 16);
+        HIP_CHECK(rocprim::segmented_radix_sort_keys(S.sort_tmp.ptr, bytes, keys_in, S.ei.ptr, (unsigned)total, (unsigned)rows, ptr, ptr + 1, 0u, bits, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    *dp = ptr; *di = S.ei.ptr;
+    return 0;
+}
+
+}  // namespace cmfhip
+
+extern "C" {
+
 static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u, int_t p, const real_t *U,
                                  const real_t *U_colmeans, const int_t ixA[], const int_t ixB[], const real_t *X,
                                  size_t nnz, const size_t Xcsr_p[], const int_t Xcsr_i[], const real_t *Xcsr,
@@ -3553,325 +4072,31 @@ static int factors_multiple_impl(real_t *A, real_t *biasA, int_t m_x, int_t m_u,
                                  real_t l1_lam, real_t l1_lam_bias, const NewRowsExtra &ex)
 {
     return guarded([&]() {
-        const real_t *weight = ex.weight, *Xfull = ex.Xfull, *weight_full = ex.weight_full, *Bi = ex.Bi;
-        if (implicit && (weight || Xfull || weight_full || Bi)) {
-            g_last_error = "cmfrec_hip_factors_multiple: observation weights, dense X and implicit features belong to the explicit model";
-            return 2;
-        }
-        if (Xfull && (nnz > 0 || Xcsr_p)) {
-            g_last_error = "cmfrec_hip_factors_multiple: X given both as a dense and as a sparse matrix";
-            return 2;
-        }
-        if ((weight_full && !Xfull) || (weight && Xfull)) {
-            g_last_error = "cmfrec_hip_factors_multiple: the weights must have the form of X (weight with sparse X, weight_full with Xfull)";
-            return 2;
-        }
-        if (Xfull) { nnz = 0; ixA = nullptr; ixB = nullptr; X = nullptr; weight = nullptr; }
-        if (m_x <= 0 || (!Xfull && !Xcsr_p && nnz == 0)) weight = nullptr;
-        // sparse side information (COO or CSR over m_u rows, missing = absent): second gather source of the row kernel
-        const bool spU = (U == nullptr && p > 0 && ((nnz_U > 0 && U_row && U_col && U_sp) || U_csr_p));
-        const int m_max = std::max(m_x, (p > 0 && (U || spU)) ? m_u : 0);
-        if (m_max <= 0) return 0;
-        if (!A || !B || n <= 0 || k < 0 || (p > 0 && (U || spU) && !C) || (nnz > 0 && !Xcsr_p && (!ixA || !ixB || !X)) ||
-            (implicit && biasA)) {
+        NewRowsBatchArgs bt;
+        bt.m_x = m_x; bt.m_u = m_u; bt.n = n; bt.U = U;
+        bt.U_row = U_row; bt.U_col = U_col; bt.U_sp = U_sp; bt.nnz_U = nnz_U; bt.U_csr_p = U_csr_p; bt.U_csr_i = U_csr_i; bt.U_csr = U_csr;
+        bt.ixA = ixA; bt.ixB = ixB; bt.X = X; bt.nnz = nnz; bt.Xcsr_p = Xcsr_p; bt.Xcsr_i = Xcsr_i; bt.Xcsr = Xcsr;
+        bt.weight = ex.weight; bt.Xfull = ex.Xfull; bt.weight_full = ex.weight_full; bt.glob_mean_full = ex.glob_mean_full;
+        if (int frc = newrows_form_check(implicit, ex.Bi != nullptr, bt)) return frc;
+        const bool side = p > 0 && (U || (nnz_U > 0 && U_row && U_col && U_sp) || U_csr_p);
+        if (std::max(m_x, side ? m_u : 0) <= 0) return 0;          // a batch without rows
+        if (!A) {
             g_last_error = "cmfrec_hip_factors_multiple: invalid arguments";
             return 2;
         }
-        if (spU && !implicit && scale_lam_sideinfo) {
-            g_last_error = "cmfrec_hip_factors_multiple: sparse side information with scale_lam_sideinfo is not supported "
-                           "(the reference scales the rows without observations differently, collective.c:3397-3411)";
-            return 2;
-        }
-        if (!(p > 0 && (U || spU))) { p = 0; m_u = 0; }
-        // index validation on the host, before anything reaches the device (the fit entry points do the same,
-        // fit.hip): a row id outside [0, m_x) or an item id outside [0, n) would corrupt device memory silently
-        {
-            auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_factors_multiple: ") + what; return 2; };
-            if (Bi && ((size_t)k + (size_t)k_main == 0)) return bad("implicit features without factors");
-            if (ex.BiTBi_pre && !Bi) return bad("BiTBi without Bi");
-            if (Xcsr_p) {
-                const size_t nz = Xcsr_p[m_x];
-                for (int r = 0; r < m_x; r++) if (Xcsr_p[r] > Xcsr_p[r + 1]) return bad("Xcsr_p is not non-decreasing");
-                if (nz > 0 && (!Xcsr_i || !Xcsr)) return bad("Xcsr_i / Xcsr missing");
-                for (size_t e = 0; e < nz; e++) if (Xcsr_i[e] < 0 || Xcsr_i[e] >= n) return bad("item index of X outside [0, n)");
-            } else {
-                for (size_t e = 0; e < nnz; e++)
-                    if (ixA[e] < 0 || ixA[e] >= m_x || ixB[e] < 0 || ixB[e] >= n) return bad("row / item index of X outside [0, m_x) x [0, n)");
-            }
-            if (spU) {
-                if (U_csr_p) {
-                    const size_t nz = U_csr_p[m_u];
-                    for (int r = 0; r < m_u; r++) if (U_csr_p[r] > U_csr_p[r + 1]) return bad("U_csr_p is not non-decreasing");
-                    if (nz > 0 && (!U_csr_i || !U_csr)) return bad("U_csr_i / U_csr missing");
-                    for (size_t e = 0; e < nz; e++) if (U_csr_i[e] < 0 || U_csr_i[e] >= p) return bad("attribute index of U outside [0, p)");
-                } else {
-                    for (size_t e = 0; e < nnz_U; e++)
-                        if (U_row[e] < 0 || U_row[e] >= m_u || U_col[e] < 0 || U_col[e] >= p) return bad("row / attribute index of U outside [0, m_u) x [0, p)");
-                }
-            }
-        }
-        DeviceInfo dev;
-        init_device(dev, -1);
-        hipStream_t st = dev.stream;
-        const int ub = biasA ? 1 : 0;
-        // non-negative factors: every row system below goes through solve_nonneg with the reference's sweep limit for
-        // new rows, 10 x the number of unknowns (collective.c:3401, :3800-3931, :4041-4054)
-        dev.nonneg_now = nonneg;
-        dev.max_cd_steps = 10 * (k_user + k + k_main + ub);
-        const bool l1on = l1_lam != (real_t)0 || (ub && l1_lam_bias != (real_t)0);
-        if (l1on && TransCtCinvCt_pre) {
-            g_last_error = "cmfrec_hip_factors_multiple: TransCtCinvCt cannot be used with an L1 penalty (collective.c:3378)";
-            return 2;
-        }
-        dev.l1_now = l1_lam;
-        dev.l1_last_now = ub ? l1_lam_bias : l1_lam;
-        dev.l1_scale = 1;
-        const int kc = k_user + k, kk = k + k_main, kt = k_user + kk + ub, ktA = k_user + kk;
-        const size_t ldb_host = (size_t)(k_item + kk), ldB = ldb_host + ub, ldA = (size_t)kt;
-        DevBuf<real_t> dA, dB, dC, dU, dmeans, dbias, dG, dM, dCtC, dcold, dT;
-        GramWorkspace gws;
-        SparseShard Xs;
-        dB.alloc((size_t)n * ldB);
-        HIP_CHECK(hipMemcpy2DAsync(dB.ptr, ldB * sizeof(real_t), B, ldb_host * sizeof(real_t), ldb_host * sizeof(real_t),
-                                   (size_t)n, hipMemcpyHostToDevice, st));
-        if (ub) hipLaunchKernelGGL(col_fill_kernel<real_t>, grid1d(n), dim3(256), 0, st, dB.ptr, ldB, n, (int)ldb_host, (real_t)1);
-        if (biasB) dbias.upload(biasB, (size_t)n, st);
-        dA.alloc((size_t)m_max * ldA);
-        HIP_CHECK(hipMemsetAsync(dA.ptr, 0, dA.n * sizeof(real_t), st));
-        auto empty_shard = [&]() {
-            std::vector<size_t> pp((size_t)m_max + 1, 0);
-            shard_from_csr(Xs, m_max, pp.data(), nullptr, nullptr, n, st);
-        };
-        // dense X: the block is compacted on the device into the triplets of its present entries (dense_rows_device.hpp), in
-        // blocks of rows so that its device copy (and the weights') stays within a budget; with TransBtBinvBt and nothing that
-        // changes the row systems, the rows without a missing entry are  x^T TransBtBinvBt  (common.c:736-758)
-        DevBuf<int> dmiss;
-        DevBuf<real_t> dTB, dTBout;
-        const int kT = kk + ub;
-        const bool use_TB = Xfull != nullptr && ex.TransBtBinvBt_pre != nullptr && !weight_full && !nonneg && !l1on && p == 0 && !Bi;
-        if (Xfull) {
-            const size_t per_row = (size_t)n * sizeof(real_t) * (weight_full ? 2 : 1);
-            long long block_rows = (long long)std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_row, 1));
-            if (switches().newrows_block_rows > 0) block_rows = switches().newrows_block_rows;     // test hook
-            block_rows = std::min<long long>(block_rows, m_x);
-            dmiss.alloc((size_t)m_x);
-            if (use_TB) { dTB.upload(ex.TransBtBinvBt_pre, (size_t)n * kT, st); dTBout.alloc((size_t)m_x * kT); }
-            DevBuf<real_t> dXb, dWb;
-            std::vector<std::unique_ptr<DenseRowsCoo>> parts;
-            size_t total = 0;
-            for (long long r0 = 0; r0 < m_x; r0 += block_rows) {
-                const int rows = (int)std::min<long long>(block_rows, m_x - r0);
-                dXb.upload(Xfull + (size_t)r0 * n, (size_t)rows * n, st);
-                if (weight_full) dWb.upload(weight_full + (size_t)r0 * n, (size_t)rows * n, st);
-                parts.emplace_back(new DenseRowsCoo);
-                dense_rows_to_coo(dXb.ptr, weight_full ? dWb.ptr : nullptr, rows, n, (int)r0, ex.glob_mean_full, dmiss.ptr + r0,
-                                  *parts.back(), st);
-                total += parts.back()->nnz;
-                if (use_TB) {
-                    hipLaunchKernelGGL(dense_rows_center_kernel<real_t>, grid1d(std::min<size_t>((size_t)rows * n, (size_t)1 << 22)), dim3(256), 0,
-                                       st, dXb.ptr, (size_t)rows, n, ex.glob_mean_full, biasB ? dbias.ptr : nullptr, dmiss.ptr + r0);
-                    HIP_CHECK(hipGetLastError());
-                    launch_gemm<false>(dev, rows, kT, n, (real_t)1, dXb.ptr, (size_t)n, dTB.ptr, (size_t)kT, dTBout.ptr + (size_t)r0 * kT,
-                                       (size_t)kT);
-                    HIP_CHECK(hipStreamSynchronize(st));
-                }
-            }
-            if (total == 0) empty_shard();
-            else if (parts.size() == 1) {
-                DenseRowsCoo &c = *parts[0];
-                shard_from_coo(Xs, m_max, n, c.row.ptr, c.col.ptr, c.val.ptr, total, (real_t)0, (real_t)1, st, weight_full ? c.wt.ptr : nullptr);
-                HIP_CHECK(hipStreamSynchronize(st));
-            } else {
-                DenseRowsCoo all;
-                all.row.alloc(total); all.col.alloc(total); all.val.alloc(total);
-                if (weight_full) all.wt.alloc(total);
-                size_t at = 0;
-                for (auto &c : parts) {
-                    if (c->nnz == 0) continue;
-                    HIP_CHECK(hipMemcpyAsync(all.row.ptr + at, c->row.ptr, c->nnz * sizeof(int), hipMemcpyDeviceToDevice, st));
-                    HIP_CHECK(hipMemcpyAsync(all.col.ptr + at, c->col.ptr, c->nnz * sizeof(int), hipMemcpyDeviceToDevice, st));
-                    HIP_CHECK(hipMemcpyAsync(all.val.ptr + at, c->val.ptr, c->nnz * sizeof(real_t), hipMemcpyDeviceToDevice, st));
-                    if (weight_full) HIP_CHECK(hipMemcpyAsync(all.wt.ptr + at, c->wt.ptr, c->nnz * sizeof(real_t), hipMemcpyDeviceToDevice, st));
-                    at += c->nnz;
-                }
-                HIP_CHECK(hipStreamSynchronize(st));
-                parts.clear();
-                shard_from_coo(Xs, m_max, n, all.row.ptr, all.col.ptr, all.val.ptr, total, (real_t)0, (real_t)1, st, weight_full ? all.wt.ptr : nullptr);
-                HIP_CHECK(hipStreamSynchronize(st));
-            }
-        } else if (Xcsr_p) {
-            std::vector<size_t> pp((size_t)m_max + 1);
-            for (int r = 0; r <= m_max; r++) pp[r] = Xcsr_p[std::min(r, m_x)];
-            shard_from_csr(Xs, m_max, pp.data(), Xcsr_i, Xcsr, n, st, Xcsr_p[m_x] > 0 ? weight : nullptr);
-        } else if (nnz == 0) {
-            empty_shard();
-        } else {
-            DevBuf<int> dr, dc; DevBuf<real_t> dv, dw;
-            dr.upload(ixA, std::max<size_t>(nnz, 1), st); dc.upload(ixB, std::max<size_t>(nnz, 1), st);
-            dv.upload(X, std::max<size_t>(nnz, 1), st);
-            if (weight) dw.upload(weight, nnz, st);
-            shard_from_coo(Xs, m_max, n, dr.ptr, dc.ptr, dv.ptr, nnz, (real_t)0, (real_t)1, st, weight ? dw.ptr : nullptr);
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-        // implicit features: w_i Bi^T Bi joins the X block of every row's matrix (collective.c:1704-1707), w_i sum_{j observed} Bi_j
-        // its right-hand side (:1757-1771); the matrix term carries the weight of the batch driver (:11016-11020), the right-hand
-        // side the one the row function rescales by w_main (:3706-3714)
-        DevBuf<real_t> dBi, dBiG, dBiFull;
-        if (Bi) {
-            dBi.upload(Bi, (size_t)n * kk, st);
-            dBiG.alloc((size_t)kk * kk);
-            if (ex.BiTBi_pre) dBiG.upload(ex.BiTBi_pre, dBiG.n, st);
-            else launch_gram(dev, gws, dBi.ptr, (size_t)kk, n, kk, dBiG.ptr, ex.w_implicit_gram, (real_t)0);
-        }
-        SparseShard Us;
-        if (spU) {
-            dC.upload(C, (size_t)p * kc, st);
-            if (U_csr_p) {
-                std::vector<size_t> up((size_t)m_max + 1);
-                for (int r = 0; r <= m_max; r++) up[r] = U_csr_p[std::min(r, m_u)];
-                shard_from_csr(Us, m_max, up.data(), U_csr_i, U_csr, p, st);
-            } else {
-                DevBuf<int> dr, dc; DevBuf<real_t> dv;
-                dr.upload(U_row, nnz_U, st); dc.upload(U_col, nnz_U, st); dv.upload(U_sp, nnz_U, st);
-                shard_from_coo(Us, m_max, p, dr.ptr, dc.ptr, dv.ptr, nnz_U, (real_t)0, (real_t)1, st);
-                HIP_CHECK(hipStreamSynchronize(st));
-            }
-        } else if (p > 0) {
-            dC.upload(C, (size_t)p * kc, st);
-            dU.upload(U, (size_t)m_u * p, st);
-            if (U_colmeans) {
-                dmeans.upload(U_colmeans, (size_t)p, st);
-                hipLaunchKernelGGL(sub_colmeans_kernel<real_t>, grid1d((size_t)m_u * p), dim3(256), 0, st, dU.ptr, (size_t)m_u, p,
-                                   dmeans.ptr);
-            }
-            dCtC.alloc((size_t)kc * kc);
-        }
-        const real_t *opp = dB.ptr + k_item;
-        const real_t *bias_sub = biasB ? dbias.ptr : nullptr;
+        NewRowsModelArgs M;
+        M.B = B; M.n = n; M.C = side ? C : nullptr; M.p = p; M.U_colmeans = (side && U) ? U_colmeans : nullptr; M.biasB = biasB;
+        M.k = k; M.k_user = k_user; M.k_item = k_item; M.k_main = k_main; M.user_bias = biasA != nullptr;
+        M.lam = lam; M.lam_bias = lam_bias; M.lam_x = lam_x; M.w_user = w_user;
+        M.implicit = implicit; M.scale_lam = scale_lam; M.scale_lam_sideinfo = scale_lam_sideinfo; M.scale_bias_const = scale_bias_const;
+        M.BtB_pre = BtB_pre; M.TransCtCinvCt_pre = TransCtCinvCt_pre; M.nonneg = nonneg; M.l1_lam = l1_lam; M.l1_lam_bias = l1_lam_bias;
+        M.Bi = ex.Bi; M.n_Bi = n; M.w_implicit = ex.w_implicit; M.w_implicit_gram = ex.w_implicit_gram; M.BiTBi_pre = ex.BiTBi_pre;
+        M.TransBtBinvBt_pre = ex.Xfull ? ex.TransBtBinvBt_pre : nullptr; M.n_TB = n;
         int rc = 0;
-        if (implicit) {
-            dG.alloc((size_t)kk * kk);
-            if (BtB_pre) dG.upload(BtB_pre, (size_t)kk * kk, st);
-            else launch_gram(dev, gws, opp, ldB, n, kk, dG.ptr, (real_t)1, lam_x);
-            if (p == 0) {
-                CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk, 0, nullptr, dG.ptr, 0, 0, 0, lam, lam, false, false, false,
-                           CHOL_IMPLICIT};
-                rc = launch_chol(dev, c, &Xs);
-            } else if (spU) {
-                dM.alloc((size_t)ktA * ktA);
-                hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)ktA * ktA), dim3(256), 0, st, dG.ptr, kk, k_user, lam,
-                                   dM.ptr);
-                CholCall c{dA.ptr, ldA, opp, ldB, ktA, k_user, nullptr, nullptr, kc, m_u, p, lam, lam, false, false, false,
-                           CHOL_COLLECTIVE_IMPLICIT, dM.ptr};
-                c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
-                rc = launch_chol(dev, c, &Xs);
-            } else {
-                dM.alloc((size_t)ktA * ktA);
-                hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)ktA * ktA), dim3(256), 0, st, dG.ptr, kk, k_user, lam,
-                                   dM.ptr);
-                launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, dCtC.ptr, w_user, (real_t)0);
-                launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
-                CholCall c{dA.ptr, ldA, opp, ldB, ktA, k_user, nullptr, dCtC.ptr, kc, m_u, p, lam, lam, false, false, false,
-                           CHOL_COLLECTIVE_IMPLICIT, dM.ptr};
-                rc = launch_chol(dev, c, &Xs);
-            }
-        } else if (Bi) {
-            // with implicit features every row goes through the block solver, the model without side information included
-            // (collective.c:3759-3760), and a row without observations is not a "cold" row (:3655-3659): one launch.  Rows that
-            // the kernel treats as rows with side information take the block solver's rules for the last unknown's lambda
-            // and the L1 penalty (:1349-1354); that is every row except those beyond a dense U.
-            const bool all_u = p == 0 || spU || m_u >= m_max;
-            bool sbc = scale_bias_const;
-            if (!all_u) {
-                if (l1on && scale_bias_const && (scale_lam || scale_lam_sideinfo)) {
-                    g_last_error = "cmfrec_hip_factors_multiple: implicit features with an L1 penalty, scale_bias_const and dense side "
-                                   "information for fewer rows than the batch is not supported";
-                    return 2;
-                }
-                sbc = false;
-            }
-            if (p > 0 && !spU) {
-                launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, dCtC.ptr, w_user, (real_t)0);
-                launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
-            }
-            if (Xs.nnz > 0)
-                hipLaunchKernelGGL(implicit_rhs_rows_kernel<real_t>, grid1d((size_t)m_max * 64), dim3(256), 0, st, Xs.p.ptr, Xs.i.ptr, dBi.ptr, kk,
-                                   ex.w_implicit, m_max, dA.ptr, ldA, k_user);
-            dBiFull.alloc((size_t)kt * kt);
-            hipLaunchKernelGGL(embed_block_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, dBiG.ptr, kk, k_user, kt, dBiFull.ptr);
-            HIP_CHECK(hipGetLastError());
-            CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, (p > 0 && !spU) ? dCtC.ptr : nullptr, p > 0 ? kc : 0,
-                       all_u ? m_max : m_u, p, lam, lam_bias, (bool)(scale_lam || scale_lam_sideinfo),
-                       (bool)(scale_lam_sideinfo && !spU), sbc, CHOL_COLLECTIVE};
-            c.Mfull = dBiFull.ptr; c.rhs_prefilled_all = true;
-            if (spU) { c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user; c.rows2 = m_u; }
-            rc = launch_chol(dev, c, &Xs);
-        } else if (p == 0) {
-            CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk + ub, 0, bias_sub, nullptr, 0, 0, 0, lam, lam_bias,
-                       (bool)(scale_lam || scale_lam_sideinfo), false, scale_bias_const, CHOL_EXPLICIT};
-            rc = launch_chol(dev, c, &Xs);
-        } else if (spU) {
-            // rows with attributes but no observations come out of the same launch: without scale_lam_sideinfo the
-            // "cold" solution (collective.c:3309-3440 with u_vec_sp) is the block system with an empty X part
-            CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, nullptr, kc, m_u, p, lam, lam_bias, scale_lam, false,
-                       scale_bias_const, CHOL_COLLECTIVE};
-            c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
-            rc = launch_chol(dev, c, &Xs);
-        } else {
-            launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, dCtC.ptr, w_user, (real_t)0);
-            launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
-            CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, dCtC.ptr, kc, m_u, p, lam, lam_bias,
-                       (bool)(scale_lam || scale_lam_sideinfo), scale_lam_sideinfo, scale_bias_const, CHOL_COLLECTIVE};
-            rc = launch_chol(dev, c, &Xs);
-            if (rc == 0) {
-                // cold rows
-                dcold.alloc((size_t)m_u * kc);
-                if (TransCtCinvCt_pre) {
-                    dT.upload(TransCtCinvCt_pre, (size_t)p * kc, st);
-                    launch_gemm<false>(dev, m_u, kc, p, (real_t)1, dU.ptr, (size_t)p, dT.ptr, (size_t)kc, dcold.ptr, (size_t)kc);
-                } else {
-                    dM.alloc((size_t)kc * kc);
-                    const real_t lc = lam / w_user;
-                    launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, dM.ptr, (real_t)1, scale_lam_sideinfo ? lc * (real_t)p : lc);
-                    if (scale_lam_sideinfo)
-                        hipLaunchKernelGGL(add_diag_kernel<real_t>, dim3(1), dim3(64), 0, st, dM.ptr, kc, kc - 1, kc,
-                                           lc - lc * (real_t)p);
-                    launch_gemm<false>(dev, m_u, kc, p, (real_t)1, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dcold.ptr, (size_t)kc);
-                    CholCall cc{dcold.ptr, (size_t)kc, nullptr, 0, kc, 0, nullptr, dM.ptr, 0, 0, 0, 0, 0, false, false, false,
-                                CHOL_PREFILLED};
-                    // factors_closed_form on C with l1_lam / w_user, scaled by p like lam except on the last unknown (collective.c:3385-3400)
-                    dev.l1_last_now = l1_lam / w_user;
-                    dev.l1_now = scale_lam_sideinfo ? dev.l1_last_now * (real_t)p : dev.l1_last_now;
-                    rc = launch_chol(dev, cc, nullptr, m_u);
-                    dev.l1_now = l1_lam; dev.l1_last_now = ub ? l1_lam_bias : l1_lam;
-                }
-                hipLaunchKernelGGL(cold_select_kernel<real_t>, dim3(m_u), dim3(64), 0, st, dA.ptr, ldA, kt, kc, dcold.ptr,
-                                   Xs.p.ptr, m_u);
-            }
-        }
-        HIP_CHECK(hipGetLastError());
-        if (rc) return rc;
-        if (!implicit && Xs.weighted() && (scale_lam || scale_lam_sideinfo)) {
-            hipLaunchKernelGGL(zero_weightless_rows_kernel<real_t>, dim3(m_max), dim3(64), 0, st, Xs.p.ptr, Xs.wsum.ptr, m_max, p > 0 ? m_u : 0,
-                               std::numeric_limits<real_t>::epsilon(), dA.ptr, ldA, kt);
-            HIP_CHECK(hipGetLastError());
-        }
-        if (use_TB) {
-            hipLaunchKernelGGL(dense_rows_select_complete_kernel<real_t>, grid1d(std::min<size_t>((size_t)m_x * kT, (size_t)1 << 22)), dim3(256), 0, st,
-                               dA.ptr, ldA, k_user, dTBout.ptr, kT, dmiss.ptr, (size_t)m_x);
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipMemcpy2DAsync(A, (size_t)ktA * sizeof(real_t), dA.ptr, ldA * sizeof(real_t), (size_t)ktA * sizeof(real_t),
-                                   (size_t)m_max, hipMemcpyDeviceToHost, st));
-        if (ub) {
-            DevBuf<real_t> dba;
-            dba.alloc((size_t)m_max);
-            hipLaunchKernelGGL(col_extract_kernel<real_t>, grid1d(m_max), dim3(256), 0, st, dA.ptr, ldA, m_max, ktA, dba.ptr);
-            dba.download(biasA, (size_t)m_max, st);
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        return 0;
+        NewRowsState *s = newrows_state_create(M, -1, &rc);
+        if (s == nullptr) return rc;
+        std::unique_ptr<NewRowsState, void (*)(NewRowsState *)> hold(s, newrows_state_destroy);
+        return newrows_state_run(s, bt, A, biasA);
     });
 }
 

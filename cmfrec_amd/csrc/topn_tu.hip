@@ -6,6 +6,7 @@
 // CMFREC_HIP_TOPN=wide, a cross-check and A/B switch -- topn_wide_kernel (topn_wide_kernels.hpp).
 #include <algorithm>
 #include "device_base.hpp"
+#include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
 
 using namespace cmfhip;
@@ -33,18 +34,6 @@ struct cmfrec_hip_ranker {
 namespace {
 
 constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
-
-// the calling thread's current device while a handle made on another one is used
-struct DeviceScope {
-    int prev = -1;
-    explicit DeviceScope(int device)
-    {
-        int cur = -1;
-        HIP_CHECK(hipGetDevice(&cur));
-        if (cur != device) { HIP_CHECK(hipSetDevice(device)); prev = cur; }
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // rows x cols values from a host matrix with leading dimension ld into a device matrix with leading dimension dld
 void upload_columns(real_t *dst, size_t dld, const real_t *src, size_t ld, size_t rows, size_t cols, hipStream_t st)
@@ -92,6 +81,52 @@ int check_n_top(const char *fn, int_t n_top, int_t n)
         g_last_error = std::string(fn) + ": " + LIMITS;
         return 2;
     }
+    return 0;
+}
+
+// the ranking of nu users whose factors dA [nu, lda] and exclusion lists are on the device already: the launch, the timing
+// events and the download of cmfrec_hip_ranker_topN (the caller holds the DeviceScope and has checked the limits)
+int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
+                int_t *out_ids, real_t *out_scores)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    const int k = r->k;
+    r->ids.alloc_at_least((size_t)nu * n_top);
+    if (out_scores) r->sc.alloc_at_least((size_t)nu * n_top);
+    HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    if (k <= TOPN_KMAX && !switches().topn_wide) {
+        TopnParams<real_t> P;
+        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
+        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+        const size_t smem = topn_lds_bytes(sizeof(real_t));
+        HIP_CHECK(hipFuncSetAttribute((const void *)topn_kernel<real_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        const int tiles = (nu + TOPN_UT - 1) / TOPN_UT;
+        hipLaunchKernelGGL(topn_kernel<real_t>, dim3(std::min(tiles, dev.num_cus * 2)), dim3(TOPN_TH), smem, dev.stream, P);
+        r->last_users = TOPN_UT; r->last_grid = std::min(tiles, dev.num_cus * 2);
+    } else {
+        TopnWideParams<real_t> P;
+        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
+        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+        int bpc = 1;
+        const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
+        switch (nut) {
+        case 1: r->last_grid = launch_wide<1>(dev, P, bpc); break;
+        case 2: r->last_grid = launch_wide<2>(dev, P, bpc); break;
+        case 3: r->last_grid = launch_wide<3>(dev, P, bpc); break;
+        default: r->last_grid = launch_wide<4>(dev, P, bpc); break;
+        }
+        r->last_users = 16 * nut;
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
+    r->timed = true;
+    r->ids.download(out_ids, (size_t)nu * n_top, dev.stream);
+    if (out_scores) r->sc.download(out_scores, (size_t)nu * n_top, dev.stream);
+    HIP_CHECK(hipStreamSynchronize(dev.stream));
     return 0;
 }
 
@@ -152,43 +187,7 @@ int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, in
             r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
             if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
         }
-        r->ids.alloc_at_least((size_t)nu * n_top);
-        if (out_scores) r->sc.alloc_at_least((size_t)nu * n_top);
-        HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
-        if (k <= TOPN_KMAX && !switches().topn_wide) {
-            TopnParams<real_t> P;
-            P.A = r->A.ptr; P.lda = (size_t)k; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
-            P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-            P.excl_p = excl_p ? r->ep.ptr : nullptr; P.excl_i = excl_p ? r->ei.ptr : nullptr;
-            P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
-            const size_t smem = topn_lds_bytes(sizeof(real_t));
-            HIP_CHECK(hipFuncSetAttribute((const void *)topn_kernel<real_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            const int tiles = (nu + TOPN_UT - 1) / TOPN_UT;
-            hipLaunchKernelGGL(topn_kernel<real_t>, dim3(std::min(tiles, dev.num_cus * 2)), dim3(TOPN_TH), smem, dev.stream, P);
-            r->last_users = TOPN_UT; r->last_grid = std::min(tiles, dev.num_cus * 2);
-        } else {
-            TopnWideParams<real_t> P;
-            P.A = r->A.ptr; P.lda = (size_t)k; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
-            P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-            P.excl_p = excl_p ? r->ep.ptr : nullptr; P.excl_i = excl_p ? r->ei.ptr : nullptr;
-            P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
-            int bpc = 1;
-            const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
-            switch (nut) {
-            case 1: r->last_grid = launch_wide<1>(dev, P, bpc); break;
-            case 2: r->last_grid = launch_wide<2>(dev, P, bpc); break;
-            case 3: r->last_grid = launch_wide<3>(dev, P, bpc); break;
-            default: r->last_grid = launch_wide<4>(dev, P, bpc); break;
-            }
-            r->last_users = 16 * nut;
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
-        r->timed = true;
-        r->ids.download(out_ids, (size_t)nu * n_top, dev.stream);
-        if (out_scores) r->sc.download(out_scores, (size_t)nu * n_top, dev.stream);
-        HIP_CHECK(hipStreamSynchronize(dev.stream));
-        return 0;
+        return rank_device(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids, out_scores);
     });
 }
 
@@ -243,3 +242,37 @@ int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B
 }
 
 }  // extern "C"
+
+namespace cmfhip {
+
+int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n)
+{
+    if (k > TOPNW_KMAX || k <= 0) {
+        g_last_error = std::string(fn) + ": " + LIMITS;
+        return 2;
+    }
+    return check_n_top(fn, n_top, n);
+}
+
+cmfrec_hip_ranker *ranker_create_from_device(const real_t *dB, size_t ldb, int_t n, int_t k, const real_t *dbiasB, int device)
+{
+    // (uploads are hipMemcpyDefault copies: the same create serves items that are on the device already)
+    return cmfrec_hip_ranker_create(dB, ldb, n, k, dbiasB, device);
+}
+
+int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p,
+                       const int *dexcl_i, int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || n_top <= 0 || !dA || !out_ids || lda < (size_t)r->k) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if (int rc = check_n_top(fn, n_top, r->n)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        return rank_device(r, dA, lda, nu, dexcl_p, dexcl_i, n_top, out_ids, out_scores);
+    });
+}
+
+}  // namespace cmfhip

@@ -158,6 +158,52 @@ def _new_rows_weights(X, W, row, col, dt):
     return wv
 
 
+def _new_rows_batch(self, X, U, W, dense_ok):
+    """Input handling of a batch of new rows, shared by ``factors_multiple`` and the ``NewUsers`` handle: ``X`` a SciPy sparse matrix,
+    a (row, col, val) triplet, a dense array with NaN (``dense_ok``: the explicit model) or None; ``W`` in the form of ``X``; ``U`` a
+    dense array or a SciPy sparse matrix [m_u, p] (ignored by a model fitted without side information).  Returns a dict: row, col,
+    val, m_x, Xfull, W, U (dense) or Usp (row, col, val, rows, cols), m_u, p."""
+    if X is None and U is None:
+        raise ValueError("Must pass at least one of 'X', 'U'.")
+    if W is not None and X is None:
+        raise ValueError("'W' needs 'X'.")
+    dt = self.dtype_
+    n = self.B_.shape[0]
+    Xfull = None
+    if isinstance(X, np.ndarray):
+        if not dense_ok:
+            raise ValueError("a dense 'X' belongs to the explicit model")
+        if X.ndim != 2 or X.shape[1] != n:
+            raise ValueError("a dense 'X' must be a 2-D array with one column per item of the model")
+        Xfull = np.ascontiguousarray(X, dt)
+        row = col = np.zeros(0, np.int32); val = np.zeros(0, dt); m_x = Xfull.shape[0]
+    else:
+        row, col, val, m_x = _new_rows(X, n, dt)
+    Wv = _new_rows_weights(X, W, row, col, dt)
+    Uc = Us = None
+    m_u = p = 0
+    if U is not None and self.C_.shape[0]:
+        Uc, Us = _side_info(U, dt)
+        if Uc is not None and Uc.ndim != 2:
+            raise ValueError("'U' must be a 2-D array [rows, attributes]")
+        m_u, p = Uc.shape if Uc is not None else (Us[3], Us[4])
+        if p != self.C_.shape[0]:
+            raise ValueError("'U' has %d columns, the model was fitted with %d attributes" % (p, self.C_.shape[0]))
+    return dict(row=row, col=col, val=val, m_x=int(m_x), Xfull=Xfull, W=Wv, U=Uc, Usp=Us, m_u=int(m_u), p=int(p))
+
+
+def _sparse_U_args(Us):
+    """The positional sparse-U arguments of the two factors_collective_*_multiple calls (triplets; no CSR)."""
+    if Us is None:
+        return (None, None, None, C.c_size_t(0), None, None, None)
+    return (_lib.ptr(Us[0]), _lib.ptr(Us[1]), _lib.ptr(Us[2]), C.c_size_t(len(Us[2])), None, None, None)
+
+
+def _topN_new_batch(self, X, U, W, n, exclude_seen, exclude):
+    with self.new_users() as nu:
+        return nu.topN(X=X, U=U, W=W, n=n, exclude_seen=exclude_seen, exclude=exclude)
+
+
 def _side_info(M, dt):
     """Side information for fit(): dense array -> (array, None); SciPy sparse matrix -> (None, (row, col, val, rows, cols))."""
     if M is None:
@@ -280,21 +326,18 @@ class CMF_implicit(_Base):
         """Factors of new users from their interactions ``X`` [m_x, n] (sparse) and / or dense attributes ``U`` [m_u, p]
         (reference ``CMF_implicit.factors_multiple``, cmfrec/__init__.py:5313; C function
         factors_collective_implicit_multiple).  Returns ``A`` [max(m_x, m_u), k_user+k+k_main]."""
-        if X is None and U is None:
-            raise ValueError("Must pass at least one of 'X', 'U'.")
+        b = _new_rows_batch(self, X, U, None, dense_ok=False)
         lam6 = None if self._lam6 is None else np.ascontiguousarray(self._lam6, self.dtype_)
         l1 = self.l1_lambda if self._l16 is None else float(self._l16[2])       # the reference passes l1_lambda[2], like lambda_
         lib, R = self._lib()
         dt = self.dtype_
         n = self.B_.shape[0]
-        row, col, val, m_x = _new_rows(X, n, dt)
-        Uc = None if (U is None or not self.C_.shape[0]) else np.ascontiguousarray(U, dt)
-        m_u, p = (0, 0) if Uc is None else Uc.shape
+        row, col, val, m_x, Uc, m_u, p = b["row"], b["col"], b["val"], b["m_x"], b["U"], b["m_u"], b["p"]
         A = np.empty((max(m_x, m_u), self.k_user + self.k + self.k_main), dt)
         has = lambda M: M is not None and M.shape[0] > 0
         rc = lib.factors_collective_implicit_multiple(
             _lib.ptr(A), C.c_int(m_x), _lib.ptr(Uc), C.c_int(m_u), C.c_int(p), C.c_bool(False), C.c_bool(self.nonneg),
-            None, None, None, C.c_size_t(0), None, None, None,
+            *_sparse_U_args(b["Usp"]),
             _lib.ptr(val), _lib.ptr(row), _lib.ptr(col), C.c_size_t(len(val)), None, None, None,
             _lib.ptr(self.B_), C.c_int(n), _lib.ptr(self.C_) if p else None,
             _lib.ptr(self._U_colmeans) if (p and len(self._U_colmeans)) else None,
@@ -314,6 +357,17 @@ class CMF_implicit(_Base):
 
     def _finish_scores(self, users, sc):
         return sc
+
+    def new_users(self):
+        """A ``cmfrec_amd.NewUsers`` over this model: the model goes to the device once, then ``.factors(X, U)`` /
+        ``.topN(X, U, n, exclude_seen, exclude)`` per batch of users who were not part of the fit."""
+        from .new_users import NewUsers
+        return NewUsers(self)
+
+    def topN_new_batch(self, X=None, U=None, n=10, exclude_seen=True, exclude=None):
+        """Top-``n`` items for users who were not part of the fit, from their interactions and / or attributes (batch form of
+        the reference's ``topN_new``): one ``new_users()`` handle made, used and closed."""
+        return _topN_new_batch(self, X, U, None, n, exclude_seen, exclude)
 
     def ranker(self):
         """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch."""
@@ -488,26 +542,13 @@ class CMF(_Base):
         ``X``: a SciPy sparse matrix, a (row, col, val) triplet, or a dense array with NaN for the missing entries.  ``W``:
         observation weights in the form of ``X`` (a sparse ``W`` must have ``X``'s pattern).  A model fitted with
         ``add_implicit_features`` uses its ``Bi_``.  Returns ``A`` [max(m_x, m_u), k_user+k+k_main], or ``(A, bias)``."""
-        if X is None and U is None:
-            raise ValueError("Must pass at least one of 'X', 'U'.")
+        b = _new_rows_batch(self, X, U, W, dense_ok=True)
         lam6 = None if self._lam6 is None else np.ascontiguousarray(self._lam6, self.dtype_)
         l16 = None if self._l16 is None else np.ascontiguousarray(self._l16, self.dtype_)
         lib, R = self._lib()
         dt = self.dtype_
         n = self.B_.shape[0]
-        Xfull = None
-        if isinstance(X, np.ndarray):
-            if X.ndim != 2 or X.shape[1] != n:
-                raise ValueError("a dense 'X' must be a 2-D array with one column per item of the model")
-            Xfull = np.ascontiguousarray(X, dt)
-            row = col = np.zeros(0, np.int32); val = np.zeros(0, dt); m_x = Xfull.shape[0]
-        else:
-            row, col, val, m_x = _new_rows(X, n, dt)
-        if W is not None and X is None:
-            raise ValueError("'W' needs 'X'.")
-        Wv = _new_rows_weights(X, W, row, col, dt)
-        Uc = None if (U is None or not self.C_.shape[0]) else np.ascontiguousarray(U, dt)
-        m_u, p = (0, 0) if Uc is None else Uc.shape
+        row, col, val, m_x, Xfull, Wv, Uc, m_u, p = (b[f] for f in ("row", "col", "val", "m_x", "Xfull", "W", "U", "m_u", "p"))
         mm = max(m_x, m_u)
         A = np.empty((mm, self.k_user + self.k + self.k_main), dt)
         biasA = np.empty(mm, dt) if self.user_bias else None
@@ -518,7 +559,7 @@ class CMF(_Base):
         rc = lib.factors_collective_explicit_multiple(
             _lib.ptr(A), _lib.ptr(biasA), C.c_int(m_x), _lib.ptr(Uc), C.c_int(m_u), C.c_int(p),
             C.c_bool(False), C.c_bool(False), C.c_bool(self.nonneg),
-            None, None, None, C.c_size_t(0), None, None, None, None, C.c_int(0), C.c_int(0),
+            *_sparse_U_args(b["Usp"]), None, C.c_int(0), C.c_int(0),
             _lib.ptr(self.C_) if p else None, None, R(self.glob_mean_),
             _lib.ptr(self.item_bias_) if self.item_bias else None,
             _lib.ptr(self._U_colmeans) if (p and len(self._U_colmeans)) else None,
@@ -550,6 +591,17 @@ class CMF(_Base):
         if self.user_bias:
             sc = sc + np.asarray(self.user_bias_)[users][:, None]
         return sc
+
+    def new_users(self):
+        """A ``cmfrec_amd.NewUsers`` over this model: the model goes to the device once, then ``.factors(X, U, W)`` /
+        ``.topN(X, U, W, n, exclude_seen, exclude)`` per batch of users who were not part of the fit."""
+        from .new_users import NewUsers
+        return NewUsers(self)
+
+    def topN_new_batch(self, X=None, U=None, W=None, n=10, exclude_seen=True, exclude=None):
+        """Top-``n`` items for users who were not part of the fit, from their ratings and / or attributes (batch form of the
+        reference's ``topN_new``), scores + the global mean + the new rows' bias: one ``new_users()`` handle made, used and closed."""
+        return _topN_new_batch(self, X, U, W, n, exclude_seen, exclude)
 
     def ranker(self):
         """A ``ModelRanker`` over this model's item factors and item bias: upload them once, then ``.topN(users, n, exclude)``

@@ -613,6 +613,66 @@ int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
 
+/* New rows against a model that stays on the device: factors and top-N of users who were not part of the fit, batch after
+ * batch, without uploading B (C, Bi, biasB, the precomputed matrices) or rebuilding the Gramians per call, and -- for the ranking --
+ * without the factors or the users' own items leaving the device.  The handle sits at the level of
+ * factors_collective_explicit_multiple / factors_collective_implicit_multiple (which are create, factors, destroy): the fields
+ * carry the reference's names and go through the same rescaling (lam_unique, scaling_biasA, the division by w_main, ...); what
+ * those two refuse the handle refuses, with the same messages and return codes.
+ * model: B [max(n, n_max) with include_all_X, else n; k_item+k+k_main]; C [p, k_user+k] or NULL; user_bias: the rows have a bias
+ *   unknown (the drop-in call: biasA given); Bi [n, k+k_main] with add_implicit_features.  implicit = 1 reads alpha,
+ *   w_main_multiplier, apply_log_transf and BtB, and not glob_mean, biasB, Bi, the scale_* flags, lam_unique or TransBtBinvBt.  Of the
+ *   precomputed matrices BtB (implicit), TransBtBinvBt, BiTBi and TransCtCinvCt are read when not NULL.  Everything is copied to
+ *   the device by create; the caller's arrays may go away afterwards.
+ * batch: X as triplets (X, ixA, ixB, nnz), CSR (Xcsr_*, m+1 offsets) or Xfull [m, n] with NaN = not observed (explicit model);
+ *   weight in the form of X; U [m_u, p] dense, or sparse as triplets / CSR; values as the caller has them (the handle subtracts
+ *   glob_mean, applies log / alpha).  Rows out: max(m, m_u).
+ * create: NULL on failure (cmfrec_hip_last_error / cmfrec_hip_last_error_code); device < 0: the current device.
+ * factors: A [max(m, m_u), k_user+k+k_main], biasA one value per row (explicit model with user_bias; may be NULL).
+ * topN: solves the batch like factors, then ranks its rows [0, max(m, m_u)) straight from the device factors -- columns
+ *   [k_user, k_user+k+k_main) against the columns of B from k_item, + biasB -- with the semantics, limits and return codes of
+ *   cmfrec_hip_ranker_topN (k+k_main <= 272, n_top <= min(128, items): otherwise 2, and the handle stays usable).  Rows that only
+ *   have attributes are ranked like the rest.  exclude_seen: every row skips the items of its own X (sparse, or the present
+ *   entries of Xfull); excl_p / excl_i: further lists per row in the ranker's form (CSR over the batch's rows, each sorted
+ *   ascending); both: their union.  out_ids / out_scores [rows, n_top]; A / biasA optional outputs -- NULL: the factors never
+ *   leave the device.  The ranker is made by the first topN call from the device copy of the items and holds a second, packed
+ *   copy of their scored columns (ldb = the ranking kernels' padded width, as in cmfrec_hip_ranker_create).
+ * kernel_ms: HIP-event times of the most recent call -- its solve phase (uploads of the batch, shard build, row solves) and,
+ *   after a topN, the ranking kernel (0 after a factors call); 2 before the first call.
+ * Calls on one handle must not overlap; a handle belongs to the device it was made on. */
+typedef struct cmfrec_hip_newrows_model {
+    int32_t implicit;
+    int32_t n, n_max, include_all_X;
+    int32_t p;
+    int32_t user_bias, add_implicit_features;
+    int32_t k, k_user, k_item, k_main;
+    int32_t scale_lam, scale_lam_sideinfo, scale_bias_const;
+    int32_t nonneg, apply_log_transf;
+    real_t glob_mean, lam, l1_lam, scaling_biasA, w_main, w_user, w_implicit, alpha, w_main_multiplier;
+    const real_t *B, *C, *U_colmeans, *biasB, *Bi;
+    const real_t *lam_unique, *l1_lam_unique;            /* the reference's six values each, or NULL */
+    const real_t *BtB, *TransBtBinvBt, *BiTBi, *TransCtCinvCt;
+} cmfrec_hip_newrows_model;
+typedef struct cmfrec_hip_newrows_batch {
+    int32_t m, m_u;
+    const real_t *U;
+    const int_t *U_row, *U_col; const real_t *U_sp; size_t nnz_U;
+    const size_t *U_csr_p; const int_t *U_csr_i; const real_t *U_csr;
+    const real_t *X; const int_t *ixA, *ixB; size_t nnz;
+    const size_t *Xcsr_p; const int_t *Xcsr_i; const real_t *Xcsr;
+    const real_t *Xfull;
+    const real_t *weight;
+} cmfrec_hip_newrows_batch;
+typedef struct cmfrec_hip_newrows cmfrec_hip_newrows;
+int cmfrec_hip_sizeof_newrows_model(void);
+cmfrec_hip_newrows *cmfrec_hip_newrows_create(const cmfrec_hip_newrows_model *model, int device);
+int cmfrec_hip_newrows_factors(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *A, real_t *biasA);
+int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, int exclude_seen,
+                            const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                            int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA);
+int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms);
+void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h);
+
 /* Replace precompute_collective_explicit / precompute_collective_implicit, /root/reference/src/cmfrec.h:1922-1960 (bodies
  * src/collective.c:10209-10485, :10487-10566): the matrices the prediction functions reuse, from factors the caller holds -- the
  * same positional parameters, the same return codes.  Host buffers in and out; the Gramians run on the library's MFMA kernels,
