@@ -521,6 +521,21 @@ static int launch_chol_rows(const DeviceInfo &dev, const CholCall &c, const Spar
 
 // (launch_gemm: device.hpp)
 
+// Linv [k, k] := (R^T)^-1 of the row-major upper factor R (dense_kernels.hpp, trtri_from_upper_kernel): R and the rows being built
+// staged in LDS while 2 k (k + 1) elements fit (static limit 48 KiB, raised to 96 KiB on request), in global memory beyond.
+static void launch_trtri(const DeviceInfo &dev, const real_t *R, int k, real_t *Linv)
+{
+    const size_t tr_smem = (size_t)2 * k * (k + 1) * sizeof(real_t);
+    if (tr_smem <= 96 * 1024) {
+        auto kern = trtri_from_upper_kernel<real_t, true>;
+        if (tr_smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tr_smem));
+        hipLaunchKernelGGL(kern, dim3(1), dim3(256), tr_smem, dev.stream, R, k, Linv);
+    } else {
+        hipLaunchKernelGGL((trtri_from_upper_kernel<real_t, false>), dim3(1), dim3(256), 0, dev.stream, R, k, Linv);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
 // X := X (R^T R)^-1 for the row-major [rows, k] block X (ld = ldx) and the row-major upper Cholesky factor R [k, k] of a
 // shared matrix: the multi-right-hand-side posv of optimizeA Case 3 (common.c:3171-3175).  Round 4: no library call -- the
 // inverse of the shared matrix once (L^-1 = R^-T by one workgroup, column per thread; M^-1 = L^-T L^-1 by the library's own
@@ -532,15 +547,7 @@ static void launch_potrs_rows(const DeviceInfo &dev, int rows, int k, const real
     d.potrs_inv.alloc_at_least((size_t)2 * k * k);
     d.potrs_tmp.alloc_at_least((size_t)rows * k);
     real_t *Linv = d.potrs_inv.ptr, *Minv = d.potrs_inv.ptr + (size_t)k * k;
-    const size_t tr_smem = (size_t)2 * k * (k + 1) * sizeof(real_t);
-    if (tr_smem <= 96 * 1024) {
-        auto kern = trtri_from_upper_kernel<real_t, true>;
-        if (tr_smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tr_smem));
-        hipLaunchKernelGGL(kern, dim3(1), dim3(256), tr_smem, dev.stream, R, k, Linv);
-    } else {
-        hipLaunchKernelGGL((trtri_from_upper_kernel<real_t, false>), dim3(1), dim3(256), 0, dev.stream, R, k, Linv);
-    }
-    HIP_CHECK(hipGetLastError());
+    launch_trtri(dev, R, k, Linv);
     launch_gemm<true>(dev, k, k, k, (real_t)1, Linv, (size_t)k, Linv, (size_t)k, Minv, (size_t)k);
     launch_gemm<false>(dev, rows, k, k, (real_t)1, X, ldx, Minv, (size_t)k, d.potrs_tmp.ptr, (size_t)k);
     if (sizeof(real_t) == 4) {
@@ -4383,6 +4390,65 @@ extern "C" int cmfrec_hip_sym_eig(int n, const real_t *A, real_t *Q, real_t *lam
         HIP_CHECK(hipStreamSynchronize(dev.stream));
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         if (h_info != 0) { g_last_error = "cmfrec_hip_sym_eig: a QL iteration did not converge"; return 4; }
+        return 0;
+    });
+}
+
+// The dense layer on its own (tests/test_gpu_dense_ops.py): one operation through the launch helpers the library itself uses --
+// launch_gemm<false / true>, launch_gram, the potrf_upper_kernel launch of the shared-matrix half-steps, launch_trtri and
+// launch_potrs_rows -- on host images with explicit leading dimensions.  Each device buffer is a copy of its host image, whose
+// first `off` elements precede the operand (the operand starts at image + off: alignment is the caller's choice); the whole
+// image of C, those elements and the padding of every row included, is uploaded before the operation and downloaded after it.
+//   op 0 / 1 : C[m, n] = s1 * A B with A [m, k] / s1 * A^T B with A stored [k, m]; B [k, n]
+//   op 2     : C[k, k] = s1 * B[:n, :k]^T B[:n, :k] + s2 * I                                       (ldc == k)
+//   op 3     : C[n, n] := its upper Cholesky factor in place, the strict lower triangle untouched  (ldc == n)
+//   op 4     : C[n, n] = (R^T)^-1 for the upper factor R = A [n, n]                                (lda == ldc == n)
+//   op 5     : C[m, :k] := C (R^T R)^-1 for the upper factor R = A [k, k]                          (lda == k, ldc >= k)
+extern "C" int cmfrec_hip_dense_op(int op, int m, int n, int k, real_t s1, real_t s2, const real_t *A, size_t lda, int offA,
+                                   const real_t *B, size_t ldb, int offB, real_t *C, size_t ldc, int offC)
+{
+    return guarded([&]() {
+        if (op < 0 || op > 5) { g_last_error = "cmfrec_hip_dense_op: op is 0 .. 5"; return 2; }
+        if (m < 0 || n < 0 || k < 0 || offA < 0 || offB < 0 || offC < 0) { g_last_error = "cmfrec_hip_dense_op: sizes and offsets >= 0"; return 2; }
+        // rows and live columns of the three images for this operation (0 rows: the operand is not used)
+        size_t ra = 0, ca = 0, rb = 0, cb = 0, rc = 0, cc = 0;
+        bool tight_a = false, tight_c = false;
+        switch (op) {
+            case 0: ra = m; ca = k; rb = k; cb = n; rc = m; cc = n; break;
+            case 1: ra = k; ca = m; rb = k; cb = n; rc = m; cc = n; break;
+            case 2: rb = n; cb = k; rc = k; cc = k; tight_c = true; break;
+            case 3: rc = n; cc = n; tight_c = true; break;
+            case 4: ra = n; ca = n; rc = n; cc = n; tight_a = tight_c = true; break;
+            default: ra = k; ca = k; rc = m; cc = k; tight_a = true; break;
+        }
+        if ((op == 2 && k < 1) || ((op == 3 || op == 4) && n < 1)) { g_last_error = "cmfrec_hip_dense_op: an empty matrix"; return 2; }
+        if ((ra && (lda < ca || (tight_a && lda != ca))) || (rb && ldb < cb) || (rc && (ldc < cc || (tight_c && ldc != cc)))) {
+            g_last_error = "cmfrec_hip_dense_op: a leading dimension below the row length (or not equal to it where the kernel takes none)";
+            return 2;
+        }
+        if ((ra && ca && !A) || (rb && cb && !B) || (rc && cc && !C)) { g_last_error = "cmfrec_hip_dense_op: a missing operand"; return 2; }
+        DeviceInfo dev;
+        init_device(dev, -1);
+        hipStream_t st = dev.stream;
+        const size_t na = ra ? (size_t)offA + ra * lda : 0, nb = rb ? (size_t)offB + rb * ldb : 0, nc = rc ? (size_t)offC + rc * ldc : 0;
+        DevBuf<real_t> dA, dB, dC;
+        if (na && A) dA.upload(A, na, st);
+        if (nb && B) dB.upload(B, nb, st);
+        if (nc && C) dC.upload(C, nc, st);
+        const real_t *pa = dA.ptr ? dA.ptr + offA : nullptr, *pb = dB.ptr ? dB.ptr + offB : nullptr;
+        real_t *pc = dC.ptr ? dC.ptr + offC : nullptr;
+        GramWorkspace gws;
+        switch (op) {
+            case 0: launch_gemm<false>(dev, m, n, k, s1, pa, lda, pb, ldb, pc, ldc); break;
+            case 1: launch_gemm<true>(dev, m, n, k, s1, pa, lda, pb, ldb, pc, ldc); break;
+            case 2: launch_gram(dev, gws, pb, ldb, n, k, pc, s1, s2); break;
+            case 3: hipLaunchKernelGGL(potrf_upper_kernel<real_t>, dim3(1), dim3(256), 0, st, pc, n); break;
+            case 4: launch_trtri(dev, pa, n, pc); break;
+            default: launch_potrs_rows(dev, m, k, pa, pc, ldc); break;
+        }
+        HIP_CHECK(hipGetLastError());
+        if (nc && C) dC.download(C, nc, st);
+        HIP_CHECK(hipStreamSynchronize(st));
         return 0;
     });
 }

@@ -196,3 +196,28 @@ def topN_batch(A, B, n_top=10, biasB=None, exclude=None):
                                    _lib.ptr(sc))
     _lib.check(rc, lib, "topN_batch")
     return ids, sc
+
+
+DENSE_OPS = {"gemm": 0, "gemm_ta": 1, "gram": 2, "potrf": 3, "trtri": 4, "potrs_rows": 5}
+
+
+def dense_op(op, m, n, k, C_img, ldc, offC=0, A_img=None, lda=0, offA=0, B_img=None, ldb=0, offB=0, s1=1.0, s2=0.0):
+    """One operation of the dense layer on its own (``cmfrec_hip_dense_op``, include/cmfrec_hip.h): ``op`` a key of
+    ``DENSE_OPS``.  The images are flat arrays of one dtype, ``off + rows * ld`` elements each, whose operand starts at
+    element ``off``; ``C_img`` is uploaded whole, overwritten by the operation and returned in place."""
+    dtype = C_img.dtype
+    if dtype.type not in (np.float64, np.float32):
+        raise TypeError("the images must be float64 or float32")
+    for img in (A_img, B_img, C_img):
+        if img is not None and (img.dtype != dtype or img.ndim != 1 or not img.flags.c_contiguous):
+            raise ValueError("the images must be flat contiguous arrays of one dtype")
+    rows = {0: (m, k, m), 1: (k, k, m), 2: (0, n, k), 3: (0, 0, n), 4: (n, 0, n), 5: (k, 0, m)}[DENSE_OPS[op]]
+    for img, r, ld, off in ((A_img, rows[0], lda, offA), (B_img, rows[1], ldb, offB), (C_img, rows[2], ldc, offC)):
+        if img is not None and r > 0 and len(img) < off + r * ld:
+            raise ValueError("an image is shorter than off + rows * ld")
+    lib, R = _lib.load(dtype), _lib.real(dtype)
+    rc = lib.cmfrec_hip_dense_op(C.c_int(DENSE_OPS[op]), C.c_int(m), C.c_int(n), C.c_int(k), R(s1), R(s2),
+                                 _lib.ptr(A_img), C.c_size_t(lda), C.c_int(offA), _lib.ptr(B_img), C.c_size_t(ldb), C.c_int(offB),
+                                 _lib.ptr(C_img), C.c_size_t(ldc), C.c_int(offC))
+    _lib.check(rc, lib, "dense_op")
+    return C_img

@@ -756,6 +756,18 @@ int cmfrec_hip_dense_rows_probe(int rows, int n, double present, int reps, doubl
  * Q [n, n] with Q[i][c] = component i of eigenvector c, lam [n] clamped at zero.  method 0: Householder tridiagonalisation +
  * implicit QL (the default of the path), 1: one-workgroup Jacobi (cross-check).  ms: device milliseconds per run over `reps`. */
 int cmfrec_hip_sym_eig(int n, const real_t *A, real_t *Q, real_t *lam, int method, int reps, double *ms);
+/* One operation of the dense layer on its own, through the launch helpers the library itself uses (test entry point).  Row-major
+ * host images with explicit leading dimensions; the operand of an image starts `off` elements into it (the image is that much
+ * longer), so that its 16-byte alignment on the device is the caller's choice.  The whole image of C -- those elements and the
+ * padding of every row included -- is uploaded before the operation and downloaded after it.
+ *   op 0 / 1 : C[m, n] = s1 * A B with A [m, k] / s1 * A^T B with A stored [k, m]; B [k, n]
+ *   op 2     : C[k, k] = s1 * B[:n, :k]^T B[:n, :k] + s2 * I                                       (ldc == k, k >= 1)
+ *   op 3     : C[n, n] := its upper Cholesky factor in place, the strict lower triangle untouched  (ldc == n, n >= 1)
+ *   op 4     : C[n, n] = (R^T)^-1 for the upper factor R = A [n, n]                                (lda == ldc == n, n >= 1)
+ *   op 5     : C[m, :k] := C (R^T R)^-1 for the upper factor R = A [k, k]                          (lda == k, ldc >= k)
+ * Returns 2 on negative sizes or offsets, a leading dimension below the row length, or a missing operand. */
+int cmfrec_hip_dense_op(int op, int m, int n, int k, real_t s1, real_t s2, const real_t *A, size_t lda, int offA,
+                        const real_t *B, size_t ldb, int offB, real_t *C, size_t ldc, int offC);
 
 /* Start values as the reference's random_parallel draws them (src/helpers.c:927-1043; xoshiro256++
  * seeded by splitmix64, truncated ziggurat normals or uniforms, scaled 2^-7): A <- stream(seed),
