@@ -1610,6 +1610,7 @@ struct cmfrec_hip_newrows {
     bool has_C = false, has_biasB = false, has_Bi = false, has_means = false;
     int_t n_sparse = 0;                        // rows of B a sparse batch may index (n_max with include_all_X), n: a dense one
     bool called = false, ranked = false;       // a solve on this handle; the last call ranked
+    bool imputed = false, solved = true;       // the last call imputed; it solved (an impute call without any NaN does not)
     ~cmfrec_hip_newrows()
     {
         if (ranker) cmfrec_hip_ranker_destroy(ranker);
@@ -1770,9 +1771,9 @@ int newrows_solve(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, 
         const int brc = newrows_batch_side(*h, *batch, bt, vals_tmp);
         if (brc == 1) { *empty = true; return 0; }
         if (brc) return brc;
-        h->ranked = false;
+        h->ranked = false; h->imputed = false;
         const int rc = cmfhip::newrows_state_run(h->state, bt, A, biasA);
-        if (rc == 0) h->called = true;
+        if (rc == 0) { h->called = true; h->solved = true; }
         return rc;
     });
 }
@@ -1853,6 +1854,25 @@ int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batc
     return rc;
 }
 
+int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *Xout, real_t *A, real_t *biasA)
+{
+    auto bad = [](const char *what) { cmfhip::g_last_error = std::string("cmfrec_hip_newrows_impute: ") + what; return 2; };
+    if (h == nullptr || batch == nullptr || h->state == nullptr || Xout == nullptr) return bad("invalid arguments");
+    if (h->mdl.implicit) return bad("imputation belongs to the explicit model");
+    if (batch->Xfull == nullptr || batch->nnz || batch->Xcsr_p) return bad("X must be a dense matrix (Xfull) with NaN for the entries to impute");
+    if (batch->m <= 0) return bad("a batch without rows of X");
+    return cmfhip::guarded([&]() {
+        cmfhip::NewRowsBatchArgs bt;
+        std::vector<real_t> vals_tmp;
+        if (int brc = newrows_batch_side(*h, *batch, bt, vals_tmp)) return brc;      // (1, a batch without rows, is ruled out above)
+        h->ranked = false; h->imputed = false;
+        bool solved = false;
+        const int rc = cmfhip::newrows_state_impute(h->state, bt, Xout, A, biasA, &solved);
+        if (rc == 0) { h->called = true; h->imputed = true; h->solved = solved; }
+        return rc;
+    });
+}
+
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms)
 {
     if (h == nullptr || h->state == nullptr || !h->called) {
@@ -1861,7 +1881,8 @@ int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double
     }
     return cmfhip::guarded([&]() {
         double s = 0, r = 0;
-        if (int rc = cmfhip::newrows_state_solve_ms(h->state, &s)) return rc;
+        if (h->solved) { if (int rc = cmfhip::newrows_state_solve_ms(h->state, &s)) return rc; }
+        if (h->imputed) r = cmfhip::newrows_state_fill_ms(h->state);
         if (h->ranked) { if (int rc = cmfrec_hip_ranker_kernel_ms(h->ranker, &r)) return rc; }
         if (solve_ms) *solve_ms = s;
         if (rank_ms) *rank_ms = r;
@@ -1874,7 +1895,14 @@ void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h)
     delete h;
 }
 
-int_t factors_collective_explicit_multiple(
+}  // extern "C"
+
+namespace {
+
+// factors_collective_explicit_multiple and impute_X_collective_explicit (which is that call followed by the fill, collective.c:
+// 11429-11463): handle created, one batch, handle destroyed.  Ximpute: null for the factors; else Xfull, filled in place.
+int_t explicit_multiple_dropin(
+    real_t *Ximpute, bool user_bias,
     real_t *A, real_t *biasA, int_t m,
     real_t *U, int_t m_u, int_t p,
     bool NA_as_zero_U, bool NA_as_zero_X,
@@ -1918,7 +1946,7 @@ int_t factors_collective_explicit_multiple(
     cmfrec_hip_newrows_model mdl;
     memset(&mdl, 0, sizeof mdl);
     mdl.n = n; mdl.n_max = n_max; mdl.include_all_X = include_all_X; mdl.p = side ? p : 0;
-    mdl.user_bias = biasA != nullptr; mdl.add_implicit_features = add_implicit_features;
+    mdl.user_bias = user_bias; mdl.add_implicit_features = add_implicit_features;
     mdl.k = k; mdl.k_user = k_user; mdl.k_item = k_item; mdl.k_main = k_main;
     mdl.scale_lam = scale_lam; mdl.scale_lam_sideinfo = scale_lam_sideinfo; mdl.scale_bias_const = scale_bias_const;
     mdl.nonneg = nonneg;
@@ -1941,11 +1969,99 @@ int_t factors_collective_explicit_multiple(
         return ec > 3 ? 1 : (ec ? ec : 1);
     }
     bool empty = false;
-    const int rc = newrows_solve(h, &bt, A, biasA, &empty);
+    const int rc = Ximpute ? cmfrec_hip_newrows_impute(h, &bt, Ximpute, A, biasA) : newrows_solve(h, &bt, A, biasA, &empty);
     cmfrec_hip_newrows_destroy(h);
     if (rc == 2) fprintf(stderr, "%s\n", cmfrec_hip_last_error());
     return rc > 3 ? 1 : rc;
 }
+
+}  // namespace
+
+extern "C" {
+
+int_t factors_collective_explicit_multiple(
+    real_t *A, real_t *biasA, int_t m,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U, bool NA_as_zero_X,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *Ub, int_t m_ubin, int_t pbin,
+    real_t *C, real_t *Cb,
+    real_t glob_mean, real_t *biasB,
+    real_t *U_colmeans,
+    real_t *X, int_t ixA[], int_t ixB[], size_t nnz,
+    size_t *Xcsr_p, int_t *Xcsr_i, real_t *Xcsr,
+    real_t *Xfull, int_t n,
+    real_t *weight,
+    real_t *B,
+    real_t *Bi, bool add_implicit_features,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t *lam_unique,
+    real_t l1_lam, real_t *l1_lam_unique,
+    bool scale_lam, bool scale_lam_sideinfo,
+    bool scale_bias_const, real_t scaling_biasA,
+    real_t w_main, real_t w_user, real_t w_implicit,
+    int_t n_max, bool include_all_X,
+    real_t *BtB, real_t *TransBtBinvBt, real_t *BtXbias, real_t *BeTBeChol, real_t *BiTBi,
+    real_t *TransCtCinvCt, real_t *CtCw, real_t *CtUbias, real_t *B_plus_bias,
+    int nthreads)
+{
+    return explicit_multiple_dropin(nullptr, biasA != nullptr, A, biasA, m, U, m_u, p, NA_as_zero_U, NA_as_zero_X, nonneg, U_row, U_col, U_sp, nnz_U,
+                                    U_csr_p, U_csr_i, U_csr, Ub, m_ubin, pbin, C, Cb, glob_mean, biasB, U_colmeans, X, ixA, ixB, nnz, Xcsr_p,
+                                    Xcsr_i, Xcsr, Xfull, n, weight, B, Bi, add_implicit_features, k, k_user, k_item, k_main, lam, lam_unique,
+                                    l1_lam, l1_lam_unique, scale_lam, scale_lam_sideinfo, scale_bias_const, scaling_biasA, w_main, w_user,
+                                    w_implicit, n_max, include_all_X, BtB, TransBtBinvBt, BtXbias, BeTBeChol, BiTBi, TransCtCinvCt, CtCw,
+                                    CtUbias, B_plus_bias, nthreads);
+}
+
+// impute_X_collective_explicit, reference src/cmfrec.h (body src/collective.c:11351-11544): Xfull's NaN replaced in place.  The
+// reference returns 0 for a matrix without NaN before it looks at anything else (:11424-11427); so does this.
+int_t impute_X_collective_explicit(
+    int_t m, bool user_bias,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *Ub, int_t m_ubin, int_t pbin,
+    real_t *C, real_t *Cb,
+    real_t glob_mean, real_t *biasB,
+    real_t *U_colmeans,
+    real_t *Xfull, int_t n,
+    real_t *weight,
+    real_t *B,
+    real_t *Bi, bool add_implicit_features,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t *lam_unique,
+    real_t l1_lam, real_t *l1_lam_unique,
+    bool scale_lam, bool scale_lam_sideinfo,
+    bool scale_bias_const, real_t scaling_biasA,
+    real_t w_main, real_t w_user, real_t w_implicit,
+    int_t n_max, bool include_all_X,
+    real_t *BtB,
+    real_t *TransBtBinvBt,
+    real_t *BeTBeChol,
+    real_t *BiTBi,
+    real_t *TransCtCinvCt,
+    real_t *CtCw,
+    real_t *CtUbias,
+    real_t *B_plus_bias,
+    int nthreads)
+{
+    if (Xfull == nullptr || m <= 0 || n <= 0) return 0;
+    const size_t total = (size_t)m * (size_t)n;
+    size_t e = 0;
+    while (e < total && !std::isnan(Xfull[e])) e++;
+    if (e == total) return 0;
+    return explicit_multiple_dropin(Xfull, user_bias, nullptr, nullptr, m, U, m_u, p, NA_as_zero_U, false, nonneg, U_row, U_col, U_sp, nnz_U,
+                                    U_csr_p, U_csr_i, U_csr, Ub, m_ubin, pbin, C, Cb, glob_mean, biasB, U_colmeans, nullptr, nullptr, nullptr, 0,
+                                    nullptr, nullptr, nullptr, Xfull, n, weight, B, Bi, add_implicit_features, k, k_user, k_item, k_main, lam,
+                                    lam_unique, l1_lam, l1_lam_unique, scale_lam, scale_lam_sideinfo, scale_bias_const, scaling_biasA, w_main,
+                                    w_user, w_implicit, n_max, include_all_X, BtB, TransBtBinvBt, nullptr, BeTBeChol, BiTBi, TransCtCinvCt,
+                                    CtCw, CtUbias, B_plus_bias, nthreads);
+}
+
 
 int_t factors_collective_implicit_multiple(
     real_t *A, int_t m,

@@ -65,6 +65,11 @@ NewRowsView newrows_state_view(const NewRowsState *s);
 // caller's lists (host CSR over the rows, each sorted), or their union; every list sorted ascending.  Both null: *dp = null.
 int newrows_state_exclusions(NewRowsState *s, bool seen, const size_t *excl_p, const int_t *excl_i, const size_t **dp, const int **di);
 int newrows_state_solve_ms(NewRowsState *s, double *ms);
+// Imputation of a dense batch (bt.Xfull [m_x, n] with NaN): Xout [m_x, n] = Xfull with every NaN replaced by the prediction from
+// the batch's factors; Xout may be bt.Xfull.  A batch without any NaN is copied without solving (*solved = false).  fill_ms: the
+// HIP-event time of the fill kernel over the blocks of the last impute call.
+int newrows_state_impute(NewRowsState *s, const NewRowsBatchArgs &bt, real_t *Xout, real_t *A, real_t *biasA, bool *solved);
+double newrows_state_fill_ms(const NewRowsState *s);
 
 // topn_tu.hip: a ranker over items that are on the device already (packed copy, ldb = topnw_kp(k)), and a ranking call on
 // device factors with device exclusion lists -- cmfrec_hip_ranker_topN without its uploads.  The caller has synchronised the

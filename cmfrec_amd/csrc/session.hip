@@ -14,6 +14,7 @@
 #include "eig_kernels.hpp"
 #include "gram_cg_wide_kernels.hpp"
 #include "side_zeros_kernels.hpp"
+#include "impute_kernels.hpp"
 #include "newrows.hpp"
 #include <dlfcn.h>
 #include <functional>
@@ -3578,12 +3579,28 @@ struct NewRowsState {
     DevBuf<unsigned char> sort_tmp;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the solve phase of the last batch
     bool timed = false;
+    // imputation (newrows_state_impute): does dXb still hold the caller's whole batch (one block, not centred), the events around
+    // a block's fill kernel and their sum over the blocks of the last impute call
+    bool xb_resident = false;
+    hipEvent_t ev2 = nullptr, ev3 = nullptr;
+    double fill_ms = 0;
     ~NewRowsState()
     {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
+        if (ev2) (void)hipEventDestroy(ev2);
+        if (ev3) (void)hipEventDestroy(ev3);
     }
 };
+
+// rows per device block of a dense batch: its device copy (and the weights') stays within 1 GB
+static long long newrows_block_rows(int n, bool weighted, int m_x)
+{
+    const size_t per_row = (size_t)n * sizeof(real_t) * (weighted ? 2 : 1);
+    long long block_rows = (long long)std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_row, 1));
+    if (switches().newrows_block_rows > 0) block_rows = switches().newrows_block_rows;     // test hook
+    return std::min<long long>(block_rows, m_x);
+}
 
 // the three refusals about the form of X and its weights, in front of everything else (a batch without rows included)
 static int newrows_form_check(bool implicit, bool Bi, const NewRowsBatchArgs &bt)
@@ -3668,6 +3685,8 @@ NewRowsState *newrows_state_create(const NewRowsModelArgs &M, int device, int *r
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventCreate(&S.ev0));
     HIP_CHECK(hipEventCreate(&S.ev1));
+    HIP_CHECK(hipEventCreate(&S.ev2));
+    HIP_CHECK(hipEventCreate(&S.ev3));
     HIP_CHECK(hipStreamSynchronize(st));       // the caller's matrices may go away
     S.M.B = S.M.C = S.M.U_colmeans = S.M.biasB = S.M.BtB_pre = S.M.TransCtCinvCt_pre = S.M.Bi = S.M.BiTBi_pre = S.M.TransBtBinvBt_pre = nullptr;
     return sp.release();
@@ -3718,6 +3737,7 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
     size_t nnz = bt.nnz;
     int m_x = bt.m_x, m_u = bt.m_u, p = M.p;
     S.rows = 0;
+    S.xb_resident = false;
     if (int frc = newrows_form_check(implicit, false, bt)) return frc;
     if (Xfull) { nnz = 0; ixA = nullptr; ixB = nullptr; X = nullptr; weight = nullptr; }
     if (m_x <= 0 || (!Xfull && !Xcsr_p && nnz == 0)) weight = nullptr;
@@ -3776,10 +3796,8 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
     // changes the row systems, the rows without a missing entry are  x^T TransBtBinvBt  (common.c:736-758)
     const bool use_TB = Xfull != nullptr && S.have_TB && n == M.n_TB && !weight_full && !nonneg && !l1on && p == 0 && !Bi;
     if (Xfull) {
-        const size_t per_row = (size_t)n * sizeof(real_t) * (weight_full ? 2 : 1);
-        long long block_rows = (long long)std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_row, 1));
-        if (switches().newrows_block_rows > 0) block_rows = switches().newrows_block_rows;     // test hook
-        block_rows = std::min<long long>(block_rows, m_x);
+        const long long block_rows = newrows_block_rows(n, weight_full != nullptr, m_x);
+        S.xb_resident = block_rows >= m_x && !use_TB;
         S.dmiss.alloc_at_least((size_t)m_x);
         if (use_TB) S.dTBout.alloc_at_least((size_t)m_x * kT);
         DevBuf<real_t> &dXb = S.dXb, &dWb = S.dWb;
@@ -3982,6 +4000,64 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
     HIP_CHECK(hipStreamSynchronize(st));
     return 0;
 }
+
+// ---- imputation: the NaN of a dense batch replaced by the model's predictions -------------------------------------------------
+// impute_X_collective_explicit (collective.c:11351-11544): the factors of the batch's rows (newrows_state_run), then block of
+// rows by block of rows -- the budget of the dense batch -- the caller's X on the device, impute_fill_kernel on it with the
+// device factors (the bias in the last column of their rows), the resident items and the per-row counts of missing entries the
+// compaction left in S.dmiss, and the block back to Xout (which may be bt.Xfull itself).  The kernel must see the caller's
+// values: the block the run left in S.dXb is kept only when the batch was one block and the TransBtBinvBt route did not centre
+// it; otherwise every block is uploaded again.  A batch without any NaN is copied without solving (:11427); *solved says which.
+int newrows_state_impute(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *Xout, real_t *A, real_t *biasA, bool *solved)
+{
+    NewRowsState &S = *sp;
+    *solved = false;
+    S.fill_ms = 0;
+    const int m = bt.m_x, n = bt.n;
+    const real_t *Xfull = bt.Xfull;
+    if (S.M.implicit || !Xfull || m <= 0 || n <= 0 || n > S.M.n || !Xout) {
+        g_last_error = "cmfrec_hip_newrows_impute: invalid arguments";
+        return 2;
+    }
+    const size_t total = (size_t)m * (size_t)n;
+    size_t e = 0;
+    while (e < total && !std::isnan(Xfull[e])) e++;
+    if (e == total) {
+        if (Xout != Xfull) memcpy(Xout, Xfull, total * sizeof(real_t));
+        return 0;
+    }
+    if (int rc = newrows_state_run(sp, bt, A, biasA)) return rc;
+    *solved = true;
+    DeviceScope scope(S.dev.device);
+    hipStream_t st = S.dev.stream;
+    const long long block_rows = newrows_block_rows(n, bt.weight_full != nullptr, m);
+    const bool resident = S.xb_resident && block_rows >= m;
+    ImputeParams<real_t> P;
+    P.X = S.dXb.ptr; P.ldx = (size_t)n; P.n = n;
+    P.lda = S.ldA; P.B = S.dB.ptr + S.M.k_item; P.ldb = S.ldB; P.kk = S.kk;
+    P.ldbias = S.ldA; P.biasB = S.dbias.ptr; P.glob_mean = bt.glob_mean_full;
+    P.tiles_per_block = 0;
+    for (long long r0 = 0; r0 < m; r0 += block_rows) {
+        const int rows = (int)std::min<long long>(block_rows, m - r0);
+        if (!resident) S.dXb.upload(Xfull + (size_t)r0 * n, (size_t)rows * n, st);
+        P.X = S.dXb.ptr; P.rows = rows;
+        P.A = S.dA.ptr + (size_t)r0 * S.ldA + S.M.k_user;
+        P.biasA = S.ub ? S.dA.ptr + (size_t)r0 * S.ldA + S.ktA : nullptr;
+        P.row_missing = S.dmiss.ptr + r0;
+        HIP_CHECK(hipEventRecord(S.ev2, st));
+        launch_impute_fill(S.dev, st, P);
+        HIP_CHECK(hipEventRecord(S.ev3, st));
+        S.dXb.download(Xout + (size_t)r0 * n, (size_t)rows * n, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        float t = 0;
+        HIP_CHECK(hipEventElapsedTime(&t, S.ev2, S.ev3));
+        S.fill_ms += (double)t;
+    }
+    S.xb_resident = false;                     // (the block holds the filled values now)
+    return 0;
+}
+
+double newrows_state_fill_ms(const NewRowsState *s) { return s->fill_ms; }
 
 // ---- exclusion lists of the last batch's rows ---------------------------------------------------
 // row pointers of the union: the row's own entries, then the caller's list
@@ -4448,6 +4524,42 @@ extern "C" int cmfrec_hip_dense_op(int op, int m, int n, int k, real_t s1, real_
         }
         HIP_CHECK(hipGetLastError());
         if (nc && C) dC.download(C, nc, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+
+// The fill kernel of the imputation on its own (tests/test_gpu_impute.py), through the launch helper newrows_state_impute uses:
+// X[m, ldx] is filled in place where it holds NaN.  Host images, each uploaded as it is (m * lda, n * ldb, m * ldx elements
+// from the pointer, the padding of the rows included), X downloaded whole.  biasA: m values, or -- where it points into the
+// image of A -- the column of that image it points at (stride lda: the layout of the new-rows state, whose factor rows end in
+// their bias).  row_missing: optional, one count per row; 0 leaves the row alone.
+extern "C" int cmfrec_hip_impute_dense(int m, int n, int kk, const real_t *A, size_t lda, const real_t *biasA, const real_t *B, size_t ldb,
+                                       const real_t *biasB, real_t glob_mean, real_t *X, size_t ldx, const int *row_missing)
+{
+    return guarded([&]() {
+        auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_impute_dense: ") + what; return 2; };
+        if (m < 0 || n < 0 || kk < 0 || kk > IMPUTE_KMAX) return bad("sizes >= 0 and kk <= 272");
+        if (m == 0 || n == 0) return 0;
+        if (!X || ldx < (size_t)n || (kk > 0 && (!A || !B || lda < (size_t)kk || ldb < (size_t)kk))) return bad("a missing operand or a leading dimension below the row length");
+        DeviceInfo dev;
+        init_device(dev, -1);
+        hipStream_t st = dev.stream;
+        DevBuf<real_t> dA, dB, dX, dba, dbb;
+        DevBuf<int> dmiss;
+        if (kk > 0) { dA.upload(A, (size_t)m * lda, st); dB.upload(B, (size_t)n * ldb, st); }
+        dX.upload(X, (size_t)m * ldx, st);
+        const bool strided = biasA != nullptr && kk > 0 && biasA >= A && biasA < A + (size_t)m * lda;
+        if (biasA && !strided) dba.upload(biasA, (size_t)m, st);
+        if (biasB) dbb.upload(biasB, (size_t)n, st);
+        if (row_missing) dmiss.upload(row_missing, (size_t)m, st);
+        ImputeParams<real_t> P;
+        P.X = dX.ptr; P.ldx = ldx; P.rows = m; P.n = n;
+        P.A = dA.ptr; P.lda = lda; P.B = dB.ptr; P.ldb = ldb; P.kk = kk;
+        P.biasA = !biasA ? nullptr : (strided ? dA.ptr + (biasA - A) : dba.ptr); P.ldbias = strided ? lda : 1;
+        P.biasB = dbb.ptr; P.glob_mean = glob_mean; P.row_missing = dmiss.ptr; P.tiles_per_block = 0;
+        launch_impute_fill(dev, st, P);
+        dX.download(X, (size_t)m * ldx, st);
         HIP_CHECK(hipStreamSynchronize(st));
         return 0;
     });

@@ -603,6 +603,12 @@ class CMF(_Base):
         reference's ``topN_new``), scores + the global mean + the new rows' bias: one ``new_users()`` handle made, used and closed."""
         return _topN_new_batch(self, X, U, W, n, exclude_seen, exclude)
 
+    def transform(self, X, U=None, W=None):
+        """The dense ``X`` [m, n] with its NaN replaced by the model's predictions (reference ``CMF.transform``; C function
+        impute_X_collective_explicit), a new array: one ``new_users()`` handle made, used and closed."""
+        with self.new_users() as nu:
+            return nu.impute(X, U=U, W=W)
+
     def ranker(self):
         """A ``ModelRanker`` over this model's item factors and item bias: upload them once, then ``.topN(users, n, exclude)``
         per batch, with the scores of ``topN_batch``."""

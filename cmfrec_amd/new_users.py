@@ -155,9 +155,32 @@ class NewUsers:
             return ids, sc, (A, bias)
         return ids, sc
 
+    def impute(self, X, U=None, W=None, return_factors=False):
+        """A new array: the dense ``X`` [m, n] with every NaN replaced by the model's prediction for that user and item (reference
+        ``CMF.transform``; C function impute_X_collective_explicit), from the factors this batch's rows get -- ``A_r . B_c`` + the
+        global mean + the row's bias + the item's bias, computed on the device where ``X`` is missing and nowhere else.  Present
+        entries keep their bits; ``X`` itself is not modified.  ``return_factors``: a second value, ``(A, bias)`` as
+        ``factors(..., return_bias=True)`` returns them (of a batch without any NaN, which is not solved: None)."""
+        h = self._live()
+        if self.implicit:
+            raise ValueError("imputation belongs to the explicit model")
+        if not isinstance(X, np.ndarray):
+            raise ValueError("'X' must be a dense array with NaN for the entries to impute")
+        s, keep, rows = self._batch(X, U, W)
+        out = np.empty_like(keep["Xfull"])
+        A = np.empty((rows, self.width), self.dtype) if return_factors else None
+        bias = np.empty(rows, self.dtype) if (self.has_bias and return_factors) else None
+        rc = self.lib.cmfrec_hip_newrows_impute(h, C.byref(s), _lib.ptr(out), _lib.ptr(A), _lib.ptr(bias))
+        _lib.check(rc, self.lib, "NewUsers.impute")
+        if return_factors:
+            if not np.isnan(keep["Xfull"]).any():
+                return out, None
+            return out, (A, bias)
+        return out
+
     def kernel_ms(self):
         """(solve ms, ranking ms): HIP-event times of the most recent call's solve phase and of its ranking kernel (0 after
-        ``factors``)."""
+        ``factors``; after ``impute``: of its fill kernel)."""
         a, b = C.c_double(0), C.c_double(0)
         _lib.check(self.lib.cmfrec_hip_newrows_kernel_ms(self._live(), C.byref(a), C.byref(b)), self.lib, "NewUsers.kernel_ms")
         return a.value, b.value

@@ -201,6 +201,41 @@ def topN_batch(A, B, n_top=10, biasB=None, exclude=None):
 DENSE_OPS = {"gemm": 0, "gemm_ta": 1, "gram": 2, "potrf": 3, "trtri": 4, "potrs_rows": 5}
 
 
+def impute_dense(m, n, kk, X_img, ldx, offX=0, A_img=None, lda=0, offA=0, B_img=None, ldb=0, offB=0, biasA=None, biasA_col=None,
+                 biasB=None, glob_mean=0.0, row_missing=None):
+    """The fill kernel of the imputation on its own (``cmfrec_hip_impute_dense``, include/cmfrec_hip.h): where the row-major
+    ``X[m, ldx]`` holds NaN, ``A_r . B_c + glob_mean + biasA[r] + biasB[c]`` over ``kk`` factors; present entries keep their bits.
+    The images are flat arrays of one dtype, ``off + rows * ld`` elements each, whose operand starts at element ``off``; ``X_img``
+    is overwritten in place and returned.  The rows' bias: ``biasA`` [m], or ``biasA_col``, the column of ``A_img``'s rows that
+    holds it (``kk <= biasA_col < lda``).  ``row_missing`` [m] int32: a row whose count is 0 is left alone."""
+    dtype = X_img.dtype
+    if dtype.type not in (np.float64, np.float32):
+        raise TypeError("the images must be float64 or float32")
+    for img in (A_img, B_img, X_img, biasA, biasB):
+        if img is not None and (img.dtype != dtype or img.ndim != 1 or not img.flags.c_contiguous):
+            raise ValueError("the images must be flat contiguous arrays of one dtype")
+    for img, r, ld, off in ((A_img, m, lda, offA), (B_img, n, ldb, offB), (X_img, m, ldx, offX)):
+        if img is not None and r > 0 and len(img) < off + r * ld:
+            raise ValueError("an image is shorter than off + rows * ld")
+    if (biasA is not None and len(biasA) < m) or (biasB is not None and len(biasB) < n):
+        raise ValueError("a bias is shorter than its side")
+    if biasA_col is not None and (biasA is not None or A_img is None or not kk <= biasA_col < lda):
+        raise ValueError("'biasA_col' is a column of A_img's rows behind the factors, and excludes 'biasA'")
+    if row_missing is not None:
+        row_missing = np.ascontiguousarray(row_missing, np.int32)
+        if len(row_missing) < m:
+            raise ValueError("'row_missing' is shorter than the rows")
+    lib, R = _lib.load(dtype), _lib.real(dtype)
+    sz = dtype.itemsize
+    at = lambda img, off: None if img is None else C.c_void_p(img.ctypes.data + off * sz)
+    pba = at(A_img, offA + biasA_col) if biasA_col is not None else _lib.ptr(biasA)
+    rc = lib.cmfrec_hip_impute_dense(C.c_int(m), C.c_int(n), C.c_int(kk), at(A_img, offA), C.c_size_t(lda), pba, at(B_img, offB),
+                                     C.c_size_t(ldb), _lib.ptr(biasB), R(glob_mean), at(X_img, offX), C.c_size_t(ldx),
+                                     _lib.ptr(row_missing))
+    _lib.check(rc, lib, "impute_dense")
+    return X_img
+
+
 def dense_op(op, m, n, k, C_img, ldc, offC=0, A_img=None, lda=0, offA=0, B_img=None, ldb=0, offB=0, s1=1.0, s2=0.0):
     """One operation of the dense layer on its own (``cmfrec_hip_dense_op``, include/cmfrec_hip.h): ``op`` a key of
     ``DENSE_OPS``.  The images are flat arrays of one dtype, ``off + rows * ld`` elements each, whose operand starts at

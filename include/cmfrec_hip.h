@@ -637,8 +637,16 @@ void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
  *   ascending); both: their union.  out_ids / out_scores [rows, n_top]; A / biasA optional outputs -- NULL: the factors never
  *   leave the device.  The ranker is made by the first topN call from the device copy of the items and holds a second, packed
  *   copy of their scored columns (ldb = the ranking kernels' padded width, as in cmfrec_hip_ranker_create).
- * kernel_ms: HIP-event times of the most recent call -- its solve phase (uploads of the batch, shard build, row solves) and,
- *   after a topN, the ranking kernel (0 after a factors call); 2 before the first call.
+ * impute: the explicit model's imputation of a dense batch (impute_X_collective_explicit below, without the per-call model work):
+ *   solves the batch like factors, then Xout [m, n] = batch->Xfull with every NaN replaced by
+ *   A_r . B_c + glob_mean + biasA[r] + biasB[c] from the device factors (columns [k_user, k_user+k+k_main) against the columns of
+ *   B from k_item, its first n rows); every present entry keeps its bits.  Xout may be batch->Xfull itself.  The fill runs block of rows by
+ *   block of rows on the matrix cores and skips the rows (and tiles) without a NaN; a batch without any NaN is copied without
+ *   solving.  A / biasA: optional outputs as in topN.  Return code 2, with a message, and the handle stays usable: an implicit
+ *   model, a batch whose X is not Xfull, m <= 0; whatever factors refuses for the batch is refused with the same message.
+ * kernel_ms: HIP-event times of the most recent call -- its solve phase (uploads of the batch, shard build, row solves; 0 after
+ *   an impute call that found no NaN) and, after a topN, the ranking kernel, after an impute, the fill kernel summed over the
+ *   blocks (0 after a factors call); 2 before the first call.
  * Calls on one handle must not overlap; a handle belongs to the device it was made on. */
 typedef struct cmfrec_hip_newrows_model {
     int32_t implicit;
@@ -670,8 +678,46 @@ int cmfrec_hip_newrows_factors(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_b
 int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, int exclude_seen,
                             const size_t excl_p[], const int_t excl_i[], int_t n_top,
                             int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA);
+int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *Xout, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms);
 void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h);
+
+/* Replaces impute_X_collective_explicit, /root/reference/src/cmfrec.h:2071-2103 (body src/collective.c:11351-11544; the Python class's
+ * CMF.transform): the NaN of Xfull [m, n] replaced in place by the predictions from the factors of its rows -- the same
+ * positional parameters, the same return codes.  It is cmfrec_hip_newrows_create, one cmfrec_hip_newrows_impute, destroy; what
+ * factors_collective_explicit_multiple refuses (NA_as_zero_U, Ub / Cb, ...) is refused here with the same messages.  A matrix
+ * without NaN returns 0 untouched.  The precomputed matrices are read as in factors_collective_explicit_multiple. */
+int_t impute_X_collective_explicit(
+    int_t m, bool user_bias,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *Ub, int_t m_ubin, int_t pbin,
+    real_t *C, real_t *Cb,
+    real_t glob_mean, real_t *biasB,
+    real_t *U_colmeans,
+    real_t *Xfull, int_t n,
+    real_t *weight,
+    real_t *B,
+    real_t *Bi, bool add_implicit_features,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t *lam_unique,
+    real_t l1_lam, real_t *l1_lam_unique,
+    bool scale_lam, bool scale_lam_sideinfo,
+    bool scale_bias_const, real_t scaling_biasA,
+    real_t w_main, real_t w_user, real_t w_implicit,
+    int_t n_max, bool include_all_X,
+    real_t *BtB,
+    real_t *TransBtBinvBt,
+    real_t *BeTBeChol,
+    real_t *BiTBi,
+    real_t *TransCtCinvCt,
+    real_t *CtCw,
+    real_t *CtUbias,
+    real_t *B_plus_bias,
+    int nthreads);
 
 /* Replace precompute_collective_explicit / precompute_collective_implicit, /root/reference/src/cmfrec.h:1922-1960 (bodies
  * src/collective.c:10209-10485, :10487-10566): the matrices the prediction functions reuse, from factors the caller holds -- the
@@ -768,6 +814,17 @@ int cmfrec_hip_sym_eig(int n, const real_t *A, real_t *Q, real_t *lam, int metho
  * Returns 2 on negative sizes or offsets, a leading dimension below the row length, or a missing operand. */
 int cmfrec_hip_dense_op(int op, int m, int n, int k, real_t s1, real_t s2, const real_t *A, size_t lda, int offA,
                         const real_t *B, size_t ldb, int offB, real_t *C, size_t ldc, int offC);
+
+/* The fill kernel of the imputation on its own, through the launch helper cmfrec_hip_newrows_impute uses (test entry point):
+ *   X[r, c] = isnan(X[r, c]) ? sum_{f < kk} A[r * lda + f] B[c * ldb + f] + glob_mean + biasA[r] + biasB[c] : X[r, c]
+ * in place on the row-major X[m, ldx], kk <= 272.  Host images, each uploaded as it is (m * lda, n * ldb, m * ldx elements from
+ * the pointer, the padding of every row included); X is downloaded whole.  A and B point at the first used column.  biasA
+ * (optional): m values -- or, where it points into the image of A, that column of the image (stride lda: the layout of the
+ * new-rows handle, whose factor rows end in their bias).  biasB (optional): n values.  row_missing (optional): one count per
+ * row; a row whose count is 0 is neither read nor written.  Returns 2 on negative sizes, kk > 272, a leading dimension below the
+ * row length or a missing operand. */
+int cmfrec_hip_impute_dense(int m, int n, int kk, const real_t *A, size_t lda, const real_t *biasA, const real_t *B, size_t ldb,
+                            const real_t *biasB, real_t glob_mean, real_t *X, size_t ldx, const int *row_missing);
 
 /* Start values as the reference's random_parallel draws them (src/helpers.c:927-1043; xoshiro256++
  * seeded by splitmix64, truncated ziggurat normals or uniforms, scaled 2^-7): A <- stream(seed),
