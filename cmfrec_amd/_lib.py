@@ -72,7 +72,8 @@ EXPORTED = [
     "cmfrec_hip_optimizeA_implicit", "cmfrec_hip_optimizeA_explicit", "cmfrec_hip_optimizeA_explicit_weighted",
     "cmfrec_hip_optimizeA_dense_full", "cmfrec_hip_optimizeA_collective", "cmfrec_hip_optimizeA_collective_sparse", "cmfrec_hip_topN_batch",
     "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
-    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
+    "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
+    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
     "cmfrec_hip_session_set_sideinfo", "cmfrec_hip_session_set_sideinfo_local", "cmfrec_hip_session_sideinfo_partial", "cmfrec_hip_session_sideinfo_finish", "cmfrec_hip_session_set_nonneg", "cmfrec_hip_session_set_l1", "cmfrec_hip_session_set_lam_unique", "cmfrec_hip_session_set_scale_bias_const", "cmfrec_hip_session_set_NA_as_zero_X", "cmfrec_hip_session_set_zero_rows", "cmfrec_hip_session_set_closed_form_rows", "cmfrec_hip_session_set_lambda_multipliers", "cmfrec_hip_session_set_implicit_features", "cmfrec_hip_session_get_implicit_features", "cmfrec_hip_session_set_sideinfo_sparse", "cmfrec_hip_session_set_sideinfo_sparse_zeros", "cmfrec_hip_side_zeros_products", "cmfrec_hip_session_update", "cmfrec_hip_session_iterate",
@@ -81,9 +82,10 @@ EXPORTED = [
     "cmfrec_hip_session_reset_timers", "cmfrec_hip_session_bin_overlaps", "cmfrec_hip_session_vh_mode", "cmfrec_hip_session_vh_min", "cmfrec_hip_session_lowrank_info", "cmfrec_hip_session_bin_stats", "cmfrec_hip_sizeof_real", "cmfrec_hip_sizeof_model", "cmfrec_hip_build_info", "cmfrec_hip_reload_switches", "cmfrec_hip_selftest_lanes", "cmfrec_hip_exchange_plan", "cmfrec_hip_gemm_probe", "cmfrec_hip_dense_rows_probe", "cmfrec_hip_sym_eig", "cmfrec_hip_dense_op", "cmfrec_hip_impute_dense", "precompute_collective_explicit", "precompute_collective_implicit", "topN_old_collective_explicit", "topN_old_collective_implicit", "cmfrec_hip_random_parallel",
 ]
 
-# the reference's own name outside the prefixes tests/test_abi.py compares with the header (include/cmfrec_hip.h declares it,
-# exports.map exports it)
-EXPORTED_OTHER = ["impute_X_collective_explicit"]
+# the reference's own names outside the prefixes tests/test_abi.py compares with the header (include/cmfrec_hip.h declares them,
+# exports.map exports them)
+EXPORTED_OTHER = ["impute_X_collective_explicit", "predict_X_old_collective_explicit", "predict_X_old_collective_implicit",
+                  "predict_X_new_collective_explicit", "predict_X_new_collective_implicit"]
 
 _cache = {}
 
@@ -132,6 +134,20 @@ def load(dtype=np.float64):
     lib.impute_X_collective_explicit.restype = C.c_int
     lib.cmfrec_hip_impute_dense.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                             C.c_void_p, real(dtype), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.cmfrec_hip_newrows_predict.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
+    R = real(dtype)
+    lib.cmfrec_hip_score_pairs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_int, C.c_void_p, R, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.cmfrec_hip_scorer_create.restype = C.c_void_p
+    lib.cmfrec_hip_scorer_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, R, C.c_int, C.c_int]
+    lib.cmfrec_hip_scorer_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.cmfrec_hip_scorer_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.cmfrec_hip_scorer_destroy.restype = None
+    lib.cmfrec_hip_scorer_destroy.argtypes = [C.c_void_p]
+    for name in EXPORTED_OTHER[1:]:
+        getattr(lib, name).restype = C.c_int
     lib.cmfrec_hip_newrows_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.cmfrec_hip_newrows_destroy.restype = None
     lib.cmfrec_hip_newrows_destroy.argtypes = [C.c_void_p]

@@ -70,6 +70,7 @@ struct Switches {
     bool debug_ticks = false;       // CMFREC_HIP_GRAM_TICKS / _CHOL_TICKS (timing builds only)
     int cg_teams = 0;               // CMFREC_HIP_CG_TEAMS: at most that many teams (rounded up to whole workgroups) in a launch of the dynamically scheduled CG row kernels, so that a small problem gives a team several rows (test hook; 0: by occupancy)
     int newrows_block_rows = 0;     // CMFREC_HIP_NEWROWS_BLOCK_ROWS: rows per device block of a dense batch of new rows (test hook; 0: by the 1 GB budget)
+    int predict_block = 0;          // CMFREC_HIP_PREDICT_BLOCK: pairs per upload / launch / download block of the pair scorer (test hook; 0: 2^24)
     void reload()
     {
         auto str = [](const char *n) -> const char * { const char *v = getenv(n); return (v != nullptr && v[0] != 0) ? v : nullptr; };
@@ -96,6 +97,7 @@ struct Switches {
         debug_ticks = str("CMFREC_HIP_GRAM_TICKS") != nullptr || str("CMFREC_HIP_CHOL_TICKS") != nullptr;
         cg_teams = num("CMFREC_HIP_CG_TEAMS", 0);
         newrows_block_rows = num("CMFREC_HIP_NEWROWS_BLOCK_ROWS", 0);
+        predict_block = num("CMFREC_HIP_PREDICT_BLOCK", 0);
     }
 };
 inline Switches &switches_mut() { static Switches sw; static bool first = (sw.reload(), true); (void)first; return sw; }
@@ -142,6 +144,13 @@ struct DevBuf {
         if (count) HIP_CHECK(hipMemcpyAsync(host, ptr, count * sizeof(T), hipMemcpyDeviceToHost, st));
     }
 };
+
+// rows x cols values from a host (or device) matrix with leading dimension ld into a device matrix with leading dimension dld
+inline void upload_columns(real_t *dst, size_t dld, const real_t *src, size_t ld, size_t rows, size_t cols, hipStream_t st)
+{
+    if (ld == cols && dld == cols) HIP_CHECK(hipMemcpyAsync(dst, src, rows * cols * sizeof(real_t), hipMemcpyDefault, st));
+    else HIP_CHECK(hipMemcpy2DAsync(dst, dld * sizeof(real_t), src, ld * sizeof(real_t), cols * sizeof(real_t), rows, hipMemcpyDefault, st));
+}
 
 // the calling thread's current device while a handle made on another one is used
 struct DeviceScope {

@@ -1607,12 +1607,15 @@ struct cmfrec_hip_newrows {
     cmfrec_hip_newrows_model mdl;              // the scalars; its pointers are cleared after create
     cmfhip::NewRowsState *state = nullptr;
     cmfrec_hip_ranker *ranker = nullptr;       // made by the first topN call
+    cmfhip::PairScorer *scorer = nullptr;      // made by the first predict call
     bool has_C = false, has_biasB = false, has_Bi = false, has_means = false;
     int_t n_sparse = 0;                        // rows of B a sparse batch may index (n_max with include_all_X), n: a dense one
     bool called = false, ranked = false;       // a solve on this handle; the last call ranked
     bool imputed = false, solved = true;       // the last call imputed; it solved (an impute call without any NaN does not)
+    bool predicted = false;                    // the last call scored pairs
     ~cmfrec_hip_newrows()
     {
+        cmfhip::pair_scorer_destroy(scorer);
         if (ranker) cmfrec_hip_ranker_destroy(ranker);
         cmfhip::newrows_state_destroy(state);
     }
@@ -1771,7 +1774,7 @@ int newrows_solve(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, 
         const int brc = newrows_batch_side(*h, *batch, bt, vals_tmp);
         if (brc == 1) { *empty = true; return 0; }
         if (brc) return brc;
-        h->ranked = false; h->imputed = false;
+        h->ranked = false; h->imputed = false; h->predicted = false;
         const int rc = cmfhip::newrows_state_run(h->state, bt, A, biasA);
         if (rc == 0) { h->called = true; h->solved = true; }
         return rc;
@@ -1865,12 +1868,36 @@ int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_ba
         cmfhip::NewRowsBatchArgs bt;
         std::vector<real_t> vals_tmp;
         if (int brc = newrows_batch_side(*h, *batch, bt, vals_tmp)) return brc;      // (1, a batch without rows, is ruled out above)
-        h->ranked = false; h->imputed = false;
+        h->ranked = false; h->imputed = false; h->predicted = false;
         bool solved = false;
         const int rc = cmfhip::newrows_state_impute(h->state, bt, Xout, A, biasA, &solved);
         if (rc == 0) { h->called = true; h->imputed = true; h->solved = solved; }
         return rc;
     });
+}
+
+int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, const int_t *row, const int_t *col,
+                               size_t n_pairs, real_t *out, real_t *A, real_t *biasA)
+{
+    if (h == nullptr || batch == nullptr || h->state == nullptr || (n_pairs > 0 && (!row || !col || !out))) {
+        cmfhip::g_last_error = "cmfrec_hip_newrows_predict: invalid arguments";
+        return 2;
+    }
+    bool empty = false;
+    if (int rc = newrows_solve(h, batch, A, biasA, &empty)) return rc > 3 ? 1 : rc;        // (the codes of _factors)
+    const int rc = cmfhip::guarded([&]() {
+        const cmfhip::NewRowsView v = cmfhip::newrows_state_view(h->state);
+        if (h->scorer == nullptr) h->scorer = cmfhip::pair_scorer_create(v.device);
+        const cmfrec_hip_newrows_model &m = h->mdl;
+        const int_t kk = m.k + m.k_main, rows = empty ? 0 : v.rows;
+        const bool ub = !m.implicit && v.ldA > (size_t)(m.k_user + kk);          // a factor row ends in its bias
+        return cmfhip::pair_scorer_run(h->scorer, rows ? v.dA + m.k_user : nullptr, v.ldA, rows, (ub && rows) ? v.dA + m.k_user + kk : nullptr,
+                                       v.ldA, v.dB + m.k_item, v.ldB, v.n, kk, m.implicit ? nullptr : v.dbiasB,
+                                       m.implicit ? (real_t)0 : m.glob_mean, m.implicit != 0, row, col, n_pairs, out);
+    });
+    // (a batch without rows leaves newrows_solve before it clears what the call before left: what the last call was is set here)
+    if (rc == 0) { h->called = true; h->ranked = false; h->imputed = false; h->predicted = true; if (empty) h->solved = false; }
+    return rc > 3 ? 1 : rc;
 }
 
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms)
@@ -1884,6 +1911,7 @@ int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double
         if (h->solved) { if (int rc = cmfhip::newrows_state_solve_ms(h->state, &s)) return rc; }
         if (h->imputed) r = cmfhip::newrows_state_fill_ms(h->state);
         if (h->ranked) { if (int rc = cmfrec_hip_ranker_kernel_ms(h->ranker, &r)) return rc; }
+        if (h->predicted) r = cmfhip::pair_scorer_ms(h->scorer);
         if (solve_ms) *solve_ms = s;
         if (rank_ms) *rank_ms = r;
         return 0;
@@ -1899,10 +1927,19 @@ void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h)
 
 namespace {
 
-// factors_collective_explicit_multiple and impute_X_collective_explicit (which is that call followed by the fill, collective.c:
-// 11429-11463): handle created, one batch, handle destroyed.  Ximpute: null for the factors; else Xfull, filled in place.
+// the pairs of a predict_X_new_* call: row indexes the batch's rows, col the items
+struct PredictPairs {
+    const int_t *row, *col;
+    size_t n;
+    real_t *out;
+};
+
+// factors_collective_explicit_multiple, impute_X_collective_explicit (which is that call followed by the fill, collective.c:
+// 11429-11463) and predict_X_new_collective_explicit (that call followed by predict_X_old_collective_explicit, :11913-11960):
+// handle created, one batch, handle destroyed.  Ximpute: Xfull, filled in place; pairs: scored from the device factors; both
+// null: the factors.
 int_t explicit_multiple_dropin(
-    real_t *Ximpute, bool user_bias,
+    real_t *Ximpute, const PredictPairs *pairs, bool user_bias,
     real_t *A, real_t *biasA, int_t m,
     real_t *U, int_t m_u, int_t p,
     bool NA_as_zero_U, bool NA_as_zero_X,
@@ -1939,7 +1976,7 @@ int_t explicit_multiple_dropin(
     if (Xfull && (nnz || Xcsr_p)) return unsupported_multiple("X both as a dense and as a sparse matrix");
     if (add_implicit_features && !Bi) return unsupported_multiple("add_implicit_features without Bi");
     if (U == nullptr && !spU) { m_u = 0; }
-    if (std::max(m, m_u) <= 0) return 0;
+    if (std::max(m, m_u) <= 0 && !pairs) return 0;
     if (m <= 0) { Xfull = nullptr; weight = nullptr; }
     const bool side = U != nullptr || spU;
     // the model as this batch sees it: side information only where the batch has some, a bias unknown where biasA is asked for
@@ -1969,7 +2006,9 @@ int_t explicit_multiple_dropin(
         return ec > 3 ? 1 : (ec ? ec : 1);
     }
     bool empty = false;
-    const int rc = Ximpute ? cmfrec_hip_newrows_impute(h, &bt, Ximpute, A, biasA) : newrows_solve(h, &bt, A, biasA, &empty);
+    const int rc = Ximpute ? cmfrec_hip_newrows_impute(h, &bt, Ximpute, A, biasA)
+                 : pairs ? cmfrec_hip_newrows_predict(h, &bt, pairs->row, pairs->col, pairs->n, pairs->out, A, biasA)
+                         : newrows_solve(h, &bt, A, biasA, &empty);
     cmfrec_hip_newrows_destroy(h);
     if (rc == 2) fprintf(stderr, "%s\n", cmfrec_hip_last_error());
     return rc > 3 ? 1 : rc;
@@ -2007,7 +2046,7 @@ int_t factors_collective_explicit_multiple(
     real_t *TransCtCinvCt, real_t *CtCw, real_t *CtUbias, real_t *B_plus_bias,
     int nthreads)
 {
-    return explicit_multiple_dropin(nullptr, biasA != nullptr, A, biasA, m, U, m_u, p, NA_as_zero_U, NA_as_zero_X, nonneg, U_row, U_col, U_sp, nnz_U,
+    return explicit_multiple_dropin(nullptr, nullptr, biasA != nullptr, A, biasA, m, U, m_u, p, NA_as_zero_U, NA_as_zero_X, nonneg, U_row, U_col, U_sp, nnz_U,
                                     U_csr_p, U_csr_i, U_csr, Ub, m_ubin, pbin, C, Cb, glob_mean, biasB, U_colmeans, X, ixA, ixB, nnz, Xcsr_p,
                                     Xcsr_i, Xcsr, Xfull, n, weight, B, Bi, add_implicit_features, k, k_user, k_item, k_main, lam, lam_unique,
                                     l1_lam, l1_lam_unique, scale_lam, scale_lam_sideinfo, scale_bias_const, scaling_biasA, w_main, w_user,
@@ -2054,7 +2093,7 @@ int_t impute_X_collective_explicit(
     size_t e = 0;
     while (e < total && !std::isnan(Xfull[e])) e++;
     if (e == total) return 0;
-    return explicit_multiple_dropin(Xfull, user_bias, nullptr, nullptr, m, U, m_u, p, NA_as_zero_U, false, nonneg, U_row, U_col, U_sp, nnz_U,
+    return explicit_multiple_dropin(Xfull, nullptr, user_bias, nullptr, nullptr, m, U, m_u, p, NA_as_zero_U, false, nonneg, U_row, U_col, U_sp, nnz_U,
                                     U_csr_p, U_csr_i, U_csr, Ub, m_ubin, pbin, C, Cb, glob_mean, biasB, U_colmeans, nullptr, nullptr, nullptr, 0,
                                     nullptr, nullptr, nullptr, Xfull, n, weight, B, Bi, add_implicit_features, k, k_user, k_item, k_main, lam,
                                     lam_unique, l1_lam, l1_lam_unique, scale_lam, scale_lam_sideinfo, scale_bias_const, scaling_biasA, w_main,
@@ -2063,7 +2102,14 @@ int_t impute_X_collective_explicit(
 }
 
 
-int_t factors_collective_implicit_multiple(
+}  // extern "C"
+
+namespace {
+
+// factors_collective_implicit_multiple and predict_X_new_collective_implicit (that call followed by
+// predict_X_old_collective_implicit, collective.c:12024-12059): pairs null: the factors
+int_t implicit_multiple_dropin(
+    const PredictPairs *pairs,
     real_t *A, int_t m,
     real_t *U, int_t m_u, int_t p,
     bool NA_as_zero_U,
@@ -2103,7 +2149,7 @@ int_t factors_collective_implicit_multiple(
         int_t ns = 0;
         if (int mrc = newrows_model_side(mdl, M, &ns)) return mrc;
     }
-    if (std::max(m, m_u) <= 0) return 0;                                        // rows out: max(m, m_u), collective.c:11210
+    if (std::max(m, m_u) <= 0 && !pairs) return 0;                              // rows out: max(m, m_u), collective.c:11210
     cmfrec_hip_newrows_batch bt;
     memset(&bt, 0, sizeof bt);
     bt.m = m; bt.m_u = m_u; bt.U = U;
@@ -2115,9 +2161,116 @@ int_t factors_collective_implicit_multiple(
         return ec > 3 ? 1 : (ec ? ec : 1);
     }
     bool empty = false;
-    const int rc = newrows_solve(h, &bt, A, nullptr, &empty);
+    const int rc = pairs ? cmfrec_hip_newrows_predict(h, &bt, pairs->row, pairs->col, pairs->n, pairs->out, A, nullptr)
+                         : newrows_solve(h, &bt, A, nullptr, &empty);
     cmfrec_hip_newrows_destroy(h);
     return rc > 3 ? 1 : rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int_t factors_collective_implicit_multiple(
+    real_t *A, int_t m,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *X, int_t ixA[], int_t ixB[], size_t nnz,
+    size_t *Xcsr_p, int_t *Xcsr_i, real_t *Xcsr,
+    real_t *B, int_t n,
+    real_t *C,
+    real_t *U_colmeans,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t l1_lam, real_t alpha, real_t w_main, real_t w_user,
+    real_t w_main_multiplier,
+    bool apply_log_transf,
+    real_t *BeTBe, real_t *BtB, real_t *BeTBeChol, real_t *CtUbias,
+    int nthreads)
+{
+    return implicit_multiple_dropin(nullptr, A, m, U, m_u, p, NA_as_zero_U, nonneg, U_row, U_col, U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, X, ixA, ixB,
+                                    nnz, Xcsr_p, Xcsr_i, Xcsr, B, n, C, U_colmeans, k, k_user, k_item, k_main, lam, l1_lam, alpha, w_main, w_user,
+                                    w_main_multiplier, apply_log_transf, BeTBe, BtB, BeTBeChol, CtUbias, nthreads);
+}
+
+// predict_X_new_collective_explicit / _implicit, reference src/cmfrec.h (bodies src/collective.c:11861-12069): the factors of the
+// batch's rows, then the chosen pairs from them -- here without the factors leaving the device.  row indexes the batch's rows
+// [0, max(m_new, m_u)).  The argument mapping, the refusals and their messages are those of factors_collective_*_multiple.
+int_t predict_X_new_collective_explicit(
+    int_t m_new,
+    int_t row[], int_t col[], real_t *predicted, size_t n_predict,
+    int nthreads,
+    bool user_bias,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U, bool NA_as_zero_X,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *Ub, int_t m_ubin, int_t pbin,
+    real_t *C, real_t *Cb,
+    real_t glob_mean, real_t *biasB,
+    real_t *U_colmeans,
+    real_t *X, int_t ixA[], int_t ixB[], size_t nnz,
+    size_t *Xcsr_p, int_t *Xcsr_i, real_t *Xcsr,
+    real_t *Xfull, int_t n,
+    real_t *weight,
+    real_t *B,
+    real_t *Bi, bool add_implicit_features,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t *lam_unique,
+    real_t l1_lam, real_t *l1_lam_unique,
+    bool scale_lam, bool scale_lam_sideinfo,
+    bool scale_bias_const, real_t scaling_biasA,
+    real_t w_main, real_t w_user, real_t w_implicit,
+    int_t n_max, bool include_all_X,
+    real_t *BtB,
+    real_t *TransBtBinvBt,
+    real_t *BtXbias,
+    real_t *BeTBeChol,
+    real_t *BiTBi,
+    real_t *TransCtCinvCt,
+    real_t *CtCw,
+    real_t *CtUbias,
+    real_t *B_plus_bias)
+{
+    const PredictPairs pairs = {row, col, n_predict, predicted};
+    return explicit_multiple_dropin(nullptr, &pairs, user_bias, nullptr, nullptr, m_new, U, m_u, p, NA_as_zero_U, NA_as_zero_X, nonneg, U_row, U_col,
+                                    U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, Ub, m_ubin, pbin, C, Cb, glob_mean, biasB, U_colmeans, X, ixA, ixB, nnz,
+                                    Xcsr_p, Xcsr_i, Xcsr, Xfull, n, weight, B, Bi, add_implicit_features, k, k_user, k_item, k_main, lam,
+                                    lam_unique, l1_lam, l1_lam_unique, scale_lam, scale_lam_sideinfo, scale_bias_const, scaling_biasA, w_main,
+                                    w_user, w_implicit, n_max, include_all_X, BtB, TransBtBinvBt, BtXbias, BeTBeChol, BiTBi, TransCtCinvCt,
+                                    CtCw, CtUbias, B_plus_bias, nthreads);
+}
+
+int_t predict_X_new_collective_implicit(
+    int_t m_new,
+    int_t row[], int_t col[], real_t *predicted, size_t n_predict,
+    int nthreads,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *X, int_t ixA[], int_t ixB[], size_t nnz,
+    size_t *Xcsr_p, int_t *Xcsr_i, real_t *Xcsr,
+    real_t *B, int_t n,
+    real_t *C,
+    real_t *U_colmeans,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t l1_lam, real_t alpha, real_t w_main, real_t w_user,
+    real_t w_main_multiplier,
+    bool apply_log_transf,
+    real_t *BeTBe,
+    real_t *BtB,
+    real_t *BeTBeChol,
+    real_t *CtUbias)
+{
+    const PredictPairs pairs = {row, col, n_predict, predicted};
+    return implicit_multiple_dropin(&pairs, nullptr, m_new, U, m_u, p, NA_as_zero_U, nonneg, U_row, U_col, U_sp, nnz_U, U_csr_p, U_csr_i, U_csr, X,
+                                    ixA, ixB, nnz, Xcsr_p, Xcsr_i, Xcsr, B, n, C, U_colmeans, k, k_user, k_item, k_main, lam, l1_lam, alpha,
+                                    w_main, w_user, w_main_multiplier, apply_log_transf, BeTBe, BtB, BeTBeChol, CtUbias, nthreads);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// newrows.hpp -- what the three units behind the new-rows handle share (cmfrec_hip_newrows_*, include/cmfrec_hip.h): the
+// newrows.hpp -- what the units behind the new-rows handle share (cmfrec_hip_newrows_*, include/cmfrec_hip.h): the
 // device-resident model of a batch of new rows and its batch run (session.hip), the ranking of device factors against device
 // items (topn_tu.hip), the C entry points and the rescaling rules of the two drop-in functions (fit.hip).  No kernels.
 #pragma once
@@ -78,5 +78,17 @@ cmfrec_hip_ranker *ranker_create_from_device(const real_t *dB, size_t ldb, int_t
 int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p,
                        const int *dexcl_i, int_t n_top, int_t *out_ids, real_t *out_scores);
 int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n);
+
+// predict_tu.hip: the scoring of chosen (row, col) pairs against operands that are on the device already -- the stream, the
+// pair buffers and the timing of cmfrec_hip_scorer_predict without its factor uploads.  dA [m, lda] / dB [n, ldb] point at the
+// first scored column; dbiasA: m values with stride ldbiasA, or null.  Throws HipError (call inside guarded()); the caller has
+// synchronised the stream that wrote the operands.
+struct PairScorer;
+PairScorer *pair_scorer_create(int device);
+void pair_scorer_destroy(PairScorer *ps);
+int pair_scorer_run(PairScorer *ps, const real_t *dA, size_t lda, int_t m, const real_t *dbiasA, size_t ldbiasA, const real_t *dB, size_t ldb,
+                    int_t n, int_t kk, const real_t *dbiasB, real_t glob_mean, bool implicit, const int_t *row, const int_t *col,
+                    size_t n_pairs, real_t *out);
+double pair_scorer_ms(const PairScorer *ps);               // the kernel over the blocks of the last run
 
 }  // namespace cmfhip

@@ -35,13 +35,6 @@ namespace {
 
 constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
 
-// rows x cols values from a host matrix with leading dimension ld into a device matrix with leading dimension dld
-void upload_columns(real_t *dst, size_t dld, const real_t *src, size_t ld, size_t rows, size_t cols, hipStream_t st)
-{
-    if (ld == cols && dld == cols) HIP_CHECK(hipMemcpyAsync(dst, src, rows * cols * sizeof(real_t), hipMemcpyDefault, st));
-    else HIP_CHECK(hipMemcpy2DAsync(dst, dld * sizeof(real_t), src, ld * sizeof(real_t), cols * sizeof(real_t), rows, hipMemcpyDefault, st));
-}
-
 // User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
 // unless fewer finish the nu users in fewer or cheaper waves of workgroups.  A workgroup's time per item round is about
 // (nut + 1/2) -- its MFMAs and the item fetch they share -- times the workgroups that share its CU.

@@ -100,6 +100,15 @@ class ModelRanker:
         self.close()
 
 
+def _scorer(self, biasA, biasB, glob_mean, implicit):
+    """A ``cmfrec_amd.Scorer`` over the fitted factors: the k_user / k_item columns are skipped by offset (row-strided views)."""
+    from .score import Scorer
+    dt = self.A_.dtype
+    return Scorer(self.A_[:, self.k_user:], np.asarray(self.B_, dt)[:, self.k_item:],
+                  None if biasA is None else np.ascontiguousarray(biasA, dt), None if biasB is None else np.ascontiguousarray(biasB, dt),
+                  glob_mean=glob_mean, implicit=implicit)
+
+
 def _new_rows(X, n, dt):
     """COO triplet of new rows: ``X`` is a SciPy sparse matrix [m_x, n], a (row, col, val) triplet or None."""
     if X is None:
@@ -373,8 +382,26 @@ class CMF_implicit(_Base):
         """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch."""
         return ModelRanker(self, None)
 
+    def scorer(self):
+        """A ``cmfrec_amd.Scorer`` over this model: both factor matrices go to the device once, then ``.predict(user, item)``
+        per batch of pairs (NaN for a pair outside the model).  The caller closes it; a refit needs a new one."""
+        return _scorer(self, None, None, 0.0, True)
+
+    def predict_batch(self, user, item):
+        """``predict`` on the device: one ``scorer()`` made, used and closed.  Equal to ``predict`` within the rounding of kk
+        products summed in another order; a pair outside the model gives NaN where ``predict`` raises."""
+        with self.scorer() as sc:
+            return sc.predict(user, item)
+
+    def predict_new_batch(self, X=None, U=None, row=None, item=None):
+        """Predictions for chosen pairs (row of the batch, item) of users who were not part of the fit (reference
+        ``predict_new``; C function predict_X_new_collective_implicit): one ``new_users()`` handle made, used and closed."""
+        with self.new_users() as nu:
+            return nu.predict(X=X, U=U, row=row, item=item)
+
     def predict(self, user, item):
-        """A_u . B_i for paired user / item ids (reference predict_multiple, common.c:5066-5106)."""
+        """A_u . B_i for paired user / item ids (reference predict_multiple, common.c:5066-5106).  NumPy on the host;
+        ``predict_batch`` scores the pairs on the device."""
         user = np.asarray(user); item = np.asarray(item)
         return np.einsum("ij,ij->i", self.A_[user, self.k_user:], self.B_[item, self.k_item:])
 
@@ -614,8 +641,28 @@ class CMF(_Base):
         per batch, with the scores of ``topN_batch``."""
         return ModelRanker(self, self.item_bias_ if self.item_bias else None)
 
+    def scorer(self):
+        """A ``cmfrec_amd.Scorer`` over this model: both factor matrices, the biases and the global mean go to the device once,
+        then ``.predict(user, item)`` per batch of pairs (a pair outside the model: the global mean + the bias of the side in
+        range).  The caller closes it; a refit needs a new one."""
+        return _scorer(self, self.user_bias_ if self.user_bias else None, self.item_bias_ if self.item_bias else None,
+                       self.glob_mean_, False)
+
+    def predict_batch(self, user, item):
+        """``predict`` on the device: one ``scorer()`` made, used and closed.  Equal to ``predict`` within the rounding of
+        kk products and three additions summed in another order, not bit for bit."""
+        with self.scorer() as sc:
+            return sc.predict(user, item)
+
+    def predict_new_batch(self, X=None, U=None, W=None, row=None, item=None):
+        """Predictions for chosen pairs (row of the batch, item) of users who were not part of the fit (reference
+        ``predict_new``; C function predict_X_new_collective_explicit): one ``new_users()`` handle made, used and closed."""
+        with self.new_users() as nu:
+            return nu.predict(X=X, U=U, W=W, row=row, item=item)
+
     def predict(self, user, item):
-        """glob_mean + biasA[u] + biasB[i] + A_u . B_i (reference predict_multiple, common.c:5098-5106)."""
+        """glob_mean + biasA[u] + biasB[i] + A_u . B_i (reference predict_multiple, common.c:5098-5106).  NumPy on the host;
+        ``predict_batch`` scores the pairs on the device."""
         user = np.asarray(user); item = np.asarray(item)
         ku, ki = self.k_user, self.k_item
         out = np.einsum("ij,ij->i", self.A_[user, ku:], self.B_[item, ki:]) + self.glob_mean_

@@ -178,9 +178,33 @@ class NewUsers:
             return out, (A, bias)
         return out
 
+    def predict(self, X=None, U=None, W=None, row=None, item=None, return_factors=False):
+        """The predictions [len(row)] for the chosen pairs (row[i], item[i]) of a batch of new users: ``row`` indexes the rows of
+        the batch, ``item`` the model's items.  The batch is solved like ``factors``; the pairs are scored on the device from the
+        factors it leaves there, the resident items and their bias: ``A_r . B_i`` + the global mean + the row's bias + the item's
+        bias for ``CMF`` (a pair outside the batch's rows or the items: the global mean + the bias of the side in range),
+        ``A_r . B_i`` for ``CMF_implicit`` (NaN outside).  ``return_factors``: a second value, ``(A, bias)`` as
+        ``factors(..., return_bias=True)`` returns them."""
+        from .score import check_pairs
+        h = self._live()
+        if row is None or item is None:
+            raise ValueError("NewUsers.predict needs 'row' and 'item'")
+        row, item = check_pairs(row, item, "NewUsers.predict")
+        s, keep, rows = self._batch(X, U, W)
+        out = np.empty(len(row), self.dtype)
+        A = np.empty((rows, self.width), self.dtype) if return_factors else None
+        bias = np.empty(rows, self.dtype) if (self.has_bias and return_factors) else None
+        rc = self.lib.cmfrec_hip_newrows_predict(h, C.byref(s), _lib.ptr(row), _lib.ptr(item), len(row), _lib.ptr(out), _lib.ptr(A),
+                                                 _lib.ptr(bias))
+        _lib.check(rc, self.lib, "NewUsers.predict")
+        del keep
+        if return_factors:
+            return out, (A, bias)
+        return out
+
     def kernel_ms(self):
         """(solve ms, ranking ms): HIP-event times of the most recent call's solve phase and of its ranking kernel (0 after
-        ``factors``; after ``impute``: of its fill kernel)."""
+        ``factors``; after ``impute``: of its fill kernel; after ``predict``: of its scoring kernel)."""
         a, b = C.c_double(0), C.c_double(0)
         _lib.check(self.lib.cmfrec_hip_newrows_kernel_ms(self._live(), C.byref(a), C.byref(b)), self.lib, "NewUsers.kernel_ms")
         return a.value, b.value

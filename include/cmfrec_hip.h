@@ -644,9 +644,14 @@ void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
  *   block of rows on the matrix cores and skips the rows (and tiles) without a NaN; a batch without any NaN is copied without
  *   solving.  A / biasA: optional outputs as in topN.  Return code 2, with a message, and the handle stays usable: an implicit
  *   model, a batch whose X is not Xfull, m <= 0; whatever factors refuses for the batch is refused with the same message.
+ * predict: solves the batch like factors, then scores the n_pairs chosen pairs (row[i], col[i]) straight from the device factors,
+ *   the resident items and their bias, with the rule of cmfrec_hip_scorer_predict below (explicit or implicit by the model):
+ *   row indexes the batch's rows [0, max(m, m_u)), col the items [0, n) -- [0, max(n, n_max)) with include_all_X; a pair outside
+ *   gets the fallback value.  A / biasA optional outputs as in topN.  What factors refuses for the batch is refused with the same
+ *   message and code, out is left alone and the handle stays usable.  The return codes of factors (0, 1, 2, 3).
  * kernel_ms: HIP-event times of the most recent call -- its solve phase (uploads of the batch, shard build, row solves; 0 after
  *   an impute call that found no NaN) and, after a topN, the ranking kernel, after an impute, the fill kernel summed over the
- *   blocks (0 after a factors call); 2 before the first call.
+ *   blocks, after a predict, the scoring kernel summed over the blocks (0 after a factors call); 2 before the first call.
  * Calls on one handle must not overlap; a handle belongs to the device it was made on. */
 typedef struct cmfrec_hip_newrows_model {
     int32_t implicit;
@@ -679,6 +684,8 @@ int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batc
                             const size_t excl_p[], const int_t excl_i[], int_t n_top,
                             int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *Xout, real_t *A, real_t *biasA);
+int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, const int_t *row, const int_t *col,
+                               size_t n_pairs, real_t *out, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms);
 void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h);
 
@@ -718,6 +725,114 @@ int_t impute_X_collective_explicit(
     real_t *CtUbias,
     real_t *B_plus_bias,
     int nthreads);
+
+/* Predictions for chosen (row, col) pairs with both factor matrices resident on the device (the evaluation loop after a fit:
+ * millions of pairs against one model).  With a = A[row, 0 .. kk) and b = B[col, 0 .. kk) -- A and B point at the first scored
+ * column: skip k_user / k_item by offsetting the pointers, kk = k + k_main --
+ *   explicit:  row in [0, m) and col in [0, n):  a . b + biasA[row] + biasB[col] + glob_mean   (a missing bias adds nothing)
+ *              otherwise:                        glob_mean + (biasA[row] if 0 <= row < m) + (biasB[col] if 0 <= col < n)
+ *   implicit:  row in [0, m) and col in [0, n):  a . b;   otherwise NaN
+ * The dot product is accumulated in the working precision, in an order that depends on kk alone: a pair's bits do not depend on
+ * its position in the call, on the other pairs or on the block size.  Pairs out of range are decided on the device.
+ * create: uploads the kk scored columns of A [m, lda] and B [n, ldb] packed and zero-padded to 16 bytes, and the biases (each
+ *   optional); implicit != 0 selects the implicit rule (biases and glob_mean are then ignored, given or not: a . b alone); device < 0: the
+ *   current device.  NULL on failure (cmfrec_hip_last_error / cmfrec_hip_last_error_code): 2 for m, n or kk < 1, a leading
+ *   dimension below kk or a missing matrix.
+ * predict: out[i] for the pairs (row[i], col[i]), i < n_pairs; the pairs go up and the values come down in blocks of at most 2^24
+ *   pairs (CMFREC_HIP_PREDICT_BLOCK: test hook for that size).  The handle's buffers are reused and grow on demand; n_pairs = 0
+ *   returns 0.  Calls on one handle must not overlap.
+ * kernel_ms: HIP-event time of the scoring kernel over the blocks of the most recent predict call (2 before the first). */
+typedef struct cmfrec_hip_scorer cmfrec_hip_scorer;
+cmfrec_hip_scorer *cmfrec_hip_scorer_create(const real_t *A, size_t lda, int_t m, const real_t *B, size_t ldb, int_t n, int_t kk,
+                                            const real_t *biasA, const real_t *biasB, real_t glob_mean, int implicit, int device);
+int cmfrec_hip_scorer_predict(cmfrec_hip_scorer *s, const int_t *row, const int_t *col, size_t n_pairs, real_t *out);
+int cmfrec_hip_scorer_kernel_ms(cmfrec_hip_scorer *s, double *ms);
+void cmfrec_hip_scorer_destroy(cmfrec_hip_scorer *s);
+
+/* Replace predict_X_old_collective_explicit / _implicit and predict_X_new_collective_explicit / _implicit of the reference's
+ * src/cmfrec.h (bodies src/collective.c:11797-12069 over predict_multiple, src/common.c:5066-5110) -- the same positional
+ * parameters, the same return codes; nthreads is accepted and ignored.
+ * _old: the pairs against factors the caller holds: a scorer (above) created, used once, destroyed; A [m, k_user+k+k_main],
+ *   B [n_max (n), k_item+k+k_main]; m = 0 or n = 0 is legal (that side is not read: every pair gets the fallback value), a negative
+ *   size, k + k_main < 1 or a missing array returns 2.  _new: the factors of a batch of new rows, then the pairs from them (row indexes the batch's
+ *   rows, m = max(m_new, m_u)): cmfrec_hip_newrows_create, one cmfrec_hip_newrows_predict, destroy -- the argument mapping,
+ *   refusals and messages of factors_collective_*_multiple; a refused call leaves predicted untouched.
+ * Two deliberate differences from the reference: the dot product runs over k + k_main factors, as the
+ * model, topN and the imputation define a prediction (the reference's predict_multiple stops after k; equal for k_main = 0); and
+ * a negative row / col is treated like one beyond the end (the reference's fallback reads biasA[row] / biasB[col] for it). */
+int_t predict_X_old_collective_explicit(
+    int_t row[], int_t col[], real_t *predicted, size_t n_predict,
+    real_t *A, real_t *biasA,
+    real_t *B, real_t *biasB,
+    real_t glob_mean,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    int_t m, int_t n_max,
+    int nthreads);
+int_t predict_X_old_collective_implicit(
+    int_t row[], int_t col[], real_t *predicted, size_t n_predict,
+    real_t *A,
+    real_t *B,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    int_t m, int_t n,
+    int nthreads);
+int_t predict_X_new_collective_explicit(
+    int_t m_new,
+    int_t row[], int_t col[], real_t *predicted, size_t n_predict,
+    int nthreads,
+    bool user_bias,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U, bool NA_as_zero_X,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *Ub, int_t m_ubin, int_t pbin,
+    real_t *C, real_t *Cb,
+    real_t glob_mean, real_t *biasB,
+    real_t *U_colmeans,
+    real_t *X, int_t ixA[], int_t ixB[], size_t nnz,
+    size_t *Xcsr_p, int_t *Xcsr_i, real_t *Xcsr,
+    real_t *Xfull, int_t n,
+    real_t *weight,
+    real_t *B,
+    real_t *Bi, bool add_implicit_features,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t *lam_unique,
+    real_t l1_lam, real_t *l1_lam_unique,
+    bool scale_lam, bool scale_lam_sideinfo,
+    bool scale_bias_const, real_t scaling_biasA,
+    real_t w_main, real_t w_user, real_t w_implicit,
+    int_t n_max, bool include_all_X,
+    real_t *BtB,
+    real_t *TransBtBinvBt,
+    real_t *BtXbias,
+    real_t *BeTBeChol,
+    real_t *BiTBi,
+    real_t *TransCtCinvCt,
+    real_t *CtCw,
+    real_t *CtUbias,
+    real_t *B_plus_bias);
+int_t predict_X_new_collective_implicit(
+    int_t m_new,
+    int_t row[], int_t col[], real_t *predicted, size_t n_predict,
+    int nthreads,
+    real_t *U, int_t m_u, int_t p,
+    bool NA_as_zero_U,
+    bool nonneg,
+    int_t U_row[], int_t U_col[], real_t *U_sp, size_t nnz_U,
+    size_t U_csr_p[], int_t U_csr_i[], real_t *U_csr,
+    real_t *X, int_t ixA[], int_t ixB[], size_t nnz,
+    size_t *Xcsr_p, int_t *Xcsr_i, real_t *Xcsr,
+    real_t *B, int_t n,
+    real_t *C,
+    real_t *U_colmeans,
+    int_t k, int_t k_user, int_t k_item, int_t k_main,
+    real_t lam, real_t l1_lam, real_t alpha, real_t w_main, real_t w_user,
+    real_t w_main_multiplier,
+    bool apply_log_transf,
+    real_t *BeTBe,
+    real_t *BtB,
+    real_t *BeTBeChol,
+    real_t *CtUbias);
 
 /* Replace precompute_collective_explicit / precompute_collective_implicit, /root/reference/src/cmfrec.h:1922-1960 (bodies
  * src/collective.c:10209-10485, :10487-10566): the matrices the prediction functions reuse, from factors the caller holds -- the
@@ -825,6 +940,17 @@ int cmfrec_hip_dense_op(int op, int m, int n, int k, real_t s1, real_t s2, const
  * row length or a missing operand. */
 int cmfrec_hip_impute_dense(int m, int n, int kk, const real_t *A, size_t lda, const real_t *biasA, const real_t *B, size_t ldb,
                             const real_t *biasB, real_t glob_mean, real_t *X, size_t ldx, const int *row_missing);
+
+/* The scoring kernel of the chosen pairs on its own, through the launch helper every prediction path uses (test entry point):
+ * the rule of cmfrec_hip_scorer_predict on host images that are uploaded as they are.  A is the image of the row factors,
+ * offA + m * lda elements whose operand [m, lda] starts offA elements in (so that its 16-byte alignment on the device is the
+ * caller's choice: aligned operands with even pitches are fetched 16 bytes per lane, the others element by element, with the same
+ * bits); B likewise.  biasA (optional): m values -- or, where it points into the image of A, that column of the image (stride
+ * lda).  biasB (optional): n values.  Returns 2 on negative sizes or offsets, kk < 1, a leading dimension below kk or a missing
+ * operand. */
+int cmfrec_hip_score_pairs(int m, int n, int kk, const real_t *A, size_t lda, int offA, const real_t *biasA, const real_t *B, size_t ldb,
+                           int offB, const real_t *biasB, real_t glob_mean, int implicit, const int_t *row, const int_t *col, size_t n_pairs,
+                           real_t *out);
 
 /* Start values as the reference's random_parallel draws them (src/helpers.c:927-1043; xoshiro256++
  * seeded by splitmix64, truncated ziggurat normals or uniforms, scaled 2^-7): A <- stream(seed),
