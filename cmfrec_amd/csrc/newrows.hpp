@@ -77,6 +77,10 @@ double newrows_state_fill_ms(const NewRowsState *s);
 cmfrec_hip_ranker *ranker_create_from_device(const real_t *dB, size_t ldb, int_t n, int_t k, const real_t *dbiasB, int device);
 int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p,
                        const int *dexcl_i, int_t n_top, int_t *out_ids, real_t *out_scores);
+// the same over each row's candidate list (host CSR over the nu rows, uploaded here; topn_cand_kernels.hpp)
+int ranker_topN_candidates_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t cand_p[],
+                                  const int_t cand_i[], const size_t *dexcl_p, const int *dexcl_i, int_t n_top, int_t *out_ids,
+                                  real_t *out_scores);
 int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n);
 
 // predict_tu.hip: the scoring of chosen (row, col) pairs against operands that are on the device already -- the stream, the

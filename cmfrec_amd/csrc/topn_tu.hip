@@ -3,11 +3,14 @@
 // instantiations stay out of session.hip's compile.
 //
 // Routing: k <= TOPN_KMAX (64) launches topn_kernel, the kernel of every release so far; beyond that -- or for every k under
-// CMFREC_HIP_TOPN=wide, a cross-check and A/B switch -- topn_wide_kernel (topn_wide_kernels.hpp).
+// CMFREC_HIP_TOPN=wide, a cross-check and A/B switch -- topn_wide_kernel (topn_wide_kernels.hpp).  A call with candidate lists
+// (cmfrec_hip_ranker_topN_candidates and its kin) launches topn_cand_kernel (topn_cand_kernels.hpp) for every k.
 #include <algorithm>
+#include <vector>
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
+#include "topn_cand_kernels.hpp"
 
 using namespace cmfhip;
 
@@ -20,6 +23,9 @@ struct cmfrec_hip_ranker {
     DevBuf<real_t> A, sc;                    // per call; they grow on demand
     DevBuf<size_t> ep;
     DevBuf<int> ei, ids;
+    DevBuf<size_t> cp;                       // candidate lists of a candidate call
+    DevBuf<int> ci, corder;                  // ... and the users by descending list length
+    DevBuf<unsigned> next;                   // work counter of topn_cand_kernel
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the ranking kernel of the last call
     bool timed = false;
     int last_users = 0, last_grid = 0;       // users per workgroup and workgroups of that launch
@@ -79,15 +85,30 @@ int check_n_top(const char *fn, int_t n_top, int_t n)
 
 // the ranking of nu users whose factors dA [nu, lda] and exclusion lists are on the device already: the launch, the timing
 // events and the download of cmfrec_hip_ranker_topN (the caller holds the DeviceScope and has checked the limits)
+// dcand_p != null: over each user's candidate list (device CSR) on topn_cand_kernel
 int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
-                int_t *out_ids, real_t *out_scores)
+                int_t *out_ids, real_t *out_scores, const size_t *dcand_p = nullptr, const int *dcand_i = nullptr)
 {
     const cmfrec_hip_ranker::Device &dev = r->dev;
     const int k = r->k;
     r->ids.alloc_at_least((size_t)nu * n_top);
     if (out_scores) r->sc.alloc_at_least((size_t)nu * n_top);
+    if (dcand_p) {
+        r->next.alloc_at_least(1);
+        HIP_CHECK(hipMemsetAsync(r->next.ptr, 0, sizeof(unsigned), dev.stream));
+    }
     HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
-    if (k <= TOPN_KMAX && !switches().topn_wide) {
+    if (dcand_p) {
+        TopnCandParams<real_t> P;
+        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
+        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+        P.cand_p = dcand_p; P.cand_i = dcand_i;
+        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+        P.next = r->next.ptr; P.order = r->corder.ptr;
+        r->last_grid = launch_topn_cand(dev.stream, dev.num_cus, P, switches().topn_cand_waves);
+        r->last_users = TOPNC_NW;
+    } else if (k <= TOPN_KMAX && !switches().topn_wide) {
         TopnParams<real_t> P;
         P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
         P.biasB = r->has_bias ? r->bias.ptr : nullptr;
@@ -123,7 +144,30 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
     return 0;
 }
 
+// the candidate lists of a call (host CSR over the nu users) into the ranker's buffers; 2 with a message for lists that are not a CSR
+int upload_candidates(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size_t cand_p[], const int_t cand_i[])
+{
+    bool bad = cand_p == nullptr;
+    for (int_t u = 0; !bad && u < nu; u++) bad = cand_p[u] > cand_p[u + 1];
+    if (bad || (cand_p[nu] > 0 && cand_i == nullptr)) {
+        g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    // the order the kernel hands the users out in: longest list first (a long list that starts last is the launch's tail)
+    std::vector<int> order((size_t)nu);
+    for (int_t u = 0; u < nu; u++) order[u] = u;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cand_p[a + 1] - cand_p[a] > cand_p[b + 1] - cand_p[b]; });
+    r->corder.upload(order.data(), (size_t)nu, r->dev.stream);
+    HIP_CHECK(hipStreamSynchronize(r->dev.stream));          // `order` goes away
+    r->cp.upload(cand_p, (size_t)nu + 1, r->dev.stream);
+    r->ci.alloc_at_least(std::max<size_t>(cand_p[nu], 1));
+    if (cand_p[nu] > 0) r->ci.upload(cand_i, cand_p[nu], r->dev.stream);
+    return 0;
+}
+
 }  // namespace
+
+static_assert(TOPNC_KMAX == TOPNW_KMAX, "topn_cand_kernel holds a user's row of the widest model in registers");
 
 extern "C" {
 
@@ -184,6 +228,34 @@ int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, in
     });
 }
 
+int cmfrec_hip_ranker_topN_candidates(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t cand_p[], const int_t cand_i[],
+                                      const size_t excl_p[], const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    const char *fn = "cmfrec_hip_ranker_topN_candidates";
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || n_top <= 0 || !A || !out_ids || !cand_p || lda < (size_t)r->k ||
+            (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if (int rc = check_n_top(fn, n_top, r->n)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        const int k = r->k;
+        if (int rc = upload_candidates(r, fn, nu, cand_p, cand_i)) return rc;
+        r->A.alloc_at_least((size_t)nu * k);
+        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        if (excl_p) {
+            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
+            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
+            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
+        }
+        return rank_device(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids, out_scores,
+                           r->cp.ptr, r->ci.ptr);
+    });
+}
+
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms)
 {
     return guarded([&]() {
@@ -234,6 +306,25 @@ int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B
     return rc;
 }
 
+int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                                     const real_t *biasB, const size_t cand_p[], const int_t cand_i[], const size_t excl_p[],
+                                     const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids || !cand_p) {
+        g_last_error = "cmfrec_hip_topN_candidates_batch: invalid arguments";
+        return 2;
+    }
+    if (k > TOPNW_KMAX || n_top > TOPN_NMAX || n_top > n) {
+        g_last_error = std::string("cmfrec_hip_topN_candidates_batch: ") + LIMITS;
+        return 2;
+    }
+    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
+    if (r == nullptr) return g_last_rc;
+    const int rc = cmfrec_hip_ranker_topN_candidates(r, A, lda, nu, cand_p, cand_i, excl_p, excl_i, n_top, out_ids, out_scores);
+    cmfrec_hip_ranker_destroy(r);
+    return rc;
+}
+
 }  // extern "C"
 
 namespace cmfhip {
@@ -265,6 +356,23 @@ int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, s
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
         return rank_device(r, dA, lda, nu, dexcl_p, dexcl_i, n_top, out_ids, out_scores);
+    });
+}
+
+int ranker_topN_candidates_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t cand_p[],
+                                  const int_t cand_i[], const size_t *dexcl_p, const int *dexcl_i, int_t n_top, int_t *out_ids,
+                                  real_t *out_scores)
+{
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || n_top <= 0 || !dA || !out_ids || !cand_p || lda < (size_t)r->k) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if (int rc = check_n_top(fn, n_top, r->n)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        if (int rc = upload_candidates(r, fn, nu, cand_p, cand_i)) return rc;
+        return rank_device(r, dA, lda, nu, dexcl_p, dexcl_i, n_top, out_ids, out_scores, r->cp.ptr, r->ci.ptr);
     });
 }
 

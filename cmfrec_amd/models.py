@@ -63,18 +63,20 @@ def _topN_inputs(self, users, exclude):
     return users, A, excl
 
 
-def _topN(self, users, n, exclude, biasB):
+def _topN(self, users, n, exclude, biasB, include=None):
     """Shared body of ``CMF.topN_batch`` / ``CMF_implicit.topN_batch``."""
     from . import ops
     _, A, excl = _topN_inputs(self, users, exclude)
     B = np.ascontiguousarray(self.B_[:, self.k_item:])
-    return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl)
+    if include is None:
+        return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl)
+    return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl, include=include)
 
 
 class ModelRanker:
     """What ``CMF.ranker()`` / ``CMF_implicit.ranker()`` return: the fitted model's item factors (and item bias) held on the
-    device by a ``cmfrec_amd.Ranker``; ``topN(users, n, exclude)`` takes user ids of the fitted model and returns what the model's
-    ``topN_batch`` returns.  The caller closes it (``close()`` or a ``with`` block); a refit needs a new one."""
+    device by a ``cmfrec_amd.Ranker``; ``topN(users, n, exclude, include)`` takes user ids of the fitted model and returns what the
+    model's ``topN_batch`` returns.  The caller closes it (``close()`` or a ``with`` block); a refit needs a new one."""
 
     def __init__(self, model, biasB):
         from .rank import Ranker
@@ -82,9 +84,12 @@ class ModelRanker:
         self._ranker = Ranker(np.ascontiguousarray(model.B_[:, model.k_item:]),
                               None if biasB is None else np.ascontiguousarray(biasB, model.B_.dtype))
 
-    def topN(self, users, n=10, exclude=None):
+    def topN(self, users, n=10, exclude=None, include=None):
         users, A, excl = _topN_inputs(self._model, users, exclude)
-        ids, sc = self._ranker.topN(A, n=n, exclude=excl)
+        if include is None:
+            ids, sc = self._ranker.topN(A, n=n, exclude=excl)
+        else:
+            ids, sc = self._ranker.topN(A, n=n, exclude=excl, include=include)
         return ids, self._model._finish_scores(users, sc)
 
     def kernel_ms(self):
@@ -208,9 +213,11 @@ def _sparse_U_args(Us):
     return (_lib.ptr(Us[0]), _lib.ptr(Us[1]), _lib.ptr(Us[2]), C.c_size_t(len(Us[2])), None, None, None)
 
 
-def _topN_new_batch(self, X, U, W, n, exclude_seen, exclude):
+def _topN_new_batch(self, X, U, W, n, exclude_seen, exclude, include=None):
     with self.new_users() as nu:
-        return nu.topN(X=X, U=U, W=W, n=n, exclude_seen=exclude_seen, exclude=exclude)
+        if include is None:
+            return nu.topN(X=X, U=U, W=W, n=n, exclude_seen=exclude_seen, exclude=exclude)
+        return nu.topN(X=X, U=U, W=W, n=n, exclude_seen=exclude_seen, exclude=exclude, include=include)
 
 
 def _side_info(M, dt):
@@ -359,10 +366,12 @@ class CMF_implicit(_Base):
         _lib.check(rc, lib, "factors_collective_implicit_multiple")
         return A
 
-    def topN_batch(self, users, n=10, exclude=None):
+    def topN_batch(self, users, n=10, exclude=None, include=None):
         """Top-``n`` item ids and scores (A_u . B_i) for a batch of users, ranked on the GPU; ``exclude``: CSR of items
-        to skip per user (e.g. the training matrix).  Batch form of the reference's ``topN`` (common.c:5127-5380)."""
-        return _topN(self, users, n, exclude, None)
+        to skip per user (e.g. the training matrix).  Batch form of the reference's ``topN`` (common.c:5127-5380).
+        ``include``: candidate lists -- (indptr, indices) CSR over the users OF THIS CALL (one list per entry of ``users``), a
+        SciPy CSR matrix of that many rows, or one 1-D array shared by all: each user is ranked over its own list only."""
+        return _topN(self, users, n, exclude, None, include)
 
     def _finish_scores(self, users, sc):
         return sc
@@ -373,10 +382,11 @@ class CMF_implicit(_Base):
         from .new_users import NewUsers
         return NewUsers(self)
 
-    def topN_new_batch(self, X=None, U=None, n=10, exclude_seen=True, exclude=None):
+    def topN_new_batch(self, X=None, U=None, n=10, exclude_seen=True, exclude=None, include=None):
         """Top-``n`` items for users who were not part of the fit, from their interactions and / or attributes (batch form of
-        the reference's ``topN_new``): one ``new_users()`` handle made, used and closed."""
-        return _topN_new_batch(self, X, U, None, n, exclude_seen, exclude)
+        the reference's ``topN_new``): one ``new_users()`` handle made, used and closed.  ``include``: candidate lists over the
+        rows of the batch, as ``NewUsers.topN`` takes them."""
+        return _topN_new_batch(self, X, U, None, n, exclude_seen, exclude, include)
 
     def ranker(self):
         """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch."""
@@ -606,11 +616,13 @@ class CMF(_Base):
             return A, biasA
         return A
 
-    def topN_batch(self, users, n=10, exclude=None):
+    def topN_batch(self, users, n=10, exclude=None, include=None):
         """Top-``n`` item ids and scores for a batch of users, ranked on the GPU by A_u . B_i + item_bias[i] (the user
         bias and the global mean do not change the order; the reference adds them to the scores, common.c:5339-5345,
-        and so does this method).  ``exclude``: CSR of items to skip per user."""
-        ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None)
+        and so does this method).  ``exclude``: CSR of items to skip per user.  ``include``: candidate lists -- (indptr,
+        indices) CSR over the users OF THIS CALL (one list per entry of ``users``), a SciPy CSR matrix of that many rows, or
+        one 1-D array shared by all: each user is ranked over its own list only."""
+        ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None, include)
         return ids, self._finish_scores(np.atleast_1d(np.asarray(users, np.int64)), sc)
 
     def _finish_scores(self, users, sc):
@@ -625,10 +637,11 @@ class CMF(_Base):
         from .new_users import NewUsers
         return NewUsers(self)
 
-    def topN_new_batch(self, X=None, U=None, W=None, n=10, exclude_seen=True, exclude=None):
+    def topN_new_batch(self, X=None, U=None, W=None, n=10, exclude_seen=True, exclude=None, include=None):
         """Top-``n`` items for users who were not part of the fit, from their ratings and / or attributes (batch form of the
-        reference's ``topN_new``), scores + the global mean + the new rows' bias: one ``new_users()`` handle made, used and closed."""
-        return _topN_new_batch(self, X, U, W, n, exclude_seen, exclude)
+        reference's ``topN_new``), scores + the global mean + the new rows' bias: one ``new_users()`` handle made, used and closed.
+        ``include``: candidate lists over the rows of the batch, as ``NewUsers.topN`` takes them."""
+        return _topN_new_batch(self, X, U, W, n, exclude_seen, exclude, include)
 
     def transform(self, X, U=None, W=None):
         """The dense ``X`` [m, n] with its NaN replaced by the model's predictions (reference ``CMF.transform``; C function

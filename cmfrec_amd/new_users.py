@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _sorted_exclude
+from .ops import _sorted_exclude, _sorted_include
 
 
 def _has(M):
@@ -122,7 +122,7 @@ class NewUsers:
             return A, bias
         return A
 
-    def _topN_raw(self, X, U, W, n, exclude_seen, exclude, want_factors):
+    def _topN_raw(self, X, U, W, n, exclude_seen, exclude, want_factors, include=None):
         """(ids, the device's own scores A_u . B_i + biasB_i, A or None, bias or None)."""
         h = self._live()
         s, keep, rows = self._batch(X, U, W)
@@ -133,20 +133,28 @@ class NewUsers:
         ids = np.empty((rows, n), np.int32); sc = np.empty((rows, n), self.dtype)
         A = np.empty((rows, self.width), self.dtype) if want_factors else None
         bias = np.empty(rows, self.dtype) if self.has_bias else None
-        rc = self.lib.cmfrec_hip_newrows_topN(h, C.byref(s), C.c_int(1 if exclude_seen else 0), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
-                                              _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(A), _lib.ptr(bias))
+        if include is not None:
+            cp, ci = _sorted_include(include, rows)
+            rc = self.lib.cmfrec_hip_newrows_topN_candidates(h, C.byref(s), _lib.ptr(cp), _lib.ptr(ci), C.c_int(1 if exclude_seen else 0),
+                                                             _lib.ptr(ep), _lib.ptr(ei), C.c_int(n), _lib.ptr(ids), _lib.ptr(sc),
+                                                             _lib.ptr(A), _lib.ptr(bias))
+        else:
+            rc = self.lib.cmfrec_hip_newrows_topN(h, C.byref(s), C.c_int(1 if exclude_seen else 0), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
+                                                  _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(A), _lib.ptr(bias))
         _lib.check(rc, self.lib, "NewUsers.topN")
         del keep
         return ids, sc, A, bias
 
-    def topN(self, X=None, U=None, W=None, n=10, exclude_seen=True, exclude=None, return_factors=False):
+    def topN(self, X=None, U=None, W=None, n=10, exclude_seen=True, exclude=None, return_factors=False, include=None):
         """(ids [rows, n] int32, scores [rows, n]) for the rows of the batch, ranked on the device from the factors the batch
         run leaves there: descending score, ties by lower id, -1 / -inf where fewer than ``n`` items remain.  ``exclude_seen``
         skips each row's own items of ``X``; ``exclude`` = (indptr, indices) CSR (or a SciPy CSR matrix) over the rows of the
         batch adds further lists.  The scores are those of ``topN_batch``: + the global mean and the new rows' bias for ``CMF``.
         ``return_factors``: a third value, the factors as ``factors(..., return_bias=True)`` returns them (``(A, bias)``; bias
-        None without a user bias)."""
-        ids, sc, A, bias = self._topN_raw(X, U, W, n, exclude_seen, exclude, return_factors)
+        None without a user bias).  ``include``: candidate lists -- (indptr, indices) CSR over the rows of the batch, a SciPy CSR
+        matrix, or one 1-D array shared by every row: each row is ranked over its own list only, minus what ``exclude_seen`` and
+        ``exclude`` take out."""
+        ids, sc, A, bias = self._topN_raw(X, U, W, n, exclude_seen, exclude, return_factors, include)
         if not self.implicit:                               # as CMF.topN_batch finishes its scores (common.c:5339-5345)
             sc = sc + self._model.glob_mean_
             if bias is not None:

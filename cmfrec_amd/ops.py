@@ -179,10 +179,63 @@ def _sorted_exclude(exclude, nu):
     return ep, np.ascontiguousarray(ei[np.lexsort((ei, owner))])
 
 
-def topN_batch(A, B, n_top=10, biasB=None, exclude=None):
+def _sorted_include(include, nu):
+    """(indptr uint64, indices int32) of the per-user candidate lists, each list ascending and free of duplicates (what the
+    candidate kernel's tie rule asks for); (None, None) without lists.  ``include``: (indptr, indices) CSR over the ``nu`` users
+    of the call, a SciPy CSR matrix, or one 1-D array of ids -- a single list shared by every user.  An id that does not fit
+    int32 becomes -1 (the device skips every id outside the items).  No loop over the users."""
+    if include is None:
+        return None, None
+    if hasattr(include, "indptr") and hasattr(include, "indices"):
+        include = (include.indptr, include.indices)
+    shared = not (isinstance(include, (tuple, list)) and len(include) == 2 and np.ndim(include[0]) == 1 and np.ndim(include[1]) == 1)
+    ix = np.asarray(include if shared else include[1])
+    if ix.ndim != 1:
+        raise ValueError("include: (indptr, indices), a CSR matrix or one 1-D array of item ids, got a %d-D array" % ix.ndim)
+    if ix.size and not np.issubdtype(ix.dtype, np.integer):
+        raise ValueError("include: the item ids must be integers, got %s" % ix.dtype)
+    if shared:
+        ix = ix.astype(np.int64)
+        ix[(ix < 0) | (ix > np.iinfo(np.int32).max)] = -1
+        ix = np.unique(ix)
+        ep = (np.arange(nu + 1, dtype=np.uint64) * np.uint64(len(ix))).astype(np.uint64)
+        return ep, np.ascontiguousarray(np.tile(ix, nu), np.int32)
+    ip = np.asarray(include[0])
+    if len(ip) != nu + 1:
+        raise ValueError("include: indptr must have one entry per user plus one (%d), got %d" % (nu + 1, len(ip)))
+    if not (np.issubdtype(ip.dtype, np.integer) or np.all(ip == np.floor(ip))):
+        raise ValueError("include: indptr must hold integers, got %s" % ip.dtype)
+    ip = ip.astype(np.int64)
+    lens = np.diff(ip)
+    if ip[0] < 0 or (lens < 0).any():
+        raise ValueError("include: indptr must not decrease")
+    if ip[-1] != len(ix):
+        raise ValueError("include: the last entry of indptr (%d) is not the number of indices (%d)" % (ip[-1], len(ix)))
+    ix = ix[ip[0]:]
+    if ix.dtype == np.int32:
+        # what a retrieval stage usually hands over -- int32 ids, every list ascending and unique -- passes with one comparison
+        # per entry and without a copy (a negative id stays: the device skips it)
+        up = ix[1:] > ix[:-1]
+        first = ip[1:-1][lens[1:] > 0] - ip[0]               # where the lists after the first begin
+        up[first[(first > 0) & (first < len(ix))] - 1] = True
+        if up.all():
+            return (ip - ip[0]).astype(np.uint64), np.ascontiguousarray(ix)
+    # one key per entry, (user, id + 1), sorted and de-duplicated in one go
+    ix = ix.astype(np.int64)
+    ix[(ix < 0) | (ix > np.iinfo(np.int32).max)] = -1
+    key = np.unique((np.repeat(np.arange(nu, dtype=np.int64), lens) << 32) | (ix + 1))
+    ep = np.zeros(nu + 1, np.uint64)
+    ep[1:] = np.cumsum(np.bincount(key >> 32, minlength=nu))
+    return ep, np.ascontiguousarray((key & 0xffffffff) - 1, np.int32)
+
+
+def topN_batch(A, B, n_top=10, biasB=None, exclude=None, include=None):
     """Top-N item ids (and scores) for every row of ``A``: score = A_u . B_i (+ biasB[i]), descending, ties by lower
     id; ``exclude`` = (indptr, indices) CSR of items to skip per user (sorted here).  Batch counterpart of the
     reference's per-user ``topN`` (src/common.c:5127-5380).  Every width the library fits (k <= 272), n_top <= min(128, n).
+    ``include``: candidate lists -- (indptr, indices) CSR over the rows of ``A``, a SciPy CSR matrix, or one 1-D array shared by
+    every user (sorted and de-duplicated here): each user is ranked over its own list only, with the result the full ranking
+    gives when every other item is excluded (the reference's ``include_ix``, batched); ``exclude`` may come along.
     B is uploaded on every call: to rank several batches against the same items, hold a ``cmfrec_amd.Ranker``."""
     A = np.ascontiguousarray(A); B = np.ascontiguousarray(B, A.dtype)
     lib, R = _prep(A, B)
@@ -191,6 +244,13 @@ def topN_batch(A, B, n_top=10, biasB=None, exclude=None):
     ids = np.empty((nu, n_top), np.int32); sc = np.empty((nu, n_top), A.dtype)
     bs = None if biasB is None else np.ascontiguousarray(biasB, A.dtype)
     ep, ei = _sorted_exclude(exclude, nu)
+    if include is not None:
+        cp, ci = _sorted_include(include, nu)
+        rc = lib.cmfrec_hip_topN_candidates_batch(_lib.ptr(A), C.c_size_t(lda), C.c_int(nu), _lib.ptr(B), C.c_size_t(ldb), C.c_int(n),
+                                                  C.c_int(lda), _lib.ptr(bs), _lib.ptr(cp), _lib.ptr(ci), _lib.ptr(ep), _lib.ptr(ei),
+                                                  C.c_int(n_top), _lib.ptr(ids), _lib.ptr(sc))
+        _lib.check(rc, lib, "topN_batch")
+        return ids, sc
     rc = lib.cmfrec_hip_topN_batch(_lib.ptr(A), C.c_size_t(lda), C.c_int(nu), _lib.ptr(B), C.c_size_t(ldb), C.c_int(n),
                                    C.c_int(lda), _lib.ptr(bs), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n_top), _lib.ptr(ids),
                                    _lib.ptr(sc))

@@ -6,12 +6,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _sorted_exclude
+from .ops import _sorted_exclude, _sorted_include
 
 
 class Ranker:
     """``Ranker(B, biasB=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype or None.
-    ``topN(A, n=10, exclude=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns the handle:
+    ``topN(A, n=10, exclude=None, include=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns the handle:
     ``close()`` it, or use it as a context manager."""
 
     def __init__(self, B, biasB=None, device=-1):
@@ -45,9 +45,12 @@ class Ranker:
             raise RuntimeError("Ranker: the handle is closed")
         return self.handle
 
-    def topN(self, A, n=10, exclude=None):
+    def topN(self, A, n=10, exclude=None, include=None):
         """(ids [nu, n] int32, scores [nu, n]) for every row of ``A``: score = A_u . B_i (+ biasB[i]), descending, ties by
-        lower id, -1 / -inf where fewer than ``n`` items remain; ``exclude`` = (indptr, indices) CSR over the rows of A."""
+        lower id, -1 / -inf where fewer than ``n`` items remain; ``exclude`` = (indptr, indices) CSR over the rows of A.
+        ``include``: candidate lists -- (indptr, indices) CSR over the rows of A, a SciPy CSR matrix, or one 1-D array shared by
+        every user: each user is ranked over its own list only (minus its exclusion list), with the result of the full ranking
+        when every other item is excluded; only the listed rows of the items are read."""
         h = self._live()
         A = np.asarray(A)
         if A.ndim != 2 or A.shape[1] != self.k:
@@ -59,6 +62,12 @@ class Ranker:
         n = int(n)
         ids = np.empty((nu, n), np.int32); sc = np.empty((nu, n), self.dtype)
         ep, ei = _sorted_exclude(exclude, nu)
+        if include is not None:
+            cp, ci = _sorted_include(include, nu)
+            rc = self.lib.cmfrec_hip_ranker_topN_candidates(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(cp), _lib.ptr(ci),
+                                                            _lib.ptr(ep), _lib.ptr(ei), C.c_int(n), _lib.ptr(ids), _lib.ptr(sc))
+            _lib.check(rc, self.lib, "Ranker.topN")
+            return ids, sc
         rc = self.lib.cmfrec_hip_ranker_topN(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
                                              _lib.ptr(ids), _lib.ptr(sc))
         _lib.check(rc, self.lib, "Ranker.topN")
@@ -71,7 +80,8 @@ class Ranker:
         return ms.value
 
     def launch_shape(self):
-        """(users per workgroup, workgroups) of that kernel launch: the items are streamed once per workgroup's users."""
+        """(users per workgroup, workgroups) of that kernel launch: the items are streamed once per workgroup's users.  After a
+        call with ``include``: (wavefronts per workgroup -- each holds one user at a time --, workgroups)."""
         u, g = C.c_int(0), C.c_int(0)
         _lib.check(self.lib.cmfrec_hip_ranker_launch_shape(self._live(), C.byref(u), C.byref(g)), self.lib, "Ranker.launch_shape")
         return u.value, g.value

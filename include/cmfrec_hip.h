@@ -609,6 +609,26 @@ cmfrec_hip_ranker *cmfrec_hip_ranker_create(const real_t *B, size_t ldb, int_t n
 int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
                            const size_t excl_p[], const int_t excl_i[], int_t n_top,
                            int_t *out_ids, real_t *out_scores);
+/* Top-N over per-user candidate lists (the batch form of the reference's include_ix, src/common.c:5134-5260): user u is ranked
+ * over the items of its own list, cand_i[cand_p[u] .. cand_p[u + 1]) (CSR over the nu users, required), and gets exactly what
+ * cmfrec_hip_ranker_topN returns with every item outside the list in the user's exclusion list: the same score, order, tie rule
+ * (lower id first, whatever the order of the list), -1 / -inf filling and limits (code 2 beyond them; cand_p == NULL: code 2).
+ * Each list is ascending and free of duplicates, like the exclusion lists; an unsorted list or one with duplicates gives an
+ * unspecified tie order or a repeated id.  An id outside [0, n) never enters (decided on the device).  A list may be empty, shorter
+ * or longer than n_top.  excl_p / excl_i (optional, as in ranker_topN) may come along -- the reference refuses both on one user,
+ * the batch form takes both: a candidate that is also in the user's exclusion list is dropped.
+ * One wavefront ranks one user at a time from the handle's packed copy of B and gathers only the listed rows (every k <= 272
+ * on the same kernel, topn_cand_kernels.hpp); a score has the value cmfrec_hip_score_pairs returns for the same two rows with
+ * biasA = NULL and glob_mean = 0.  kernel_ms / launch_shape report that kernel after such a call: the wavefronts of a workgroup
+ * (a wavefront holds one user at a time) and the workgroups.  cmfrec_hip_topN_candidates_batch is create, one such call, destroy. */
+int cmfrec_hip_ranker_topN_candidates(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                                      const size_t cand_p[], const int_t cand_i[],
+                                      const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                                      int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                                     const real_t *biasB, const size_t cand_p[], const int_t cand_i[],
+                                     const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                                     int_t *out_ids, real_t *out_scores);
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
@@ -637,6 +657,10 @@ void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
  *   ascending); both: their union.  out_ids / out_scores [rows, n_top]; A / biasA optional outputs -- NULL: the factors never
  *   leave the device.  The ranker is made by the first topN call from the device copy of the items and holds a second, packed
  *   copy of their scored columns (ldb = the ranking kernels' padded width, as in cmfrec_hip_ranker_create).
+ * topN_candidates: topN over each row's candidate list, cand_p / cand_i (CSR over the batch's rows, required, each list ascending
+ *   and free of duplicates), with the semantics of cmfrec_hip_ranker_topN_candidates; exclude_seen and excl_p / excl_i as in topN
+ *   -- a candidate among the row's own items or in its list is dropped.  The batch is solved exactly as in topN; the candidate
+ *   lists are uploaded, nothing else enters or leaves the device.  What topN refuses is refused with the same message.
  * impute: the explicit model's imputation of a dense batch (impute_X_collective_explicit below, without the per-call model work):
  *   solves the batch like factors, then Xout [m, n] = batch->Xfull with every NaN replaced by
  *   A_r . B_c + glob_mean + biasA[r] + biasB[c] from the device factors (columns [k_user, k_user+k+k_main) against the columns of
@@ -683,6 +707,10 @@ int cmfrec_hip_newrows_factors(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_b
 int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, int exclude_seen,
                             const size_t excl_p[], const int_t excl_i[], int_t n_top,
                             int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA);
+int cmfrec_hip_newrows_topN_candidates(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch,
+                                       const size_t cand_p[], const int_t cand_i[], int exclude_seen,
+                                       const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                                       int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *Xout, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, const int_t *row, const int_t *col,
                                size_t n_pairs, real_t *out, real_t *A, real_t *biasA);
