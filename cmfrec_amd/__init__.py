@@ -6,5 +6,6 @@ from . import ops  # noqa: F401
 from .rank import Ranker  # noqa: F401
 from .new_users import NewUsers  # noqa: F401
 from .score import Scorer  # noqa: F401
+from . import metrics  # noqa: F401
 
-__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "NewUsers", "Scorer", "ops"]
+__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "NewUsers", "Scorer", "ops", "metrics"]

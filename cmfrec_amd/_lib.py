@@ -71,9 +71,9 @@ EXPORTED = [
     "factors_collective_explicit_multiple", "factors_collective_implicit_multiple", "cmfrec_hip_factors_multiple", "cmfrec_hip_factors_multiple_l1", "cmfrec_hip_factors_multiple_ex",
     "cmfrec_hip_optimizeA_implicit", "cmfrec_hip_optimizeA_explicit", "cmfrec_hip_optimizeA_explicit_weighted",
     "cmfrec_hip_optimizeA_dense_full", "cmfrec_hip_optimizeA_collective", "cmfrec_hip_optimizeA_collective_sparse", "cmfrec_hip_topN_batch",
-    "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_topN_candidates", "cmfrec_hip_topN_candidates_batch", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
+    "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_topN_candidates", "cmfrec_hip_topN_candidates_batch", "cmfrec_hip_ranker_ranks", "cmfrec_hip_ranks_batch", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
     "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
-    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
+    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
     "cmfrec_hip_session_set_sideinfo", "cmfrec_hip_session_set_sideinfo_local", "cmfrec_hip_session_sideinfo_partial", "cmfrec_hip_session_sideinfo_finish", "cmfrec_hip_session_set_nonneg", "cmfrec_hip_session_set_l1", "cmfrec_hip_session_set_lam_unique", "cmfrec_hip_session_set_scale_bias_const", "cmfrec_hip_session_set_NA_as_zero_X", "cmfrec_hip_session_set_zero_rows", "cmfrec_hip_session_set_closed_form_rows", "cmfrec_hip_session_set_lambda_multipliers", "cmfrec_hip_session_set_implicit_features", "cmfrec_hip_session_get_implicit_features", "cmfrec_hip_session_set_sideinfo_sparse", "cmfrec_hip_session_set_sideinfo_sparse_zeros", "cmfrec_hip_side_zeros_products", "cmfrec_hip_session_update", "cmfrec_hip_session_iterate",
@@ -124,6 +124,8 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_session_create.restype = C.c_void_p
     lib.cmfrec_hip_ranker_create.restype = C.c_void_p
     lib.cmfrec_hip_ranker_destroy.restype = None
+    lib.cmfrec_hip_ranker_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 7
+    lib.cmfrec_hip_ranks_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 8
     nrm = newrows_model_mirror(dtype)
     lib.cmfrec_hip_newrows_create.restype = C.c_void_p
     lib.cmfrec_hip_newrows_create.argtypes = [C.POINTER(nrm), C.c_int]
@@ -132,6 +134,8 @@ def load(dtype=np.float64):
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cmfrec_hip_newrows_topN_candidates.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cmfrec_hip_newrows_ranks.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cmfrec_hip_newrows_impute.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.impute_X_collective_explicit.restype = C.c_int
     lib.cmfrec_hip_impute_dense.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,

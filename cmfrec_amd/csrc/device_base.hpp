@@ -66,6 +66,7 @@ struct Switches {
     bool topn_wide = false;         // CMFREC_HIP_TOPN=wide: the MFMA ranking kernel (topn_wide_kernels.hpp) for every k, not only beyond 64 (cross-check, A/B)
     int topn_tiles = 0;             // CMFREC_HIP_TOPN_TILES: user tiles per workgroup of that kernel, 1..4 (test hook; 0: by shape)
     int topn_cand_waves = 0;        // CMFREC_HIP_TOPN_CAND_WAVES: at most that many wavefronts (rounded up to whole workgroups) in a launch of the candidate-list ranking kernel (topn_cand_kernels.hpp), so that a small batch gives a wavefront several users (test hook; 0: by occupancy)
+    int rank_slice = 0;             // CMFREC_HIP_RANK_SLICE: held-out items per user and pass of the rank kernel (topn_rank_kernels.hpp); test hook; 0: by what fits the LDS
     bool eig_jacobi = false;        // CMFREC_HIP_EIG=jacobi: the one-workgroup Jacobi kernel instead of tridiagonalisation + QL (cross-check)
     int debug_skip = 0;             // CMFREC_HIP_CG_SKIP / _CHOL_SKIP / _WAVE_SKIP (timing builds only: -DCMF_CG_DEBUG / -DCMF_CHOL_DEBUG)
     bool debug_ticks = false;       // CMFREC_HIP_GRAM_TICKS / _CHOL_TICKS (timing builds only)
@@ -94,6 +95,7 @@ struct Switches {
         v = str("CMFREC_HIP_TOPN"); topn_wide = v && strcmp(v, "wide") == 0;
         topn_tiles = num("CMFREC_HIP_TOPN_TILES", 0);
         topn_cand_waves = num("CMFREC_HIP_TOPN_CAND_WAVES", 0);
+        rank_slice = num("CMFREC_HIP_RANK_SLICE", 0);
         v = str("CMFREC_HIP_EIG"); eig_jacobi = v && strcmp(v, "jacobi") == 0;
         debug_skip = num("CMFREC_HIP_CG_SKIP", num("CMFREC_HIP_CHOL_SKIP", num("CMFREC_HIP_WAVE_SKIP", 0)));
         debug_ticks = str("CMFREC_HIP_GRAM_TICKS") != nullptr || str("CMFREC_HIP_CHOL_TICKS") != nullptr;

@@ -1887,6 +1887,36 @@ int cmfrec_hip_newrows_topN_candidates(cmfrec_hip_newrows *h, const cmfrec_hip_n
     return rc;
 }
 
+int cmfrec_hip_newrows_ranks(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, const size_t held_p[], const int_t held_i[],
+                             int exclude_seen, const size_t excl_p[], const int_t excl_i[], int_t *out_rank, real_t *out_scores,
+                             int_t *out_pool, real_t *A, real_t *biasA)
+{
+    const char *fn = "cmfrec_hip_newrows_ranks";
+    if (h == nullptr || batch == nullptr || h->state == nullptr || held_p == nullptr) {
+        cmfhip::g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    const int_t kr = h->mdl.k + h->mdl.k_main;
+    if (int rc = cmfhip::ranker_check_limits(fn, kr, 1, cmfhip::newrows_state_view(h->state).n)) return rc;
+    bool empty = false;
+    if (int rc = newrows_solve(h, batch, A, biasA, &empty)) return rc;
+    if (empty) return 0;
+    const int rc = cmfhip::guarded([&]() {
+        const cmfhip::NewRowsView v = cmfhip::newrows_state_view(h->state);
+        if (h->ranker == nullptr) {
+            h->ranker = cmfhip::ranker_create_from_device(v.dB + h->mdl.k_item, v.ldB, v.n, kr, v.dbiasB, v.device);
+            if (h->ranker == nullptr) return cmfhip::g_last_rc ? cmfhip::g_last_rc : 4;
+        }
+        const size_t *dp = nullptr;
+        const int *di = nullptr;
+        if (int erc = cmfhip::newrows_state_exclusions(h->state, exclude_seen != 0, excl_p, excl_i, &dp, &di)) return erc;
+        return cmfhip::ranker_ranks_device(h->ranker, fn, v.dA + h->mdl.k_user, v.ldA, v.rows, held_p, held_i, dp, di, out_rank,
+                                           out_scores, out_pool);
+    });
+    if (rc == 0) h->ranked = true;
+    return rc;
+}
+
 int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *Xout, real_t *A, real_t *biasA)
 {
     auto bad = [](const char *what) { cmfhip::g_last_error = std::string("cmfrec_hip_newrows_impute: ") + what; return 2; };

@@ -81,6 +81,11 @@ int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, s
 int ranker_topN_candidates_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t cand_p[],
                                   const int_t cand_i[], const size_t *dexcl_p, const int *dexcl_i, int_t n_top, int_t *out_ids,
                                   real_t *out_scores);
+// the ranks of each row's held-out items (host CSR over the nu rows, uploaded here; topn_rank_kernels.hpp); out_rank / out_scores
+// [held_p[nu]], out_pool [nu], the last two optional
+int ranker_ranks_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t held_p[],
+                        const int_t held_i[], const size_t *dexcl_p, const int *dexcl_i, int_t *out_rank, real_t *out_scores,
+                        int_t *out_pool);
 int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n);
 
 // predict_tu.hip: the scoring of chosen (row, col) pairs against operands that are on the device already -- the stream, the

@@ -4,13 +4,15 @@
 //
 // Routing: k <= TOPN_KMAX (64) launches topn_kernel, the kernel of every release so far; beyond that -- or for every k under
 // CMFREC_HIP_TOPN=wide, a cross-check and A/B switch -- topn_wide_kernel (topn_wide_kernels.hpp).  A call with candidate lists
-// (cmfrec_hip_ranker_topN_candidates and its kin) launches topn_cand_kernel (topn_cand_kernels.hpp) for every k.
+// (cmfrec_hip_ranker_topN_candidates and its kin) launches topn_cand_kernel (topn_cand_kernels.hpp) for every k.  A rank call
+// (cmfrec_hip_ranker_ranks and its kin) launches topn_rank_kernel (topn_rank_kernels.hpp) for every k.
 #include <algorithm>
 #include <vector>
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
 #include "topn_cand_kernels.hpp"
+#include "topn_rank_kernels.hpp"
 
 using namespace cmfhip;
 
@@ -26,6 +28,7 @@ struct cmfrec_hip_ranker {
     DevBuf<size_t> cp;                       // candidate lists of a candidate call
     DevBuf<int> ci, corder;                  // ... and the users by descending list length
     DevBuf<unsigned> next;                   // work counter of topn_cand_kernel
+    DevBuf<int> pool;                        // per-user pool of a rank call (its held-out lists use cp / ci, its ranks ids)
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the ranking kernel of the last call
     bool timed = false;
     int last_users = 0, last_grid = 0;       // users per workgroup and workgroups of that launch
@@ -40,6 +43,7 @@ struct cmfrec_hip_ranker {
 namespace {
 
 constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
+constexpr const char *RANK_LIMITS = "needs k <= 272";
 
 // User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
 // unless fewer finish the nu users in fewer or cheaper waves of workgroups.  A workgroup's time per item round is about
@@ -71,6 +75,47 @@ int launch_wide(const cmfrec_hip_ranker::Device &dev, const TopnWideParams<real_
     const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
     const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
     hipLaunchKernelGGL((topn_wide_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
+    return grid;
+}
+
+// User tiles per workgroup and slice length of the rank kernel (DESIGN.md "Ranks of held-out items"): the longest held-out list
+// decides how many passes over the items a tile may need; per tile count the cost of a pass is pick_user_tiles' model.  Among
+// the tile counts the one with the least passes x cost wins, the larger on a tie.  CMFREC_HIP_TOPN_TILES clamps the tiles,
+// CMFREC_HIP_RANK_SLICE the slice (test hooks).  Returns 0 tiles when not even one threshold per user fits (cannot happen for
+// k <= TOPNW_KMAX).
+int pick_rank_shape(int nu, int k, size_t max_held, int num_cus, int *ts, int *tsp, int *blocks_per_cu)
+{
+    const int forced = switches().topn_tiles, slice = switches().rank_slice;
+    int best = 0;
+    double best_cost = 0;
+    for (int nut = 1; nut <= TOPNW_MAX_NUT; nut++) {
+        if (forced > 0 && nut > forced && best > 0) break;
+        int cap = 0;                                                          // the largest padded slice that fits
+        for (int p = 1; p <= TOPNR_TS_MAX && topnr_lds_bytes(nut, k, p, sizeof(real_t)) <= TOPNW_LDS_MAX; p <<= 1) cap = p;
+        if (cap == 0) break;
+        int s = cap;
+        if (slice > 0) s = std::min(s, slice);
+        const int need = (int)std::min<size_t>((size_t)s, std::max<size_t>(max_held, 1));
+        const int pad = topnr_pow2(need);
+        const size_t smem = topnr_lds_bytes(nut, k, pad, sizeof(real_t));
+        const int bpc = (int)std::min<size_t>(TOPNW_LDS_MAX / smem, (size_t)(2048 / TOPNW_TH));
+        const long tiles = ((long)nu + 16 * nut - 1) / (16 * nut), slots = (long)num_cus * bpc;
+        const long share = std::min<long>(bpc, (tiles + num_cus - 1) / num_cus);
+        const double passes = (double)((std::max<size_t>(max_held, 1) + s - 1) / s);
+        const double cost = passes * (double)((tiles + slots - 1) / slots) * share * (nut + 0.5);
+        if (best == 0 || (forced > 0 ? nut <= forced : cost <= best_cost)) { best = nut; best_cost = cost; *ts = need; *tsp = pad; *blocks_per_cu = bpc; }
+    }
+    return best;
+}
+
+template <int NUT>
+int launch_rank(const cmfrec_hip_ranker::Device &dev, const TopnRankParams<real_t> &P, int blocks_per_cu)
+{
+    const size_t smem = topnr_lds_bytes(NUT, P.k, P.tsp, sizeof(real_t));
+    HIP_CHECK(hipFuncSetAttribute((const void *)topn_rank_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
+    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
+    hipLaunchKernelGGL((topn_rank_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
     return grid;
 }
 
@@ -165,6 +210,67 @@ int upload_candidates(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size
     return 0;
 }
 
+// the held-out lists of a call (host CSR over the nu users) into the ranker's buffers; 2 with a message for lists that are not a
+// CSR; *max_held = the longest list
+int upload_held(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size_t held_p[], const int_t held_i[], size_t *max_held)
+{
+    bool bad = held_p == nullptr;
+    size_t longest = 0;
+    for (int_t u = 0; !bad && u < nu; u++) {
+        bad = held_p[u] > held_p[u + 1];
+        if (!bad) longest = std::max(longest, held_p[u + 1] - held_p[u]);
+    }
+    if (bad || longest > (size_t)0x7fffffff || (held_p[nu] > held_p[0] && held_i == nullptr)) {
+        g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    r->cp.upload(held_p, (size_t)nu + 1, r->dev.stream);
+    r->ci.alloc_at_least(std::max<size_t>(held_p[nu], 1));
+    if (held_p[nu] > 0) r->ci.upload(held_i, held_p[nu], r->dev.stream);
+    *max_held = longest;
+    return 0;
+}
+
+// the ranks of nu users whose factors dA [nu, lda], held-out lists (r->cp / r->ci, total entries) and exclusion lists are on the
+// device: the launch, the timing events (around topn_rank_kernel, whose threshold and exclusion steps are part of it) and the
+// download.  Nothing is written to the outputs before the kernel has run.
+int ranks_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, size_t total, size_t max_held, const size_t *dexcl_p,
+                 const int *dexcl_i, int_t *out_rank, real_t *out_scores, int_t *out_pool)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    r->ids.alloc_at_least(std::max<size_t>(total, 1));
+    if (out_scores) r->sc.alloc_at_least(std::max<size_t>(total, 1));
+    if (out_pool) r->pool.alloc_at_least((size_t)nu);
+    TopnRankParams<real_t> P;
+    P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
+    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+    P.held_p = r->cp.ptr; P.held_i = r->ci.ptr;
+    P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+    P.out_rank = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr; P.out_pool = out_pool ? r->pool.ptr : nullptr;
+    int bpc = 1;
+    const int nut = pick_rank_shape(nu, r->k, max_held, dev.num_cus, &P.ts, &P.tsp, &bpc);
+    if (nut == 0) {
+        g_last_error = "cmfrec_hip_ranker_ranks: the model does not fit the rank kernel's LDS";
+        return 2;
+    }
+    HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    switch (nut) {
+    case 1: r->last_grid = launch_rank<1>(dev, P, bpc); break;
+    case 2: r->last_grid = launch_rank<2>(dev, P, bpc); break;
+    case 3: r->last_grid = launch_rank<3>(dev, P, bpc); break;
+    default: r->last_grid = launch_rank<4>(dev, P, bpc); break;
+    }
+    r->last_users = 16 * nut;
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
+    r->timed = true;
+    r->ids.download(out_rank, total, dev.stream);
+    if (out_scores) r->sc.download(out_scores, total, dev.stream);
+    if (out_pool) r->pool.download(out_pool, (size_t)nu, dev.stream);
+    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    return 0;
+}
+
 }  // namespace
 
 static_assert(TOPNC_KMAX == TOPNW_KMAX, "topn_cand_kernel holds a user's row of the widest model in registers");
@@ -256,6 +362,34 @@ int cmfrec_hip_ranker_topN_candidates(cmfrec_hip_ranker *r, const real_t *A, siz
     });
 }
 
+int cmfrec_hip_ranker_ranks(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t held_p[], const int_t held_i[],
+                            const size_t excl_p[], const int_t excl_i[], int_t *out_rank, real_t *out_scores, int_t *out_pool)
+{
+    const char *fn = "cmfrec_hip_ranker_ranks";
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || !A || !held_p || lda < (size_t)r->k || (held_p[nu] > 0 && !out_rank) ||
+            (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        const int k = r->k;
+        size_t max_held = 0;
+        if (int rc = upload_held(r, fn, nu, held_p, held_i, &max_held)) return rc;
+        r->A.alloc_at_least((size_t)nu * k);
+        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        if (excl_p) {
+            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
+            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
+            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
+        }
+        return ranks_device(r, r->A.ptr, (size_t)k, nu, held_p[nu], max_held, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr,
+                            out_rank, out_scores, out_pool);
+    });
+}
+
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms)
 {
     return guarded([&]() {
@@ -325,6 +459,25 @@ int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, cons
     return rc;
 }
 
+int cmfrec_hip_ranks_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB,
+                           const size_t held_p[], const int_t held_i[], const size_t excl_p[], const int_t excl_i[],
+                           int_t *out_rank, real_t *out_scores, int_t *out_pool)
+{
+    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B || !held_p) {
+        g_last_error = "cmfrec_hip_ranks_batch: invalid arguments";
+        return 2;
+    }
+    if (k > TOPNW_KMAX) {
+        g_last_error = std::string("cmfrec_hip_ranks_batch: ") + RANK_LIMITS;
+        return 2;
+    }
+    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
+    if (r == nullptr) return g_last_rc;
+    const int rc = cmfrec_hip_ranker_ranks(r, A, lda, nu, held_p, held_i, excl_p, excl_i, out_rank, out_scores, out_pool);
+    cmfrec_hip_ranker_destroy(r);
+    return rc;
+}
+
 }  // extern "C"
 
 namespace cmfhip {
@@ -373,6 +526,23 @@ int ranker_topN_candidates_device(cmfrec_hip_ranker *r, const char *fn, const re
         switches_mut().reload();
         if (int rc = upload_candidates(r, fn, nu, cand_p, cand_i)) return rc;
         return rank_device(r, dA, lda, nu, dexcl_p, dexcl_i, n_top, out_ids, out_scores, r->cp.ptr, r->ci.ptr);
+    });
+}
+
+int ranker_ranks_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, size_t lda, int_t nu, const size_t held_p[],
+                        const int_t held_i[], const size_t *dexcl_p, const int *dexcl_i, int_t *out_rank, real_t *out_scores,
+                        int_t *out_pool)
+{
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || !dA || !held_p || lda < (size_t)r->k || (held_p[nu] > 0 && !out_rank)) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        size_t max_held = 0;
+        if (int rc = upload_held(r, fn, nu, held_p, held_i, &max_held)) return rc;
+        return ranks_device(r, dA, lda, nu, held_p[nu], max_held, dexcl_p, dexcl_i, out_rank, out_scores, out_pool);
     });
 }
 

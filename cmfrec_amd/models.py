@@ -92,6 +92,13 @@ class ModelRanker:
             ids, sc = self._ranker.topN(A, n=n, exclude=excl, include=include)
         return ids, self._model._finish_scores(users, sc)
 
+    def ranks(self, users, heldout, exclude=None):
+        """(indptr, items, ranks, pool) as ``Ranker.ranks`` for user ids of the fitted model: ``heldout`` = (indptr, indices) CSR
+        over the users OF THIS CALL (one list per entry of ``users``) or a SciPy CSR matrix of that many rows; ``exclude`` as in
+        ``topN``, over all users of the model."""
+        users, A, excl = _topN_inputs(self._model, users, exclude)
+        return self._ranker.ranks(A, heldout, exclude=excl)
+
     def kernel_ms(self):
         return self._ranker.kernel_ms()
 
@@ -103,6 +110,69 @@ class ModelRanker:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _ranks(self, users, heldout, exclude, biasB):
+    """Shared body of ``CMF.ranks_batch`` / ``CMF_implicit.ranks_batch``."""
+    from . import ops
+    _, A, excl = _topN_inputs(self, users, exclude)
+    B = np.ascontiguousarray(self.B_[:, self.k_item:])
+    return ops.ranks_batch(A, B, heldout, biasB=biasB, exclude=excl)
+
+
+def _csr_rows(M, users, m, what):
+    """(indptr int64, indices) of the rows ``users`` of a CSR over all ``m`` users: a SciPy sparse matrix or (indptr, indices)."""
+    if hasattr(M, "tocsr"):
+        M = M.tocsr()
+    ip, ix = (M.indptr, M.indices) if hasattr(M, "indptr") else M
+    ip = np.asarray(ip, np.int64); ix = np.asarray(ix)
+    if len(ip) != m + 1:
+        raise ValueError("%s must have one row per user of the model (%d), got %d" % (what, m, len(ip) - 1))
+    lens = ip[users + 1] - ip[users]
+    out = np.zeros(len(users) + 1, np.int64)
+    out[1:] = np.cumsum(lens)
+    take = np.repeat(ip[users] - out[:-1], lens) + np.arange(out[-1])
+    return out, ix[take]
+
+
+def _evaluate_ranking(self, X_test, X_train, k, users, batch_users):
+    """Shared body of ``evaluate_ranking``: the users with held-out items, in batches, through one ``ModelRanker``."""
+    from .metrics import METRICS, ranking_metrics
+    m = self.A_.shape[0]
+    if hasattr(X_test, "tocsr"):
+        X_test = X_test.tocsr()
+    tp = np.asarray(X_test.indptr if hasattr(X_test, "indptr") else X_test[0], np.int64)
+    if len(tp) != m + 1:
+        raise ValueError("X_test must have one row per user of the model (%d), got %d" % (m, len(tp) - 1))
+    todo = np.flatnonzero(np.diff(tp) > 0) if users is None else np.unique(np.atleast_1d(np.asarray(users, np.int64)))
+    todo = todo[tp[todo + 1] > tp[todo]]
+    batch_users = max(1, int(batch_users))
+    sums = dict.fromkeys(METRICS, 0.); counts = dict.fromkeys(METRICS, 0)
+    scored = 0
+    if len(todo):
+        with self.ranker() as rk:
+            for s in range(0, len(todo), batch_users):
+                ub = todo[s:s + batch_users]
+                excl = None if X_train is None else _csr_rows(X_train, ub, m, "X_train")
+                ip, _, ranks, pool = rk._ranker.ranks(np.ascontiguousarray(self.A_[ub][:, self.k_user:]),
+                                                      _csr_rows(X_test, ub, m, "X_test"), exclude=excl)
+                per = ranking_metrics(ip, ranks, pool, k=k)
+                scored += int((per["T"] > 0).sum())
+                for name in METRICS:
+                    good = ~np.isnan(per[name])
+                    sums[name] += float(per[name][good].sum()); counts[name] += int(good.sum())
+    res = {name: (sums[name] / counts[name] if counts[name] else float("nan")) for name in METRICS}
+    res["users"] = scored
+    return res
+
+
+_EVALUATE_DOC = """Ranking quality on held-out interactions, ranked on the device: ``X_test`` (SciPy sparse matrix or
+        (indptr, indices) CSR over all users of the model) holds each user's held-out items; ``X_train`` (same forms, optional)
+        the items to leave out of each user's ranking -- with None nothing is excluded.  The users that have held-out items
+        (among ``users`` if given) go through one ``ranker()`` in batches of ``batch_users``; the ranks of their held-out items
+        (``Ranker.ranks``) become ``cmfrec_amd.metrics.ranking_metrics`` at cut-off ``k``.  Returns a dict: the means over the
+        users of hit, precision, recall, ap, ndcg (at k), rr, auc, mean_rank, and ``users``, the number of users scored (a user
+        whose held-out items are all excluded or unrankable counts for nothing)."""
 
 
 def _scorer(self, biasA, biasB, glob_mean, implicit):
@@ -373,6 +443,16 @@ class CMF_implicit(_Base):
         SciPy CSR matrix of that many rows, or one 1-D array shared by all: each user is ranked over its own list only."""
         return _topN(self, users, n, exclude, None, include)
 
+    def ranks_batch(self, users, heldout, exclude=None):
+        """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by A_u . B_i, counted
+        on the GPU (``ops.ranks_batch``).  ``heldout``: (indptr, indices) CSR over the users OF THIS CALL or a SciPy CSR matrix
+        of that many rows; ``exclude``: CSR over all users, as in ``topN_batch``."""
+        return _ranks(self, users, heldout, exclude, None)
+
+    def evaluate_ranking(self, X_test, X_train=None, k=10, users=None, batch_users=4096):
+        return _evaluate_ranking(self, X_test, X_train, k, users, batch_users)
+    evaluate_ranking.__doc__ = _EVALUATE_DOC
+
     def _finish_scores(self, users, sc):
         return sc
 
@@ -624,6 +704,16 @@ class CMF(_Base):
         one 1-D array shared by all: each user is ranked over its own list only."""
         ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None, include)
         return ids, self._finish_scores(np.atleast_1d(np.asarray(users, np.int64)), sc)
+
+    def ranks_batch(self, users, heldout, exclude=None):
+        """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by
+        A_u . B_i + item_bias[i], counted on the GPU (``ops.ranks_batch``).  ``heldout``: (indptr, indices) CSR over the users
+        OF THIS CALL or a SciPy CSR matrix of that many rows; ``exclude``: CSR over all users, as in ``topN_batch``."""
+        return _ranks(self, users, heldout, exclude, self.item_bias_ if self.item_bias else None)
+
+    def evaluate_ranking(self, X_test, X_train=None, k=10, users=None, batch_users=4096):
+        return _evaluate_ranking(self, X_test, X_train, k, users, batch_users)
+    evaluate_ranking.__doc__ = _EVALUATE_DOC
 
     def _finish_scores(self, users, sc):
         sc = sc + self.glob_mean_

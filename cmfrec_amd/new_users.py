@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _sorted_exclude, _sorted_include
+from .ops import _heldout_lists, _sorted_exclude, _sorted_include
 
 
 def _has(M):
@@ -162,6 +162,28 @@ class NewUsers:
         if return_factors:
             return ids, sc, (A, bias)
         return ids, sc
+
+    def ranks(self, X=None, U=None, W=None, heldout=None, exclude_seen=True, exclude=None, return_factors=False):
+        """(indptr, items, ranks, pool) for the rows of the batch and their held-out lists, as ``Ranker.ranks`` on the factors the
+        batch run leaves on the device: ``heldout`` = (indptr, indices) CSR over the rows of the batch or a SciPy CSR matrix.
+        ``exclude_seen`` / ``exclude`` as in ``topN``: a held-out item among the row's own items of ``X`` or in its list gets -1.
+        ``return_factors``: a fifth value, ``(A, bias)`` as ``factors(..., return_bias=True)`` returns them."""
+        h = self._live()
+        s, keep, rows = self._batch(X, U, W)
+        hp, hi = _heldout_lists(heldout, rows, "NewUsers.ranks")
+        if exclude is not None and hasattr(exclude, "indptr"):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, rows)
+        ranks = np.empty(len(hi), np.int32); pool = np.empty(rows, np.int32)
+        A = np.empty((rows, self.width), self.dtype) if return_factors else None
+        bias = np.empty(rows, self.dtype) if (self.has_bias and return_factors) else None
+        rc = self.lib.cmfrec_hip_newrows_ranks(h, C.byref(s), _lib.ptr(hp), _lib.ptr(hi), C.c_int(1 if exclude_seen else 0), _lib.ptr(ep),
+                                               _lib.ptr(ei), _lib.ptr(ranks), None, _lib.ptr(pool), _lib.ptr(A), _lib.ptr(bias))
+        _lib.check(rc, self.lib, "NewUsers.ranks")
+        del keep
+        if return_factors:
+            return hp.astype(np.int64), hi, ranks, pool, (A, bias)
+        return hp.astype(np.int64), hi, ranks, pool
 
     def impute(self, X, U=None, W=None, return_factors=False):
         """A new array: the dense ``X`` [m, n] with every NaN replaced by the model's prediction for that user and item (reference

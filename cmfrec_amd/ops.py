@@ -258,6 +258,47 @@ def topN_batch(A, B, n_top=10, biasB=None, exclude=None, include=None):
     return ids, sc
 
 
+def _heldout_lists(heldout, nu, what):
+    """The held-out lists of a rank call through ``_sorted_include`` (ascending, unique, ids outside int32 -> -1)."""
+    if heldout is None:
+        raise ValueError("%s: 'heldout' is required: (indptr, indices) CSR over the users or a SciPy CSR matrix" % what)
+    if _is_csr(heldout):
+        heldout = (heldout.indptr, heldout.indices)
+    if not (isinstance(heldout, (tuple, list)) and len(heldout) == 2):
+        raise ValueError("%s: 'heldout' must be (indptr, indices) or a SciPy CSR matrix" % what)
+    return _sorted_include(heldout, nu)
+
+
+def _is_csr(x):
+    return hasattr(x, "indptr") and hasattr(x, "indices")
+
+
+def ranks_batch(A, B, heldout, biasB=None, exclude=None):
+    """(indptr, items, ranks, pool): for every row of ``A`` and every item of its held-out list, the 0-based place the item
+    holds in the user's full ranking by score = A_u . B_i (+ biasB[i]) (descending, ties by lower id) -- the number of items
+    that are not in the user's ``exclude`` list, do not score NaN and come before it.  ``heldout``: (indptr, indices) CSR over
+    the rows of ``A`` or a SciPy CSR matrix, sorted and de-duplicated here; ``indptr`` / ``items`` are the normalised lists the
+    ``ranks`` (int32) line up with.  A rank is -1 for an item outside the items, in the user's exclusion list, or with a NaN
+    score.  ``pool`` [nu] int32: the items of each user's ranking.  ``cmfrec_amd.metrics.ranking_metrics`` turns these into
+    hit / precision / recall / AP / NDCG at k, reciprocal rank, AUC and mean rank.  Every width the library fits (k <= 272).
+    B is uploaded on every call: to rank several batches against the same items, hold a ``cmfrec_amd.Ranker``."""
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B, A.dtype)
+    lib, R = _prep(A, B)
+    nu, lda = A.shape
+    n, ldb = B.shape
+    hp, hi = _heldout_lists(heldout, nu, "ranks_batch")
+    if exclude is not None and _is_csr(exclude):
+        exclude = (exclude.indptr, exclude.indices)
+    ep, ei = _sorted_exclude(exclude, nu)
+    bs = None if biasB is None else np.ascontiguousarray(biasB, A.dtype)
+    ranks = np.empty(len(hi), np.int32); pool = np.empty(nu, np.int32)
+    rc = lib.cmfrec_hip_ranks_batch(_lib.ptr(A), C.c_size_t(lda), C.c_int(nu), _lib.ptr(B), C.c_size_t(ldb), C.c_int(n),
+                                    C.c_int(lda), _lib.ptr(bs), _lib.ptr(hp), _lib.ptr(hi), _lib.ptr(ep), _lib.ptr(ei),
+                                    _lib.ptr(ranks), None, _lib.ptr(pool))
+    _lib.check(rc, lib, "ranks_batch")
+    return hp.astype(np.int64), hi, ranks, pool
+
+
 DENSE_OPS = {"gemm": 0, "gemm_ta": 1, "gram": 2, "potrf": 3, "trtri": 4, "potrs_rows": 5}
 
 

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _sorted_exclude, _sorted_include
+from .ops import _heldout_lists, _is_csr, _sorted_exclude, _sorted_include
 
 
 class Ranker:
@@ -73,8 +73,37 @@ class Ranker:
         _lib.check(rc, self.lib, "Ranker.topN")
         return ids, sc
 
+    def ranks(self, A, heldout, exclude=None, return_scores=False):
+        """(indptr, items, ranks, pool) for the rows of ``A`` and their held-out lists, as ``ops.ranks_batch``: ``ranks[j]`` is
+        the 0-based place of ``items[j]`` in its user's full ranking (-1: outside the items, excluded, or a NaN score), ``pool``
+        the number of items of each user's ranking.  Under ``CMFREC_HIP_TOPN=wide`` (and for every k > 64)
+        ``topN(A, n, exclude)[0][u, rank] == item`` wherever ``rank < n``, with the same score bits; against the default top-N
+        kernel of k <= 64 the two agree up to rounding.  ``return_scores``: a fifth value, the items' scores (NaN where the
+        rank is -1)."""
+        h = self._live()
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[1] != self.k:
+            raise ValueError("Ranker.ranks: A must be [users, %d], got shape %s" % (self.k, A.shape))
+        if A.dtype != self.dtype:
+            raise ValueError("Ranker.ranks: A is %s, the ranker's items are %s" % (A.dtype, self.dtype))
+        A = np.ascontiguousarray(A)
+        nu = A.shape[0]
+        hp, hi = _heldout_lists(heldout, nu, "Ranker.ranks")
+        if exclude is not None and _is_csr(exclude):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, nu)
+        ranks = np.empty(len(hi), np.int32); pool = np.empty(nu, np.int32)
+        sc = np.empty(len(hi), self.dtype) if return_scores else None
+        rc = self.lib.cmfrec_hip_ranker_ranks(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(hp), _lib.ptr(hi), _lib.ptr(ep),
+                                              _lib.ptr(ei), _lib.ptr(ranks), _lib.ptr(sc), _lib.ptr(pool))
+        _lib.check(rc, self.lib, "Ranker.ranks")
+        if return_scores:
+            return hp.astype(np.int64), hi, ranks, pool, sc
+        return hp.astype(np.int64), hi, ranks, pool
+
     def kernel_ms(self):
-        """HIP-event time (ms) of the ranking kernel of the most recent ``topN`` call."""
+        """HIP-event time (ms) of the ranking kernel of the most recent ``topN`` or ``ranks`` call (of ``ranks``: the whole rank
+        kernel, its threshold and exclusion steps included)."""
         ms = C.c_double(0)
         _lib.check(self.lib.cmfrec_hip_ranker_kernel_ms(self._live(), C.byref(ms)), self.lib, "Ranker.kernel_ms")
         return ms.value

@@ -629,6 +629,31 @@ int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, cons
                                      const real_t *biasB, const size_t cand_p[], const int_t cand_i[],
                                      const size_t excl_p[], const int_t excl_i[], int_t n_top,
                                      int_t *out_ids, real_t *out_scores);
+/* Ranks of held-out items: for user u and every t of its held-out list held_i[held_p[u] .. held_p[u + 1]) (CSR over the nu users,
+ * required, held_p[0] = 0; each list ascending and free of duplicates),
+ *   out_rank = #{ i in [0, n) : i not in the user's exclusion list, score(u, i) not NaN, score(u, i) before score(u, t) }
+ * in the order of cmfrec_hip_ranker_topN (higher score first, then lower id): the 0-based place of t in the user's full ranking;
+ * the user's other held-out items count like any item.  out_rank = -1 where t is outside [0, n), in the user's exclusion list,
+ * or scores NaN (decided on the device).  out_scores (optional) [held_p[nu]]: score(u, t), NaN where out_rank = -1.  out_pool
+ * (optional) [nu]: the number of items of the user's ranking (not excluded, not NaN).  No n_top limit: every place up to n - 1
+ * is counted.  excl_p / excl_i as in ranker_topN (each list ascending; a repeated id counts once).
+ * One pass over the items per workgroup of 16..64 users on the MFMA, as the wide top-N kernel (topn_rank_kernels.hpp), for every
+ * k <= 272; a user with more held-out items than one pass holds (by what fits the LDS, 1024 at the most) costs its workgroup
+ * further passes.  A score has the bits the wide top-N kernel gives the pair: with CMFREC_HIP_TOPN=wide,
+ * topN(...)[u, out_rank] == t and the scores are equal bit for bit wherever out_rank < n_top; against the default top-N kernel
+ * of k <= 64 the two agree up to rounding (a near tie may swap neighbours).  All results are integer counts and do not depend on
+ * the launch shape.  Code 2 when held_p == NULL (and, for ranks_batch, k > 272); the outputs are then untouched.
+ * kernel_ms / launch_shape report the rank kernel after such a call (its threshold and exclusion steps included): users per
+ * workgroup and workgroups.  Top-N, candidate and rank calls may be interleaved on one handle.
+ * cmfrec_hip_ranks_batch is create, one such call, destroy. */
+int cmfrec_hip_ranker_ranks(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                            const size_t held_p[], const int_t held_i[],
+                            const size_t excl_p[], const int_t excl_i[],
+                            int_t *out_rank, real_t *out_scores, int_t *out_pool);
+int cmfrec_hip_ranks_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                           const real_t *biasB, const size_t held_p[], const int_t held_i[],
+                           const size_t excl_p[], const int_t excl_i[],
+                           int_t *out_rank, real_t *out_scores, int_t *out_pool);
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
@@ -661,6 +686,10 @@ void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
  *   and free of duplicates), with the semantics of cmfrec_hip_ranker_topN_candidates; exclude_seen and excl_p / excl_i as in topN
  *   -- a candidate among the row's own items or in its list is dropped.  The batch is solved exactly as in topN; the candidate
  *   lists are uploaded, nothing else enters or leaves the device.  What topN refuses is refused with the same message.
+ * ranks: the ranks of each row's held-out items held_p / held_i (CSR over the batch's rows, required), with the semantics of
+ *   cmfrec_hip_ranker_ranks; exclude_seen and excl_p / excl_i as in topN -- a held-out item among the row's own items or in its
+ *   list gets -1.  The batch is solved exactly as in topN; the held-out lists go up, out_rank / out_scores [held_p[rows]] and
+ *   out_pool [rows] (the last two optional) come down.  What topN refuses is refused with the same message.
  * impute: the explicit model's imputation of a dense batch (impute_X_collective_explicit below, without the per-call model work):
  *   solves the batch like factors, then Xout [m, n] = batch->Xfull with every NaN replaced by
  *   A_r . B_c + glob_mean + biasA[r] + biasB[c] from the device factors (columns [k_user, k_user+k+k_main) against the columns of
@@ -711,6 +740,10 @@ int cmfrec_hip_newrows_topN_candidates(cmfrec_hip_newrows *h, const cmfrec_hip_n
                                        const size_t cand_p[], const int_t cand_i[], int exclude_seen,
                                        const size_t excl_p[], const int_t excl_i[], int_t n_top,
                                        int_t *out_ids, real_t *out_scores, real_t *A, real_t *biasA);
+int cmfrec_hip_newrows_ranks(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch,
+                             const size_t held_p[], const int_t held_i[], int exclude_seen,
+                             const size_t excl_p[], const int_t excl_i[],
+                             int_t *out_rank, real_t *out_scores, int_t *out_pool, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *Xout, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, const int_t *row, const int_t *col,
                                size_t n_pairs, real_t *out, real_t *A, real_t *biasA);
