@@ -5,7 +5,7 @@ from .session import AlsSession  # noqa: F401
 from . import ops  # noqa: F401
 from .rank import Ranker  # noqa: F401
 from .new_users import NewUsers  # noqa: F401
-from .score import Scorer  # noqa: F401
+from .score import EvalSet, Scorer  # noqa: F401
 from . import metrics  # noqa: F401
 
-__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "NewUsers", "Scorer", "ops", "metrics"]
+__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "NewUsers", "Scorer", "EvalSet", "ops", "metrics"]

@@ -62,6 +62,18 @@ class NewRowsBatch(C.Structure):
                 ("Xfull", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class Errors(C.Structure):
+    """``cmfrec_hip_errors`` (include/cmfrec_hip.h): the same layout in both precisions."""
+    _fields_ = [("n", C.c_uint64 * 2), ("n_skipped", C.c_uint64)] + \
+        [(n, C.c_double * 2) for n in ("sum_w", "sum_we", "sum_wabs", "sum_wsq", "max_abs")]
+
+    def as_dict(self):
+        out = {"n": np.array(self.n[:], np.uint64), "n_skipped": np.uint64(self.n_skipped)}
+        for name in ("sum_w", "sum_we", "sum_wabs", "sum_wsq", "max_abs"):
+            out[name] = np.array(getattr(self, name)[:], np.float64)
+        return out
+
+
 def newrows_model_mirror(dtype):
     return NewRowsModel if np.dtype(dtype) == np.float64 else NewRowsModelF
 
@@ -73,6 +85,7 @@ EXPORTED = [
     "cmfrec_hip_optimizeA_dense_full", "cmfrec_hip_optimizeA_collective", "cmfrec_hip_optimizeA_collective_sparse", "cmfrec_hip_topN_batch",
     "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_topN_candidates", "cmfrec_hip_topN_candidates_batch", "cmfrec_hip_ranker_ranks", "cmfrec_hip_ranks_batch", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
     "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
+    "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
     "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
@@ -152,6 +165,15 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_scorer_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.cmfrec_hip_scorer_destroy.restype = None
     lib.cmfrec_hip_scorer_destroy.argtypes = [C.c_void_p]
+    lib.cmfrec_hip_evalset_create.restype = C.c_void_p
+    lib.cmfrec_hip_evalset_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    lib.cmfrec_hip_evalset_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.cmfrec_hip_evalset_launch_waves.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    lib.cmfrec_hip_evalset_destroy.restype = None
+    lib.cmfrec_hip_evalset_destroy.argtypes = [C.c_void_p]
+    lib.cmfrec_hip_scorer_errors.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Errors)]
+    lib.cmfrec_hip_session_errors.argtypes = [C.c_void_p, C.c_void_p, R, C.POINTER(Errors)]
+    lib.cmfrec_hip_pair_errors.argtypes = lib.cmfrec_hip_score_pairs.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Errors)]
     for name in EXPORTED_OTHER[1:]:
         getattr(lib, name).restype = C.c_int
     lib.cmfrec_hip_newrows_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]

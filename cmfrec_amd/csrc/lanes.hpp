@@ -93,32 +93,33 @@ template <typename T> __device__ __forceinline__ T recv_xor8(T a, T b)
     return map2(a, b, [](int x, int y) { int t = dpp_new<ROW_ROR8, 0x3>(x); return dpp<ROW_ROR8, 0xC>(t, y); });
 }
 
-// result: lanes < 32 : a[l] + a[l+32] ;  lanes >= 32 : b[l-32] + b[l]
-template <typename T> __device__ __forceinline__ T tswap32_add(T a, T b);
-template <> __device__ __forceinline__ float tswap32_add(float a, float b)
+// the two values a permlane swap leaves in a lane, combined by op (a sum, a maximum, ...):
+// result: lanes < 32 : op(a[l], a[l+32]) ;  lanes >= 32 : op(b[l-32], b[l])
+template <typename Op> __device__ __forceinline__ float tswap32_op(float a, float b, Op op)
 {
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    return op(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-template <> __device__ __forceinline__ double tswap32_add(double a, double b)
+template <typename Op> __device__ __forceinline__ double tswap32_op(double a, double b, Op op)
 {
     auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
     auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+    return op(__hiloint2double((int)hi[0], (int)lo[0]), __hiloint2double((int)hi[1], (int)lo[1]));
 }
-// result: lanes with (lane&16)==0 : a[l] + a[l+16] ;  others : b[l-16] + b[l]
-template <typename T> __device__ __forceinline__ T tswap16_add(T a, T b);
-template <> __device__ __forceinline__ float tswap16_add(float a, float b)
+// result: lanes with (lane&16)==0 : op(a[l], a[l+16]) ;  others : op(b[l-16], b[l])
+template <typename Op> __device__ __forceinline__ float tswap16_op(float a, float b, Op op)
 {
     auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    return op(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-template <> __device__ __forceinline__ double tswap16_add(double a, double b)
+template <typename Op> __device__ __forceinline__ double tswap16_op(double a, double b, Op op)
 {
     auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
     auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+    return op(__hiloint2double((int)hi[0], (int)lo[0]), __hiloint2double((int)hi[1], (int)lo[1]));
 }
+template <typename T> __device__ __forceinline__ T tswap32_add(T a, T b) { return tswap32_op(a, b, [](T x, T y) { return x + y; }); }
+template <typename T> __device__ __forceinline__ T tswap16_add(T a, T b) { return tswap16_op(a, b, [](T x, T y) { return x + y; }); }
 
 // value of lane ((lane & ~7) | t) for every lane (t compile-time): two row_newbcast moves, one per half of the 16-lane row
 // (bank masks 0x3 / 0xC).  A double moves as ONE v_mov_b64_dpp per half -- row_newbcast is the one DPP control the 64-bit move
@@ -153,18 +154,30 @@ template <typename T> __device__ __forceinline__ T qxor4(T x)
 #endif
 }
 
+// all 64 lanes combined by op, identical on every lane: op is commutative bit for bit (a sum, a maximum, an integer sum of
+// counts that travel as a double's two dwords), so every level leaves the same bits in both partner lanes -- which is also what
+// lets the third level use qxor4
+template <typename T, typename Op> __device__ __forceinline__ T wave_fold(T v, Op op)
+{
+    v = op(v, xor1(v));
+    v = op(v, xor2(v));
+    v = op(v, qxor4(v));
+    v = op(v, xor8(v));
+    v = tswap16_op(v, v, op);
+    v = tswap32_op(v, v, op);
+    return v;
+}
 // full wave sum, identical on every lane
 // (tried in round 4: rows 1 / 3 adding lane 15 of the row below, rows 2 / 3 lane 31 -- the row_bcast controls -- and v_readlane 63:
 //  the compiler does not fold the masked move into the add, 801 -> 815 vector instructions in the fp32 tiny kernel; not kept)
-template <typename T> __device__ __forceinline__ T wave_sum(T v)
+template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_fold(v, [](T x, T y) { return x + y; }); }
+// a 64-bit count: moved as a double (the moves do not look at the bits), added as an integer
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 {
-    v += xor1(v);
-    v += xor2(v);
-    v += qxor4(v);
-    v += xor8(v);
-    v = tswap16_add(v, v);
-    v = tswap32_add(v, v);
-    return v;
+    auto add = [](double a, double b) {
+        return __longlong_as_double((long long)((unsigned long long)__double_as_longlong(a) + (unsigned long long)__double_as_longlong(b)));
+    };
+    return (unsigned long long)__double_as_longlong(wave_fold(__longlong_as_double((long long)v), add));
 }
 
 }  // namespace lanes

@@ -100,4 +100,12 @@ int pair_scorer_run(PairScorer *ps, const real_t *dA, size_t lda, int_t m, const
                     size_t n_pairs, real_t *out);
 double pair_scorer_ms(const PairScorer *ps);               // the kernel over the blocks of the last run
 
+// predict_tu.hip: the error record of a resident evaluation set (cmfrec_hip_evalset_*) against operands that are on the device
+// already, with pair_scorer_run's operand arguments: the two kernels on stream st behind what is queued there, one
+// synchronisation, the record in *out.  device / num_cus: the operands' device (the set must live there, otherwise 2 with fn's
+// name in the message).  dpred: the predictions too ([n_pairs] on the device), or null.  Throws HipError.
+int evalset_run(cmfrec_hip_evalset *e, const char *fn, int device, int num_cus, hipStream_t st, const real_t *dA, size_t lda, int_t m,
+                const real_t *dbiasA, size_t ldbiasA, const real_t *dB, size_t ldb, int_t n, int_t kk, const real_t *dbiasB, real_t glob_mean,
+                bool implicit, real_t *dpred, cmfrec_hip_errors *out);
+
 }  // namespace cmfhip

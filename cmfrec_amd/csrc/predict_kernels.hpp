@@ -1,6 +1,7 @@
 // predict_kernels.hpp -- the predicted value of chosen (row, col) pairs: score_pairs_kernel and its launch helper
 // launch_score_pairs, the one way to it (cmfrec_hip_score_pairs, the scorer handle, cmfrec_hip_newrows_predict and the four
-// predict_X_* names: predict_tu.hip).  DESIGN.md section 3.8.
+// predict_X_* names: predict_tu.hip).  DESIGN.md section 3.8.  The kernel's loop is score_chunks, which score_errors_kernel
+// (predict_error_kernels.hpp) runs too: "stores" below is the epilogue of this kernel, ScoreStore.
 //
 //   explicit:  row in [0, m) and col in [0, n):  a . b + biasA[row] + biasB[col] + glob_mean   (a missing bias adds nothing)
 //              otherwise:                        glob_mean + (biasA[row] if row in [0, m)) + (biasB[col] if col in [0, n))
@@ -89,13 +90,19 @@ __device__ __forceinline__ T score_group_sum(T v)
     return v;
 }
 
-template <typename T, int G, bool VA, bool VB>
-__global__ __launch_bounds__(SCORE_TH) void score_pairs_kernel(const ScoreParams<T> P)
+// The wavefront's loop over its chunks of (64 / G) * SCORE_STEPS pairs, shared by score_pairs_kernel and score_errors_kernel
+// (predict_error_kernels.hpp): the prediction of a pair is the same code in both.  What happens to it is the epilogue's business:
+//   epi.begin(u, i, mine)    before the index loads of step u are waited for; mine: this lane is lane 0 of the group of the live pair i
+//   epi.middle(u, i, mine)   after the last round's arithmetic, in front of the butterflies (the registers of the pieces are free again)
+//   epi.end(u, i, ok, res)   on that lane alone, after the butterfly: ok = the pair is inside the model, res = its prediction
+// Returns the wavefront's index and the number of wavefronts of the launch through wave / nwaves.
+template <typename T, int G, bool VA, bool VB, typename Epi>
+__device__ __forceinline__ void score_chunks(const ScoreParams<T> &P, Epi &epi, size_t &wave, size_t &nwaves)
 {
     constexpr int Ve = 16 / (int)sizeof(T), PS = 64 / G, U = SCORE_STEPS;
     const int lane = threadIdx.x & 63, g = lane & (G - 1), sub = lane / G;
-    const size_t wave = (size_t)blockIdx.x * (SCORE_TH / 64) + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const size_t nwaves = (size_t)gridDim.x * (SCORE_TH / 64);
+    wave = (size_t)blockIdx.x * (SCORE_TH / 64) + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    nwaves = (size_t)gridDim.x * (SCORE_TH / 64);
     constexpr size_t per_chunk = (size_t)PS * U;
     const size_t chunks = (P.n_pairs + per_chunk - 1) / per_chunk;
     const int kk = P.kk;
@@ -113,6 +120,7 @@ __global__ __launch_bounds__(SCORE_TH) void score_pairs_kernel(const ScoreParams
             live[u] = pr[u] < P.n_pairs;
             rr[u] = live[u] ? P.row[pr[u]] : -1;
             cc[u] = live[u] ? P.col[pr[u]] : -1;
+            epi.begin(u, pr[u], g == 0 && live[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
@@ -149,6 +157,8 @@ __global__ __launch_bounds__(SCORE_TH) void score_pairs_kernel(const ScoreParams
                 }
         }
 #pragma unroll
+        for (int u = 0; u < U; u++) epi.middle(u, pr[u], g == 0 && live[u]);
+#pragma unroll
         for (int u = 0; u < U; u++) {
             const T dot = score_group_sum<G>(acc[u]);
             if (g == 0 && live[u]) {
@@ -167,10 +177,26 @@ __global__ __launch_bounds__(SCORE_TH) void score_pairs_kernel(const ScoreParams
                     if (P.biasA && rr[u] >= 0 && rr[u] < P.m) res += ba[u];
                     if (P.biasB && cc[u] >= 0 && cc[u] < P.n) res += bb[u];
                 }
-                P.out[pr[u]] = res;
+                epi.end(u, pr[u], ok[u], res);
             }
         }
     }
+}
+
+template <typename T>
+struct ScoreStore {
+    T *out;
+    __device__ __forceinline__ void begin(int, size_t, bool) {}
+    __device__ __forceinline__ void middle(int, size_t, bool) {}
+    __device__ __forceinline__ void end(int, size_t i, bool, T res) { out[i] = res; }
+};
+
+template <typename T, int G, bool VA, bool VB>
+__global__ __launch_bounds__(SCORE_TH) void score_pairs_kernel(const ScoreParams<T> P)
+{
+    ScoreStore<T> epi{P.out};
+    size_t wave, nwaves;
+    score_chunks<T, G, VA, VB>(P, epi, wave, nwaves);
 }
 
 // grid-stride launch: as many workgroups as are resident at once (by the kernel's own register use: 5 to 7 wavefronts per SIMD),

@@ -1,11 +1,14 @@
 // predict_tu.hip -- predictions for chosen (row, col) pairs: cmfrec_hip_score_pairs (the kernel alone, test entry point), the
 // cmfrec_hip_scorer_* handle (both factor matrices resident), the pair scorer cmfrec_hip_newrows_predict runs on device factors
 // (newrows.hpp) and predict_X_old_collective_explicit / _implicit.  A translation unit of its own, like topn_tu.hip.  Every
-// path launches through launch_score_pairs (predict_kernels.hpp).
+// path launches through launch_score_pairs (predict_kernels.hpp).  The error of the predictions on a resident held-out set
+// (cmfrec_hip_evalset_*, cmfrec_hip_scorer_errors, cmfrec_hip_pair_errors, and evalset_run for cmfrec_hip_session_errors in
+// session.hip) launches through launch_score_errors (predict_error_kernels.hpp).
 #include <algorithm>
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "predict_kernels.hpp"
+#include "predict_error_kernels.hpp"
 
 using namespace cmfhip;
 
@@ -91,6 +94,96 @@ int pair_scorer_run(PairScorer *ps, const real_t *dA, size_t lda, int_t m, const
 }
 
 double pair_scorer_ms(const PairScorer *ps) { return ps->ms; }
+
+}  // namespace cmfhip
+
+// a held-out set resident on the device, with the records of its evaluations' wavefronts and the events around their kernels
+struct cmfrec_hip_evalset {
+    int device = 0, num_cus = 256;
+    hipStream_t stream = nullptr;              // the uploads; an evaluation runs on the stream of whoever owns the factors
+    size_t n_pairs = 0;
+    DevBuf<int> row, col;
+    DevBuf<real_t> x, weight;
+    DevBuf<cmfrec_hip_errors> partials;        // one record per wavefront of the launch, then the final one; grows on demand
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double ms = 0;
+    size_t waves = 0;                          // wavefronts of the most recent evaluation's scoring launch
+    bool timed = false;
+    ~cmfrec_hip_evalset()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace cmfhip {
+
+// the one host pass over the weights: each finite and >= 0
+static bool weights_ok(const real_t *w, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (!(w[i] >= (real_t)0) || w[i] > std::numeric_limits<real_t>::max()) return false;
+    return true;
+}
+
+// the body of cmfrec_hip_evalset_create; the arrays have been checked
+static void evalset_fill(cmfrec_hip_evalset &e, const int_t *row, const int_t *col, const real_t *x, const real_t *weight, size_t n_pairs, int device)
+{
+    open_device(device, &e.device, &e.num_cus, &e.stream);
+    HIP_CHECK(hipEventCreate(&e.ev0));
+    HIP_CHECK(hipEventCreate(&e.ev1));
+    e.n_pairs = n_pairs;
+    if (n_pairs == 0) return;
+    e.row.upload(row, n_pairs, e.stream);
+    e.col.upload(col, n_pairs, e.stream);
+    e.x.upload(x, n_pairs, e.stream);
+    if (weight) e.weight.upload(weight, n_pairs, e.stream);
+    HIP_CHECK(hipStreamSynchronize(e.stream));     // the caller's arrays may go away
+}
+
+int evalset_run(cmfrec_hip_evalset *e, const char *fn, int device, int num_cus, hipStream_t st, const real_t *dA, size_t lda, int_t m,
+                const real_t *dbiasA, size_t ldbiasA, const real_t *dB, size_t ldb, int_t n, int_t kk, const real_t *dbiasB, real_t glob_mean,
+                bool implicit, real_t *dpred, cmfrec_hip_errors *out)
+{
+    if (e == nullptr || out == nullptr) {
+        g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    if (e->device != device) {
+        g_last_error = std::string(fn) + ": the evaluation set lives on device " + std::to_string(e->device) + ", the factors on device " +
+                       std::to_string(device);
+        return 2;
+    }
+    DeviceScope scope(device);
+    memset(out, 0, sizeof *out);
+    e->ms = 0;
+    e->waves = 0;
+    e->timed = true;
+    if (e->n_pairs == 0) return 0;
+    ScoreParams<real_t> P;
+    P.A = dA; P.lda = lda; P.m = m; P.B = dB; P.ldb = ldb; P.n = n; P.kk = kk;
+    P.biasA = dbiasA; P.ldbiasA = ldbiasA; P.biasB = dbiasB; P.glob_mean = glob_mean; P.implicit = implicit ? 1 : 0;
+    P.row = e->row.ptr; P.col = e->col.ptr; P.n_pairs = e->n_pairs;
+    ErrorParams<real_t> E;
+    E.x = e->x.ptr; E.weight = e->weight.ptr; E.pred = dpred;
+    const char *cap = getenv("CMFREC_HIP_EVAL_WAVES");               // test hook, read per call
+    const int max_waves = (cap != nullptr && cap[0] != 0) ? atoi(cap) : 0;
+    const size_t waves = launch_score_errors(st, num_cus, max_waves, P, E, true);
+    e->waves = waves;
+    e->partials.alloc_at_least(waves + 1);
+    E.partials = e->partials.ptr;
+    HIP_CHECK(hipEventRecord(e->ev0, st));
+    launch_score_errors(st, num_cus, max_waves, P, E, false);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(e->ev1, st));
+    HIP_CHECK(hipMemcpyAsync(out, e->partials.ptr + waves, sizeof *out, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    float t = 0;
+    HIP_CHECK(hipEventElapsedTime(&t, e->ev0, e->ev1));
+    e->ms = (double)t;
+    return 0;
+}
 
 }  // namespace cmfhip
 
@@ -217,6 +310,108 @@ void cmfrec_hip_scorer_destroy(cmfrec_hip_scorer *s)
     const bool sw = hipGetDevice(&cur) == hipSuccess && cur != s->ps.device && hipSetDevice(s->ps.device) == hipSuccess;
     delete s;
     if (sw) (void)hipSetDevice(cur);
+}
+
+cmfrec_hip_evalset *cmfrec_hip_evalset_create(const int_t *row, const int_t *col, const real_t *x, const real_t *weight, size_t n_pairs,
+                                              int device)
+{
+    cmfrec_hip_evalset *e = nullptr;
+    const int rc = guarded([&]() {
+        if (n_pairs > 0 && (!row || !col || !x)) {
+            g_last_error = "cmfrec_hip_evalset_create: row, col and x are required";
+            return 2;
+        }
+        if (weight && !weights_ok(weight, n_pairs)) {
+            g_last_error = "cmfrec_hip_evalset_create: a weight is negative, NaN or infinite";
+            return 2;
+        }
+        e = new cmfrec_hip_evalset();
+        evalset_fill(*e, row, col, x, weight, n_pairs, device);
+        return 0;
+    });
+    g_last_rc = rc;
+    if (rc != 0) {
+        delete e;
+        return nullptr;
+    }
+    return e;
+}
+
+int cmfrec_hip_evalset_kernel_ms(cmfrec_hip_evalset *e, double *ms)
+{
+    if (e == nullptr || ms == nullptr || !e->timed) {
+        g_last_error = "cmfrec_hip_evalset_kernel_ms: no evaluation of this set yet";
+        return 2;
+    }
+    *ms = e->ms;
+    return 0;
+}
+
+int cmfrec_hip_evalset_launch_waves(cmfrec_hip_evalset *e, size_t *waves)
+{
+    if (e == nullptr || waves == nullptr || !e->timed) {
+        g_last_error = "cmfrec_hip_evalset_launch_waves: no evaluation of this set yet";
+        return 2;
+    }
+    *waves = e->waves;
+    return 0;
+}
+
+void cmfrec_hip_evalset_destroy(cmfrec_hip_evalset *e)
+{
+    if (e == nullptr) return;
+    int cur = -1;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != e->device && hipSetDevice(e->device) == hipSuccess;
+    delete e;
+    if (sw) (void)hipSetDevice(cur);
+}
+
+int cmfrec_hip_scorer_errors(cmfrec_hip_scorer *s, cmfrec_hip_evalset *e, cmfrec_hip_errors *out)
+{
+    return guarded([&]() {
+        if (s == nullptr) {
+            g_last_error = "cmfrec_hip_scorer_errors: invalid arguments";
+            return 2;
+        }
+        return evalset_run(e, "cmfrec_hip_scorer_errors", s->ps.device, s->ps.num_cus, s->ps.stream, s->A.ptr, s->ld, s->m,
+                           s->has_biasA ? s->biasA.ptr : nullptr, 1, s->B.ptr, s->ld, s->n, s->kk, s->has_biasB ? s->biasB.ptr : nullptr,
+                           s->glob_mean, s->implicit, nullptr, out);
+    });
+}
+
+int cmfrec_hip_pair_errors(int m, int n, int kk, const real_t *A, size_t lda, int offA, const real_t *biasA, const real_t *B, size_t ldb,
+                           int offB, const real_t *biasB, real_t glob_mean, int implicit, const int_t *row, const int_t *col, size_t n_pairs,
+                           const real_t *x, const real_t *weight, real_t *pred, cmfrec_hip_errors *out)
+{
+    return guarded([&]() {
+        auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_pair_errors: ") + what; return 2; };
+        if (m < 0 || n < 0 || offA < 0 || offB < 0) return bad("sizes and offsets >= 0");
+        if (kk < 1) return bad("kk >= 1");
+        if ((m > 0 && (!A || lda < (size_t)kk)) || (n > 0 && (!B || ldb < (size_t)kk)) || (n_pairs > 0 && (!row || !col || !x)) || !out)
+            return bad("a missing operand or a leading dimension below the row length");
+        if (weight && !weights_ok(weight, n_pairs)) return bad("a weight is negative, NaN or infinite");
+        cmfrec_hip_evalset e;
+        evalset_fill(e, row, col, x, weight, n_pairs, -1);
+        hipStream_t st = e.stream;
+        DevBuf<real_t> dA, dB, dba, dbb, dpred;
+        const size_t na = m > 0 ? (size_t)offA + (size_t)m * lda : 0, nb = n > 0 ? (size_t)offB + (size_t)n * ldb : 0;
+        if (n_pairs > 0) {
+            if (na) dA.upload(A, na, st);
+            if (nb) dB.upload(B, nb, st);
+        }
+        const bool strided = biasA != nullptr && na > 0 && biasA >= A && biasA < A + na;
+        if (n_pairs > 0 && biasA && !strided && m > 0) dba.upload(biasA, (size_t)m, st);
+        if (n_pairs > 0 && biasB && n > 0) dbb.upload(biasB, (size_t)n, st);
+        if (pred) dpred.alloc(n_pairs);
+        const int rc = evalset_run(&e, "cmfrec_hip_pair_errors", e.device, e.num_cus, st, na ? dA.ptr + offA : nullptr, lda, m,
+                                   strided ? dA.ptr + (biasA - A) : dba.ptr, strided ? lda : 1, nb ? dB.ptr + offB : nullptr, ldb, n, kk,
+                                   dbb.ptr, glob_mean, implicit != 0, dpred.ptr, out);
+        if (rc == 0 && pred && n_pairs > 0) {
+            dpred.download(pred, n_pairs, st);
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+        return rc;
+    });
 }
 
 // scorer created, used once, destroyed

@@ -2909,6 +2909,31 @@ int cmfrec_hip_session_iterate(cmfrec_hip_session *s, int niter, int finalize_ch
     return 0;
 }
 
+// the error of the current factors' predictions on a resident held-out set (predict_tu.hip, evalset_run): reads A, B and the
+// biases where they are, behind the updates queued on the session's stream; writes nothing of the session's
+int cmfrec_hip_session_errors(cmfrec_hip_session *s, cmfrec_hip_evalset *e, real_t glob_mean, cmfrec_hip_errors *out)
+{
+    return guarded([&]() {
+        if (s == nullptr) {
+            g_last_error = "cmfrec_hip_session_errors: invalid arguments";
+            return 2;
+        }
+        const cmfrec_hip_model &m = s->mdl;
+        if (m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n) {
+            g_last_error = "cmfrec_hip_session_errors: needs a session that owns all rows";
+            return 2;
+        }
+        if (m.k + m.k_main < 1) {
+            g_last_error = "cmfrec_hip_session_errors: k + k_main >= 1";
+            return 2;
+        }
+        const bool implicit = m.implicit != 0;
+        return evalset_run(e, "cmfrec_hip_session_errors", s->dev.device, s->dev.num_cus, s->dev.stream, s->A.ptr + m.k_user, s->ldA, m.m,
+                           (!implicit && m.user_bias) ? s->biasA.ptr : nullptr, 1, s->B.ptr + m.k_item, s->ldB, m.n, m.k + m.k_main,
+                           (!implicit && m.item_bias) ? s->biasB.ptr : nullptr, implicit ? (real_t)0 : glob_mean, implicit, nullptr, out);
+    });
+}
+
 int cmfrec_hip_session_sync(cmfrec_hip_session *s)
 {
     return guarded([&]() {

@@ -1,4 +1,5 @@
-"""Ranking metrics from the ranks of held-out items (``Ranker.ranks``, ``ops.ranks_batch``): pure NumPy on integers, no device."""
+"""Ranking metrics from the ranks of held-out items (``Ranker.ranks``, ``ops.ranks_batch``) and error metrics from the error
+record of held-out values (``Scorer.errors``, ``AlsSession.errors``): pure NumPy, no device."""
 import numpy as np
 
 METRICS = ("hit", "precision", "recall", "ap", "ndcg", "rr", "auc", "mean_rank")
@@ -67,6 +68,33 @@ def ranking_metrics(indptr, ranks, pool, k=10):
         out[name][none] = np.nan
     out["auc"][(pool == T) & ~none] = np.nan
     out["T"] = T
+    return out
+
+
+def error_metrics(rec, include_fallback=True):
+    """RMSE, MAE and their kin from an error record (``Scorer.errors``, ``AlsSession.errors``, ``ops.pair_errors``): per class
+    -- [0] scored pairs, [1] fallback pairs (outside the model, predicted by the global mean and the bias in range) -- the
+    record holds ``n``, ``sum_w``, ``sum_we``, ``sum_wabs``, ``sum_wsq``, ``max_abs``.  With S the sums over class 0, or over both
+    classes when ``include_fallback``:
+
+        mse   S(w e^2) / S(w)        rmse  sqrt(mse)        mae  S(w |e|) / S(w)        bias  S(w e) / S(w)
+        max_abs  max |e|             sum_w  S(w)            n    the pairs that count
+
+    plus ``n_fallback`` (the fallback pairs of the set, counted or not) and ``n_skipped``.  Where ``sum_w`` is 0 the four
+    ratios are NaN.  Pure NumPy."""
+    cls = slice(0, 2) if include_fallback else slice(0, 1)
+    get = lambda name: np.asarray(rec[name], np.float64)[cls]
+    sw = float(get("sum_w").sum())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = lambda name: float(np.float64(get(name).sum()) / np.float64(sw)) if sw != 0 else float("nan")
+        mse = ratio("sum_wsq")
+        out = {"rmse": float(np.sqrt(mse)), "mse": mse, "mae": ratio("sum_wabs"), "bias": ratio("sum_we")}
+    n = np.asarray(rec["n"]).astype(np.int64)
+    out["max_abs"] = float(get("max_abs").max())
+    out["n"] = int(n[cls].sum())
+    out["n_fallback"] = int(n[1])
+    out["n_skipped"] = int(rec["n_skipped"])
+    out["sum_w"] = sw
     return out
 
 

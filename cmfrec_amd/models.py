@@ -184,6 +184,18 @@ def _scorer(self, biasA, biasB, glob_mean, implicit):
                   glob_mean=glob_mean, implicit=implicit)
 
 
+def _evaluate_error(self, X_test, W, include_fallback):
+    """Shared body of ``evaluate_error``: one ``scorer()`` and one ``EvalSet`` made for the call, the record reduced on the device."""
+    from .metrics import error_metrics
+    from .score import EvalSet
+    if isinstance(X_test, tuple):
+        row, col, val = X_test
+    else:
+        row, col, val, _, _ = _coo_triplet(X_test)
+    with EvalSet(row, col, val, W, dtype=self.A_.dtype) as es, self.scorer() as sc:
+        return error_metrics(sc.errors(es), include_fallback=include_fallback)
+
+
 def _new_rows(X, n, dt):
     """COO triplet of new rows: ``X`` is a SciPy sparse matrix [m_x, n], a (row, col, val) triplet or None."""
     if X is None:
@@ -483,6 +495,13 @@ class CMF_implicit(_Base):
         with self.scorer() as sc:
             return sc.predict(user, item)
 
+    def evaluate_error(self, X_test):
+        """Squared and absolute error of A_u . B_i on held-out values, reduced on the device: ``X_test`` a SciPy sparse matrix or
+        a (row, col, value) triplet, as ``fit`` takes.  One ``scorer()`` and one ``cmfrec_amd.EvalSet`` made, used and closed;
+        returns ``cmfrec_amd.metrics.error_metrics``' dict (rmse, mse, mae, bias, max_abs, n, n_fallback, n_skipped, sum_w).  An
+        entry whose user or item lies outside the model has no prediction and is counted in ``n_skipped``, as is a NaN value."""
+        return _evaluate_error(self, X_test, None, True)
+
     def predict_new_batch(self, X=None, U=None, row=None, item=None):
         """Predictions for chosen pairs (row of the batch, item) of users who were not part of the fit (reference
         ``predict_new``; C function predict_X_new_collective_implicit): one ``new_users()`` handle made, used and closed."""
@@ -756,6 +775,17 @@ class CMF(_Base):
         kk products and three additions summed in another order, not bit for bit."""
         with self.scorer() as sc:
             return sc.predict(user, item)
+
+    def evaluate_error(self, X_test, W=None, include_fallback=True):
+        """Squared and absolute error of the predictions on held-out values, reduced on the device: ``X_test`` a SciPy sparse
+        matrix or a (row, col, value) triplet, as ``fit`` takes; ``W``: one weight (finite, >= 0) per entry, or None -- entry i of the
+        triplet, or of ``X_test.tocoo()`` for a matrix: for a CSR / CSC matrix that is the order of its ``data``, row by row / column
+        by column, not the order in which the entries were once given; pass a triplet where that order matters.  One
+        ``scorer()`` and one ``cmfrec_amd.EvalSet`` made, used and closed; returns ``cmfrec_amd.metrics.error_metrics``' dict
+        (rmse, mse, mae, bias, max_abs, n, n_fallback, n_skipped, sum_w).  An entry whose user or item lies outside the model is
+        predicted by the global mean + the bias of the side in range; ``include_fallback=False`` leaves those entries out of
+        the metrics (``n_fallback`` still counts them).  A NaN value is skipped."""
+        return _evaluate_error(self, X_test, W, include_fallback)
 
     def predict_new_batch(self, X=None, U=None, W=None, row=None, item=None):
         """Predictions for chosen pairs (row of the batch, item) of users who were not part of the fit (reference

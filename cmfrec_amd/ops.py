@@ -373,6 +373,42 @@ def score_pairs(m, n, kk, row, col, A_img=None, lda=0, offA=0, B_img=None, ldb=0
     return out
 
 
+def pair_errors(m, n, kk, row, col, x, w=None, A_img=None, lda=0, offA=0, B_img=None, ldb=0, offB=0, biasA=None, biasA_col=None,
+                biasB=None, glob_mean=0.0, implicit=False, return_pred=True):
+    """The two kernels of the error reduction on their own (``cmfrec_hip_pair_errors``, include/cmfrec_hip.h), beside
+    ``score_pairs`` and with its image arguments: the error record of the pairs' predictions against ``x`` (NaN: the pair is
+    skipped) under the optional weights ``w`` -- the dict ``Scorer.errors`` returns.  ``return_pred``: (record, pred), with
+    ``pred`` the prediction of every pair as the kernel formed it (``score_pairs``' values, bit for bit)."""
+    from .score import check_heldout
+    imgs = [a for a in (A_img, B_img, biasA, biasB) if a is not None]
+    if not imgs:
+        raise ValueError("pair_errors needs at least one image")
+    dtype = imgs[0].dtype
+    if dtype.type not in (np.float64, np.float32):
+        raise TypeError("the images must be float64 or float32")
+    for img in imgs:
+        if img.dtype != dtype or img.ndim != 1 or not img.flags.c_contiguous:
+            raise ValueError("the images must be flat contiguous arrays of one dtype")
+    for img, r, ld, off in ((A_img, m, lda, offA), (B_img, n, ldb, offB)):
+        if img is not None and r > 0 and len(img) < off + r * ld:
+            raise ValueError("an image is shorter than off + rows * ld")
+    if (biasA is not None and len(biasA) < m) or (biasB is not None and len(biasB) < n):
+        raise ValueError("a bias is shorter than its side")
+    if biasA_col is not None and (biasA is not None or A_img is None or not kk <= biasA_col < lda):
+        raise ValueError("'biasA_col' is a column of A_img's rows behind the factors, and excludes 'biasA'")
+    row, col, x, w = check_heldout(row, col, x, w, dtype, "pair_errors")
+    lib = _lib.load(dtype)
+    sz = dtype.itemsize
+    pba = C.c_void_p(A_img.ctypes.data + (offA + biasA_col) * sz) if biasA_col is not None else _lib.ptr(biasA)
+    pred = np.empty(len(row), dtype) if return_pred else None
+    rec = _lib.Errors()
+    rc = lib.cmfrec_hip_pair_errors(m, n, kk, _lib.ptr(A_img), lda, offA, pba, _lib.ptr(B_img), ldb, offB, _lib.ptr(biasB),
+                                    float(glob_mean), int(bool(implicit)), _lib.ptr(row), _lib.ptr(col), len(row), _lib.ptr(x),
+                                    _lib.ptr(w), _lib.ptr(pred), C.byref(rec))
+    _lib.check(rc, lib, "pair_errors")
+    return (rec.as_dict(), pred) if return_pred else rec.as_dict()
+
+
 def dense_op(op, m, n, k, C_img, ldc, offC=0, A_img=None, lda=0, offA=0, B_img=None, ldb=0, offB=0, s1=1.0, s2=0.0):
     """One operation of the dense layer on its own (``cmfrec_hip_dense_op``, include/cmfrec_hip.h): ``op`` a key of
     ``DENSE_OPS``.  The images are flat arrays of one dtype, ``off + rows * ld`` elements each, whose operand starts at

@@ -249,6 +249,22 @@ class AlsSession:
         _lib.check(self.lib.cmfrec_hip_session_iterate(self.handle, C.c_int(niter), C.c_int(int(finalize_chol))),
                    self.lib, "iterate")
 
+    def errors(self, evalset, glob_mean=0.0):
+        """The error record (``Scorer.errors``) of the session's current factors on a resident ``cmfrec_amd.EvalSet``, evaluated
+        where the factors are, behind the updates queued on the session's stream: the biases where the model has them, the
+        implicit rule for an implicit model; ``glob_mean`` is the caller's (the session does not own one).  Nothing in the
+        session changes.  A session that does not own all rows is refused."""
+        from .score import EvalSet
+        if not isinstance(evalset, EvalSet):
+            raise TypeError("AlsSession.errors: an EvalSet is required")
+        if not self.handle:
+            raise RuntimeError("AlsSession: the handle is closed")
+        rec = _lib.Errors()
+        R = _lib.real(self.dtype)
+        rc = self.lib.cmfrec_hip_session_errors(self.handle, evalset._for(self.dtype, "AlsSession.errors"), R(glob_mean), C.byref(rec))
+        _lib.check(rc, self.lib, "AlsSession.errors")
+        return rec.as_dict()
+
     def sync(self):
         _lib.check(self.lib.cmfrec_hip_session_sync(self.handle), self.lib, "sync")
 

@@ -810,6 +810,46 @@ int cmfrec_hip_scorer_predict(cmfrec_hip_scorer *s, const int_t *row, const int_
 int cmfrec_hip_scorer_kernel_ms(cmfrec_hip_scorer *s, double *ms);
 void cmfrec_hip_scorer_destroy(cmfrec_hip_scorer *s);
 
+/* Squared and absolute error on held-out pairs, reduced on the device.  An evaluation set -- row, col,
+ * the held-out value x and an optional weight per pair -- goes to the device once and stays there; an evaluation then is the
+ * scoring kernel of cmfrec_hip_scorer_predict ending in a reduction instead of a store, and a download of this one record.
+ * With p the prediction of a pair (the value cmfrec_hip_scorer_predict returns for it, bit for bit), in double precision in
+ * either library  e = (double)p - (double)x  and  w = weight ? (double)weight : 1.  Two classes of pairs:
+ *   [0] scored:    row in [0, m) and col in [0, n)
+ *   [1] fallback:  explicit rule, the pair outside the model, p the fallback value
+ * and per class n (pairs), sum_w, sum_we = sum w e, sum_wabs = sum w |e|, sum_wsq = sum w e^2, max_abs = max |e|.  n_skipped: the
+ * pairs that add to nothing else -- x is NaN, or, under the implicit rule, the pair is outside the model (its prediction is NaN by
+ * definition).  Only NaN skips a pair: an infinite x is counted as it is.  n[0] + n[1] + n_skipped = n_pairs.  The sums are added in
+ * an order that depends on the device, the launch shape and the order of the pairs, not on the run: the same call returns the
+ * same bytes (no atomics).  cmfrec_amd.metrics.error_metrics turns a record into RMSE, MAE, the mean signed error.
+ * evalset_create: uploads the four arrays whole (weight optional); n_pairs = 0 is legal; device < 0: the current device.  NULL
+ *   on failure: 2 for a NaN, infinite or negative weight and for a missing row / col / x with n_pairs > 0, 1 when the device has no
+ *   room.  The indices are not checked: the kernel decides them as it does for predictions.  The order of the pairs is free; pairs
+ *   sorted by row are scored faster (section 3.8).
+ * evalset_kernel_ms: HIP-event time of both kernels of the most recent evaluation of the set (2 before the first).
+ * evalset_launch_waves: the wavefronts of the scoring launch of the most recent evaluation (0 for a set without pairs; 2 before
+ *   the first): what CMFREC_HIP_EVAL_WAVES below caps.
+ * scorer_errors: against the scorer's resident matrices, biases, mean and rule; 2 when the set lives on another device.
+ * session_errors: against the session's factors as they are on the device (the columns behind k_user / k_item, k + k_main wide,
+ *   biasA / biasB where the model has them, the implicit rule for an implicit model); glob_mean is the caller's, the session does
+ *   not own one.  Launched on the session's stream behind the updates queued there; synchronises; changes nothing in the session.
+ *   2 for a session that does not own all rows and for a set on another device.
+ * One set may serve any number of scorers and sessions, one call at a time.
+ * CMFREC_HIP_EVAL_WAVES (read per call): at most that many wavefronts, rounded up to whole workgroups, in the scoring launch, so
+ *   that a small set gives a wavefront several chunks (test hook; 0: by occupancy). */
+typedef struct cmfrec_hip_errors {      /* all classes: [0] scored, [1] fallback */
+    uint64_t n[2]; uint64_t n_skipped;
+    double sum_w[2], sum_we[2], sum_wabs[2], sum_wsq[2], max_abs[2];
+} cmfrec_hip_errors;
+typedef struct cmfrec_hip_evalset cmfrec_hip_evalset;
+cmfrec_hip_evalset *cmfrec_hip_evalset_create(const int_t *row, const int_t *col, const real_t *x, const real_t *weight, size_t n_pairs,
+                                              int device);
+int cmfrec_hip_evalset_kernel_ms(cmfrec_hip_evalset *e, double *ms);
+int cmfrec_hip_evalset_launch_waves(cmfrec_hip_evalset *e, size_t *waves);
+void cmfrec_hip_evalset_destroy(cmfrec_hip_evalset *e);
+int cmfrec_hip_scorer_errors(cmfrec_hip_scorer *s, cmfrec_hip_evalset *e, cmfrec_hip_errors *out);
+int cmfrec_hip_session_errors(cmfrec_hip_session *s, cmfrec_hip_evalset *e, real_t glob_mean, cmfrec_hip_errors *out);
+
 /* Replace predict_X_old_collective_explicit / _implicit and predict_X_new_collective_explicit / _implicit of the reference's
  * src/cmfrec.h (bodies src/collective.c:11797-12069 over predict_multiple, src/common.c:5066-5110) -- the same positional
  * parameters, the same return codes; nthreads is accepted and ignored.
@@ -1012,6 +1052,14 @@ int cmfrec_hip_impute_dense(int m, int n, int kk, const real_t *A, size_t lda, c
 int cmfrec_hip_score_pairs(int m, int n, int kk, const real_t *A, size_t lda, int offA, const real_t *biasA, const real_t *B, size_t ldb,
                            int offB, const real_t *biasB, real_t glob_mean, int implicit, const int_t *row, const int_t *col, size_t n_pairs,
                            real_t *out);
+
+/* The two kernels of the error reduction on their own (test entry point), beside cmfrec_hip_score_pairs and with its arguments
+ * and return codes: the same host images, uploaded as they are, then x [n_pairs], weight [n_pairs] or NULL (2 for a NaN, infinite
+ * or negative one), pred [n_pairs] or NULL -- the prediction of every pair as the kernel formed it, skipped pairs included -- and
+ * out, the record (all zeros for n_pairs = 0). */
+int cmfrec_hip_pair_errors(int m, int n, int kk, const real_t *A, size_t lda, int offA, const real_t *biasA, const real_t *B, size_t ldb,
+                           int offB, const real_t *biasB, real_t glob_mean, int implicit, const int_t *row, const int_t *col, size_t n_pairs,
+                           const real_t *x, const real_t *weight, real_t *pred, cmfrec_hip_errors *out);
 
 /* Start values as the reference's random_parallel draws them (src/helpers.c:927-1043; xoshiro256++
  * seeded by splitmix64, truncated ziggurat normals or uniforms, scaled 2^-7): A <- stream(seed),
