@@ -74,6 +74,34 @@ class Errors(C.Structure):
         return out
 
 
+RANK_METRICS = ("hit", "precision", "recall", "ap", "ndcg", "rr", "auc", "mean_rank")     # the order of cmfrec_hip_rank_record
+WATCH = {"rmse": 0, "mae": 1}                       # CMFREC_HIP_WATCH_*
+WATCH.update({name: 2 + i for i, name in enumerate(RANK_METRICS)})
+STEP_IMPROVED, STEP_STOP, STEP_EVALUATE = 1, 2, 4   # CMFREC_HIP_STEP_*
+
+
+class RankRecord(C.Structure):
+    """``cmfrec_hip_rank_record`` (include/cmfrec_hip.h): the same layout in both precisions."""
+    _fields_ = [("sum", C.c_double * 8), ("count", C.c_uint64 * 8), ("users", C.c_uint64)]
+
+    def as_dict(self):
+        return {"sum": np.array(self.sum[:], np.float64), "count": np.array(self.count[:], np.uint64), "users": np.uint64(self.users)}
+
+
+class FitMonitor(C.Structure):
+    """``cmfrec_hip_fit_monitor`` (include/cmfrec_hip.h): the same layout in both precisions."""
+    _fields_ = [("evalset", C.c_void_p), ("rankset", C.c_void_p), ("metric", C.c_int), ("k_at", C.c_int), ("every", C.c_int),
+                ("patience", C.c_int), ("restore_best", C.c_int), ("min_delta", C.c_double), ("values", C.POINTER(C.c_double)),
+                ("records", C.POINTER(Errors)), ("rank_records", C.POINTER(RankRecord)), ("iters_run", C.POINTER(C.c_int)),
+                ("best_iter", C.POINTER(C.c_int))]
+
+
+class EarlyStop(C.Structure):
+    """``cmfrec_hip_early_stop``: the state of ``cmfrec_hip_early_stop_step``."""
+    _fields_ = [("every", C.c_int), ("patience", C.c_int), ("higher_is_better", C.c_int), ("min_delta", C.c_double),
+                ("best", C.c_double), ("best_iter", C.c_int), ("misses", C.c_int)]
+
+
 def newrows_model_mirror(dtype):
     return NewRowsModel if np.dtype(dtype) == np.float64 else NewRowsModelF
 
@@ -86,6 +114,8 @@ EXPORTED = [
     "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_topN_candidates", "cmfrec_hip_topN_candidates_batch", "cmfrec_hip_ranker_ranks", "cmfrec_hip_ranks_batch", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
     "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
     "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
+    "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
+    "cmfrec_hip_rankset_create", "cmfrec_hip_rankset_destroy", "cmfrec_hip_ranker_metrics", "cmfrec_hip_session_ranking",
     "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
@@ -173,6 +203,17 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_evalset_destroy.argtypes = [C.c_void_p]
     lib.cmfrec_hip_scorer_errors.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Errors)]
     lib.cmfrec_hip_session_errors.argtypes = [C.c_void_p, C.c_void_p, R, C.POINTER(Errors)]
+    lib.cmfrec_hip_session_snapshot.argtypes = [C.c_void_p]
+    lib.cmfrec_hip_session_restore.argtypes = [C.c_void_p]
+    lib.cmfrec_hip_fit_set_monitor.argtypes = [C.POINTER(FitMonitor)]
+    lib.cmfrec_hip_rankset_create.restype = C.c_void_p
+    lib.cmfrec_hip_rankset_create.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+    lib.cmfrec_hip_rankset_destroy.restype = None
+    lib.cmfrec_hip_rankset_destroy.argtypes = [C.c_void_p]
+    lib.cmfrec_hip_ranker_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.POINTER(RankRecord),
+                                              C.c_void_p, C.c_void_p]
+    lib.cmfrec_hip_session_ranking.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RankRecord)]
+    lib.cmfrec_hip_early_stop_step.argtypes = [C.POINTER(EarlyStop), C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.cmfrec_hip_pair_errors.argtypes = lib.cmfrec_hip_score_pairs.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Errors)]
     for name in EXPORTED_OTHER[1:]:
         getattr(lib, name).restype = C.c_int

@@ -234,40 +234,160 @@ void sparse_colmeans(const int_t *col, const real_t *val, size_t nnz, int_t cols
     for (int_t c = 0; c < cols; c++) means[c] = (real_t)(sum[c] / (double)cnt[c]);
 }
 
+// ---- validation while fitting (cmfrec_hip_fit_set_monitor, include/cmfrec_hip.h) -------------------------------------
+// The monitor waits here, per thread, for the next fit call; take_monitor() at the top of both fit functions empties the slot on
+// every path out of them.
+struct FitMonitor {
+    bool on = false;
+    cmfrec_hip_fit_monitor m;
+    real_t glob_mean = 0;        // the explicit fit's, set once it is known
+    int returned = -1;           // run_loop: the 0-based iteration whose factors the session holds when the loop is over
+};
+thread_local FitMonitor g_monitor;
+std::vector<int> devices_from_env();
+bool sharded_fit_wanted(const std::vector<int> &devs);
+FitMonitor take_monitor()
+{
+    FitMonitor out = g_monitor;
+    g_monitor = FitMonitor();
+    return out;
+}
+int refuse_monitor(bool verbose, const std::string &msg)
+{
+    cmfhip::g_last_error = msg;
+    if (verbose) fprintf(stderr, "%s\n", msg.c_str());
+    return 2;
+}
+// the refusals that need no session, before the fit writes to any output: 0 or 2
+int check_monitor(const FitMonitor &mon, const char *fn, int_t m, int_t n, int_t kk, int_t niter, bool verbose)
+{
+    if (!mon.on) return 0;
+    const std::string name(fn);
+    if (niter < 1) return refuse_monitor(verbose, name + ": a monitor needs niter >= 1");
+    const bool ranking = mon.m.rankset != nullptr;
+    if ((mon.m.evalset != nullptr) == ranking)
+        return refuse_monitor(verbose, name + ": the monitor needs an evaluation set or a ranking set, one of the two");
+    if (ranking ? (mon.m.metric < CMFREC_HIP_WATCH_HIT || mon.m.metric > CMFREC_HIP_WATCH_MEAN_RANK)
+                : (mon.m.metric != CMFREC_HIP_WATCH_RMSE && mon.m.metric != CMFREC_HIP_WATCH_MAE))
+        return refuse_monitor(verbose, name + ": the monitor's metric must be CMFREC_HIP_WATCH_RMSE or _MAE with an evaluation set, "
+                                              "CMFREC_HIP_WATCH_HIT .. _MEAN_RANK with a ranking set");
+    const std::vector<int> devs = devices_from_env();
+    if (sharded_fit_wanted(devs))
+        return refuse_monitor(verbose, name + ": a monitor needs a fit on one device (CMFREC_HIP_DEVICES names several, or "
+                                              "CMFREC_HIP_SHARDED is set)");
+    const int device = devs.empty() ? -1 : devs[0];
+    const int rc = cmfhip::guarded([&]() {
+        return ranking ? cmfhip::rankset_usable(mon.m.rankset, fn, device, m, n, kk, mon.m.k_at) : cmfhip::evalset_usable(mon.m.evalset, fn, device, m, n);
+    });
+    if (rc && verbose) fprintf(stderr, "%s\n", cmfhip::g_last_error.c_str());
+    return rc;
+}
+double watched_value(const cmfrec_hip_errors &r, int metric)
+{
+    const double sw = r.sum_w[0] + r.sum_w[1];
+    if (sw == 0) return std::nan("");
+    if (metric == CMFREC_HIP_WATCH_MAE) return (r.sum_wabs[0] + r.sum_wabs[1]) / sw;
+    return std::sqrt((r.sum_wsq[0] + r.sum_wsq[1]) / sw);
+}
+double watched_value(const cmfrec_hip_rank_record &r, int metric)
+{
+    const int f = metric - CMFREC_HIP_WATCH_HIT;
+    return r.count[f] ? r.sum[f] / (double)r.count[f] : std::nan("");
+}
+const char *watched_name(int metric)
+{
+    static const char *names[] = {"RMSE", "MAE", "hit", "precision", "recall", "AP", "NDCG", "RR", "AUC", "mean rank"};
+    return names[metric];
+}
+
 // chol_A / chol_B: that half-step is a closed-form solve whatever use_cg says (dense X without weights whose rows / columns are
 // all or nearly all complete: optimizeA Case 1, common.c:2787-2993)
+// mon: the held-out set is evaluated between the iterations, and the loop may end early and go back to its best iterate
 int run_loop(cmfrec_hip_session *s, const cmfrec_hip_model &mdl, int niter, bool finalize_chol, bool verbose, bool implicit_feats = false,
-             bool chol_A = false, bool chol_B = false)
+             bool chol_A = false, bool chol_B = false, FitMonitor *mon = nullptr)
 {
+    cmfrec_hip_early_stop es;
+    memset(&es, 0, sizeof es);
+    int ran = 0;
+    bool snapshot_taken = false;
+    if (mon) {
+        es.every = mon->m.every; es.patience = mon->m.patience; es.min_delta = mon->m.min_delta; es.best_iter = -1;
+        es.higher_is_better = (mon->m.rankset != nullptr && mon->m.metric != CMFREC_HIP_WATCH_MEAN_RANK) ? 1 : 0;
+        for (int it = 0; it < niter && mon->m.values; it++) mon->m.values[it] = std::nan("");
+        if (mon->m.records) memset(mon->m.records, 0, (size_t)niter * sizeof(cmfrec_hip_errors));
+        if (mon->m.rank_records) memset(mon->m.rank_records, 0, (size_t)niter * sizeof(cmfrec_hip_rank_record));
+    }
+    // what the monitor reports however the loop ends; the best iterate comes back when the loop ended on a later one
+    auto finish = [&](int rc) {
+        if (!mon) return rc;
+        if (mon->m.iters_run) *mon->m.iters_run = ran;
+        if (mon->m.best_iter) *mon->m.best_iter = es.best_iter;
+        mon->returned = ran - 1;
+        if (rc == 0 && snapshot_taken && es.best_iter != ran - 1) {
+            rc = cmfrec_hip_session_restore(s);
+            mon->returned = es.best_iter;
+        }
+        return rc;
+    };
     for (int it = 0; it < niter; it++) {
-        if (g_stop) return 3;
+        if (g_stop) return finish(3);
         int chol = (finalize_chol && mdl.use_cg && it == niter - 1) ? 1 : 0;
         int rc;
         if (mdl.p > 0) { if (verbose) { printf("Updating C..."); fflush(stdout); }
-            if ((rc = cmfrec_hip_session_update(s, 'C', chol))) return rc; if (verbose) printf(" done\n"); }
-        if (g_stop) return 3;
+            if ((rc = cmfrec_hip_session_update(s, 'C', chol))) return finish(rc); if (verbose) printf(" done\n"); }
+        if (g_stop) return finish(3);
         if (mdl.q > 0) { if (verbose) { printf("Updating D..."); fflush(stdout); }
-            if ((rc = cmfrec_hip_session_update(s, 'D', chol))) return rc; if (verbose) printf(" done\n"); }
-        if (g_stop) return 3;
+            if ((rc = cmfrec_hip_session_update(s, 'D', chol))) return finish(rc); if (verbose) printf(" done\n"); }
+        if (g_stop) return finish(3);
         if (implicit_feats) {                                             // collective.c:8448-8534
             if (verbose) { printf("Updating Bi..."); fflush(stdout); }
-            if ((rc = cmfrec_hip_session_update(s, 'b', 1))) return rc;
+            if ((rc = cmfrec_hip_session_update(s, 'b', 1))) return finish(rc);
             if (verbose) { printf(" done\nUpdating Ai..."); fflush(stdout); }
-            if ((rc = cmfrec_hip_session_update(s, 'a', 1))) return rc;
+            if ((rc = cmfrec_hip_session_update(s, 'a', 1))) return finish(rc);
             if (verbose) printf(" done\n");
-            if (g_stop) return 3;
+            if (g_stop) return finish(3);
         }
         if (verbose) { printf("Updating B..."); fflush(stdout); }
-        if ((rc = cmfrec_hip_session_update(s, 'B', (chol || chol_B) ? 1 : 0))) return rc;
-        if ((rc = cmfrec_hip_session_after_gather(s, 'B'))) return rc;
+        if ((rc = cmfrec_hip_session_update(s, 'B', (chol || chol_B) ? 1 : 0))) return finish(rc);
+        if ((rc = cmfrec_hip_session_after_gather(s, 'B'))) return finish(rc);
         if (verbose) { cmfrec_hip_session_sync(s); printf(" done\n"); }
-        if (g_stop) return 3;
+        if (g_stop) return finish(3);
         if (verbose) { printf("Updating A..."); fflush(stdout); }
-        if ((rc = cmfrec_hip_session_update(s, 'A', (chol || chol_A) ? 1 : 0))) return rc;
-        if ((rc = cmfrec_hip_session_after_gather(s, 'A'))) return rc;
+        if ((rc = cmfrec_hip_session_update(s, 'A', (chol || chol_A) ? 1 : 0))) return finish(rc);
+        if ((rc = cmfrec_hip_session_after_gather(s, 'A'))) return finish(rc);
         if (verbose) { cmfrec_hip_session_sync(s); printf(" done\n\tCompleted ALS iteration %2d\n\n", it + 1); fflush(stdout); }
+        ran = it + 1;
+        if (mon && cmfrec_hip_early_stop_step(&es, it, niter, nullptr)) {
+            double value;
+            if (mon->m.rankset != nullptr) {
+                cmfrec_hip_rank_record rec;
+                if ((rc = cmfrec_hip_session_ranking(s, mon->m.rankset, mon->m.k_at, &rec))) return finish(rc);
+                value = watched_value(rec, mon->m.metric);
+                if (mon->m.rank_records) mon->m.rank_records[it] = rec;
+            } else {
+                cmfrec_hip_errors rec;
+                if ((rc = cmfrec_hip_session_errors(s, mon->m.evalset, mon->glob_mean, &rec))) return finish(rc);
+                value = watched_value(rec, mon->m.metric);
+                if (mon->m.records) mon->m.records[it] = rec;
+            }
+            if (mon->m.values) mon->m.values[it] = value;
+            const int step = cmfrec_hip_early_stop_step(&es, it, niter, &value);
+            if (verbose) {
+                printf("\tHeld-out %s after iteration %2d: %.6g%s\n\n", watched_name(mon->m.metric), it + 1, value,
+                       (step & CMFREC_HIP_STEP_IMPROVED) ? " (best so far)" : "");
+                fflush(stdout);
+            }
+            if ((step & CMFREC_HIP_STEP_IMPROVED) && mon->m.restore_best) {
+                if ((rc = cmfrec_hip_session_snapshot(s))) return finish(rc);
+                snapshot_taken = true;
+            }
+            if (step & CMFREC_HIP_STEP_STOP) {
+                if (verbose) { printf("\tStopping early: no improvement in %d evaluations\n\n", es.patience); fflush(stdout); }
+                break;
+            }
+        }
     }
-    return 0;
+    return finish(0);
 }
 
 // Dense X (Xfull [m, n] row-major, NaN = missing; weight, if given, dense too) -> the COO of its present entries in row-major
@@ -700,6 +820,34 @@ int cmfrec_hip_exchange_plan(int D, const int *bb, int *out, int cap)
     return (int)ops.size();
 }
 
+/* validation while fitting (include/cmfrec_hip.h): the monitor of this thread's next fit call */
+int cmfrec_hip_fit_set_monitor(const cmfrec_hip_fit_monitor *monitor)
+{
+    g_monitor = FitMonitor();
+    if (monitor != nullptr) { g_monitor.on = true; g_monitor.m = *monitor; }
+    return 0;
+}
+
+/* the rule of the monitor, host only: which iterations are evaluated, what improves, when to stop */
+int cmfrec_hip_early_stop_step(cmfrec_hip_early_stop *st, int iter, int niter, const double *value)
+{
+    if (st == nullptr) return 0;
+    if (value == nullptr) {
+        const int every = st->every < 1 ? 1 : st->every;
+        return ((iter + 1) % every == 0 || iter == niter - 1) ? CMFREC_HIP_STEP_EVALUATE : 0;
+    }
+    const double v = *value;
+    bool improved = false;
+    if (!std::isnan(v))
+        improved = st->best_iter < 0 || (st->higher_is_better ? v > st->best + st->min_delta : v < st->best - st->min_delta);
+    if (improved) {
+        st->best = v; st->best_iter = iter; st->misses = 0;
+        return CMFREC_HIP_STEP_IMPROVED;
+    }
+    st->misses++;
+    return (st->patience > 0 && st->misses >= st->patience) ? CMFREC_HIP_STEP_STOP : 0;
+}
+
 /* Start values exactly as the reference's random_parallel (helpers.c:927-1043) draws them. */
 int cmfrec_hip_random_parallel(real_t *A, size_t sizeA, real_t *B, size_t sizeB, int_t seed, bool normal)
 {
@@ -725,6 +873,8 @@ int_t fit_collective_implicit_als(
 {
 
     (void)nthreads;
+    FitMonitor mon = take_monitor();
+    if (const int rc_mon = check_monitor(mon, "fit_collective_implicit_als", m, n, k + k_main, niter, verbose)) return rc_mon;
     // collective.c:9406-9435
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
@@ -932,7 +1082,7 @@ int_t fit_collective_implicit_als(
     if (verbose && !rc) { printf("Starting ALS optimization routine\n\n"); fflush(stdout); }
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("set_factors");
-    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose);
+    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, false, false, false, mon.on ? &mon : nullptr);
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("ALS iterations");
     if (rc_loop == 0 || rc_loop == 3) {
@@ -942,7 +1092,8 @@ int_t fit_collective_implicit_als(
     tm.lap("get_factors");
     if ((rc_loop == 0 || rc_loop == 3) && precompute_for_predictions) {   // collective.c:10056-10115 (also after an interrupt, :10034-10043)
         if (verbose) { printf("Finishing precomputed matrices..."); fflush(stdout); }
-        const int last_chol = (!use_cg || (finalize_chol && niter > 0)) ? 1 : 0;
+        // (a monitored fit that returns an earlier iterate than niter - 1 returns one whose last A-step was not the Cholesky pass)
+        const int last_chol = (!use_cg || (finalize_chol && niter > 0 && (!mon.on || mon.returned == niter - 1))) ? 1 : 0;
         int rc2 = cmfrec_hip_session_precompute(s, last_chol, 0, precomputedBtB, nullptr, hadU ? precomputedBeTBe : nullptr,
                                                 hadU ? precomputedBeTBeChol : nullptr, nullptr, nullptr);
         if (rc2) rc_loop = rc2;
@@ -975,6 +1126,8 @@ int_t fit_collective_explicit_als(
 {
     (void)max_cd_steps;
     (void)precomputedBiTBi;        // with add_implicit_features the prediction matrices are not produced here
+    FitMonitor mon = take_monitor();
+    if (const int rc_mon = check_monitor(mon, "fit_collective_explicit_als", m, n, k + k_main, niter, verbose)) return rc_mon;
     // collective.c:7308-7329
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
@@ -1535,7 +1688,8 @@ int_t fit_collective_explicit_als(
     if (!rc && !dense_mult_A.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, 'A', dense_mult_A.data());
     if (!rc && !dense_mult_B.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, 'B', dense_mult_B.data());
     if (verbose && !rc) { printf("Starting ALS optimization routine\n\n"); fflush(stdout); }
-    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, add_implicit_features, dense_chol_A, dense_chol_B);
+    mon.glob_mean = gm;
+    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, add_implicit_features, dense_chol_A, dense_chol_B, mon.on ? &mon : nullptr);
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("ALS iterations");
     if (rc_loop == 0 || rc_loop == 3) {

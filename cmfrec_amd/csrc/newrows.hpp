@@ -87,6 +87,12 @@ int ranker_ranks_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, 
                         const int_t held_i[], const size_t *dexcl_p, const int *dexcl_i, int_t *out_rank, real_t *out_scores,
                         int_t *out_pool);
 int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n);
+// topn_tu.hip: the ranking metrics of a resident set (cmfrec_hip_rankset_*, rank_metrics_kernels.hpp) against factors that are on
+// the device, through a ranker the caller owns (*owned: null before the first call; cmfrec_hip_ranker_destroy it), and what a fit
+// asks of the set it is to watch.  Both report through g_last_error and throw HipError (call inside guarded()).
+int rankset_run_on_factors(cmfrec_hip_ranker **owned, cmfrec_hip_rankset *set, const char *fn, int device, const real_t *dA, size_t ldA, int_t m,
+                           const real_t *dB, size_t ldB, int_t n, int_t kk, const real_t *dbiasB, int k_at, cmfrec_hip_rank_record *out);
+int rankset_usable(cmfrec_hip_rankset *set, const char *fn, int device, int_t m, int_t n, int_t kk, int k_at);
 
 // predict_tu.hip: the scoring of chosen (row, col) pairs against operands that are on the device already -- the stream, the
 // pair buffers and the timing of cmfrec_hip_scorer_predict without its factor uploads.  dA [m, lda] / dB [n, ldb] point at the
@@ -107,5 +113,9 @@ double pair_scorer_ms(const PairScorer *ps);               // the kernel over th
 int evalset_run(cmfrec_hip_evalset *e, const char *fn, int device, int num_cus, hipStream_t st, const real_t *dA, size_t lda, int_t m,
                 const real_t *dbiasA, size_t ldbiasA, const real_t *dB, size_t ldb, int_t n, int_t kk, const real_t *dbiasB, real_t glob_mean,
                 bool implicit, real_t *dpred, cmfrec_hip_errors *out);
+// what a fit asks of the set it is to watch (cmfrec_hip_fit_set_monitor), before it writes anything: the set lives on `device`
+// (< 0: the current one) and at least one pair lies inside [0, m) x [0, n) with a value that is not NaN -- one download of the
+// set's three arrays.  0, or 2 with fn's name in the message.  Throws HipError.
+int evalset_usable(cmfrec_hip_evalset *e, const char *fn, int device, int_t m, int_t n);
 
 }  // namespace cmfhip

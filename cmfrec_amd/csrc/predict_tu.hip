@@ -5,6 +5,8 @@
 // (cmfrec_hip_evalset_*, cmfrec_hip_scorer_errors, cmfrec_hip_pair_errors, and evalset_run for cmfrec_hip_session_errors in
 // session.hip) launches through launch_score_errors (predict_error_kernels.hpp).
 #include <algorithm>
+#include <cmath>
+#include <vector>
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "predict_kernels.hpp"
@@ -140,6 +142,37 @@ static void evalset_fill(cmfrec_hip_evalset &e, const int_t *row, const int_t *c
     e.x.upload(x, n_pairs, e.stream);
     if (weight) e.weight.upload(weight, n_pairs, e.stream);
     HIP_CHECK(hipStreamSynchronize(e.stream));     // the caller's arrays may go away
+}
+
+int evalset_usable(cmfrec_hip_evalset *e, const char *fn, int device, int_t m, int_t n)
+{
+    if (e == nullptr) {
+        g_last_error = std::string(fn) + ": the monitor has no evaluation set";
+        return 2;
+    }
+    if (device < 0) HIP_CHECK(hipGetDevice(&device));
+    if (e->device != device) {
+        g_last_error = std::string(fn) + ": the evaluation set lives on device " + std::to_string(e->device) + ", the fit runs on device " +
+                       std::to_string(device);
+        return 2;
+    }
+    bool any = false;
+    if (e->n_pairs > 0) {
+        DeviceScope scope(e->device);
+        std::vector<int> row(e->n_pairs), col(e->n_pairs);
+        std::vector<real_t> x(e->n_pairs);
+        e->row.download(row.data(), e->n_pairs, e->stream);
+        e->col.download(col.data(), e->n_pairs, e->stream);
+        e->x.download(x.data(), e->n_pairs, e->stream);
+        HIP_CHECK(hipStreamSynchronize(e->stream));
+        for (size_t i = 0; i < e->n_pairs && !any; i++)
+            any = row[i] >= 0 && row[i] < m && col[i] >= 0 && col[i] < n && !std::isnan(x[i]);
+    }
+    if (!any) {
+        g_last_error = std::string(fn) + ": the evaluation set has no pair inside X with a value: nothing to watch";
+        return 2;
+    }
+    return 0;
 }
 
 int evalset_run(cmfrec_hip_evalset *e, const char *fn, int device, int num_cus, hipStream_t st, const real_t *dA, size_t lda, int_t m,

@@ -989,6 +989,10 @@ struct cmfrec_hip_session {
     bool side_local = false;
     DevBuf<real_t> side_part;
     GramWorkspace gws;
+    // cmfrec_hip_session_snapshot / _restore: a second copy of A, B, biasA, biasB, C, D, Ai, Bi, allocated on first use
+    DevBuf<real_t> snap[8];
+    bool has_snapshot = false;
+    cmfrec_hip_ranker *ranker = nullptr;  // cmfrec_hip_session_ranking: the session's own ranker, refreshed from B where it lives
     std::vector<EventPair> evA, evB;     // whole half-steps
     BinTimers binA, binB;                // row-update kernel launches per nnz bin
 
@@ -1004,6 +1008,7 @@ struct cmfrec_hip_session {
         for (auto &p : evB) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
         binA.clear(); binB.clear();
         for (auto e : partEv) (void)hipEventDestroy(e);
+        if (ranker) cmfrec_hip_ranker_destroy(ranker);
     }
 };
 
@@ -2933,6 +2938,75 @@ int cmfrec_hip_session_errors(cmfrec_hip_session *s, cmfrec_hip_evalset *e, real
                            (!implicit && m.item_bias) ? s->biasB.ptr : nullptr, implicit ? (real_t)0 : glob_mean, implicit, nullptr, out);
     });
 }
+
+// the ranking metrics of the current factors on a resident ranking set (topn_tu.hip, rankset_run_on_factors): the listed users' rows
+// of A are gathered on the device, the session's ranker takes B (and the item bias of an explicit model that has one) by a
+// device-to-device copy, then the rank kernel and the reduction run; writes nothing of the session's
+int cmfrec_hip_session_ranking(cmfrec_hip_session *s, cmfrec_hip_rankset *set, int k_at, cmfrec_hip_rank_record *out)
+{
+    const char *fn = "cmfrec_hip_session_ranking";
+    return guarded([&]() {
+        if (s == nullptr) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        const cmfrec_hip_model &m = s->mdl;
+        if (m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n) {
+            g_last_error = std::string(fn) + ": needs a session that owns all rows";
+            return 2;
+        }
+        if (m.k + m.k_main < 1) {
+            g_last_error = std::string(fn) + ": k + k_main >= 1";
+            return 2;
+        }
+        HIP_CHECK(hipSetDevice(s->dev.device));
+        HIP_CHECK(hipStreamSynchronize(s->dev.stream));          // the ranker has a stream of its own
+        return rankset_run_on_factors(&s->ranker, set, fn, s->dev.device, s->A.ptr + m.k_user, s->ldA, m.m, s->B.ptr + m.k_item, s->ldB, m.n,
+                                      m.k + m.k_main, (!m.implicit && m.item_bias) ? s->biasB.ptr : nullptr, k_at, out);
+    });
+}
+
+// A second copy of everything cmfrec_hip_session_get_factors / _get_implicit_features return -- A and B in their padded layout
+// (the bias column rides in them), the bias vectors, C, D, Ai, Bi -- so that a fit can go back to its best iterate.  The copies
+// are device to device on the session's stream, behind the updates queued there.  What an update derives from the factors
+// (Gramians, U C, the eigenvectors of C^T C) is rebuilt by the update that needs it; the cached eigenvectors are marked stale.
+static int snapshot_copy(cmfrec_hip_session *s, const char *fn, bool restore)
+{
+    return guarded([&]() {
+        if (s == nullptr) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        const cmfrec_hip_model &m = s->mdl;
+        if (m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n || s->side_local) {
+            g_last_error = std::string(fn) + ": needs a session that owns all rows";
+            return 2;
+        }
+        if (restore && !s->has_snapshot) {
+            g_last_error = std::string(fn) + ": no snapshot has been taken";
+            return 2;
+        }
+        HIP_CHECK(hipSetDevice(s->dev.device));
+        hipStream_t st = s->dev.stream;
+        DevBuf<real_t> *live[8] = {&s->A, &s->B, &s->biasA, &s->biasB, &s->C, &s->D, &s->Ai, &s->Bi};
+        for (int e = 0; e < 8; e++) {
+            DevBuf<real_t> &cur = *live[e], &snap = s->snap[e];
+            if (restore && snap.n != cur.n) {                 // (implicit features switched on after the snapshot, for instance)
+                g_last_error = std::string(fn) + ": the session's matrices have changed shape since the snapshot";
+                return 2;
+            }
+            if (!restore && snap.n != cur.n) snap.alloc(cur.n);
+            if (cur.n == 0) continue;
+            HIP_CHECK(hipMemcpyAsync(restore ? cur.ptr : snap.ptr, restore ? snap.ptr : cur.ptr, cur.n * sizeof(real_t),
+                                     hipMemcpyDeviceToDevice, st));
+        }
+        if (restore) { s->eigA.fresh = false; s->eigB.fresh = false; }
+        else s->has_snapshot = true;
+        return 0;
+    });
+}
+int cmfrec_hip_session_snapshot(cmfrec_hip_session *s) { return snapshot_copy(s, "cmfrec_hip_session_snapshot", false); }
+int cmfrec_hip_session_restore(cmfrec_hip_session *s) { return snapshot_copy(s, "cmfrec_hip_session_restore", true); }
 
 int cmfrec_hip_session_sync(cmfrec_hip_session *s)
 {

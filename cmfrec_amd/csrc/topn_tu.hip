@@ -7,12 +7,16 @@
 // (cmfrec_hip_ranker_topN_candidates and its kin) launches topn_cand_kernel (topn_cand_kernels.hpp) for every k.  A rank call
 // (cmfrec_hip_ranker_ranks and its kin) launches topn_rank_kernel (topn_rank_kernels.hpp) for every k.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
 #include <vector>
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
 #include "topn_cand_kernels.hpp"
 #include "topn_rank_kernels.hpp"
+#include "rank_metrics_kernels.hpp"
 
 using namespace cmfhip;
 
@@ -234,19 +238,23 @@ int upload_held(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size_t hel
 // the ranks of nu users whose factors dA [nu, lda], held-out lists (r->cp / r->ci, total entries) and exclusion lists are on the
 // device: the launch, the timing events (around topn_rank_kernel, whose threshold and exclusion steps are part of it) and the
 // download.  Nothing is written to the outputs before the kernel has run.
+// dheld_p / dheld_i: the held-out lists where they are (null: the ranker's own r->cp / r->ci, filled by upload_held).  stay: the
+// ranks and the pool stay on the device (r->ids, r->pool) for rank_metrics_kernel behind the launch; nothing is downloaded and
+// the stream is not waited for.
 int ranks_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, size_t total, size_t max_held, const size_t *dexcl_p,
-                 const int *dexcl_i, int_t *out_rank, real_t *out_scores, int_t *out_pool)
+                 const int *dexcl_i, int_t *out_rank, real_t *out_scores, int_t *out_pool, const size_t *dheld_p = nullptr,
+                 const int *dheld_i = nullptr, bool stay = false)
 {
     const cmfrec_hip_ranker::Device &dev = r->dev;
     r->ids.alloc_at_least(std::max<size_t>(total, 1));
     if (out_scores) r->sc.alloc_at_least(std::max<size_t>(total, 1));
-    if (out_pool) r->pool.alloc_at_least((size_t)nu);
+    if (out_pool || stay) r->pool.alloc_at_least((size_t)nu);
     TopnRankParams<real_t> P;
     P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
     P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-    P.held_p = r->cp.ptr; P.held_i = r->ci.ptr;
+    P.held_p = dheld_p ? dheld_p : r->cp.ptr; P.held_i = dheld_p ? dheld_i : r->ci.ptr;
     P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
-    P.out_rank = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr; P.out_pool = out_pool ? r->pool.ptr : nullptr;
+    P.out_rank = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr; P.out_pool = (out_pool || stay) ? r->pool.ptr : nullptr;
     int bpc = 1;
     const int nut = pick_rank_shape(nu, r->k, max_held, dev.num_cus, &P.ts, &P.tsp, &bpc);
     if (nut == 0) {
@@ -264,6 +272,7 @@ int ranks_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, s
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
     r->timed = true;
+    if (stay) return 0;
     r->ids.download(out_rank, total, dev.stream);
     if (out_scores) r->sc.download(out_scores, total, dev.stream);
     if (out_pool) r->pool.download(out_pool, (size_t)nu, dev.stream);
@@ -272,6 +281,167 @@ int ranks_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, s
 }
 
 }  // namespace
+
+// a ranking set resident on the device: user ids, held-out lists, exclusion lists; and what its evaluations need beside them --
+// the two NDCG tables of the last cut-off, the gathered rows of the users, the per-user values, the wavefronts' records
+struct cmfrec_hip_rankset {
+    int device = 0, num_cus = 256;
+    hipStream_t stream = nullptr;              // the uploads; an evaluation runs on the ranker's stream
+    int nu = 0;
+    size_t total = 0, max_held = 0;
+    bool has_excl = false;
+    std::vector<int> users_host, held_host, excl_host;     // host copies: the gather of cmfrec_hip_ranker_metrics, rankset_usable
+    std::vector<size_t> held_p_host, excl_p_host;
+    int max_user = -1;
+    DevBuf<int> users, held_i, excl_i;
+    DevBuf<size_t> held_p, excl_p;
+    int table_k = 0;                           // the cut-off disc / ideal were made for (0: none yet)
+    DevBuf<double> disc, ideal, per_user;
+    DevBuf<real_t> A;                          // [nu, k] rows of the set's users
+    DevBuf<cmfrec_hip_rank_record> partials;
+    ~cmfrec_hip_rankset() { if (stream) (void)hipStreamDestroy(stream); }
+};
+
+namespace cmfhip {
+
+// The metrics of a set whose users' factors dA [nu, lda] are on the device, on the ranker's stream: the rank kernel, then the
+// reduction; one synchronisation.  per_user [nu, 8] / out_rank [total]: optional host outputs.
+int rankset_run(cmfrec_hip_ranker *r, cmfrec_hip_rankset *set, const char *fn, const real_t *dA, size_t lda, int k_at,
+                cmfrec_hip_rank_record *out, double *per_user, int_t *out_rank)
+{
+    if (r == nullptr || set == nullptr || out == nullptr || dA == nullptr || k_at < 1 || lda < (size_t)r->k) {
+        g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    if (set->device != r->dev.device) {
+        g_last_error = std::string(fn) + ": the ranking set lives on device " + std::to_string(set->device) + ", the items on device " +
+                       std::to_string(r->dev.device);
+        return 2;
+    }
+    DeviceScope scope(r->dev.device);
+    switches_mut().reload();
+    hipStream_t st = r->dev.stream;
+    memset(out, 0, sizeof *out);
+    if (set->nu == 0) return 0;
+    if (set->table_k != k_at) {
+        // the discounts and the ideal sums as NumPy forms them: 1 / log2(j + 1) for j = 1 .. k, and their running sums
+        std::vector<double> disc((size_t)k_at), ideal((size_t)k_at + 1, 0.0);
+        for (int j = 1; j <= k_at; j++) { disc[j - 1] = 1.0 / std::log2((double)j + 1.0); ideal[j] = ideal[j - 1] + disc[j - 1]; }
+        set->disc.upload(disc.data(), disc.size(), st);
+        set->ideal.upload(ideal.data(), ideal.size(), st);
+        HIP_CHECK(hipStreamSynchronize(st));                 // the vectors go away
+        set->table_k = k_at;
+    }
+    if (int rc = ranks_device(r, dA, lda, set->nu, set->total, set->max_held, set->has_excl ? set->excl_p.ptr : nullptr,
+                              set->has_excl ? set->excl_i.ptr : nullptr, nullptr, nullptr, nullptr, set->held_p.ptr, set->held_i.ptr, true))
+        return rc;
+    const char *cap = getenv("CMFREC_HIP_RANKMETRIC_WAVES");            // test hook, read per call
+    const int max_waves = (cap != nullptr && cap[0] != 0) ? atoi(cap) : 0;
+    const size_t waves = rank_metrics_waves(set->nu, r->dev.num_cus, max_waves);
+    set->partials.alloc_at_least(waves + 1);
+    if (per_user) set->per_user.alloc_at_least((size_t)set->nu * RANKM_METRICS);
+    RankMetricParams P;
+    P.ranks = r->ids.ptr; P.pool = r->pool.ptr; P.held_p = set->held_p.ptr; P.nu = set->nu; P.k_at = k_at;
+    P.disc = set->disc.ptr; P.ideal = set->ideal.ptr; P.per_user = per_user ? set->per_user.ptr : nullptr; P.partials = set->partials.ptr;
+    launch_rank_metrics(st, waves, P);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, set->partials.ptr + waves, sizeof *out, hipMemcpyDeviceToHost, st));
+    if (per_user) set->per_user.download(per_user, (size_t)set->nu * RANKM_METRICS, st);
+    if (out_rank && set->total > 0) r->ids.download(out_rank, set->total, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// dst [nu, k] = the rows users[0 .. nu) of src [., lds], columns [0, k)
+__global__ void gather_user_rows_kernel(real_t *__restrict__ dst, const real_t *__restrict__ src, size_t lds, const int *__restrict__ users,
+                                        int nu, int k)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)nu * (size_t)k) return;
+    const size_t u = i / (size_t)k, c = i % (size_t)k;
+    dst[i] = src[(size_t)users[u] * lds + c];
+}
+
+// what a fit asks of the set it is to watch before it writes anything (cmfrec_hip_fit_set_monitor): the set lives on `device`
+// (< 0: the current one), kk fits the rank kernel, every user is a row of A, and at least one user has a held-out item inside
+// [0, n) that its exclusion list does not take away (T > 0) -- from the set's host copies.  0, or 2 with fn's name in the message.
+int rankset_usable(cmfrec_hip_rankset *set, const char *fn, int device, int_t m, int_t n, int_t kk, int k_at)
+{
+    if (set == nullptr || k_at < 1) {
+        g_last_error = std::string(fn) + ": the monitor needs a ranking set and k_at >= 1";
+        return 2;
+    }
+    if (device < 0) HIP_CHECK(hipGetDevice(&device));
+    if (set->device != device) {
+        g_last_error = std::string(fn) + ": the ranking set lives on device " + std::to_string(set->device) + ", the fit runs on device " +
+                       std::to_string(device);
+        return 2;
+    }
+    if (kk > TOPNW_KMAX) {
+        g_last_error = std::string(fn) + ": a ranking watch " + RANK_LIMITS + " (k + k_main)";
+        return 2;
+    }
+    if (set->max_user >= m) {
+        g_last_error = std::string(fn) + ": the ranking set names user " + std::to_string(set->max_user) + ", X has " + std::to_string(m) + " rows";
+        return 2;
+    }
+    for (int u = 0; u < set->nu; u++)
+        for (size_t e = set->held_p_host[u]; e < set->held_p_host[u + 1]; e++) {
+            const int item = set->held_host[e];
+            if (item < 0 || item >= n) continue;
+            if (set->has_excl && std::binary_search(set->excl_host.begin() + set->excl_p_host[u], set->excl_host.begin() + set->excl_p_host[u + 1], item))
+                continue;
+            return 0;
+        }
+    g_last_error = std::string(fn) + ": no user of the ranking set has a held-out item that can be ranked: nothing to watch";
+    return 2;
+}
+
+// The metrics of a set against factors that are on the device (cmfrec_hip_session_ranking): A [m, ldA] and B [n, ldB] point at the
+// first ranked column, kk wide.  *owned: a ranker the caller keeps between calls -- made from B on the first call, refreshed
+// from B on every later one by a device-to-device column copy into its padded layout (topnw_kp), no host round trip.  The users'
+// rows are gathered on the device.  The caller has synchronised the stream that wrote the factors.
+int rankset_run_on_factors(cmfrec_hip_ranker **owned, cmfrec_hip_rankset *set, const char *fn, int device, const real_t *dA, size_t ldA, int_t m,
+                           const real_t *dB, size_t ldB, int_t n, int_t kk, const real_t *dbiasB, int k_at, cmfrec_hip_rank_record *out)
+{
+    if (owned == nullptr || set == nullptr || out == nullptr || k_at < 1) {
+        g_last_error = std::string(fn) + ": invalid arguments";
+        return 2;
+    }
+    if (kk > TOPNW_KMAX) {
+        g_last_error = std::string(fn) + ": " + RANK_LIMITS;
+        return 2;
+    }
+    if (set->device != device) {
+        g_last_error = std::string(fn) + ": the ranking set lives on device " + std::to_string(set->device) + ", the factors on device " +
+                       std::to_string(device);
+        return 2;
+    }
+    if (set->max_user >= m) {
+        g_last_error = std::string(fn) + ": the ranking set names user " + std::to_string(set->max_user) + ", A has " + std::to_string(m) + " rows";
+        return 2;
+    }
+    cmfrec_hip_ranker *r = *owned;
+    if (r == nullptr) {
+        r = *owned = cmfrec_hip_ranker_create(dB, ldB, n, kk, dbiasB, device);
+        if (r == nullptr) return g_last_rc ? g_last_rc : 4;
+    } else {
+        DeviceScope scope(device);
+        upload_columns(r->B.ptr, r->ldb, dB, ldB, (size_t)n, (size_t)kk, r->dev.stream);
+        if (dbiasB) r->bias.upload(dbiasB, (size_t)n, r->dev.stream);
+    }
+    memset(out, 0, sizeof *out);
+    if (set->nu == 0) return 0;
+    DeviceScope scope(device);
+    set->A.alloc_at_least((size_t)set->nu * (size_t)kk);
+    const size_t cells = (size_t)set->nu * (size_t)kk;
+    hipLaunchKernelGGL(gather_user_rows_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, r->dev.stream, set->A.ptr, dA, ldA,
+                       set->users.ptr, set->nu, (int)kk);
+    HIP_CHECK(hipGetLastError());
+    return rankset_run(r, set, fn, set->A.ptr, (size_t)kk, k_at, out, nullptr, nullptr);
+}
+
+}  // namespace cmfhip
 
 static_assert(TOPNC_KMAX == TOPNW_KMAX, "topn_cand_kernel holds a user's row of the widest model in registers");
 
@@ -387,6 +557,91 @@ int cmfrec_hip_ranker_ranks(cmfrec_hip_ranker *r, const real_t *A, size_t lda, i
         }
         return ranks_device(r, r->A.ptr, (size_t)k, nu, held_p[nu], max_held, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr,
                             out_rank, out_scores, out_pool);
+    });
+}
+
+cmfrec_hip_rankset *cmfrec_hip_rankset_create(const int_t *users, int_t nu, const size_t *held_p, const int_t *held_i,
+                                              const size_t *excl_p, const int_t *excl_i, int device)
+{
+    const char *fn = "cmfrec_hip_rankset_create";
+    cmfrec_hip_rankset *set = nullptr;
+    const int rc = guarded([&]() {
+        bool bad = nu < 0 || (nu > 0 && (users == nullptr || held_p == nullptr));
+        size_t longest = 0;
+        int max_user = -1;
+        for (int_t u = 0; !bad && u < nu; u++) {
+            bad = users[u] < 0 || held_p[u] > held_p[u + 1] || (excl_p != nullptr && excl_p[u] > excl_p[u + 1]);
+            if (!bad) { longest = std::max(longest, held_p[u + 1] - held_p[u]); max_user = std::max(max_user, (int)users[u]); }
+        }
+        if (!bad && nu > 0)
+            bad = held_p[0] != 0 || longest > (size_t)0x7fffffff || (held_p[nu] > 0 && held_i == nullptr) ||
+                  (excl_p != nullptr && (excl_p[0] != 0 || (excl_p[nu] > 0 && excl_i == nullptr)));
+        if (bad) {
+            g_last_error = std::string(fn) + ": invalid arguments (user ids >= 0; held-out and exclusion lists a CSR over the users)";
+            return 2;
+        }
+        set = new cmfrec_hip_rankset();
+        open_device(device, &set->device, &set->num_cus, &set->stream);
+        set->nu = nu; set->max_held = longest; set->max_user = max_user;
+        if (nu == 0) return 0;
+        set->total = held_p[nu];
+        set->users_host.assign(users, users + nu);
+        set->held_p_host.assign(held_p, held_p + nu + 1);
+        if (set->total > 0) set->held_host.assign(held_i, held_i + set->total);
+        if (excl_p) {
+            set->excl_p_host.assign(excl_p, excl_p + nu + 1);
+            if (excl_p[nu] > 0) set->excl_host.assign(excl_i, excl_i + excl_p[nu]);
+        }
+        set->users.upload(set->users_host.data(), (size_t)nu, set->stream);
+        set->held_p.upload(held_p, (size_t)nu + 1, set->stream);
+        set->held_i.alloc(std::max<size_t>(set->total, 1));
+        if (set->total > 0) set->held_i.upload(held_i, set->total, set->stream);
+        set->has_excl = excl_p != nullptr;
+        if (excl_p) {
+            set->excl_p.upload(excl_p, (size_t)nu + 1, set->stream);
+            set->excl_i.alloc(std::max<size_t>(excl_p[nu], 1));
+            if (excl_p[nu] > 0) set->excl_i.upload(excl_i, excl_p[nu], set->stream);
+        }
+        HIP_CHECK(hipStreamSynchronize(set->stream));        // the caller's arrays may go away
+        return 0;
+    });
+    g_last_rc = rc;
+    if (rc != 0) {
+        delete set;
+        return nullptr;
+    }
+    return set;
+}
+
+void cmfrec_hip_rankset_destroy(cmfrec_hip_rankset *set)
+{
+    if (set == nullptr) return;
+    (void)hipSetDevice(set->device);
+    delete set;
+}
+
+int cmfrec_hip_ranker_metrics(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t m, cmfrec_hip_rankset *set, int k_at,
+                              cmfrec_hip_rank_record *out, double *per_user, int_t *out_rank)
+{
+    const char *fn = "cmfrec_hip_ranker_metrics";
+    return guarded([&]() {
+        if (r == nullptr || set == nullptr || A == nullptr || out == nullptr || k_at < 1 || lda < (size_t)r->k) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if (set->max_user >= m) {
+            g_last_error = std::string(fn) + ": the ranking set names user " + std::to_string(set->max_user) + ", A has " + std::to_string(m) + " rows";
+            return 2;
+        }
+        if (set->device != r->dev.device) return rankset_run(r, set, fn, A, lda, k_at, out, per_user, out_rank);   // (refused there)
+        DeviceScope scope(r->dev.device);
+        const size_t k = (size_t)r->k;
+        std::vector<real_t> rows((size_t)set->nu * k);
+        for (int u = 0; u < set->nu; u++) memcpy(rows.data() + (size_t)u * k, A + (size_t)set->users_host[u] * lda, k * sizeof(real_t));
+        set->A.alloc_at_least(std::max<size_t>(rows.size(), 1));
+        if (!rows.empty()) HIP_CHECK(hipMemcpyAsync(set->A.ptr, rows.data(), rows.size() * sizeof(real_t), hipMemcpyHostToDevice, r->dev.stream));
+        HIP_CHECK(hipStreamSynchronize(r->dev.stream));      // `rows` goes away
+        return rankset_run(r, set, fn, set->A.ptr, k, k_at, out, per_user, out_rank);
     });
 }
 

@@ -98,6 +98,17 @@ def error_metrics(rec, include_fallback=True):
     return out
 
 
+def mean_from_record(rec):
+    """What ``mean_metrics(ranking_metrics(...))`` returns, from the record of a reduction on the device (``Ranker.metrics``,
+    ``AlsSession.ranking``): per metric ``sum / count`` over the users that count (NaN where none does), and ``users``."""
+    res = {}
+    for i, name in enumerate(METRICS):
+        cnt = int(rec["count"][i])
+        res[name] = float(np.float64(rec["sum"][i]) / np.float64(cnt)) if cnt else float("nan")
+    res["users"] = int(rec["users"])
+    return res
+
+
 def mean_metrics(per_user):
     """The means over the users with held-out items (NaN entries left out) and ``users``, their number."""
     res = {}

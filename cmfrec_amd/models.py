@@ -313,6 +313,24 @@ def _side_info(M, dt):
     return np.ascontiguousarray(M, dt), None
 
 
+def _monitored(watch, fit, *args):
+    """The fit call of ``fit(..., validation=)``: whatever it does, the monitor and its resident set do not outlive it."""
+    try:
+        return fit(*args)
+    finally:
+        if watch is not None:
+            watch.close()
+
+
+def _validation_results(self, watch):
+    """``validation_history_`` / ``validation_records_`` / ``best_iteration_`` / ``n_iter_`` of a fit (``watch`` None: a fit
+    without validation)."""
+    if watch is None:
+        self.validation_history_, self.validation_records_, self.best_iteration_, self.n_iter_ = [], [], None, self.niter
+    else:
+        self.validation_history_, self.validation_records_, self.best_iteration_, self.n_iter_ = watch.results()
+
+
 def _penalty(value, name):
     """``lambda_`` / ``l1_lambda``: a number, or six numbers (user bias, item bias, A, B, C, D) like the reference
     (cmfrec/__init__.py:99-101).  Returns (scalar, array-or-None); with an array the scalar handed to C is 0, as the
@@ -354,10 +372,12 @@ class CMF_implicit(_Base):
         self.nonneg_C = bool(nonneg_C); self.nonneg_D = bool(nonneg_D); self.max_cd_steps = int(max_cd_steps)
         self.l1_lambda, self._l16 = _penalty(l1_lambda, "l1_lambda")
 
-    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None):
+    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, validation=None):
         """Fits the model.  ``A0``/``B0`` (optional) inject the start values instead of drawing
         them from ``random_state`` (C argument ``reset_values=false``).  ``U`` / ``I``: dense side
-        information without missing values, or SciPy sparse matrices (missing = absent)."""
+        information without missing values, or SciPy sparse matrices (missing = absent).
+        ``validation``: a ``cmfrec_amd.Validation`` -- a held-out set evaluated on the device while fitting, early stopping and the
+        best iterate (default metric "ndcg" at ``k=10``, the training items left out of every ranking)."""
         row, col, val, m, n = _coo_triplet(X, shape)
         lib, R = self._lib()
         dt = self.dtype_
@@ -388,7 +408,8 @@ class CMF_implicit(_Base):
         BeTBe = np.zeros((kq, kq), dt) if (pre and p) else None
         BeTBeChol = np.zeros((kq, kq), dt) if (pre and p) else None
         CtUbias = np.zeros(self.k_user + self.k, dt) if (pre and p and Us is not None and self.NA_as_zero_user) else None
-        rc = lib.fit_collective_implicit_als(
+        watch = None if validation is None else validation._begin(lib, dt, self.niter, "ndcg", (row, col, m, n))
+        rc = _monitored(watch, lib.fit_collective_implicit_als,
             _lib.ptr(A), _lib.ptr(B), _lib.ptr(Cm), _lib.ptr(Dm), C.c_bool(reset), C.c_int(self.random_state),
             _lib.ptr(Ucm) if (p and self.center_U) else None, _lib.ptr(Icm) if (q and self.center_I) else None,
             C.c_int(m), C.c_int(n), C.c_int(self.k), _lib.ptr(row), _lib.ptr(col), _lib.ptr(val),
@@ -406,6 +427,7 @@ class CMF_implicit(_Base):
         # an interrupted fit returns 3 with usable factors; like the reference's wrapper, raise only when the caller did
         # not ask for the interrupt to be handled (cmfrec/wrapper_untyped.pxi: `if ret_code == 3 and not handle_interrupt`)
         _lib.check(rc, lib, "fit_collective_implicit_als", interrupt_ok=self.handle_interrupt)
+        _validation_results(self, watch)
         self.A_, self.B_ = A, B
         self.C_ = Cm if Cm is not None else np.empty((0, 0), dt)
         self.D_ = Dm if Dm is not None else np.empty((0, 0), dt)
@@ -564,10 +586,12 @@ class CMF(_Base):
         self.handle_interrupt = bool(handle_interrupt)
         self._setup(use_float, nthreads, n_jobs)
 
-    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, biasA0=None, biasB0=None, W=None):
+    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, biasA0=None, biasB0=None, W=None, validation=None):
         """``X``: SciPy sparse matrix / COO triplet, or a dense 2-D array with NaN for the missing entries (the plain model:
         no side information).  ``W``: observation weights, one per entry of ``X`` in its COO order (reference
-        ``CMF.fit(X, ..., W=...)``, cmfrec/__init__.py:3066; an array(nnz,) for sparse ``X``, an array(m, n) for dense ``X``)."""
+        ``CMF.fit(X, ..., W=...)``, cmfrec/__init__.py:3066; an array(nnz,) for sparse ``X``, an array(m, n) for dense ``X``).
+        ``validation``: a ``cmfrec_amd.Validation`` -- a held-out set evaluated on the device while fitting (default metric
+        "rmse"), early stopping and the best iterate; the model then has ``validation_history_``, ``best_iteration_``, ``n_iter_``."""
         lib, R = self._lib()
         dt = self.dtype_
         Xfull = None
@@ -627,7 +651,9 @@ class CMF(_Base):
             raise NotImplementedError("NA_as_zero with side information or implicit features: precompute_for_predictions is not "
                                       "implemented in cmfrec_amd (pass False)")
         BtXbias = np.zeros(kp, dt) if (pre and self.NA_as_zero) else None       # reference attribute BtXbias_ (cmfrec/__init__.py)
-        rc = lib.fit_collective_explicit_als(
+        watch = None if validation is None else validation._begin(
+            lib, dt, self.niter, "rmse", (row, col, m, n) if Xfull is None else (*np.nonzero(~np.isnan(Xfull)), m, n))
+        rc = _monitored(watch, lib.fit_collective_explicit_als,
             _lib.ptr(biasA), _lib.ptr(biasB), _lib.ptr(A), _lib.ptr(B), _lib.ptr(Cm), _lib.ptr(Dm), _lib.ptr(Ai), _lib.ptr(Bi),
             C.c_bool(imp), C.c_bool(reset), C.c_int(self.random_state), _lib.ptr(glob_mean),
             # no column means = the side information is used as given (cmfrec/__init__.py passes an empty array for center_U=False)
@@ -648,6 +674,7 @@ class CMF(_Base):
             C.c_bool(pre), C.c_bool(True), _lib.ptr(Bpb), _lib.ptr(BtB), _lib.ptr(TBt), _lib.ptr(BtXbias), _lib.ptr(BeChol), None,
             _lib.ptr(TCt), _lib.ptr(CtCw), _lib.ptr(CtUbias))
         _lib.check(rc, lib, "fit_collective_explicit_als", interrupt_ok=self.handle_interrupt)
+        _validation_results(self, watch)
         # precomputed matrices for predictions on new data, reference attribute names (cmfrec/__init__.py:3211-3247)
         e = np.empty((0, 0), dt)
         self._B_plus_bias = Bpb if Bpb is not None else e

@@ -9,6 +9,69 @@ from . import _lib
 from .ops import _heldout_lists, _is_csr, _sorted_exclude, _sorted_include
 
 
+def check_rankset(users, heldout, exclude):
+    """The arrays of a ``RankSet``, checked without a device: (users int32 [nu], held_p uint64, held_i int32, excl_p, excl_i) --
+    ``heldout`` / ``exclude`` as ``Ranker.ranks`` takes them, over the users of the set; the exclusion lists come out sorted."""
+    users = np.atleast_1d(np.asarray(users))
+    if users.ndim != 1 or (len(users) and not np.issubdtype(users.dtype, np.integer)):
+        raise ValueError("RankSet: users must be a 1-D array of integer ids")
+    if len(users) and (users.min() < 0 or users.max() > np.iinfo(np.int32).max):
+        raise ValueError("RankSet: user ids must be >= 0 and fit 32 bits")
+    users = np.ascontiguousarray(users, np.int32)
+    nu = len(users)
+    if _is_csr(heldout):
+        heldout = (heldout.indptr, heldout.indices)
+    hp, hi = _heldout_lists(heldout, nu, "RankSet")
+    if exclude is not None and _is_csr(exclude):
+        exclude = (exclude.indptr, exclude.indices)
+    ep, ei = _sorted_exclude(exclude, nu)
+    return users, hp, hi, ep, ei
+
+
+class RankSet:
+    """``RankSet(users, heldout, exclude=None, dtype=np.float64, device=-1)``: user ids, their held-out lists and (optionally) their
+    exclusion lists -- (indptr, indices) CSR over the users OF THE SET or a SciPy CSR matrix of that many rows -- uploaded once and
+    resident on the device (``cmfrec_hip_rankset_*``) for ``Ranker.metrics`` / ``AlsSession.ranking`` of the same dtype.  The
+    caller owns the handle: ``close()`` it, or use it as a context manager."""
+
+    def __init__(self, users, heldout, exclude=None, dtype=np.float64, device=-1):
+        self.handle = None
+        users, hp, hi, ep, ei = check_rankset(users, heldout, exclude)
+        self.dtype = np.dtype(dtype)
+        self.nu = len(users)
+        self.indptr = hp.astype(np.int64)           # the normalised lists (sorted, de-duplicated) the ranks line up with
+        self.items = hi
+        self.lib = _lib.load(self.dtype)
+        h = self.lib.cmfrec_hip_rankset_create(_lib.ptr(users), self.nu, _lib.ptr(hp), _lib.ptr(hi), _lib.ptr(ep), _lib.ptr(ei), int(device))
+        if not h:
+            _lib.check(self.lib.cmfrec_hip_last_error_code() or 4, self.lib, "RankSet")
+        self.handle = C.c_void_p(h)
+
+    def _for(self, dtype, what):
+        if not getattr(self, "handle", None):
+            raise RuntimeError("RankSet: the handle is closed")
+        if np.dtype(dtype) != self.dtype:
+            raise ValueError("%s: the ranking set is %s, the factors are %s" % (what, self.dtype, np.dtype(dtype)))
+        return self.handle
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.cmfrec_hip_rankset_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Ranker:
     """``Ranker(B, biasB=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype or None.
     ``topN(A, n=10, exclude=None, include=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns the handle:
@@ -100,6 +163,32 @@ class Ranker:
         if return_scores:
             return hp.astype(np.int64), hi, ranks, pool, sc
         return hp.astype(np.int64), hi, ranks, pool
+
+    def metrics(self, A, rankset, k=10, per_user=False, return_ranks=False):
+        """The ranking metrics of a resident ``RankSet`` at cut-off ``k``, reduced on the device: ``A`` [m, k] holds the factors
+        of ALL users, the set's user ids pick its rows.  Returns the record -- ``sum`` [8] and ``count`` [8] in the order of
+        ``cmfrec_amd.metrics.METRICS`` and ``users``; ``metrics.mean_from_record`` turns it into the means.  ``per_user``: a second
+        value, the eight values per user [users of the set, 8] (NaN where the user does not count); ``return_ranks``: one more,
+        the ranks of the held-out entries as ``ranks`` returns them."""
+        h = self._live()
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[1] != self.k:
+            raise ValueError("Ranker.metrics: A must be [users, %d], got shape %s" % (self.k, A.shape))
+        if A.dtype != self.dtype:
+            raise ValueError("Ranker.metrics: A is %s, the ranker's items are %s" % (A.dtype, self.dtype))
+        if not isinstance(rankset, RankSet):
+            raise TypeError("Ranker.metrics: a RankSet is required")
+        if int(k) < 1:
+            raise ValueError("Ranker.metrics: k must be at least 1")
+        A = np.ascontiguousarray(A)
+        rec = _lib.RankRecord()
+        pu = np.empty((rankset.nu, 8), np.float64) if per_user else None
+        rk = np.empty(int(rankset.indptr[-1]) if rankset.nu else 0, np.int32) if return_ranks else None
+        rc = self.lib.cmfrec_hip_ranker_metrics(h, _lib.ptr(A), A.shape[1], A.shape[0], rankset._for(self.dtype, "Ranker.metrics"), int(k),
+                                                C.byref(rec), _lib.ptr(pu), _lib.ptr(rk))
+        _lib.check(rc, self.lib, "Ranker.metrics")
+        out = (rec.as_dict(),) + ((pu,) if per_user else ()) + ((rk,) if return_ranks else ())
+        return out[0] if len(out) == 1 else out
 
     def kernel_ms(self):
         """HIP-event time (ms) of the ranking kernel of the most recent ``topN`` or ``ranks`` call (of ``ranks``: the whole rank

@@ -265,6 +265,30 @@ class AlsSession:
         _lib.check(rc, self.lib, "AlsSession.errors")
         return rec.as_dict()
 
+    def ranking(self, rankset, k=10):
+        """The ranking-metric record (``Ranker.metrics``) of the session's current factors on a resident ``cmfrec_amd.RankSet``:
+        the set's users' rows of A are gathered on the device, a ranker the session owns takes B (and an explicit model's item
+        bias) where it lives, the ranks are reduced on the device.  Nothing in the session changes."""
+        from .rank import RankSet
+        if not isinstance(rankset, RankSet):
+            raise TypeError("AlsSession.ranking: a RankSet is required")
+        if not self.handle:
+            raise RuntimeError("AlsSession: the handle is closed")
+        rec = _lib.RankRecord()
+        rc = self.lib.cmfrec_hip_session_ranking(self.handle, rankset._for(self.dtype, "AlsSession.ranking"), int(k), C.byref(rec))
+        _lib.check(rc, self.lib, "AlsSession.ranking")
+        return rec.as_dict()
+
+    def snapshot(self):
+        """Keeps a second copy of the factors as they are now -- everything ``get_factors`` and ``get_implicit_features`` return --
+        on the device (allocated on first use; device-to-device copies on the session's stream).  A later snapshot replaces it."""
+        _lib.check(self.lib.cmfrec_hip_session_snapshot(self.handle), self.lib, "AlsSession.snapshot")
+
+    def restore(self):
+        """Puts the factors of the last ``snapshot`` back, bit for bit; the next update starts from them.  Without a snapshot, and
+        on a session that does not own all rows, a ``RuntimeError`` (code 2)."""
+        _lib.check(self.lib.cmfrec_hip_session_restore(self.handle), self.lib, "AlsSession.restore")
+
     def sync(self):
         _lib.check(self.lib.cmfrec_hip_session_sync(self.handle), self.lib, "sync")
 

@@ -850,6 +850,121 @@ void cmfrec_hip_evalset_destroy(cmfrec_hip_evalset *e);
 int cmfrec_hip_scorer_errors(cmfrec_hip_scorer *s, cmfrec_hip_evalset *e, cmfrec_hip_errors *out);
 int cmfrec_hip_session_errors(cmfrec_hip_session *s, cmfrec_hip_evalset *e, real_t glob_mean, cmfrec_hip_errors *out);
 
+/* Going back to an earlier iterate.  snapshot: a second set of device buffers, allocated on first use,
+ * takes everything cmfrec_hip_session_get_factors and _get_implicit_features return -- A, B, the biases, C, D, Ai, Bi -- by
+ * device-to-device copies on the session's stream, behind the updates queued there; a later snapshot overwrites it.  restore:
+ * the copies the other way round; the factors then are bit for bit those of the snapshot, and the next update starts from them.
+ * Neither synchronises.  2 with a message: restore without a snapshot, and either call on a session that does not own all rows
+ * (a shard of a multi-device fit), as cmfrec_hip_session_errors. */
+int cmfrec_hip_session_snapshot(cmfrec_hip_session *s);
+int cmfrec_hip_session_restore(cmfrec_hip_session *s);
+
+/* Validation while fitting: a held-out set is evaluated where the factors are, between the iterations
+ * of fit_collective_explicit_als / fit_collective_implicit_als, and the fit may stop early and return its best iterate.  The
+ * signatures of those two functions do not change: the monitor is handed over beforehand,
+ *   cmfrec_hip_fit_set_monitor(&mon);  fit_collective_explicit_als(...);
+ * It is kept per thread (the struct is copied, the arrays it points to are the caller's) and is consumed by the next of the two
+ * fit calls on that thread, whatever that call returns; NULL clears it.  A fit without a monitor runs exactly as before.
+ *   evalset      a resident held-out set (cmfrec_hip_evalset_create, the fit's precision), evaluated as
+ *                cmfrec_hip_session_errors does: the biases and the global mean of the explicit model, the implicit rule; or
+ *   rankset      a resident ranking set (cmfrec_hip_rankset_create below) with its cut-off k_at, evaluated as
+ *                cmfrec_hip_session_ranking does.  Exactly one of the two.
+ *   metric       what is watched.  From an evalset, both classes of the record together as cmfrec_amd.metrics.error_metrics
+ *                forms them: CMFREC_HIP_WATCH_RMSE  sqrt(S(w e^2) / S(w)),  CMFREC_HIP_WATCH_MAE  S(w |e|) / S(w); lower is better.
+ *                From a rankset, sum / count of the record: CMFREC_HIP_WATCH_HIT, _PRECISION, _RECALL, _AP, _NDCG, _RR, _AUC
+ *                (higher is better) and _MEAN_RANK (lower is better); NaN where no user counts
+ *   every        evaluate after iterations every, 2 every, ... (1-based) and after the last one; < 1 counts as 1
+ *   patience     stop once that many evaluations in a row have not improved; <= 0: never stop (monitor only)
+ *   min_delta    an evaluation improves when it beats the best so far by more than this (the first one always does); NaN never does
+ *   restore_best != 0: every improvement takes a cmfrec_hip_session_snapshot, and when the loop ends -- stopped or run to niter --
+ *                on a later iterate than the best one, cmfrec_hip_session_restore runs right after the loop, before anything reads
+ *                the factors: A, B, the biases, C, D, Ai, Bi and every precompute_for_predictions output then come from the best
+ *                iterate.  0: the last iterate is returned, stopped or not.
+ *   values       [niter] out, optional: the watched value per iteration, NaN where the iteration was not evaluated or not run
+ *   records      [niter] out, optional, with an evalset: the full record per evaluated iteration (the others are zeroed)
+ *   rank_records [niter] out, optional, with a rankset: the same
+ *   iters_run    out, optional: the iterations that ran;  best_iter  out, optional: the 0-based iteration of the best evaluation,
+ *                -1 when none improved (every value NaN)
+ * finalize_chol keeps its meaning: the Cholesky pass belongs to iteration niter - 1 alone; a fit that stops before it does not
+ * add one, and a fit that ran it but restores an earlier iterate returns conjugate-gradient factors.  An interrupt (return 3)
+ * leaves the iterate it was at; iters_run and best_iter are still written.
+ * Refused with 2 and a message (cmfrec_hip_last_error), before the fit writes to any of its outputs: niter < 1; an unknown metric;
+ * CMFREC_HIP_DEVICES naming several devices or CMFREC_HIP_SHARDED=1 (the sharded driver and every fit that would fall back from
+ * it); both sets or none; a metric that does not belong to the set; a set on another device than the fit's; an evalset without a
+ * single pair inside the m x n of X whose value is not NaN; a rankset with k + k_main > 272, with a user beyond the rows of X, or
+ * in which no user has a held-out item inside the n items that its exclusion list leaves (no user with T > 0).
+ * verbose prints the watched value per evaluated iteration.
+ * cmfrec_hip_early_stop_step is that rule alone, host only, for the loop above and for tests.  The caller zeroes the struct, sets
+ * every / patience / min_delta / higher_is_better and best_iter = -1.  With value == NULL it returns CMFREC_HIP_STEP_EVALUATE when
+ * 0-based iteration `iter` of `niter` is one to evaluate, else 0.  With a value it books the evaluation and returns a mask of
+ * CMFREC_HIP_STEP_IMPROVED (best / best_iter updated, misses = 0) and CMFREC_HIP_STEP_STOP (misses has reached patience). */
+#define CMFREC_HIP_WATCH_RMSE 0
+#define CMFREC_HIP_WATCH_MAE 1
+#define CMFREC_HIP_WATCH_HIT 2          /* 2 .. 9: from a rankset, the metric's place in cmfrec_hip_rank_record + 2 */
+#define CMFREC_HIP_WATCH_PRECISION 3
+#define CMFREC_HIP_WATCH_RECALL 4
+#define CMFREC_HIP_WATCH_AP 5
+#define CMFREC_HIP_WATCH_NDCG 6
+#define CMFREC_HIP_WATCH_RR 7
+#define CMFREC_HIP_WATCH_AUC 8
+#define CMFREC_HIP_WATCH_MEAN_RANK 9
+#define CMFREC_HIP_STEP_IMPROVED 1
+#define CMFREC_HIP_STEP_STOP 2
+#define CMFREC_HIP_STEP_EVALUATE 4
+typedef struct cmfrec_hip_rankset cmfrec_hip_rankset;          /* the ranking set and its record: described below */
+typedef struct cmfrec_hip_rank_record {
+    double sum[8]; uint64_t count[8]; uint64_t users;
+} cmfrec_hip_rank_record;
+typedef struct cmfrec_hip_fit_monitor {
+    cmfrec_hip_evalset *evalset;
+    cmfrec_hip_rankset *rankset;
+    int metric, k_at, every, patience, restore_best;
+    double min_delta;
+    double *values;
+    cmfrec_hip_errors *records;
+    cmfrec_hip_rank_record *rank_records;
+    int *iters_run, *best_iter;
+} cmfrec_hip_fit_monitor;
+typedef struct cmfrec_hip_early_stop {
+    int every, patience, higher_is_better;
+    double min_delta;
+    double best;
+    int best_iter, misses;
+} cmfrec_hip_early_stop;
+int cmfrec_hip_fit_set_monitor(const cmfrec_hip_fit_monitor *monitor);
+
+/* The ranking metrics of held-out items, reduced on the device (rank_metrics_kernels.hpp).  A ranking set
+ * -- nu user ids, their held-out lists (CSR over the nu users) and, optionally, their exclusion lists (CSR over the nu users, each
+ * list sorted ascending, as cmfrec_hip_ranker_ranks takes them) -- goes to the device once and stays there.  An evaluation ranks
+ * the held-out items (topn_rank_kernel, the ranks cmfrec_hip_ranker_ranks returns, bit for bit) and reduces them where they are:
+ * per user exactly the quantities of cmfrec_amd.metrics.ranking_metrics at cut-off k_at -- hit, precision, recall, ap, ndcg, rr,
+ * auc, mean_rank, in this order -- and over the users one record: per metric the float64 sum over the users that count and their
+ * number (a user without a valid held-out item counts nowhere, a user whose pool holds nothing but its held-out items not in
+ * auc), and `users`, the users with a valid held-out item.  A mean is sum / count.  The NDCG discounts and ideal sums come from
+ * two tables the host computes in float64 with libm's log2, as NumPy forms them; the sums are added in an order that depends on the
+ * device and the launch, not on the run: the same call returns the same bytes (no atomics).
+ * The place of a rank among a user's own ranks is counted, not sorted: the work per user grows with the square of its list
+ * (fine for the tens to hundreds of held-out items of an evaluation; a list of tens of thousands makes its user the launch's tail).
+ * rankset_create: NULL on failure (cmfrec_hip_last_error_code: 2 for lists that are not a CSR or a negative user id, 1 for no room).
+ * ranker_metrics: A [m, lda] on the host, the rows of the set's users are taken from it (2 for a user id >= m); per_user [nu, 8]
+ *   and out_rank [held_p[nu]] optional outputs.  2 when the set lives on another device than the ranker.
+ * CMFREC_HIP_RANKMETRIC_WAVES (read per call): at most that many wavefronts, rounded up to whole workgroups, in the metric launch,
+ *   so that a small set gives a wavefront several users in a row (test hook; 0: one wavefront per user up to what the device runs).
+ * cmfrec_hip_rank_record (declared above, before the monitor that points to it): double sum[8]; uint64_t count[8]; uint64_t users. */
+cmfrec_hip_rankset *cmfrec_hip_rankset_create(const int_t *users, int_t nu, const size_t *held_p, const int_t *held_i,
+                                              const size_t *excl_p, const int_t *excl_i, int device);
+void cmfrec_hip_rankset_destroy(cmfrec_hip_rankset *set);
+int cmfrec_hip_ranker_metrics(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t m, cmfrec_hip_rankset *set, int k_at,
+                              cmfrec_hip_rank_record *out, double *per_user, int_t *out_rank);
+/* session_ranking: the counterpart of cmfrec_hip_session_errors -- the record of the session's factors as they are on the device
+ * (the columns behind k_user / k_item, k + k_main wide; an explicit model's item bias is added to the scores as
+ * cmfrec_hip_ranker_create's biasB is).  The rows of the set's users are gathered on the device; a ranker the session owns takes B
+ * by a device-to-device column copy into its padded layout on every call, no host round trip.  Waits for the updates queued on
+ * the session's stream; changes nothing in the session.  2: a session that does not own all rows, k + k_main > 272, a set on
+ * another device, a user id beyond the rows of A. */
+int cmfrec_hip_session_ranking(cmfrec_hip_session *s, cmfrec_hip_rankset *set, int k_at, cmfrec_hip_rank_record *out);
+int cmfrec_hip_early_stop_step(cmfrec_hip_early_stop *st, int iter, int niter, const double *value);
+
 /* Replace predict_X_old_collective_explicit / _implicit and predict_X_new_collective_explicit / _implicit of the reference's
  * src/cmfrec.h (bodies src/collective.c:11797-12069 over predict_multiple, src/common.c:5066-5110) -- the same positional
  * parameters, the same return codes; nthreads is accepted and ignored.
