@@ -55,6 +55,7 @@ constexpr int CG_NTSEL_MAX_S = 7;
 // no spills), the body for 8 alone is the round-4 kernel (160-167: three).
 template <typename T, int W, int NRES_, int NTSEL = 0> constexpr int cg_waves_per_simd()
 {
+    if (sizeof(T) == 8 && NTSEL == 1 && NRES_ == 2) return 2;      // two resident tiles of 5 / 6 entries per lane group (below)
     if (sizeof(T) == 8 && NTSEL == 1 && W <= 8) return CMF_CG_WAVES_PER_SIMD_LOW;
     if (sizeof(T) == 4 && NTSEL == 1 && W <= 4 && NRES_ == 0) return CMF_CG_WAVES_PER_SIMD_F32 + 1;
     return (sizeof(T) == 4 && W <= 4 && NRES_ == 0) ? CMF_CG_WAVES_PER_SIMD_F32 : CMF_CG_WAVES_PER_SIMD;
@@ -272,7 +273,9 @@ template <typename T> constexpr bool pass_vector_in_lds() { return CMF_PASS_VECT
 template <typename T, int S>
 __device__ __forceinline__ void replicate(T vdist, T (&vrep)[S], int lane);
 // GR: rows of the staged Gramian per lane group (gram_rows below) -- the group jj multiplies the rows GR jj + t, t < GR
-template <typename T, int S, int GR = 8>
+// WTS = false: the Gramian weights stay in the buffer until pass_vector_lds_weights fetches them behind the tile products (two resident
+// tiles in double precision: GR register pairs less while both tiles are multiplied); the buffer is rewritten by the next pass only.
+template <typename T, int S, int GR = 8, bool WTS = true>
 __device__ __forceinline__ void pass_vector_lds(T vdist, T (&vrep)[S], T (&wts)[8], int lane, T *__restrict__ pv)
 {
     const int jj = lane >> 3, ll = lane & 7;
@@ -280,7 +283,18 @@ __device__ __forceinline__ void pass_vector_lds(T vdist, T (&vrep)[S], T (&wts)[
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int s = 0; s < S; s++) vrep[s] = pv[ll + 8 * s];
-    const T *wp = pv + GR * jj;
+    if constexpr (WTS) {
+        const T *wp = pv + GR * jj;
+#pragma unroll
+        for (int t = 0; t < GR; t++) wts[t] = wp[t];
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+template <typename T, int GR>
+__device__ __forceinline__ void pass_vector_lds_weights(T (&wts)[8], int lane, const T *__restrict__ pv)
+{
+    asm volatile("" ::: "memory");          // (not hoisted back above the tile products)
+    const T *wp = pv + GR * (lane >> 3);
 #pragma unroll
     for (int t = 0; t < GR; t++) wts[t] = wp[t];
     __builtin_amdgcn_wave_barrier();
@@ -409,7 +423,9 @@ __device__ __forceinline__ void load_tile_slot(TILE &tile, const char *base, uns
 // zero and the result lanes >= k are cleared).  One v_mad_u64_u32 per gathered row forms its address.
 // NT entries per lane group (round 5): the tile holds 8 NT entries, entry jj NT + t of the tile in the lane group jj; its index
 // (my_idx) and value sit in lane (jj, t).  NT = 8 is the 64-entry tile of rounds 1-4.
-template <typename T, int S, int NT = 8>
+// UCMP: the slot's bound as t < cnt - jj NT -- one register per tile instead of the NT sums jj NT + t, which the compiler keeps in
+// registers across the rows (the two-tile double-precision kernels have none to spare; the same selection).
+template <typename T, int S, int NT = 8, bool UCMP = false>
 __device__ __forceinline__ void load_tile(RegTile<T, S> &tile, const T *__restrict__ Bm, size_t ldb,
                                           int k, int my_idx, int cnt, int lane)
 {
@@ -425,9 +441,11 @@ __device__ __forceinline__ void load_tile(RegTile<T, S> &tile, const T *__restri
     const int col_last = min(ll + 8 * (S - 1), k - 1) - ll;
     const char *base = reinterpret_cast<const char *>(Bm + ll);
     const unsigned ldb_bytes = (unsigned)(ldb * sizeof(T));
+    const int slots_in = cnt - jj * NT;
 #pragma unroll
     for (int t = 0; t < NT; t++) {
-        const unsigned it = (unsigned)(((jj * NT + t) < cnt) ? its[t] : first_idx);
+        const bool in_tile = UCMP ? (t < slots_in) : ((jj * NT + t) < cnt);
+        const unsigned it = (unsigned)(in_tile ? its[t] : first_idx);
         const T *rp = reinterpret_cast<const T *>(base + (unsigned long long)it * ldb_bytes);
 #pragma unroll
         for (int s = 0; s < S; s++) tile.set(t, s, rp[(s < S - 1) ? 8 * s : col_last]);
@@ -639,7 +657,8 @@ __device__ __forceinline__ void replicate(T vdist, T (&vrep)[S], int lane)
 // NRES_: resident tiles per wavefront (0: two for the 8-wave teams of the single-precision build, one otherwise).  Round 4: the
 // single-precision rows of 257..512 entries run on FOUR waves with two tiles each instead of eight waves of which three to
 // five only take part in the barriers (config 4: the 257..1024 bin ran at 0.43-0.46 of the HBM peak against 0.55-0.62 for the
-// 4-wave bin below it).
+// 4-wave bin below it).  Double precision: two tiles of 5 or 6 entries per lane group fit 256 registers (NRES_ = 2 with NTSEL = 1, LATEV
+// below) -- rows of 65..96 entries on ONE wavefront, rows of 257..384 on FOUR (device.hpp, launch_cg_bin_by_tile).
 template <typename T, int S, bool IMPLICIT, int W, int RPB, bool GRAMX = false, int NRES_ = 0, int NTSEL = 0>
 __global__ void __launch_bounds__(64 * W * RPB, (cg_waves_per_simd<T, W, NRES_, NTSEL>()))
 cg_rows_kernel(const CgParams<T> P)
@@ -702,7 +721,8 @@ cg_rows_kernel(const CgParams<T> P)
     // of this launch -- are gathered once instead of once per pass (config 4: the bin ran at 2.9 TB/s against 4.5-5.2 for
     // the bins that already were resident).  The register budget goes from three to two wavefronts per SIMD.
     constexpr int NRES = NRES_ > 0 ? NRES_ : ((std::is_same<T, float>::value && W == 8) ? 2 : 1);
-    static_assert(NRES == 1 || std::is_same<T, float>::value, "two resident tiles: single precision");
+    static_assert(NRES == 1 || std::is_same<T, float>::value || NTSEL == 1,
+                  "two resident tiles: single precision, or the double-precision launch of 5 / 6 entries per lane group");
     // Round 5 -- the tile follows the row: a resident row of nnz entries runs on tiles of 8 NT entries, NT = entries per lane
     // group = ceil(nnz / (8 W NRES)) in [NT_MIN, 8] (single precision: even, the entries of a lane travel in pairs), instead of
     // always 8.  A launch holds rows of (W NRES 32, W NRES 64] entries, so with the 64-entry tile a third of all tile slots were
@@ -710,7 +730,8 @@ cg_rows_kernel(const CgParams<T> P)
     // pass, its share of the reduction over the column lanes, a weight broadcast and S gather instructions.  NT is a function of
     // the row's length alone, so a row's arithmetic (and its bits) do not depend on the launch, the shard or the neighbours.
     // Rows that are not resident (more than W NRES 64 entries: launches outside the length bins) keep the 64-entry tile.
-    static_assert(NTSEL == 0 || (S >= CMF_CG_NT_MIN_S && (sizeof(T) == 4 || S <= CG_NTSEL_MAX_S) && NRES_ == 0),
+    static_assert(NTSEL == 0 || (S >= CMF_CG_NT_MIN_S && (sizeof(T) == 4 || S <= CG_NTSEL_MAX_S) &&
+                                 (NRES_ == 0 || (sizeof(T) == 8 && NTSEL == 1 && NRES_ == 2))),
                   "launches by tile size: tiles by row length (double precision: k <= 56)");
     constexpr int NT_MIN = (S >= CMF_CG_NT_MIN_S && (CMF_CG_NT_F32 || !std::is_same<T, float>::value)) ? (std::is_same<T, float>::value ? 6 : 5) : 8;
     auto nt_of = [&](int nnz_) -> int {
@@ -719,6 +740,11 @@ cg_rows_kernel(const CgParams<T> P)
         return (nt > 8) ? 8 : (nt < NT_MIN ? NT_MIN : nt);
     };
     struct Pre { int idx; T x; T a; int idx2; T x2; T g; T g2; };
+    // Two resident tiles in double precision: 2 x 6 x S register pairs of tiles leave no room to carry the next row's entry values and
+    // warm start through this row's passes (the compiler parked them in scratch).  Only the next row's indices -- what its gather
+    // waits for -- are fetched a row ahead; values, weights and warm start are fetched beside the row's own gather, whose latency
+    // covers theirs.
+    constexpr bool LATEV = NRES == 2 && sizeof(T) == 8;
     auto load_desc = [&](int rix_) -> RowDesc {
         RowDesc d; d.row = 0; d.nnz = 0; d.st = 0;
         if (rix_ < P.nrows) d = P.desc[rix_];
@@ -738,22 +764,47 @@ cg_rows_kernel(const CgParams<T> P)
         if (b < nt && ent < cnt) {
             const size_t pos = d.st + (size_t)wr * tl + ent;
             q.idx = P.indices[pos];
-            q.x = P.values[pos];
-            q.g = entry_weight<T, IMPLICIT>(P, pos);
-            if (!IMPLICIT && P.bias_sub != nullptr) q.x -= P.bias_sub[q.idx];
+            if constexpr (!LATEV) {
+                q.x = P.values[pos];
+                q.g = entry_weight<T, IMPLICIT>(P, pos);
+                if (!IMPLICIT && P.bias_sub != nullptr) q.x -= P.bias_sub[q.idx];
+            }
         }
         if (NRES == 2) {
             const int cnt2 = min(tl, d.nnz - (wr + W) * tl);
             if (b < nt && ent < cnt2) {
                 const size_t pos = d.st + (size_t)(wr + W) * tl + ent;
                 q.idx2 = P.indices[pos];
-                q.x2 = P.values[pos];
-                q.g2 = entry_weight<T, IMPLICIT>(P, pos);
-                if (!IMPLICIT && P.bias_sub != nullptr) q.x2 -= P.bias_sub[q.idx2];
+                if constexpr (!LATEV) {
+                    q.x2 = P.values[pos];
+                    q.g2 = entry_weight<T, IMPLICIT>(P, pos);
+                    if (!IMPLICIT && P.bias_sub != nullptr) q.x2 -= P.bias_sub[q.idx2];
+                }
             }
         }
-        if (d.nnz > 0 && lane < k) q.a = P.A[(size_t)d.row * P.lda + lane];
+        if constexpr (!LATEV) {
+            if (d.nnz > 0 && lane < k) q.a = P.A[(size_t)d.row * P.lda + lane];
+        }
         return q;
+    };
+    // LATEV: the rest of load_pre for the row that is about to be solved (its indices are in q)
+    auto load_pre_values = [&](const RowDesc &d, Pre &q) {
+        const int nt = nt_of(d.nnz), tl = 8 * nt;
+        const int b = lane & 7;
+        const int ent = (lane >> 3) * nt + b;
+        if (b < nt && ent < min(tl, d.nnz - wr * tl)) {
+            const size_t pos = d.st + (size_t)wr * tl + ent;
+            q.x = P.values[pos];
+            q.g = entry_weight<T, IMPLICIT>(P, pos);
+            if (!IMPLICIT && P.bias_sub != nullptr) q.x -= P.bias_sub[q.idx];
+        }
+        if (b < nt && ent < min(tl, d.nnz - (wr + W) * tl)) {
+            const size_t pos = d.st + (size_t)(wr + W) * tl + ent;
+            q.x2 = P.values[pos];
+            q.g2 = entry_weight<T, IMPLICIT>(P, pos);
+            if (!IMPLICIT && P.bias_sub != nullptr) q.x2 -= P.bias_sub[q.idx2];
+        }
+        if (d.nnz > 0 && lane < k) q.a = P.A[(size_t)d.row * P.lda + lane];
     };
     int rix = blockIdx.x * RPB + grp;
     RowDesc dcur = load_desc(rix);
@@ -847,15 +898,19 @@ cg_rows_kernel(const CgParams<T> P)
         const bool lane_has = (NT == 8) || (lane & 7) < NT;
         const int cnt0 = min(TL, nnz - wr * TL);
         T x_res = pcur.x;
-        const T g_res = pcur.g;
+        T g_res = pcur.g;
         bool valid_res = lane_has && ent < cnt0;
         if (CMF_DBG(P, 1)) dbg_fill_tile<8, S>(tile, (T)(pcur.idx & 3) * (T)0.001);
-        else if (!EARLY && cnt0 > 0) load_tile<T, S, NT>(tile, P.B, P.ldb, k, pcur.idx, cnt0, lane);
+        else if (!EARLY && cnt0 > 0) load_tile<T, S, NT, LATEV>(tile, P.B, P.ldb, k, pcur.idx, cnt0, lane);
         const int cnt1 = (NRES == 2) ? min(TL, nnz - (wr + W) * TL) : 0;
-        const T x2_res = pcur.x2, g2_res = pcur.g2;
+        T x2_res = pcur.x2, g2_res = pcur.g2;
         const bool valid2_res = lane_has && ent < cnt1;
         if constexpr (NRES == 2) {
-            if (!EARLY && cnt1 > 0 && !CMF_DBG(P, 1)) load_tile<T, S, NT>(tile2, P.B, P.ldb, k, pcur.idx2, cnt1, lane);
+            if (!EARLY && cnt1 > 0 && !CMF_DBG(P, 1)) load_tile<T, S, NT, LATEV>(tile2, P.B, P.ldb, k, pcur.idx2, cnt1, lane);
+        }
+        if constexpr (LATEV) {
+            load_pre_values(dcur, pcur);
+            a_d = pcur.a; x_res = pcur.x; g_res = pcur.g; x2_res = pcur.x2; g2_res = pcur.g2;
         }
         dnn = load_desc(rnn);
         pnxt = load_pre(dnxt);
@@ -875,7 +930,7 @@ cg_rows_kernel(const CgParams<T> P)
             asm volatile("" ::: "memory");
             T vrep[S];
             T gw[8];
-            if constexpr (PV) pass_vector_lds<T, S, GR>(vdist, vrep, gw, lane, &s_pv[wave][0]);
+            if constexpr (PV) pass_vector_lds<T, S, GR, !(LATEV && GRAM)>(vdist, vrep, gw, lane, &s_pv[wave][0]);
             else replicate<T, S>(vdist, vrep, lane);
             PassAcc<T> acc;
             acc.zero();
@@ -943,6 +998,7 @@ cg_rows_kernel(const CgParams<T> P)
                 if (!CMF_DBG(P, 4)) tile_pass<T, S, IMPLICIT, MODE, NT>(tile, vrep, x, valid, acc, lane, g);
             }
             if (GRAM && !CMF_DBG(P, 2)) {   // common.c:1932 / :1958; collective.c:2609-2643
+                if constexpr (PV && LATEV) pass_vector_lds_weights<T, GR>(gw, lane, &s_pv[wave][0]);
                 if constexpr (PV) gram_pass_w<MODE == 0, T, S, W, GR>(G, gw, acc, lane, wr);
                 else gram_pass<T, S, W>(G, (MODE == 0) ? -vdist : vdist, acc, lane, wr);
             }

@@ -771,6 +771,29 @@ inline void launch_cg_bin_by_tile(const DeviceInfo &dev, const CgParams<real_t> 
     constexpr bool by_tile = S >= CMF_CG_NT_MIN_S && S <= CG_NTSEL_MAX_S && (W == 1 || W == 4 || W == 8);
 #endif
     if (count <= 0) return;
+#ifndef CMFREC_HIP_FLOAT
+    // Two resident tiles per wavefront (cg_rows_kernel, NRES_ = 2) for the rows of 5 or 6 entries per lane group of the two- and the
+    // eight-wave bins: 65..96 entries on ONE wavefront (four rows per workgroup share a Gramian copy; no barrier, no exchange), 257..384
+    // on FOUR (two rows in flight per CU, half the per-wavefront fixed work per row).  W NRES is what it was, so a row keeps its tile
+    // and differs only in the order its tile partials are added.  The upper ranges stay on their teams, the two-wave one as a launch
+    // of the bodies for 7 and 8 entries (CMFREC_HIP_NT_SPLIT=0: of every body, as that switch has it everywhere -- the same bits).
+    // CMFREC_HIP_TWO_TILES=0: the routing before; 2 / 3: only the two- / the eight-wave bin's rows move (A/B switch).
+    // (block systems with S = 7: those two instantiations keep 16-44 bytes of scratch per lane and stay where they were)
+    constexpr bool two_tiles = S >= CMF_CG_NT_MIN_S && S <= CG_NTSEL_MAX_S && (W == 2 || W == 8) && RPB == 1 && !(GRAMX && S == CG_NTSEL_MAX_S);
+    if constexpr (two_tiles) {
+        const int tt = switches().two_tiles;
+        if (tt == 1 || tt == (W == 2 ? 2 : 3)) {
+            const int n_hi = std::min(count, std::max(0, X.n_gt_low[W == 2 ? 1 : 3] - first));
+            EventPair ev{nullptr, nullptr};
+            if (tm) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); HIP_CHECK(hipEventRecord(ev.a, st)); }
+            if (switches().nt_split) launch_cg_bin<S, IMPLICIT, W, 1, GRAMX, 0, 2>(dev, P, first, n_hi, nullptr, bin, st);
+            else launch_cg_bin<S, IMPLICIT, W, 1, GRAMX>(dev, P, first, n_hi, nullptr, bin, st);
+            launch_cg_bin<S, IMPLICIT, W / 2, (W == 2) ? 4 : 1, GRAMX, 2, 1>(dev, P, first + n_hi, count - n_hi, nullptr, bin, st, NBINS + 2 + bin);
+            if (tm) { HIP_CHECK(hipEventRecord(ev.b, st)); tm->ev[bin].push_back(ev); }
+            return;
+        }
+    }
+#endif
     if constexpr (by_tile) {
         if (switches().nt_split) {
             const int n_hi = std::min(count, std::max(0, X.n_gt_low[W == 1 ? 0 : W == 2 ? 1 : W == 4 ? 2 : 3] - first));

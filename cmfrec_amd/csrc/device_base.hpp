@@ -56,6 +56,7 @@ struct Switches {
     bool gram_slice = false;        // CMFREC_HIP_GRAM_KERNEL=slice: LDS-staged workgroup kernel for the slice partials
     int bins_par = 2;               // CMFREC_HIP_BINS_PAR: streams the nnz bins of a half-step are spread over (1: in line)
     bool nt_split = true;           // CMFREC_HIP_NT_SPLIT=0: a double-precision length bin as one launch instead of two by tile size
+    int two_tiles = 1;              // CMFREC_HIP_TWO_TILES: double-precision rows of 65..96 / 257..384 entries on one / four wavefronts with two resident tiles each (1); 0 = on two- / eight-wave teams with one tile per wavefront (as before), 2 / 3 = only the first / the second range moves
     bool cg_generic = false;        // CMFREC_HIP_CG_KERNEL=generic: lane <-> unknown CG kernel everywhere
     int chol = 0;                   // CMFREC_HIP_CHOL: 1 = rows (workgroup-per-row kernel only), 2 = noslices
     int parts_coop = 1;             // CMFREC_HIP_PARTS_COOP: the rank-k update of those rows with ONE gather shared by the row's two wavefronts through LDS (chol_parts_coop_kernels.hpp; 3: three steps in flight instead of four); 0 = each wavefront gathers for itself (round 5)
@@ -84,6 +85,7 @@ struct Switches {
         v = str("CMFREC_HIP_GRAM_KERNEL"); gram_slice = v && strcmp(v, "slice") == 0;
         bins_par = num("CMFREC_HIP_BINS_PAR", 2);
         nt_split = num("CMFREC_HIP_NT_SPLIT", 1) != 0;
+        two_tiles = num("CMFREC_HIP_TWO_TILES", 1);
         v = str("CMFREC_HIP_CG_KERNEL"); cg_generic = v && strcmp(v, "generic") == 0;
         v = str("CMFREC_HIP_CHOL"); chol = !v ? 0 : strcmp(v, "rows") == 0 ? 1 : strcmp(v, "noslices") == 0 ? 2 : 0;
         parts_coop = num("CMFREC_HIP_PARTS_COOP", 1);
