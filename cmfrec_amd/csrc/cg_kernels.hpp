@@ -658,7 +658,7 @@ __device__ __forceinline__ void replicate(T vdist, T (&vrep)[S], int lane)
 // single-precision rows of 257..512 entries run on FOUR waves with two tiles each instead of eight waves of which three to
 // five only take part in the barriers (config 4: the 257..1024 bin ran at 0.43-0.46 of the HBM peak against 0.55-0.62 for the
 // 4-wave bin below it).  Double precision: two tiles of 5 or 6 entries per lane group fit 256 registers (NRES_ = 2 with NTSEL = 1, LATEV
-// below) -- rows of 65..96 entries on ONE wavefront, rows of 257..384 on FOUR (device.hpp, launch_cg_bin_by_tile).
+// below) -- rows of 65..96 entries on ONE wavefront, rows of 257..384 on FOUR (launch_cg.hip, launch_cg_bin_by_tile).
 template <typename T, int S, bool IMPLICIT, int W, int RPB, bool GRAMX = false, int NRES_ = 0, int NTSEL = 0>
 __global__ void __launch_bounds__(64 * W * RPB, (cg_waves_per_simd<T, W, NRES_, NTSEL>()))
 cg_rows_kernel(const CgParams<T> P)

@@ -1,6 +1,6 @@
 // chol_wg_tu.hip -- the four-wavefront factorisation of the eight-block closed-form rows (chol_wg_kernels.hpp) in a translation unit
-// of its own: the kernel is four instantiations of a long row function, and a unit of its own keeps it out of session.hip's
-// four-minute compile (an experiment on it rebuilds in seconds).
+// of its own: the kernel is four instantiations of a long row function, and a unit of its own keeps it out of launch_chol.hip's
+// compile (an experiment on it rebuilds in seconds).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "../../include/cmfrec_hip.h"

@@ -235,7 +235,7 @@ __global__ void set_rowvec_kernel(T *__restrict__ M, size_t ld, size_t rows, int
     M[r * ld + c] = (v != nullptr) ? v[c] : T(0);
 }
 
-// the refinement step of the shared-matrix solve (session.hip, launch_potrs_rows)
+// the refinement step of the shared-matrix solve (launch_dense.hip, launch_potrs_rows)
 // out = the upper triangle of the row-major k x k factor R, zeros below (the factorisation leaves the lower triangle as it was)
 template <typename T>
 __global__ void upper_only_kernel(const T *__restrict__ R, int k, T *__restrict__ out)

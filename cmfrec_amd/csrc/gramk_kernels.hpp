@@ -25,7 +25,7 @@ constexpr int GK_NB = 17;                               // blocks of 16 unknowns
 constexpr int GK_NT = GK_NB * (GK_NB + 1) / 2;          // 153 tiles of the upper triangle, packed as tile_bi / tile_bj do
 constexpr int GK_PART = GK_NT * 256 + GK_NB * 16;       // elements of one work item's partial: the tiles, then the right-hand side
 #ifndef GK_OPEN_SLOTS
-#define GK_OPEN_SLOTS 32                                  // workgroup slots of the 2 x CUs a launch leaves to other streams: one per shader engine (session.hip; 24: no effect, 32-40: best, profiles/r04)
+#define GK_OPEN_SLOTS 32                                  // workgroup slots of the 2 x CUs a launch leaves to other streams: one per shader engine (launch_chol.hip; 24: no effect, 32-40: best, profiles/r04)
 #endif
 constexpr int GK_PD = 2;                                // k-steps of operands in flight (5 loads each; the counter tracks 63)
 

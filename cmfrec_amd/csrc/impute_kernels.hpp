@@ -28,7 +28,7 @@
 
 #include "dense_kernels.hpp"
 #include "dense_rows_device.hpp"
-#include "device.hpp"
+#include "launch.hpp"
 
 namespace cmfhip {
 

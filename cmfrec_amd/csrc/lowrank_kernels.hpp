@@ -28,7 +28,7 @@ namespace cmfhip {
 // wavefronts; a tournament round pairs every column exactly once, a wavefront rotates its pairs (columns are
 // contiguous: W, V are column-major), one barrier per round.  n = 256: ~7 sweeps x 255 rounds to tol = 1e-9 (what a
 // single-precision system can see; 1e-13 for double: two more sweeps, the convergence is quadratic).  The launch runs on
-// the auxiliary stream beside the kernels that do not need its result (session.hip).
+// the auxiliary stream beside the kernels that do not need its result (launch_lowrank.hip).
 // A [n, n] row-major symmetric (any precision T); W, V: n x n doubles of workspace each;
 // Q [n, ldq] row-major: Q[i][c] = component i of eigenvector c;  Qt its transpose;  lam [n].
 template <typename T>

@@ -1,18 +1,15 @@
 // session.hip -- device-resident ALS session (level 3 of include/cmfrec_hip.h) and the
-// operator-level entry points with host buffers (level 2).
+// operator-level entry points with host buffers (level 2).  The row solvers and the dense layer are reached through
+// launch.hpp (launch_cg.hip, launch_chol.hip, launch_lowrank.hip, launch_dense.hip); of the kernels only the preprocessing
+// (coo_device.hpp, dense_rows_device.hpp, side_zeros_kernels.hpp, impute_kernels.hpp) and small dense helpers are built here.
 //
 // The session owns the state the reference's fit drivers keep on the host
 // (/root/reference/src/collective.c:7651-7677, :9468-9473): the factor matrices in the
 // "[rows, k_tot + bias]" layout, the bias vectors, CSR and CSC copies of X, side information and
 // the small k x k work matrices -- all resident in HBM for the whole fit.
-#include "device.hpp"
+#include "launch.hpp"
 #include "coo_device.hpp"
 #include "dense_rows_device.hpp"
-#include "chol_wave_kernels.hpp"
-#include "gramk_kernels.hpp"
-#include "lowrank_kernels.hpp"
-#include "eig_kernels.hpp"
-#include "gram_cg_wide_kernels.hpp"
 #include "side_zeros_kernels.hpp"
 #include "impute_kernels.hpp"
 #include "newrows.hpp"
@@ -27,868 +24,19 @@ namespace cmfhip {
 thread_local std::string g_last_error;
 thread_local int g_last_rc = 0;      // return code that goes with g_last_error where the entry point returns a pointer
 
-CgVariant cg_variant_from_env() { return switches().cg_generic ? CgVariant::Generic : CgVariant::Auto; }
-
-inline dim3 grid1d(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
-// (chol_wg_tu.hip: the four-wavefront factorisation of the eight-block rows, double precision)
-hipError_t launch_chol_wg8(int num_cus, bool border, int waves_per_row, hipStream_t st, const CholParams<real_t> &W, const RowDesc *desc, const CholSlices<real_t> &SL);
-hipError_t launch_chol_parts_coop(int num_cus, bool border, int depth, hipStream_t st, const CholParams<real_t> &W, const RowDesc *desc, const CholSlices<real_t> &SL);
-
-struct CholCall {
-    real_t *A; size_t lda;
-    const real_t *B; size_t ldb;
-    int kt, koff;
-    const real_t *bias_sub;
-    const real_t *Minit; int kc; int rows_with_u; int p_side;
-    real_t lam, lam_last;
-    bool scale_lam, scale_lam_sideinfo, scale_bias_const;
-    int mode;
-    const real_t *Mfull = nullptr;
-    // second gather source (sparse side information): rows of B2[*, ldb2] selected by X2's entries, unknowns [0, kc2)
-    const SparseShard *X2 = nullptr;
-    const real_t *B2 = nullptr;
-    size_t ldb2 = 0;
-    int kc2 = 0;
-    real_t w2 = 0;
-    // non-negative factors: coordinate descent on the assembled system instead of the Cholesky solve
-    bool nonneg = false;
-    int max_cd_steps = 100;
-    // second source placed at unknown koff2 and used for the right-hand side only (implicit-features term)
-    int koff2 = 0;
-    bool w2_syr_zero = false;
-    int rows2 = -1;
-    const real_t *values2 = nullptr;         // values of the second source (default: X2's own)
-    const real_t *values_override = nullptr; // values of the first source (default: X's own)
-    bool rhs_only = false;                   // CHOL_NAZ: gather the right-hand sides only
-    bool rhs_prefilled_all = false;          // every row starts from the right-hand side left in A
-    const real_t *weights_override = nullptr; // CHOL_NAZ_W: the entries' rank-1 weights (w - 1), CSR order of X
-    bool x_rhs_only = false;                 // the entries of X add to the right-hand sides only (their Gramian is inside Mfull)
-    bool entry_pairs = false;                // weights_override / values_override are the entries' rank-1 and right-hand-side weights
-    const real_t *mult_override = nullptr;   // per-row lambda multipliers of the collective modes instead of the rows' lengths
-    bool all_rows = false;                   // CHOL_NAZ_W: rows without entries are solved too (from the prefilled right-hand side)
-    int row_limit = -1;                      // only the first row_limit positions of the processing order (the others are solved elsewhere)
-    // CG on the row's Gramian instead of the factorisation (gram_cg_wide_kernels.hpp): the producer build of the wave kernel runs
-    // every row's rank-k update, gram_cg_wide_kernel takes the partials; the parameters of the CG (explicit model)
-    const CgParams<real_t> *cg_wide = nullptr;
-};
-
-static int launch_chol_rows(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, CholParams<real_t> P, bool two_src,
-                            size_t smem_nonneg);
-
-static int launch_plain_lowrank(const DeviceInfo &dev, const CholCall &c, const SparseShard &X);
-
-#ifndef CMF_PARTS_NP
-#define CMF_PARTS_NP 2             // wavefronts per row of chol_parts_producer_kernel: 2 = halves of 18 tiles (default), 4 = quarters of 9 (measured on par with the round-2 producer)
-#define CMF_PARTS_PD 2             // steps of four gathered rows in flight per wavefront (quarters: 4)
-#define CMF_PARTS_WPS 2            // wavefronts per SIMD
-#endif
-// X may be null for CHOL_PREFILLED (then nrows_prefilled rows are solved in natural order)
-static int launch_chol(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, int nrows_prefilled = 0)
-{
-    if (X != nullptr && c.mode == CHOL_EXPLICIT && c.row_limit < 0 && c.cg_wide == nullptr) {
-        const int rc_lr = launch_plain_lowrank(dev, c, *X);      // rows with few entries against many unknowns (-1: not applicable)
-        if (rc_lr >= 0) return rc_lr;
-    }
-    CholParams<real_t> P;
-    P.A = c.A; P.lda = c.lda; P.B = c.B; P.ldb = c.ldb; P.kt = c.kt; P.koff = c.koff;
-    P.indptr = X ? X->p.ptr : nullptr; P.indices = X ? X->i.ptr : nullptr; P.values = X ? X->v.ptr : nullptr;
-    P.bias_sub = c.bias_sub;
-    // observation weights of the explicit model ride on the shard (SparseShard::w / wsum)
-    const bool weighted = X != nullptr && X->weighted() && (c.mode == CHOL_EXPLICIT || c.mode == CHOL_COLLECTIVE) && c.values_override == nullptr;
-    if (weighted) { P.weights = X->w.ptr; P.wsum = X->wsum.ptr; }
-    if (c.mode == CHOL_NAZ_W) { P.weights = c.weights_override; P.wsum = X->wsum_naz.ptr; }
-    if (c.mult_override != nullptr) P.wsum = c.mult_override;
-    P.x_rhs_only = c.x_rhs_only ? 1 : 0;
-    if (c.entry_pairs) { P.entry_pairs = 1; P.weights = c.weights_override; }
-    P.order = X ? X->order.ptr : nullptr;
-    if (c.mode == CHOL_PREFILLED) P.nrows = nrows_prefilled;
-    else if (c.mode == CHOL_COLLECTIVE || c.mode == CHOL_COLLECTIVE_IMPLICIT || (c.mode == CHOL_NAZ_W && c.all_rows)) P.nrows = X->nrows;   // empty rows too
-    else P.nrows = X->n_nonempty;                                                // non-empty rows
-    if (c.row_limit >= 0) P.nrows = std::min(P.nrows, c.row_limit);
-    P.Minit = c.Minit; P.Mfull = c.Mfull; P.kc = c.kc; P.rows_with_u = c.rows_with_u; P.p_side = c.p_side;
-    P.lam = c.lam; P.lam_last = c.lam_last;
-    P.scale_lam = c.scale_lam; P.scale_lam_sideinfo = c.scale_lam_sideinfo; P.scale_bias_const = c.scale_bias_const;
-    P.mode = c.mode;
-    if (c.X2) {
-        P.indptr2 = c.X2->p.ptr; P.indices2 = c.X2->i.ptr; P.values2 = c.values2 ? c.values2 : c.X2->v.ptr;
-        P.B2 = c.B2; P.ldb2 = c.ldb2; P.kc2 = c.kc2; P.w2 = c.w2; P.koff2 = c.koff2; P.w2_syr_zero = c.w2_syr_zero ? 1 : 0; P.rows_src2 = c.rows2;
-    }
-    P.values_override = c.values_override; P.rhs_only = c.rhs_only ? 1 : 0; P.rhs_prefilled_all = c.rhs_prefilled_all ? 1 : 0;
-    const bool l1on = dev.l1_now != (real_t)0 || dev.l1_last_now != (real_t)0;
-    const bool nonneg = c.nonneg || dev.nonneg_now;
-    P.nonneg = nonneg ? 1 : 0; P.max_cd_steps = (dev.nonneg_now || l1on) ? dev.max_cd_steps : c.max_cd_steps;
-    // PREFILLED launches carry their lambda inside the prefilled matrix, scaled on the host (common.c:2832-2833): their L1
-    // penalty takes the same factor (solve_elasticnet_batch / solve_nonneg_batch calls, :2876-2902)
-    const real_t l1_mult = (c.mode == CHOL_PREFILLED || c.mode == CHOL_NAZ) ? dev.l1_scale : (real_t)1;
-    P.l1 = dev.l1_now * l1_mult; P.l1_last = dev.l1_last_now * l1_mult;
-    if (P.nrows <= 0) return 0;
-    const int T = chol_tiles(c.kt);
-    const size_t smem_nonneg = (nonneg || l1on) ? ((size_t)c.kt * c.kt + 2 * (size_t)c.kt + 64) * sizeof(real_t) : 0;
-    if (smem_nonneg > 160 * 1024) {
-        g_last_error = "cmfrec_hip: nonneg: the k_t x k_t system must fit the 160 KB of LDS (k_t <= 140 in double, 199 in single precision)";
-        return 2;
-    }
-    if (T > 17 || (sizeof(real_t) == 8 && T > 16)) {
-        g_last_error = "cmfrec_hip: Cholesky path: k_t too large for the register-resident normal matrix "
-                       "(k_t <= 256 in double, <= 272 in single precision)";
-        return 2;
-    }
-    if (dev.row_counter.n < ROW_COUNTER_INTS) const_cast<DeviceInfo &>(dev).row_counter.alloc(ROW_COUNTER_INTS);
-    HIP_CHECK(hipMemsetAsync(dev.row_counter.ptr, 0, 4 * sizeof(int), dev.stream));   // [0, 4): first launches of this call
-    P.counter = dev.row_counter.ptr;
-    P.row_first = 0;
-    const bool two_src = c.X2 != nullptr || c.mode == CHOL_NAZ || c.mode == CHOL_NAZ_W || c.x_rhs_only || c.entry_pairs;   // (that build only)
-    // Rows of up to WAVE_ROW_MAX entries: one wavefront per row, the matrix in its registers (chol_wave_kernels.hpp).
-    // The rows beyond (they lead the processing order) stay with the workgroup-per-row kernel below; the two launches
-    // run side by side on two streams.  CMFREC_HIP_CHOL=rows keeps everything on the workgroup-per-row kernel (A/B
-    // switch and on-device cross-check).
-    {
-        const int chol_sw = switches().chol;        // 1: rows, 2: noslices
-        const bool border = (c.kt > 16) && ((c.kt - 1) % 16 == 0);
-        const int nbw = (c.kt - (border ? 1 : 0) + 15) / 16;
-        const bool wave_ok = X != nullptr && !two_src && !nonneg && !l1on && !c.rhs_only && nbw <= 8 && !weighted &&
-                             (c.mode == CHOL_EXPLICIT || c.mode == CHOL_IMPLICIT || c.mode == CHOL_COLLECTIVE ||
-                              c.mode == CHOL_COLLECTIVE_IMPLICIT) &&
-                             chol_sw != 1;
-        if (wave_ok) {
-            // rows beyond 1024 entries: sliced (their slice tables are the ones of the split-row CG path, SparseShard::sl_*);
-            // CMFREC_HIP_CHOL=noslices leaves them to the workgroup-per-row kernel (A/B switch)
-            const bool sliced = chol_sw != 2;
-            const int n_heavy = std::min(X->bin_rows[BIN_VHEAVY], P.nrows);
-            const int total = P.nrows;
-            DeviceInfo &d = const_cast<DeviceInfo &>(dev);
-            // one launch of the wave kernel over the positions [first, last) of the processing order (or over work items)
-            auto wave_launch = [&](int wmode, int first, int last, int counter, const CholSlices<real_t> &SL, hipStream_t st) {
-                if (last <= first) return;
-                CholParams<real_t> W = P;
-                W.row_first = first; W.nrows = last; W.counter = dev.row_counter.ptr + counter;
-                auto wlaunch = [&](auto kern, int nb_, int wps) {
-                    poison_lds(st, dev.num_cus);      // test hook, device.hpp
-                    const size_t smem = 4 * (wmode == 1 ? chol_wave_lds_elems_producer(nb_) : chol_wave_lds_elems<real_t>(nb_)) * sizeof(real_t);
-                    const int grid = std::min((last - first + 3) / 4, dev.num_cus * wps);
-                    if (smem > 48 * 1024)
-                        HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, W, X->desc.ptr, SL);
-                };
-                // <16-blocks, border, gather steps in flight, wavefronts per SIMD, overflow tiles, mode>
-#define WAVE_KERN_M(nb_, pd, wps, nov, wm) (border ? chol_wave_kernel<real_t, nb_, true, pd, wps, nov, wm, false> : chol_wave_kernel<real_t, nb_, false, pd, wps, nov, wm, false>)
-#define WAVE_KERN(nb_, pd, wps, nov) \
-    (wmode == 1 ? WAVE_KERN_M(nb_, pd, wps, nov, 1) : wmode == 2 ? WAVE_KERN_M(nb_, pd, wps, nov, 2) : WAVE_KERN_M(nb_, pd, wps, nov, 0))
-#ifdef CMFREC_HIP_FLOAT
-                if (nbw <= 2) wlaunch(WAVE_KERN(2, 4, 4, 0), 2, 4);
-                else if (nbw <= 4) wlaunch(WAVE_KERN(4, 4, 2, 0), 4, 2);
-                else if (nbw <= 6) wlaunch(WAVE_KERN(6, 3, 2, 0), 6, 2);
-                else wlaunch(WAVE_KERN(8, 2, 1, 0), 8, 1);
-#else
-                if (nbw <= 2) wlaunch(WAVE_KERN(2, 4, 3, 0), 2, 3);
-                else if (nbw <= 4) wlaunch(WAVE_KERN(4, 3, 2, 0), 4, 2);
-                else if (nbw <= 6) wlaunch(WAVE_KERN(6, 2, 1, 0), 6, 1);
-                // 7 and 8 blocks in double: two kernels, see below
-                // Round 5: one wavefront per SIMD issues a double-precision MFMA every ~130 cycles, two keep the pipe busy (35-38 against
-                // 75 TFLOP/s, profiles/r05/r05_za_mfma_f64_occupancy.txt).  Where every unknown of the tiles is gathered (koff = 0,
-                // k_t = 128 / 129: config 3) the rank-k update is done by TWO wavefronts per row with 18 tiles each, four workgroups
-                // of 128 threads per CU (chol_parts_producer_kernel; config 3 15.10 -> 14.75-14.84 ms, r05_ze); the other shapes and
-                // -DCMF_WAVE_PROD_ONE_WAVE keep the round-2 producer (one wavefront per row and SIMD, 32 + 4 tiles in two sweeps).
-                else if (wmode == 1) {
-                    const bool fullq = c.koff == 0 && c.kt - (border ? 1 : 0) == 128;
-#ifdef CMF_WAVE_PROD_ONE_WAVE
-                    const bool parts = false;
-#else
-                    const bool parts = fullq;
-#endif
-                    if (!parts) wlaunch(WAVE_KERN_M(8, 3, 1, 32, 1), 8, 1);      // 32 tiles per sweep
-                    else if (switches().parts_coop && CMF_PARTS_NP == 2) {
-                        // Round 6: the row's two wavefronts share ONE gather through LDS (chol_parts_coop_kernels.hpp, chol_wg_tu.hip):
-                        // config 3 12.97 -> 12.80 ms, the partials bit for bit the same (CMFREC_HIP_PARTS_COOP=0: round 5's kernel)
-                        poison_lds(st, dev.num_cus);
-                        HIP_CHECK(launch_chol_parts_coop(dev.num_cus, border, switches().parts_coop == 3 ? 3 : 4, st, W, X->desc.ptr, SL));
-                    }
-                    else {
-                        poison_lds(st, dev.num_cus);
-                        constexpr int NPQ = CMF_PARTS_NP;
-                        auto kern = border ? chol_parts_producer_kernel<real_t, 8, true, CMF_PARTS_PD, CMF_PARTS_WPS, true, NPQ>
-                                           : chol_parts_producer_kernel<real_t, 8, false, CMF_PARTS_PD, CMF_PARTS_WPS, true, NPQ>;
-                        const int grid = std::min(last - first, dev.num_cus * CMF_PARTS_WPS * 4 / NPQ);
-                        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NPQ), 0, st, W, X->desc.ptr, SL);
-                    }
-                }
-                else if (switches().chol_wg) {
-                    // Round 6: the factorisation by one workgroup of TWO wavefronts per row, the 36 tiles dealt to them, four rows per CU in
-                    // flight (chol_wg_kernels.hpp) instead of one wavefront per row and SIMD with 263 spilled registers: config 3
-                    // 14.2 -> 13.0 ms (profiles/r06/r06_j_*).  CMFREC_HIP_CHOL_WG=4: four wavefronts per row, two rows per CU (14.0);
-                    // =0: the one-wavefront build below (A/B switch and on-device cross-check).
-                    poison_lds(st, dev.num_cus);
-                    HIP_CHECK(launch_chol_wg8(dev.num_cus, border, switches().chol_wg == 2 ? 2 : 4, st, W, X->desc.ptr, SL));       // chol_wg_tu.hip
-                }
-                else wlaunch((border ? chol_wave_kernel<real_t, 8, true, 1, 1, 6, 2, true> : chol_wave_kernel<real_t, 8, false, 1, 1, 6, 2, true>), 8, 1);
-#endif
-#undef WAVE_KERN
-#undef WAVE_KERN_M
-                HIP_CHECK(hipGetLastError());
-            };
-            const int nb_inst = nbw <= 2 ? 2 : nbw <= 4 ? 4 : nbw <= 6 ? 6 : 8;
-            const size_t part_elems = chol_wave_part_elems(nb_inst);
-            CholSlices<real_t> SLT;
-            if (n_heavy > 0) {
-                SLT.vrow = X->sl_vrow.ptr; SLT.first = X->sl_first.ptr; SLT.count = X->sl_count.ptr; SLT.row_off = X->row_sl_off.ptr;
-                SLT.n_slices = X->n_slices;
-            }
-            SLT.n_heavy = n_heavy;
-            SLT.dbg_skip = switches().debug_skip;
-            const bool cg_wide = c.cg_wide != nullptr;
-            if ((sizeof(real_t) == 8 && nbw > 6) || cg_wide) {
-                // (cg_wide: the second kernel is the CG on the summed partials, gram_cg_wide_kernels.hpp -- every precision and width)
-                // Two kernels (7 and 8 blocks in double: 28 / 36 tiles of 8 registers + the factorisation's temporaries exceed
-                // what one kernel can keep in registers -- hipcc emits the accumulator-file form of the MFMAs at one wave per
-                // SIMD, 256 registers for all MFMA destinations).  The producer build runs every row's rank-k update at full
-                // MFMA rate (no spills, three gather steps in flight) and leaves the raw tiles in HBM, the second build adds the
-                // initial matrix and factorises.  76 KB per work item each way; batches bound the scratch buffer.
-                const int BATCH = 32768;
-                const std::vector<int> &ho = X->h_row_sl_off;
-                int max_row_items = 1;
-                for (int r = 0; r < n_heavy; r++) max_row_items = std::max(max_row_items, ho[r + 1] - ho[r]);
-                const int nsl = n_heavy > 0 ? X->n_slices : 0;
-                const size_t cap_items = (size_t)std::min<long long>((long long)nsl + (total - n_heavy), std::max(BATCH, max_row_items));
-                if (X->chol_part.n < cap_items * part_elems) X->chol_part.alloc(cap_items * part_elems);
-                SLT.part = X->chol_part.ptr;
-                // the launch's initial matrices once, in the tile layout of the partials (the row kernel then adds them like a
-                // partial, 16 values per round trip, instead of 144 dependent loads per row)
-                if (!cg_wide) {
-                    const bool fullm = (c.mode == CHOL_IMPLICIT);
-                    const real_t *M1 = fullm ? c.Minit : c.Mfull, *M2 = fullm ? nullptr : c.Minit;
-                    const size_t tl = (size_t)36 * 256;
-                    if (M1 != nullptr || (M2 != nullptr && c.kc > 0)) d.tile_init.alloc_at_least(2 * tl);
-                    if (M1 != nullptr) {
-                        hipLaunchKernelGGL(tile_pack_kernel<real_t>, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, dev.stream, M1, c.kt, 8, d.tile_init.ptr);
-                        SLT.init1 = d.tile_init.ptr;
-                    }
-                    if (M2 != nullptr && c.kc > 0) {
-                        hipLaunchKernelGGL(tile_pack_kernel<real_t>, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, dev.stream, M2, c.kc, 8, d.tile_init.ptr + tl);
-                        SLT.init2 = d.tile_init.ptr + tl;
-                    }
-                }
-                int ctr = 4;
-                auto run_batch = [&](int item0, int item1, int row0, int row1) {
-                    if (ctr + 2 > 60) ctr = 4;
-                    HIP_CHECK(hipMemsetAsync(dev.row_counter.ptr + ctr, 0, 2 * sizeof(int), dev.stream));
-                    CholSlices<real_t> SL = SLT;
-                    SL.part_base = item0;
-                    wave_launch(1, item0, item1, ctr, SL, dev.stream);
-                    if (cg_wide) {
-                        WideCgParams<real_t> Wp;
-                        Wp.part = SL.part; Wp.part_base = item0; Wp.NB = nb_inst; Wp.border = border ? 1 : 0;
-                        Wp.row_off = X->row_sl_off.ptr; Wp.n_heavy = n_heavy; Wp.n_slices = nsl;
-                        Wp.row_first = row0; Wp.row_last = row1;
-                        const size_t smem = gcw_lds_elems<real_t>(c.kt) * sizeof(real_t);
-                        auto kern = gram_cg_wide_kernel<real_t>;
-                        HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                        const int per_cu = std::max(1, (int)((size_t)160 * 1024 / smem));
-                        poison_lds(dev.stream, dev.num_cus);
-                        hipLaunchKernelGGL(kern, dim3(std::min(row1 - row0, dev.num_cus * per_cu)), dim3(64 * GCW_NW), smem, dev.stream, *c.cg_wide, Wp);
-                        HIP_CHECK(hipGetLastError());
-                    } else
-                    wave_launch(2, row0, row1, ctr + 1, SL, dev.stream);
-                    ctr += 2;
-                };
-                for (int r = 0; r < n_heavy;) {                 // heavy rows: whole rows per batch
-                    int r1 = r + 1;
-                    while (r1 < n_heavy && ho[r1 + 1] - ho[r] <= (int)cap_items) r1++;
-                    run_batch(ho[r], ho[r1], r, r1);
-                    r = r1;
-                }
-                for (int r = n_heavy; r < total; r += (int)cap_items) {   // the others: item n_slices + i <-> position n_heavy + i
-                    const int r1 = (int)std::min<long long>(total, (long long)r + (long long)cap_items);
-                    run_batch(nsl + (r - n_heavy), nsl + (r1 - n_heavy), r, r1);
-                }
-                return 0;
-            }
-            const bool two = n_heavy > 0 && total > n_heavy;
-            if (two) {
-                d.ensure_aux();
-                HIP_CHECK(hipEventRecord(d.fork_ev, dev.stream));
-                HIP_CHECK(hipStreamWaitEvent(d.aux_stream, d.fork_ev, 0));
-            }
-            hipStream_t heavy_stream = two ? d.aux_stream : dev.stream;
-            CholSlices<real_t> none;
-            int rc_heavy = 0;
-            if (n_heavy > 0 && sliced) {
-                CholSlices<real_t> SL = SLT;
-                const size_t need = (size_t)X->n_slices * part_elems;
-                if (X->chol_part.n < need) X->chol_part.alloc(need);
-                SL.part = X->chol_part.ptr;
-                wave_launch(1, 0, X->n_slices, 1, SL, heavy_stream);       // partial Gramians of the slices
-                wave_launch(2, 0, n_heavy, 3, SL, heavy_stream);           // their rows: sum, factorise, solve
-            }
-            wave_launch(0, n_heavy, total, 2, none, dev.stream);          // everything up to 1024 entries
-            if (n_heavy > 0 && !sliced) {
-                CholParams<real_t> H = P;
-                H.nrows = n_heavy;
-                // (on the stream the call was issued on: the k_t <= 64 variant of the row kernel forks onto the auxiliary one itself)
-                rc_heavy = launch_chol_rows(dev, c, X, H, two_src, smem_nonneg);
-            } else if (two) {
-                HIP_CHECK(hipEventRecord(d.join_ev, d.aux_stream));
-                HIP_CHECK(hipStreamWaitEvent(dev.stream, d.join_ev, 0));
-            }
-            return rc_heavy;
-        }
-        if (c.cg_wide != nullptr) {
-            // the wide CG (launch_cg_wide) exists only as the second kernel of the wave path above: falling through would hand
-            // its rows a factorisation without a word -- other numbers than the reference's CG
-            g_last_error = "cmfrec_hip: internal: the Gramian CG beyond 64 unknowns needs the wave-per-row producer (weights, nonneg, L1 or "
-                           "CMFREC_HIP_CHOL=rows keep it off)";
-            return 2;
-        }
-    }
-#ifdef CMFREC_HIP_FLOAT
-    {
-        // 17-block rows (k_t = 257 .. 272, config 5's item step): the rank-k update by gramk_producer_kernel (four independent
-        // wavefronts per row or slice, operands straight from the gather), the partial matrices through HBM, the factorisation
-        // and the substitutions by gramk_consumer_kernel (four wavefronts per row, two rows per CU).  CMFREC_HIP_GRAMK=0 keeps
-        // the 16-wavefront row kernel with its own LDS-staged rank-k loop (A/B switch and cross-check).
-        const bool gk_off = switches().gramk == 0;
-        const bool gk_ok = X != nullptr && T == 17 && !two_src && c.koff == 0 && !weighted && !c.rhs_only && c.values_override == nullptr &&
-                           (c.mode == CHOL_EXPLICIT || c.mode == CHOL_COLLECTIVE) && !nonneg && !l1on && !gk_off;
-        if (gk_ok) {
-            DeviceInfo &d = const_cast<DeviceInfo &>(dev);
-            const int total = P.nrows;
-            const int n_heavy = std::min(X->bin_rows[BIN_VHEAVY], total);
-            const int nsl = n_heavy > 0 ? X->n_slices : 0;
-            CholSlices<real_t> SLT;
-            if (n_heavy > 0) {
-                SLT.vrow = X->sl_vrow.ptr; SLT.first = X->sl_first.ptr; SLT.count = X->sl_count.ptr; SLT.row_off = X->row_sl_off.ptr;
-            }
-            SLT.n_slices = nsl; SLT.n_heavy = n_heavy;
-            const std::vector<int> &ho = X->h_row_sl_off;
-            int max_row_items = 1;
-            for (int r = 0; r < n_heavy; r++) max_row_items = std::max(max_row_items, ho[r + 1] - ho[r]);
-            const int batch_env = switches().gramk_batch;
-            const int BATCH = batch_env > 0 ? batch_env : 32768;                      // x 158 KB = 5.2 GB of partials
-            const size_t cap_items = (size_t)std::min<long long>((long long)nsl + (total - n_heavy), std::max(BATCH, max_row_items));
-            // (Tried: two half-size buffers with the consumer of a batch on the second stream beside the producer of the next
-            // one -- c5 shard 146.3 against 145.8 ms / iteration in line, profiles/r03: not kept.)
-            if (X->chol_part.n < cap_items * GK_PART) X->chol_part.alloc(cap_items * GK_PART);
-            // the launch's initial matrices once, in the tile layout of the partials (the consumer adds them like a partial)
-            const real_t *init1 = nullptr, *init2 = nullptr;
-            {
-                const size_t tl = (size_t)GK_NT * 256;
-                if (c.Mfull != nullptr || (c.Minit != nullptr && c.kc > 0)) d.tile_init.alloc_at_least(2 * tl);
-                if (c.Mfull != nullptr) {
-                    hipLaunchKernelGGL(tile_pack_lane_kernel<real_t>, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, dev.stream, c.Mfull, c.kt, GK_NB,
-                                       d.tile_init.ptr);
-                    init1 = d.tile_init.ptr;
-                }
-                if (c.Minit != nullptr && c.kc > 0) {
-                    hipLaunchKernelGGL(tile_pack_lane_kernel<real_t>, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, dev.stream, c.Minit, c.kc, GK_NB,
-                                       d.tile_init.ptr + tl);
-                    init2 = d.tile_init.ptr + tl;
-                }
-            }
-            int ctr = 4, rc_all = 0;
-            // two persistent workgroups per CU fill the register file; a few slots stay open so that the small launches of
-            // another stream (the eigen-decomposition chain of the low-rank rows, EigCache) are dispatched beside a batch
-            // instead of behind it
-            const int gk_open = GK_OPEN_SLOTS;
-            const int gk_grid = std::max(2 * dev.num_cus - gk_open, dev.num_cus / 2);
-            auto run_batch = [&](int item0, int item1, int row0, int row1) {
-                if (ctr + 2 > 60) ctr = 4;
-                real_t *part = X->chol_part.ptr;
-                HIP_CHECK(hipMemsetAsync(dev.row_counter.ptr + ctr, 0, 2 * sizeof(int), dev.stream));
-                CholSlices<real_t> SL = SLT;
-                SL.part = part;
-                SL.part_base = item0;
-                CholParams<real_t> W = P;
-                W.row_first = item0; W.nrows = item1; W.counter = dev.row_counter.ptr + ctr;
-                if (item1 > item0) {
-                    poison_lds(dev.stream, dev.num_cus);
-                    hipLaunchKernelGGL(gramk_producer_kernel<real_t>, dim3(std::min(item1 - item0, gk_grid)), dim3(256), 0, dev.stream, W,
-                                       X->desc.ptr, SL);
-                    HIP_CHECK(hipGetLastError());
-                }
-                CholParams<real_t> H = P;
-                H.row_first = row0; H.nrows = row1; H.counter = dev.row_counter.ptr + ctr + 1;
-                H.gk_part = part; H.gk_row_off = X->row_sl_off.ptr; H.gk_n_heavy = n_heavy; H.gk_n_slices = nsl; H.gk_base = item0;
-                H.gk_stride = (size_t)GK_PART; H.gk_init1 = init1; H.gk_init2 = init2;
-                if (row1 > row0) {
-                    poison_lds(dev.stream, dev.num_cus);
-                    hipLaunchKernelGGL(gramk_consumer_kernel<real_t>, dim3(std::min(row1 - row0, gk_grid)), dim3(256), 0, dev.stream, H);
-                    HIP_CHECK(hipGetLastError());
-                }
-                ctr += 2;
-            };
-            for (int r = 0; r < n_heavy;) {                 // split rows: whole rows per batch
-                int r1 = r + 1;
-                while (r1 < n_heavy && ho[r1 + 1] - ho[r] <= (int)cap_items) r1++;
-                run_batch(ho[r], ho[r1], r, r1);
-                r = r1;
-            }
-            for (int r = n_heavy; r < total; r += (int)cap_items) {   // the others: item n_slices + i <-> position n_heavy + i
-                const int r1 = (int)std::min<long long>(total, (long long)r + (long long)cap_items);
-                run_batch(nsl + (r - n_heavy), nsl + (r1 - n_heavy), r, r1);
-            }
-            return rc_all;
-        }
-    }
-#endif
-    return launch_chol_rows(dev, c, X, P, two_src, smem_nonneg);
-}
-
-// the workgroup-per-row kernel over the positions [P.row_first, P.nrows) of the processing order
-static int launch_chol_rows(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, CholParams<real_t> P, bool two_src,
-                            size_t smem_nonneg)
-{
-    const int T = chol_tiles(c.kt);
-#ifdef CMF_CHOL_DEBUG
-    P.dbg = switches().debug_skip;
-    if (switches().debug_ticks && T >= 16) {
-        // phase timers of the widest kernel: printed (and reset) by the launch that follows, i.e. per half-step
-        static unsigned long long *d_ticks = nullptr;
-        unsigned long long h[8];
-        if (d_ticks == nullptr) { HIP_CHECK(hipMalloc((void **)&d_ticks, sizeof(h))); HIP_CHECK(hipMemset(d_ticks, 0, sizeof(h))); }
-        else {
-            HIP_CHECK(hipDeviceSynchronize());
-            HIP_CHECK(hipMemcpy(h, d_ticks, sizeof(h), hipMemcpyDeviceToHost));
-            if (h[5] > 0)
-                fprintf(stderr, "chol_rows ticks/row: setup %.0f rank-k|trailing %.0f init %.0f diag+wait %.0f panel %.0f back %.0f  (rows %llu, nnz/row %.0f)\n",
-                        (double)h[0] / h[5], (double)h[1] / h[5], (double)h[2] / h[5], (double)h[3] / h[5], (double)h[7] / h[5], (double)h[4] / h[5], h[5],
-                        (double)h[6] / h[5]);
-            HIP_CHECK(hipMemset(d_ticks, 0, sizeof(h)));
-        }
-        P.tstamp = d_ticks;
-    }
-#endif
-    // the two-source build (sparse side information) only where it is asked for
-#define CHOL_KERN(a, b, c_, d) (two_src ? chol_rows_kernel<real_t, a, b, c_, d, true> : chol_rows_kernel<real_t, a, b, c_, d, false>)
-    hipStream_t run_on = dev.stream;
-    auto launch = [&](auto kern, int ntt, int nw, int ch, int wgs) {
-        size_t smem = std::max(chol_lds_elems<real_t>(ntt, ch) * sizeof(real_t), smem_nonneg);
-        int grid = std::min(P.nrows - P.row_first, dev.num_cus * wgs);
-        if (grid <= 0) return;
-        if (smem > 48 * 1024)
-            HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        poison_lds(run_on, dev.num_cus);          // test hook, device.hpp
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), smem, run_on, P);
-    };
-    // <16-blocks per dimension, wavefronts per workgroup, gathered rows per round, waves per SIMD>
-    if (T <= 4) {
-        // k_t <= 64: the whole system is 10 tiles.  Rows of 129 non-zeros and more (they lead the processing order) get
-        // a four-wave workgroup, the others a two-wave one: with few gathered rows the per-row latency chain dominates
-        // and more rows in flight per CU win (C2 A-step 20.9 -> 12.8 ms).  The two launches overlap on two streams, so
-        // the light rows fill the CUs while the heaviest rows finish.
-        const int total = P.nrows;
-        const int nheavy = (X != nullptr) ? std::min(total, X->bin_first[BIN_MED2]) : total;
-        DeviceInfo &d = const_cast<DeviceInfo &>(dev);
-        const bool two = nheavy > 0 && total > nheavy;
-        if (two) {
-            d.ensure_aux();
-            HIP_CHECK(hipEventRecord(d.fork_ev, dev.stream));
-            HIP_CHECK(hipStreamWaitEvent(d.aux_stream, d.fork_ev, 0));
-        }
-        if (nheavy > 0) {
-            P.nrows = nheavy;
-            launch(CHOL_KERN(4, 4, 16, 2), 4, 4, 16, 2);
-        }
-        if (total > nheavy) {
-            P.row_first = nheavy; P.nrows = total; P.counter = dev.row_counter.ptr + 1;
-            if (two) run_on = d.aux_stream;
-            launch(CHOL_KERN(4, 2, 16, 2), 4, 2, 16, 4);
-            if (two) {
-                HIP_CHECK(hipEventRecord(d.join_ev, d.aux_stream));
-                HIP_CHECK(hipStreamWaitEvent(dev.stream, d.join_ev, 0));
-            }
-        }
-    }
-    else if (T <= 6) launch(CHOL_KERN(6, 8, 32, 1), 6, 8, 32, 1);
-    else if (T <= 9) launch(CHOL_KERN(9, 8, 32, 1), 9, 8, 32, 1);
-#ifdef CMFREC_HIP_FLOAT
-    else if (T <= 12) launch(CHOL_KERN(12, 8, 32, 1), 12, 8, 32, 1);
-    else if (T <= 16) launch(CHOL_KERN(16, 16, 16, 1), 16, 16, 16, 1);
-    // k = 256 + bias (BASELINE config 5).  Two workgroups per CU do not pay here: at the 128 VGPRs that allows the
-    // kernel spills (c5 share 1.6 -> 4.0 s per A-step; the same on 9 tiles in double: 22.6 -> 25.6 ms).
-    else {
-        // The rows the producer / consumer pair of launch_chol does not take (weights, non-negativity, L1, a second gather
-        // source): 16 wavefronts per row (10 tile slots per wave; the 8-wave build spilled ~500 registers: c5 shard B-step
-        // 377 -> 274 ms), 32 gathered rows per round (half the barriers and staging rounds of the rank-k update: 272 -> 219 ms).
-        // The build is register-starved either way (128 VGPRs at 16 waves, ~1 KB of scratch per lane).
-        launch(CHOL_KERN(17, 16, 32, 1), 17, 16, 32, 1);
-    }
-#else
-    else if (T <= 12) launch(CHOL_KERN(12, 8, 16, 1), 12, 8, 16, 1);
-    else launch(CHOL_KERN(16, 8, 16, 1), 16, 8, 16, 1);
-#endif
-#undef CHOL_KERN
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// (launch_gemm: device.hpp)
-
-// Linv [k, k] := (R^T)^-1 of the row-major upper factor R (dense_kernels.hpp, trtri_from_upper_kernel): R and the rows being built
-// staged in LDS while 2 k (k + 1) elements fit (static limit 48 KiB, raised to 96 KiB on request), in global memory beyond.
-static void launch_trtri(const DeviceInfo &dev, const real_t *R, int k, real_t *Linv)
-{
-    const size_t tr_smem = (size_t)2 * k * (k + 1) * sizeof(real_t);
-    if (tr_smem <= 96 * 1024) {
-        auto kern = trtri_from_upper_kernel<real_t, true>;
-        if (tr_smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tr_smem));
-        hipLaunchKernelGGL(kern, dim3(1), dim3(256), tr_smem, dev.stream, R, k, Linv);
-    } else {
-        hipLaunchKernelGGL((trtri_from_upper_kernel<real_t, false>), dim3(1), dim3(256), 0, dev.stream, R, k, Linv);
-    }
-    HIP_CHECK(hipGetLastError());
-}
-
-// X := X (R^T R)^-1 for the row-major [rows, k] block X (ld = ldx) and the row-major upper Cholesky factor R [k, k] of a
-// shared matrix: the multi-right-hand-side posv of optimizeA Case 3 (common.c:3171-3175).  Round 4: no library call -- the
-// inverse of the shared matrix once (L^-1 = R^-T by one workgroup, column per thread; M^-1 = L^-T L^-1 by the library's own
-// GEMM), then the rows times it as one tall GEMM on the matrix cores (rounds 1-3: two rocBLAS trsm over all rows).
-static void launch_potrs_rows(const DeviceInfo &dev, int rows, int k, const real_t *R, real_t *X, size_t ldx)
-{
-    if (rows <= 0 || k <= 0) return;
-    DeviceInfo &d = const_cast<DeviceInfo &>(dev);
-    d.potrs_inv.alloc_at_least((size_t)2 * k * k);
-    d.potrs_tmp.alloc_at_least((size_t)rows * k);
-    real_t *Linv = d.potrs_inv.ptr, *Minv = d.potrs_inv.ptr + (size_t)k * k;
-    launch_trtri(dev, R, k, Linv);
-    launch_gemm<true>(dev, k, k, k, (real_t)1, Linv, (size_t)k, Linv, (size_t)k, Minv, (size_t)k);
-    launch_gemm<false>(dev, rows, k, k, (real_t)1, X, ldx, Minv, (size_t)k, d.potrs_tmp.ptr, (size_t)k);
-    if (sizeof(real_t) == 4) {
-        // Single precision: one step of iterative refinement with the matrix itself.  The product with an explicit inverse carries
-        // an error of cond(M) eps where the two triangular solves of the reference's posv are backward stable; x1 = x0 +
-        // (b - x0 M) M^-1 brings the residual back to the level of the solves (the right-hand sides are still in X here).
-        // M = R^T R from the factor; three tall products instead of one, on rows x k x k flops -- nothing beside the half-step's gather.
-        d.potrs_ref.alloc_at_least((size_t)k * k + (size_t)rows * k);
-        real_t *Mfull = d.potrs_ref.ptr, *Res = d.potrs_ref.ptr + (size_t)k * k;
-        hipLaunchKernelGGL(upper_only_kernel<real_t>, grid1d((size_t)k * k), dim3(256), 0, dev.stream, R, k, Linv);       // (Linv is free again)
-        launch_gemm<true>(dev, k, k, k, (real_t)1, Linv, (size_t)k, Linv, (size_t)k, Mfull, (size_t)k);                    // R^T R
-        launch_gemm<false>(dev, rows, k, k, (real_t)1, d.potrs_tmp.ptr, (size_t)k, Mfull, (size_t)k, Res, (size_t)k);      // x0 M
-        hipLaunchKernelGGL(residual_rows_kernel<real_t>, grid1d((size_t)rows * k), dim3(256), 0, dev.stream, Res, (size_t)k, X, ldx, (size_t)rows, k);   // b - x0 M
-        launch_gemm<false>(dev, rows, k, k, (real_t)1, Res, (size_t)k, Minv, (size_t)k, X, ldx);                           // (b - x0 M) M^-1 -> X
-        hipLaunchKernelGGL(add_rows_kernel<real_t>, grid1d((size_t)rows * k), dim3(256), 0, dev.stream, X, ldx, d.potrs_tmp.ptr, (size_t)k, (size_t)rows, k);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    HIP_CHECK(hipMemcpy2DAsync(X, ldx * sizeof(real_t), d.potrs_tmp.ptr, (size_t)k * sizeof(real_t), (size_t)k * sizeof(real_t), (size_t)rows,
-                               hipMemcpyDeviceToDevice, dev.stream));
-}
-
-// CG of the explicit model beyond 64 unknowns (k_t <= 129): through the row's Gramian (gram_cg_wide_kernels.hpp) instead of the
-// lane <-> unknown kernel.  -1: not applicable (the caller takes launch_cg).  CMFREC_HIP_CG_KERNEL=generic keeps the generic kernel
-// (A/B switch and on-device cross-check).
-static int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X)
-{
-    const bool border = (c.k > 16) && ((c.k - 1) % 16 == 0);
-    const int nbw = (c.k - (border ? 1 : 0) + 15) / 16;
-    if (c.implicit || c.k <= 64 || nbw > 8 || c.precond || c.X2 != nullptr || c.Bi != nullptr || c.koff != 0 || X.weighted() ||
-        dev.nonneg_now || dev.l1_now != (real_t)0 || dev.l1_last_now != (real_t)0 ||      // (launch_chol's wave path is off then)
-        cg_variant_from_env() == CgVariant::Generic || switches().chol == 1 ||
-        (c.kc > 0 && (c.CtC == nullptr || c.UC == nullptr || c.kc > c.k)) || gcw_lds_elems<real_t>(c.k) * sizeof(real_t) > (size_t)160 * 1024)
-        return -1;
-    CgParams<real_t> P;
-    P.A = c.A; P.lda = c.lda; P.B = c.B; P.ldb = c.ldb; P.k = c.k;
-    P.indptr = X.p.ptr; P.indices = X.i.ptr; P.values = X.v.ptr;
-    P.bias_sub = c.bias_sub; P.order = X.order.ptr; P.desc = X.desc.ptr; P.nrows = 0; P.BtB = nullptr;
-    P.lam = c.lam; P.lam_last = c.lam_last;
-    P.scale_lam = c.scale_lam; P.scale_bias_const = c.scale_bias_const;
-    P.max_cg_steps = c.max_cg_steps; P.precond = 0;
-    P.koff = 0; P.kc = c.kc; P.CtC = c.CtC; P.UC = c.UC; P.w_side = c.w_side;
-    P.rows_with_u = c.rows_with_u; P.p_side = c.p_side; P.scale_lam_sideinfo = c.scale_lam_sideinfo ? 1 : 0;
-    // The Gramian costs k_t / 8 times the products of the CG's four passes per entry and saves three of the four gathers and the
-    // generic kernel's wave-wide reduction per gathered row: it pays on the long rows (config 3's items under CG: 18.1 -> 6.8 ms)
-    // and loses on the short ones (its users, 143 entries per row on average: 8.6 -> 15.8 ms).  So the rows beyond 256 entries --
-    // they lead the processing order -- take it, the others stay on the lane <-> unknown kernel (CgCall::skip_first).
-    const int n_wide = X.rows_longer_than(256, X.n_nonempty);
-    if (n_wide <= 0) return -1;
-    CholCall cc{c.A, c.lda, c.B, c.ldb, c.k, 0, c.bias_sub, nullptr, 0, 0, 0, c.lam, c.lam_last, c.scale_lam, c.scale_lam_sideinfo,
-                c.scale_bias_const, CHOL_EXPLICIT};
-    cc.cg_wide = &P;
-    cc.row_limit = n_wide;
-    int rc = launch_chol(dev, cc, &X);                    // positions [0, n_wide)
-    if (rc) return rc;
-    CgCall rest = c;
-    rest.skip_first = n_wide;
-    return launch_cg(dev, rest, X, nullptr);              // the shorter rows, and a block system's rows without entries
-}
-static int launch_cg_any(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinTimers *tm = nullptr)
-{
-    const int rc = launch_cg_wide(dev, c, X);
-    return rc >= 0 ? rc : launch_cg(dev, c, X, tm);
-}
-
-// Eigenvectors / values of one side's shared matrix w C^T C (eig_kernels.hpp: tridiagonalisation + implicit QL, two launches
-// of 1 and ceil(k_c / 64) workgroups -- a few milliseconds of mostly sequential work on a handful of CUs), so
-//  * inside a half-step it is enqueued BEHIND the launches of the rows that do not need it (the producer / consumer batches of
-//    the long rows), on the eigen stream, waiting only for an event recorded in front of them;
-//  * a half-step also enqueues the decomposition the NEXT half-step of the other side will ask for (`wanted`: that side took
-//    the low-rank path before), since C and D are final once their own updates have run (cmfrec's order C, D, B, A):
-//    `fresh` says the cached vectors belong to the side matrix as it stands; every update / upload of C or D clears it.
-// (Rounds 3-5 bound rocSOLVER's dsyevd here -- ~4000 launches per decomposition, 6 ms on an idle device and 33 ms beside the
-//  persistent batches, profiles/r05/r05_zg_*; round 6 replaced it and the link against rocBLAS went with it.)
-struct EigCache {
-    DevBuf<double> W, V, D, E, Tau;
-    DevBuf<int> info;
-    DevBuf<real_t> Q, Qt, Lam, M;     // M: the matrix a prefetch decomposes (the half-step's own one lives in the session's ctc)
-    hipEvent_t ev = nullptr;          // recorded behind the chain on the eigen stream
-    bool fresh = false, wanted = false;
-    int kind = 0;                     // 3 tridiagonalisation + QL (eig_kernels.hpp), 2 the one-workgroup Jacobi kernel
-    int checked_kc = 0;               // the QL kernel's status word has been read back for this matrix size (once per size and cache)
-    ~EigCache() { if (ev) (void)hipEventDestroy(ev); }
-};
-
-struct LowRankScratch {
-    DevBuf<real_t> Ct, Bt, R, T;
-    EigCache own;                 // callers without a cache per side (the stand-alone operator)
-    int last_rows = 0;            // rows the low-rank kernels solved in the most recent launch (0: path not taken)
-    int last_eig = 0;             // its eigen-decomposition: 3 tridiagonalisation + QL, 2 the one-workgroup Jacobi kernel
-};
-
-// Enqueues the decomposition of the kc x kc matrix Minit on the eigen stream, behind `after` (an event of the main stream:
-// what produced Minit), and records E.ev behind it.
-static void issue_eig(DeviceInfo &d, EigCache &E, const real_t *Minit, int kc, hipEvent_t after)
-{
-    E.W.alloc_at_least((size_t)kc * kc); E.V.alloc_at_least((size_t)kc * kc);
-    E.Q.alloc_at_least((size_t)kc * kc); E.Qt.alloc_at_least((size_t)kc * kc); E.Lam.alloc_at_least((size_t)kc);
-    if (!E.ev) HIP_CHECK(hipEventCreateWithFlags(&E.ev, hipEventDisableTiming));
-    HIP_CHECK(hipStreamWaitEvent(d.eig_stream(), after, 0));
-    // default: Householder tridiagonalisation + implicit QL with the rotations applied row-parallel (eig_kernels.hpp);
-    // CMFREC_HIP_EIG=jacobi takes the one-workgroup Jacobi kernel (on-device cross-check; also the fallback should a QL iteration
-    // ever fail to converge: the status word is read back the first time a matrix of this size goes through a cache)
-    static bool ql_bad = false;
-    bool done = false;
-    if (!ql_bad && !switches().eig_jacobi && kc <= EIG_MAX_N) {
-        E.D.alloc_at_least((size_t)kc); E.E.alloc_at_least((size_t)kc); E.Tau.alloc_at_least((size_t)kc);
-        if (E.info.n < 1) { E.info.alloc(1); HIP_CHECK(hipMemsetAsync(E.info.ptr, 0, sizeof(int), d.eig_stream())); }
-        hipLaunchKernelGGL(eig_tridiag_kernel<real_t>, dim3(1), dim3(EIG_TRIDIAG_THREADS), 0, d.eig_stream(), Minit, kc, E.W.ptr, E.D.ptr, E.E.ptr, E.Tau.ptr);
-        const bool wide = kc > 288;                          // rows of the eigenvector matrix per workgroup: 64, or 32 (LDS: kc rows doubles)
-        const int rows = wide ? 32 : 64;
-        const size_t smem = ((size_t)kc * rows + 4 * (size_t)kc) * sizeof(double);
-        auto kern = wide ? eig_ql_rows_kernel<real_t, 32> : eig_ql_rows_kernel<real_t, 64>;
-        static thread_local bool attr_set[MAX_DEVICES][2] = {{false}};
-        bool &as = attr_set[std::min(std::max(d.device, 0), MAX_DEVICES - 1)][wide ? 1 : 0];
-        if (!as) { HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); as = true; }
-        hipLaunchKernelGGL(kern, dim3((kc + rows - 1) / rows), dim3(64), smem, d.eig_stream(), kc, E.W.ptr, E.D.ptr, E.E.ptr, E.Tau.ptr, E.Q.ptr,
-                           E.Qt.ptr, (size_t)kc, E.Lam.ptr, E.info.ptr);
-        HIP_CHECK(hipGetLastError());
-        done = true;
-        if (E.checked_kc != kc) {
-            int h_info = 0;
-            HIP_CHECK(hipMemcpyAsync(&h_info, E.info.ptr, sizeof(int), hipMemcpyDeviceToHost, d.eig_stream()));
-            HIP_CHECK(hipStreamSynchronize(d.eig_stream()));
-            E.checked_kc = kc;
-            if (h_info != 0) { ql_bad = true; done = false; }
-        }
-    }
-    if (!done)
-        hipLaunchKernelGGL(jacobi_eig_kernel<real_t>, dim3(1), dim3(1024), 0, d.eig_stream(), Minit, kc, E.W.ptr, E.V.ptr, E.Q.ptr, E.Qt.ptr,
-                           (size_t)kc, E.Lam.ptr, 30, sizeof(real_t) == 4 ? 1e-9 : 1e-13);
-    E.kind = done ? 3 : 2;
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(E.ev, d.eig_stream()));
-}
-
-// Side information as the half-steps multiply by it: the dense matrix (from the operand's first row), or the sparse matrix whose
-// absent entries are zeros, centred by its column means (side_zeros_kernels.hpp).  No kernel reads U element by element: every
-// use is one of the two products below, so the solvers downstream see the same operands either way.
-struct SideOperand {
-    const real_t *dense = nullptr;
-    SideZeros *zeros = nullptr;
-    int first = 0;                              // the operand's first row within `zeros`
-    SideOperand from_row(int r, int p) const
-    {
-        SideOperand o = *this;
-        if (o.dense != nullptr) o.dense += (size_t)r * p;
-        o.first += r;
-        return o;
-    }
-};
 // out[count, kc] = alpha U[:count, :] M,  M [p, kc]
-static void side_times(const DeviceInfo &dev, const SideOperand &u, int count, int kc, int p, real_t alpha, const real_t *M, real_t *out,
+void side_times(const DeviceInfo &dev, const SideOperand &u, int count, int kc, int p, real_t alpha, const real_t *M, real_t *out,
                        size_t ldo)
 {
     if (u.zeros != nullptr) sz_times(dev, *u.zeros, u.first, count, kc, alpha, M, (size_t)kc, out, ldo);
     else launch_gemm<false>(dev, count, kc, p, alpha, u.dense, (size_t)p, M, (size_t)kc, out, ldo);
 }
 // out[p, kc] = U[:rows, :]^T F[:rows, :kc]   (sparse-as-zeros: all its rows)
-static void side_transposed_times(const DeviceInfo &dev, const SideOperand &u, int rows, int kc, int p, const real_t *F, size_t ldF,
+void side_transposed_times(const DeviceInfo &dev, const SideOperand &u, int rows, int kc, int p, const real_t *F, size_t ldF,
                                   real_t *out, size_t ldo)
 {
     if (u.zeros != nullptr) sz_transposed_times(dev, *u.zeros, kc, F, ldF, out, ldo);
     else launch_gemm<true>(dev, p, kc, rows, (real_t)1, u.dense, (size_t)p, F, ldF, out, ldo);
-}
-
-// Collective Cholesky half-step (mode CHOL_COLLECTIVE, dense side information on every row of the block) with the rows of
-// few entries solved by the low-rank update of a diagonalised shared matrix instead of a k_t^3 / 3 factorisation per row
-// (config 5's users: 20 entries against k_t = 257 unknowns).  c: the call as launch_chol would take it (right-hand sides
-// w U C already in the rows, c.Minit = w C^T C); Um: the block's rows of U; k: the factors shared with X; rows_b: rows of
-// the opposing matrix.  Returns -1 when the path does not apply (the caller launches as usual), else the return code.
-// CMFREC_HIP_LOWRANK=0 switches it off, =1 forces it whenever the shapes allow (tests).
-// mine: this side's cache (NULL: the scratch's own, never fresh); next / kc_next: the other side's cache with its matrix in
-// next->M, decomposed behind this one for the half-step that follows (NULL: nothing to prefetch).
-static int launch_collective_lowrank(const DeviceInfo &dev, LowRankScratch &S, CholCall c, const SparseShard &X, const real_t *Cm,
-                                     const SideOperand &Um, int p_self, real_t w, int k, int rows_b, EigCache *mine = nullptr,
-                                     EigCache *next = nullptr, int kc_next = 0)
-{
-    const int lr_sw = switches().lowrank;       // CMFREC_HIP_LOWRANK: 0 / 1 force the path off / on
-    const int kt = c.kt, kc = c.kc, k_side_self = c.koff;
-    // rows of up to lr_max entries: the s x s system is at most half the k_t x k_t one (and 8 blocks in single, 4 in double)
-    const int lr_type_max = (sizeof(real_t) == 4) ? 128 : 64;
-    const int lr_max = (kt >= 256 && lr_type_max >= 128) ? 128 : (kt >= 128 ? 64 : 32);
-    const int n_full = X.rows_longer_than(lr_max, X.nrows);          // positions [0, n_full): full factorisation
-    const int n_light = X.nrows - n_full;
-    const bool lr_ok = lr_sw != 0 && c.mode == CHOL_COLLECTIVE && c.Mfull == nullptr && c.X2 == nullptr &&
-                       !X.weighted() &&
-                       !c.scale_bias_const && !dev.nonneg_now && !c.nonneg && dev.l1_now == (real_t)0 && dev.l1_last_now == (real_t)0 &&
-                       c.rows_with_u >= X.nrows && !c.rhs_prefilled_all && kt <= 320 && kt >= 64 && kc > 0 && p_self > 0 &&
-                       // the penalty must be a multiple of the identity on the rotated block: the last unknown's own lambda
-                       // (a bias) has to sit outside of it
-                       (kt - 1 >= kc || c.lam_last == c.lam) &&
-                       (lr_sw == 1 || (n_light >= 32768 && kt >= 96));
-    S.last_rows = 0; S.last_eig = 0;
-    if (!lr_ok || n_light <= 0) return -1;
-    hipStream_t st = dev.stream;
-    const int ngr = (kt + 15) / 16;
-    const size_t ldbt = (size_t)16 * ngr;
-    S.Ct.alloc_at_least((size_t)p_self * kc);
-    S.Bt.alloc_at_least((size_t)rows_b * ldbt + 64);
-    S.R.alloc_at_least((size_t)X.nrows * kc);
-    S.T.alloc_at_least((size_t)n_light * kc);
-    EigCache &E = mine ? *mine : S.own;
-    if (mine) mine->wanted = true;
-    // w C^T C = Q L Q^T on the eigen stream, beside the full factorisations of the longer rows (which do not need it and are
-    // enqueued first: see EigCache)
-    {
-        DeviceInfo &d = const_cast<DeviceInfo &>(dev);
-        d.ensure_aux();
-        const bool have = mine != nullptr && mine->fresh && mine->ev != nullptr;
-        const bool ahead = next != nullptr && kc_next > 0;
-        if (!have || ahead) {
-            if (!d.eig_fork) HIP_CHECK(hipEventCreateWithFlags(&d.eig_fork, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(d.eig_fork, st));
-        }
-        c.row_limit = n_full;
-        const int rc = (n_full > 0) ? launch_chol(dev, c, &X) : 0;
-        if (rc) return rc;
-        if (!have) {
-            issue_eig(d, E, c.Minit, kc, d.eig_fork);
-            if (mine) mine->fresh = true;          // (c.Minit is the session's w C^T C of this side as it stands)
-        }
-        if (ahead) {
-            issue_eig(d, *next, next->M.ptr, kc_next, d.eig_fork);
-            next->fresh = true;
-        }
-        S.last_eig = E.kind;
-        S.last_rows = n_light;
-        HIP_CHECK(hipStreamWaitEvent(st, E.ev, 0));
-    }
-    // C~ = C Q ;  B~ = [B(:, :k) Q(k_side:, :) | B(:, k:)] ;  R = w U C~ (natural row order)
-    launch_gemm<false>(dev, p_self, kc, kc, (real_t)1, Cm, (size_t)kc, E.Q.ptr, (size_t)kc, S.Ct.ptr, (size_t)kc);
-    launch_gemm<false>(dev, rows_b, kc, k, (real_t)1, c.B, c.ldb, E.Q.ptr + (size_t)k_side_self * kc, (size_t)kc, S.Bt.ptr, ldbt);
-    if (kt > kc)
-        hipLaunchKernelGGL(copy_cols_kernel<real_t>, grid1d((size_t)rows_b * (kt - kc)), dim3(256), 0, st, S.Bt.ptr, ldbt, kc, c.B, c.ldb, k,
-                           kt - kc, (size_t)rows_b);
-    side_times(dev, Um, X.nrows, kc, p_self, w, S.Ct.ptr, S.R.ptr, (size_t)kc);
-    LrParams<real_t> L;
-    L.A = c.A; L.lda = c.lda; L.pre = S.R.ptr; L.ldpre = (size_t)kc;
-    L.Tc = S.T.ptr; L.ldt = (size_t)kc; L.pos0 = n_full;
-    L.Bt = S.Bt.ptr; L.ldbt = ldbt; L.lam_eig = E.Lam.ptr;
-    L.kt = kt; L.kc = kc; L.koff = k_side_self; L.rotated = 1;
-    L.indptr = X.p.ptr; L.indices = X.i.ptr; L.values = X.v.ptr; L.bias_sub = c.bias_sub;
-    L.lam = c.lam; L.lam_last = c.lam_last;
-    L.scale_lam = c.scale_lam ? 1 : 0; L.scale_lam_sideinfo = c.scale_lam_sideinfo ? 1 : 0;
-    L.scale_bias_const = 0; L.p_side = p_self; L.collective = 1;
-    if (dev.row_counter.n < ROW_COUNTER_INTS) const_cast<DeviceInfo &>(dev).row_counter.alloc(ROW_COUNTER_INTS);
-    HIP_CHECK(hipMemsetAsync(dev.row_counter.ptr + 8, 0, 4 * sizeof(int), st));
-    // rows sorted by length: (64, 128] entries -> 8 blocks (single precision only), (32, 64] -> 4, the rest -> 2
-    const int n_gt64 = X.rows_longer_than(64, X.nrows), n_gt32 = X.rows_longer_than(32, X.nrows);
-    auto lr_launch = [&](auto kern, int nb_, int wps, int first, int last, int counter) {
-        if (last <= first) return;
-        LrParams<real_t> Lc = L;
-        Lc.row_first = first; Lc.nrows = last; Lc.counter = dev.row_counter.ptr + 8 + counter;
-        const size_t smem = 4 * lowrank_lds_elems<real_t>(nb_) * sizeof(real_t);
-        if (smem > 48 * 1024)
-            HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        const int grid = std::min((last - first + 3) / 4, dev.num_cus * wps);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, Lc, X.desc.ptr);
-    };
-    // (two wavefronts per SIMD at least: a single wave cannot keep the matrix pipe issuing, see gramk_kernels.hpp)
-#ifdef CMFREC_HIP_FLOAT
-    lr_launch(lowrank_rows_kernel<real_t, 8, 2>, 8, 2, n_full, std::max(n_full, n_gt64), 0);
-    lr_launch(lowrank_rows_kernel<real_t, 4, 3>, 4, 3, std::max(n_full, n_gt64), std::max(n_full, n_gt32), 1);
-#else
-    lr_launch(lowrank_rows_kernel<real_t, 4, 2>, 4, 2, std::max(n_full, n_gt64), std::max(n_full, n_gt32), 1);
-#endif
-#ifdef CMFREC_HIP_FLOAT
-    lr_launch(lowrank_rows_kernel<real_t, 2, 4>, 2, 4, std::max(n_full, n_gt32), X.nrows, 2);
-#else
-    lr_launch(lowrank_rows_kernel<real_t, 2, 3>, 2, 3, std::max(n_full, n_gt32), X.nrows, 2);
-#endif
-    HIP_CHECK(hipGetLastError());
-    // x[:kc] = Q x~[:kc]: one GEMM over the light rows (in processing order), then back to their rows
-    launch_gemm<false>(dev, n_light, kc, kc, (real_t)1, S.T.ptr, (size_t)kc, E.Qt.ptr, (size_t)kc, S.R.ptr, (size_t)kc);
-    hipLaunchKernelGGL(scatter_rows_kernel<real_t>, grid1d((size_t)n_light * kc), dim3(256), 0, st, c.A, c.lda, X.desc.ptr, n_full, S.R.ptr,
-                       (size_t)kc, kc, (size_t)n_light);
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// Plain closed-form rows (factors_closed_form, common.c:978-1070: no side information) with few entries against many unknowns: the
-// row's matrix is lam_i I + sum_j B_j B_j^T -- already diagonal plus a rank-s update, so the low-rank kernel applies without any
-// rotation (lowrank_kernels.hpp, !rotated / !collective): an s x s system instead of a k_t^3 / 3 factorisation.  Config 3's users
-// (k_t = 129, double): 38 % of the rows hold at most 64 entries.  -1 when the path does not apply.
-#ifndef CMF_LR_MAX_F64
-#define CMF_LR_MAX_F64 96      // 64: the four-block build only (the A/B build of round 5)
-#endif
-static int launch_plain_lowrank(const DeviceInfo &dev, const CholCall &c, const SparseShard &X)
-{
-    const int lr_sw = switches().lowrank;       // CMFREC_HIP_LOWRANK: 0 / 1 force the path off / on
-    const int kt = c.kt;
-    // (double precision, k_t >= 128: rows of 65..96 entries on a six-block build, 21 tiles at one wavefront per SIMD -- the full
-    //  path costs such a row the 36-tile rank-k update, a 133 KB round trip through HBM and the eight-block factorisation)
-    const int lr_type_max = (sizeof(real_t) == 4) ? 128 : 64;
-    const int lr_max = (kt >= 256 && lr_type_max >= 128) ? 128 : (kt >= 128 ? (sizeof(real_t) == 8 ? CMF_LR_MAX_F64 : 64) : 32);
-    const int n_rows = X.n_nonempty;                                  // rows without entries stay as they are (common.c:3270)
-    const int n_full = X.rows_longer_than(lr_max, n_rows);
-    const int n_light = n_rows - n_full;
-    const bool ok = lr_sw != 0 && !X.weighted() && c.koff == 0 && c.X2 == nullptr && !c.rhs_only &&
-                    c.values_override == nullptr && !c.nonneg && !dev.nonneg_now && dev.l1_now == (real_t)0 && dev.l1_last_now == (real_t)0 &&
-                    kt <= 320 && (lr_sw == 1 ? kt >= 40 : (kt >= 96 && n_light >= 2048));
-    if (!ok || n_light <= 0) return -1;
-    CholCall cf = c;
-    cf.row_limit = n_full;
-    const int rc = (n_full > 0) ? launch_chol(dev, cf, &X) : 0;
-    if (rc) return rc;
-    hipStream_t st = dev.stream;
-    LrParams<real_t> L;
-    L.A = c.A; L.lda = c.lda; L.pre = nullptr; L.ldpre = 0; L.Tc = nullptr; L.ldt = 0; L.pos0 = n_full;
-    L.Bt = c.B; L.ldbt = c.ldb; L.lam_eig = nullptr;
-    L.kt = kt; L.kc = 0; L.koff = 0; L.rotated = 0;
-    L.indptr = X.p.ptr; L.indices = X.i.ptr; L.values = X.v.ptr; L.bias_sub = c.bias_sub;
-    L.lam = c.lam; L.lam_last = c.lam_last;
-    L.scale_lam = c.scale_lam ? 1 : 0; L.scale_lam_sideinfo = 0; L.scale_bias_const = c.scale_bias_const ? 1 : 0; L.p_side = 0; L.collective = 0;
-    if (dev.row_counter.n < ROW_COUNTER_INTS) const_cast<DeviceInfo &>(dev).row_counter.alloc(ROW_COUNTER_INTS);
-    HIP_CHECK(hipMemsetAsync(dev.row_counter.ptr + 8, 0, 4 * sizeof(int), st));
-    const int n_gt64 = X.rows_longer_than(64, n_rows), n_gt32 = X.rows_longer_than(32, n_rows);
-    auto lr_launch = [&](auto kern, int nb_, int wps, int first, int last, int counter) {
-        if (last <= first) return;
-        LrParams<real_t> Lc = L;
-        Lc.row_first = first; Lc.nrows = last; Lc.counter = dev.row_counter.ptr + 8 + counter;
-        const size_t smem = 4 * lowrank_lds_elems<real_t>(nb_) * sizeof(real_t);
-        if (smem > 48 * 1024)
-            HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        const int grid = std::min((last - first + 3) / 4, dev.num_cus * wps);
-        poison_lds(st, dev.num_cus);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, Lc, X.desc.ptr);
-    };
-#ifdef CMFREC_HIP_FLOAT
-    lr_launch(lowrank_rows_kernel<real_t, 8, 2>, 8, 2, n_full, std::max(n_full, n_gt64), 0);
-    lr_launch(lowrank_rows_kernel<real_t, 4, 3>, 4, 3, std::max(n_full, n_gt64), std::max(n_full, n_gt32), 1);
-    lr_launch(lowrank_rows_kernel<real_t, 2, 4>, 2, 4, std::max(n_full, n_gt32), n_rows, 2);
-#else
-    if (lr_max > 64) lr_launch(lowrank_rows_kernel<real_t, 6, 1>, 6, 1, n_full, std::max(n_full, n_gt64), 0);
-    lr_launch(lowrank_rows_kernel<real_t, 4, 2>, 4, 2, std::max(n_full, n_gt64), std::max(n_full, n_gt32), 1);
-    lr_launch(lowrank_rows_kernel<real_t, 2, 3>, 2, 3, std::max(n_full, n_gt32), n_rows, 2);
-#endif
-    HIP_CHECK(hipGetLastError());
-    return 0;
 }
 
 void open_device(int device, int *device_id, int *num_cus, hipStream_t *stream)
@@ -909,7 +57,7 @@ void open_device(int device, int *device_id, int *num_cus, hipStream_t *stream)
     HIP_CHECK(hipStreamCreateWithFlags(stream, hipStreamNonBlocking));
 }
 
-static void init_device(DeviceInfo &dev, int device)
+void init_device(DeviceInfo &dev, int device)
 {
     open_device(device, &dev.device, &dev.num_cus, &dev.stream);
 }
@@ -4519,55 +3667,6 @@ extern "C" int cmfrec_hip_dense_rows_probe(int rows, int n, double present, int 
     });
 }
 
-// The symmetric eigen-decomposition of the low-rank path on its own (tests/test_gpu_operators.py::test_sym_eig,
-// tools/microbench/eig_probe.py): A [n, n] symmetric -> Q [n, n] (Q[i][c] = component i of eigenvector c), lam [n] (clamped at
-// zero); method 0 = tridiagonalisation + QL (eig_kernels.hpp), 1 = the one-workgroup Jacobi kernel.  ms: device time of `reps` runs.
-extern "C" int cmfrec_hip_sym_eig(int n, const real_t *A, real_t *Q, real_t *lam, int method, int reps, double *ms)
-{
-    return guarded([&]() {
-        if (n < 2 || n > EIG_MAX_N) { g_last_error = "cmfrec_hip_sym_eig: 2 <= n <= 320"; return 2; }
-        DeviceInfo dev;
-        init_device(dev, -1);
-        DevBuf<real_t> dA, dQ, dQt, dL;
-        DevBuf<double> W, V, D, E, Tau;
-        DevBuf<int> info;
-        const size_t nn = (size_t)n * n;
-        dA.upload(A, nn, dev.stream); dQ.alloc(nn); dQt.alloc(nn); dL.alloc((size_t)n);
-        W.alloc(nn); V.alloc(nn); D.alloc((size_t)n); E.alloc((size_t)n); Tau.alloc((size_t)n); info.alloc(1);
-        HIP_CHECK(hipMemsetAsync(info.ptr, 0, sizeof(int), dev.stream));
-        hipEvent_t e0, e1;
-        HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
-        const bool wide = n > 288;
-        const int rows = wide ? 32 : 64;
-        const size_t smem = ((size_t)n * rows + 4 * (size_t)n) * sizeof(double);
-        auto kern = wide ? eig_ql_rows_kernel<real_t, 32> : eig_ql_rows_kernel<real_t, 64>;
-        HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        for (int r = 0; r < std::max(reps, 1) + 1; r++) {
-            if (r == 1) HIP_CHECK(hipEventRecord(e0, dev.stream));
-            if (method == 0 || method == 2) {        // (2: only the tridiagonalisation inside the timed runs -- where the time goes)
-                hipLaunchKernelGGL(eig_tridiag_kernel<real_t>, dim3(1), dim3(EIG_TRIDIAG_THREADS), 0, dev.stream, dA.ptr, n, W.ptr, D.ptr, E.ptr, Tau.ptr);
-                if (method == 0 || r == 0)
-                    hipLaunchKernelGGL(kern, dim3((n + rows - 1) / rows), dim3(64), smem, dev.stream, n, W.ptr, D.ptr, E.ptr, Tau.ptr, dQ.ptr, dQt.ptr,
-                                       (size_t)n, dL.ptr, info.ptr);
-            } else
-                hipLaunchKernelGGL(jacobi_eig_kernel<real_t>, dim3(1), dim3(1024), 0, dev.stream, dA.ptr, n, W.ptr, V.ptr, dQ.ptr, dQt.ptr, (size_t)n,
-                                   dL.ptr, 30, sizeof(real_t) == 4 ? 1e-9 : 1e-13);
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipEventRecord(e1, dev.stream));
-        HIP_CHECK(hipEventSynchronize(e1));
-        float t = 0;
-        HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = (double)t / std::max(reps, 1);
-        int h_info = 0;
-        HIP_CHECK(hipMemcpyAsync(&h_info, info.ptr, sizeof(int), hipMemcpyDeviceToHost, dev.stream));
-        dQ.download(Q, nn, dev.stream); dL.download(lam, (size_t)n, dev.stream);
-        HIP_CHECK(hipStreamSynchronize(dev.stream));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (h_info != 0) { g_last_error = "cmfrec_hip_sym_eig: a QL iteration did not converge"; return 4; }
-        return 0;
-    });
-}
 
 // The dense layer on its own (tests/test_gpu_dense_ops.py): one operation through the launch helpers the library itself uses --
 // launch_gemm<false / true>, launch_gram, the potrf_upper_kernel launch of the shared-matrix half-steps, launch_trtri and

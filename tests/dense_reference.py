@@ -324,7 +324,7 @@ def gram_cases():
 
 
 def gram_blocks(n, num_cus=256):
-    """(blocks, rows per block) of launch_gram's first stage (device.hpp)."""
+    """(blocks, rows per block) of launch_gram's first stage (launch_dense.hip)."""
     nb = max(1, min(2 * num_cus, (n + 127) // 128))
     rpb = max(1, (n + nb - 1) // nb)
     return max(1, (n + rpb - 1) // rpb), rpb

@@ -1,5 +1,5 @@
 """Parity cases of the operator tests again with the LDS of every CU filled with NaN patterns in front of each launch
-(CMFREC_HIP_POISON_LDS=1, cmfrec_amd/csrc/device.hpp): a kernel that reads LDS it has not written -- 0 x stale LDS in
+(CMFREC_HIP_POISON_LDS=1, cmfrec_amd/csrc/launch_cg.hip): a kernel that reads LDS it has not written -- 0 x stale LDS in
 gram_cg_kernel left the split rows of a launch at their start values whenever the previous tenant of that LDS had left a NaN
 pattern, which happened on some boxes in some runs (profiles/README.md) -- fails here every time."""
 import numpy as np

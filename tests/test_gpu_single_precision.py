@@ -51,7 +51,7 @@ def test_two_rows_per_wave_shapes(name):
 @pytest.mark.parametrize("name", F.SHARED_CASES)
 def test_shared_matrix_solve(name):
     """NA_as_zero_X closed form and one implicit-features half-step: one factorisation of the shared matrix, its explicit
-    inverse and the float32 refinement step (session.hip, launch_potrs_rows), on a matrix of condition ~1e4."""
+    inverse and the float32 refinement step (launch_dense.hip, launch_potrs_rows), on a matrix of condition ~1e4."""
     _run_and_check(name)
 
 

@@ -71,7 +71,7 @@ def test_process_wide_switch_agrees_with_default(default_fits, tmp_path, env):
 
 def test_launches_by_tile_size_are_bit_identical(tmp_path):
     """Double precision, 24 < k <= 56: a length bin of the CG row kernels runs as two launches by tile size (the rows of at most
-    48 W entries on the build that fits three wavefronts per SIMD; cg_kernels.hpp NTSEL, device.hpp launch_cg_bin_by_tile).  A row's
+    48 W entries on the build that fits three wavefronts per SIMD; cg_kernels.hpp NTSEL, launch_cg.hip launch_cg_bin_by_tile).  A row's
     arithmetic depends on its own length only, so CMFREC_HIP_NT_SPLIT=0 -- one launch per bin -- gives the same bits, in both CG
     models (implicit with the Gramian, explicit without), rows in every length bin."""
     a = _run(tmp_path, "split", {}, k=50, nnz=90000)

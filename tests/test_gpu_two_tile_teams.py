@@ -1,5 +1,5 @@
 """GPU: double-precision CG rows of 65..96 entries on one wavefront and of 257..384 entries on four wavefronts, two resident tiles
-per wavefront (cg_kernels.hpp, NRES_ = 2 with NTSEL = 1; device.hpp, launch_cg_bin_by_tile; CMFREC_HIP_TWO_TILES).
+per wavefront (cg_kernels.hpp, NRES_ = 2 with NTSEL = 1; launch_cg.hip, launch_cg_bin_by_tile; CMFREC_HIP_TWO_TILES).
 
 One matrix serves the parity cases: every length at which a row changes its route or its tile -- 64 | 65 (one-wavefront bin | two-wave
 bin), 80 | 81 and 320 | 321 (5 | 6 entries per lane group), 96 | 97 and 384 | 385 (two tiles | the teams as before), 128, 256 | 257,
