@@ -32,6 +32,9 @@
 #include "rng_host.hpp"
 #include "exchange_plan.hpp"
 #include "newrows.hpp"
+#include "fit_inputs.hpp"
+
+using namespace cmfit;
 
 namespace {
 
@@ -51,12 +54,6 @@ struct SigGuard {
     ~SigGuard() { if (armed) signal(SIGINT, old); }
 };
 
-#ifdef CMFREC_HIP_FLOAT
-const real_t EPS_T = FLT_EPSILON;
-#else
-const real_t EPS_T = DBL_EPSILON;
-#endif
-
 // CMFREC_HIP_TIMING=1: wall-clock of the host phases of a fit on stderr
 struct PhaseTimer {
     bool on = getenv("CMFREC_HIP_TIMING") != nullptr;
@@ -74,164 +71,6 @@ int fail(bool verbose, const char *msg)
 {
     if (verbose) fprintf(stderr, "%s\n", msg);
     return 2;
-}
-
-// Dense side information with missing values (NaN).  The reference centres the present entries of each column
-// (center_by_cols, common.c:4938-4997) and then uses, for every row / column, only what is present -- the same
-// arithmetic as its sparse-side-information route run on the centred values (collective.c:1566-1653: the C^T C block
-// and the right-hand side over the present attributes, lambda scaled by their count; optimizeA Case 2 for C / D).  So
-// such a matrix is handed to the sparse route as COO triplets of its centred present entries.
-struct DenseNanSide {
-    std::vector<int_t> row, col;
-    std::vector<real_t> val;
-    std::vector<int_t> na_col;                  // missing values per attribute
-    int_t n_rows = 0;
-    // What the reference's dense C / D update (optimizeA Cases 1-2 on the transposed matrix, common.c:2793-3116) does differently
-    // from the sparse one, per attribute.  An attribute that misses fewer than 2 kc values is solved from the precomputed Gramian
-    // minus the missing rows (factors_closed_form :759-790, ahead of the CG branch at :884): in closed form whatever use_cg says
-    // (mask 1), under scale_lam with the n_rows x lam of a complete attribute (:3031-3032 / :2832).  When at least 75 % of the
-    // attributes are complete (helpers.c:151-250) those share one factorisation (mask 1) and the ones that miss 2 kc values or
-    // more are redone by CG from zero with kc steps (mask 2; Case 1's fix-up loop, :2953-2985).  Mask 0: the solver asked for.
-    void rules(int_t kc, bool scale_lam, std::vector<unsigned char> &mask, std::vector<real_t> &mult) const
-    {
-        const int_t p = (int_t)na_col.size();
-        int_t with_na = 0;
-        bool any_few = false;
-        for (int_t c = 0; c < p; c++) { with_na += (na_col[c] > 0); any_few = any_few || (na_col[c] > 0 && na_col[c] < 2 * kc); }
-        const bool near = (p - with_na) >= (int_t)((real_t)0.75 * (real_t)p);
-        mask.resize((size_t)p);
-        for (int_t c = 0; c < p; c++) mask[c] = (na_col[c] < 2 * kc) ? 1 : (near ? 2 : 0);
-        mult.clear();
-        if (scale_lam && any_few) {
-            mult.resize((size_t)p);
-            for (int_t c = 0; c < p; c++)
-                mult[c] = (na_col[c] < 2 * kc) ? (real_t)n_rows : (na_col[c] < n_rows ? (real_t)(n_rows - na_col[c]) : (real_t)1);
-        }
-    }
-    bool convert(const real_t *M, int_t rows, int_t cols, real_t *means)
-    {
-        bool any = false;
-        for (size_t e = 0; e < (size_t)rows * cols && !any; e++) any = std::isnan(M[e]);
-        if (!any) return false;
-        std::vector<double> sum((size_t)cols, 0.0);
-        std::vector<size_t> cnt((size_t)cols, 0);
-        for (int_t r = 0; r < rows; r++)
-            for (int_t c = 0; c < cols; c++) {
-                const real_t v = M[(size_t)r * cols + c];
-                if (!std::isnan(v)) { sum[c] += v; cnt[c]++; }
-            }
-        for (int_t c = 0; means && c < cols; c++) means[c] = (real_t)(sum[c] / (double)cnt[c]);
-        n_rows = rows; na_col.resize((size_t)cols);
-        for (int_t c = 0; c < cols; c++) na_col[c] = rows - (int_t)cnt[c];
-        for (int_t r = 0; r < rows; r++)
-            for (int_t c = 0; c < cols; c++) {
-                const real_t v = M[(size_t)r * cols + c];
-                if (std::isnan(v)) continue;
-                row.push_back(r); col.push_back(c); val.push_back(means ? v - means[c] : v);
-            }
-        return true;
-    }
-};
-
-// NA_as_zero_U / NA_as_zero_I: a sparse side-information matrix whose absent entries are ZEROS is the dense matrix holding those
-// zeros, on every row of X (rows of X beyond the last row of the triplets are zero rows: the column means divide by all of
-// them).  The reference reaches the same numbers by other operations -- optimizeA Case 3 for C / D with the column means as a
-// rank-one correction (collective.c:8354-8386, common.c:3116-3205), the full w C^T C block plus a constant -w C^T colmeans on
-// every right-hand side (collective.c:1277-1457, :5790-5800, :5823-5836; block CG: :2292-2298) -- and agrees with the dense
-// route on the zero-filled matrix to 1e-15, closed form and CG, both models (tests/test_oracle_vs_ref.py).  So that is what the
-// fit runs, in one of two forms.  Up to CMFREC_HIP_ZEROFILL_MAX_GB the triplets are scattered into a [rows of X, cols] matrix here
-// and take the dense path, GEMMs and all; cost: rows x cols numbers of host and device memory instead of the triplets.  Beyond it
-// (single device) the triplets themselves go to the session (SparseZerosSide below, cmfrec_hip_session_set_sideinfo_sparse_zeros):
-// the same dense path with its two products by that matrix taken as sparse products plus the column means' rank-one term.  More
-// rows of side information than X has: refused (the reference treats the rows beyond X differently from its dense branch,
-// nothing pins them).
-struct ZeroFilledSide {
-    std::vector<real_t> dense;
-    // Size limit of the zero-filled matrix: it exists three times (here, as the centred copy, on the device).  Beyond
-    // CMFREC_HIP_ZEROFILL_MAX_GB (default 8 GB per copy; realistic sparse side information of 1e6..1e7 rows x 1e3..1e4 columns
-    // is 8e9..8e11 bytes) build() returns 3 and the fit takes the sparse form; a multi-device fit, whose row-block shards need
-    // the dense matrix, answers with a controlled "not implemented at this size" instead of a bad_alloc / hipErrorOutOfMemory
-    // late in the fit.  Read per fit: a tiny value sends any problem down the sparse form (tests, tools/bench_side_zeros.py).
-    static double max_bytes()
-    {
-        const char *e = getenv("CMFREC_HIP_ZEROFILL_MAX_GB");
-        const double gb = (e != nullptr && atof(e) > 0) ? atof(e) : 8.0;
-        return gb * 1e9;
-    }
-    // 0 ok, 1 triplets missing / out of range, 2 more rows than X, 3 larger than the limit above.  Triplets that repeat a
-    // position are SUMMED (the reference's COO -> CSR keeps both and its sums add both: the same numbers).
-    int build(int_t rows_x, int_t rows_side, int_t cols, const int_t *r, const int_t *c, const real_t *v, size_t nnz)
-    {
-        if (rows_side > rows_x) return 2;
-        if (!r || !c || !v || cols <= 0) return 1;
-        if ((double)rows_x * (double)cols * (double)sizeof(real_t) > max_bytes()) return 3;
-        dense.assign((size_t)rows_x * (size_t)cols, (real_t)0);
-        for (size_t e = 0; e < nnz; e++) {
-            if (r[e] < 0 || r[e] >= rows_side || c[e] < 0 || c[e] >= cols) return 1;
-            dense[(size_t)r[e] * (size_t)cols + (size_t)c[e]] += v[e];
-        }
-        return 0;
-    }
-};
-// ... the sparse form: the triplets as they came (validated; positions given twice add up in the products as they do in the
-// scatter above) and the column means over ALL rows of X, summed in double -- what center_cols computes of the zero-filled matrix.
-struct SparseZerosSide {
-    bool on = false;
-    const int_t *row = nullptr, *col = nullptr;
-    const real_t *val = nullptr;
-    size_t nnz = 0;
-    std::vector<real_t> means;           // empty: the caller asked for no centring (no colmeans output)
-    // 0 ok, 1 triplets missing / out of range, 4 NaN among the values
-    int take(int_t rows_x, int_t rows_side, int_t cols, const int_t *r, const int_t *c, const real_t *v, size_t n, real_t *means_out)
-    {
-        if (!r || !c || !v || cols <= 0) return 1;
-        std::vector<double> sum((size_t)cols, 0.0);
-        for (size_t e = 0; e < n; e++) {
-            if (r[e] < 0 || r[e] >= rows_side || c[e] < 0 || c[e] >= cols) return 1;
-            if (std::isnan(v[e])) return 4;
-            sum[(size_t)c[e]] += (double)v[e];
-        }
-        if (means_out != nullptr) {
-            means.resize((size_t)cols);
-            for (int_t j = 0; j < cols; j++) means_out[j] = means[(size_t)j] = (real_t)(sum[(size_t)j] / (double)rows_x);
-        }
-        row = r; col = c; val = v; nnz = n; on = true;
-        return 0;
-    }
-    const real_t *colmeans() const { return means.empty() ? nullptr : means.data(); }
-};
-// ... with one exception the reference makes: a row with neither an entry of X nor an entry of the side information is not solved
-// but set to zero, bias included (collective_closed_form_block, collective.c:1262-1271; _implicit: :1876-1884).  The list of
-// those rows, for cmfrec_hip_session_set_zero_rows.
-static std::vector<int_t> rows_without_data(int_t rows, const int_t *ix_x, size_t nnz, const int_t *ix_side, size_t nnz_side)
-{
-    std::vector<char> has((size_t)rows, 0);
-    for (size_t e = 0; e < nnz; e++) if (ix_x[e] >= 0 && ix_x[e] < rows) has[(size_t)ix_x[e]] = 1;
-    for (size_t e = 0; e < nnz_side; e++) if (ix_side[e] >= 0 && ix_side[e] < rows) has[(size_t)ix_side[e]] = 1;
-    std::vector<int_t> out;
-    for (int_t r = 0; r < rows; r++) if (!has[(size_t)r]) out.push_back(r);
-    return out;
-}
-// precomputedCtUbias of the reference's epilogue (collective.c:9244-9252, :10115-10123): -w C^T colmeans
-static void fill_CtUbias(real_t *out, const real_t *C, const real_t *colmeans, int_t p, int_t kc, real_t w)
-{
-    if (!out || !C || !colmeans) return;
-    for (int_t f = 0; f < kc; f++) {
-        double acc = 0;
-        for (int_t j = 0; j < p; j++) acc += (double)C[(size_t)j * kc + f] * (double)colmeans[j];
-        out[f] = (real_t)(-(double)w * acc);
-    }
-}
-
-// column means of sparse side information are reported like the reference does (common.c:4976-4990); the fit itself runs on
-// the values as given (the centred copy center_by_cols makes is not the one coo_to_csr_and_csc reads, collective.c:6541-6558)
-void sparse_colmeans(const int_t *col, const real_t *val, size_t nnz, int_t cols, real_t *means)
-{
-    if (!means) return;
-    std::vector<double> sum((size_t)cols, 0.0);
-    std::vector<size_t> cnt((size_t)cols, 0);
-    for (size_t e = 0; e < nnz; e++) { sum[col[e]] += val[e]; cnt[col[e]]++; }
-    for (int_t c = 0; c < cols; c++) means[c] = (real_t)(sum[c] / (double)cnt[c]);
 }
 
 // ---- validation while fitting (cmfrec_hip_fit_set_monitor, include/cmfrec_hip.h) -------------------------------------
@@ -389,45 +228,6 @@ int run_loop(cmfrec_hip_session *s, const cmfrec_hip_model &mdl, int niter, bool
     }
     return finish(0);
 }
-
-// Dense X (Xfull [m, n] row-major, NaN = missing; weight, if given, dense too) -> the COO of its present entries in row-major
-// order, which is the order every running mean of the reference's dense branches takes them in (common.c:3463-3490,
-// :4152-4180), plus what optimizeA's case selection needs (helpers.c:151-250): a half-step is "full" when no row (column) has
-// a missing entry and "near dense" when at least 75 % of them have none.
-struct DenseX {
-    std::vector<int_t> row, col;
-    std::vector<real_t> val, w;
-    bool full = false, near_row = false, near_col = false;
-    std::vector<int_t> na_row, na_col;          // missing entries per row / column
-    void convert(const real_t *Xfull, const real_t *weight, int_t m, int_t n)
-    {
-        na_row.assign((size_t)m, 0); na_col.assign((size_t)n, 0);
-        size_t present = 0;
-        for (int_t r = 0; r < m; r++)
-            for (int_t c = 0; c < n; c++) {
-                const bool na = std::isnan(Xfull[(size_t)r * n + c]);
-                na_row[r] += na; na_col[c] += na; present += !na;
-            }
-        row.reserve(present); col.reserve(present); val.reserve(present);
-        if (weight) w.reserve(present);
-        for (int_t r = 0; r < m; r++)
-            for (int_t c = 0; c < n; c++) {
-                const real_t x = Xfull[(size_t)r * n + c];
-                if (std::isnan(x)) continue;
-                row.push_back(r); col.push_back(c); val.push_back(x);
-                if (weight) w.push_back(weight[(size_t)r * n + c]);
-            }
-        full = (present == (size_t)m * (size_t)n);
-        if (!full) {
-            int_t with_na = 0;
-            for (int_t r = 0; r < m; r++) with_na += (na_row[r] > 0);
-            near_row = (m - with_na) >= (int)(0.75 * (double)m);
-            with_na = 0;
-            for (int_t c = 0; c < n; c++) with_na += (na_col[c] > 0);
-            near_col = (n - with_na) >= (int_t)((real_t)0.75 * (real_t)n);
-        }
-    }
-};
 
 // ---- several GPUs of one node behind the unchanged C signature ----------------------------------
 // CMFREC_HIP_DEVICES="0,1,2,3" (HIP device ordinals, comma separated; an ordinal may repeat, which shards one device --
@@ -804,6 +604,46 @@ bool sharded_fit_wanted(const std::vector<int> &devs)
     return devs.size() == 1 && e != nullptr && e[0] == '1';
 }
 
+int fail(bool verbose, const std::string &msg) { return fail(verbose, msg.c_str()); }
+
+// the session of a fit, or why there is none (on stderr when verbose) and the code the fit returns
+cmfrec_hip_session *create_session(const cmfrec_hip_model &mdl, int device, bool verbose, int &rc)
+{
+    cmfrec_hip_session *s = cmfrec_hip_session_create(&mdl, device);
+    if (s) return s;
+    if (verbose) fprintf(stderr, "%s\n", cmfrec_hip_last_error());
+    const int ec = cmfrec_hip_last_error_code();
+    rc = ec ? ec : 1;
+    return nullptr;
+}
+
+// side information in whichever form the intake left it: the zero rows, the centred dense matrices, the triplets taken as zeros
+// (beyond the zero-fill limit), the sparse triplets (as given, or the centred present entries of a dense matrix with NaN)
+int hand_sides_to_session(cmfrec_hip_session *s, const SideInput &su, const SideInput &si)
+{
+    int rc = 0;
+    if (!su.zero_rows.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'A', su.zero_rows.data(), (int)su.zero_rows.size());
+    if (!rc && !si.zero_rows.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'B', si.zero_rows.data(), (int)si.zero_rows.size());
+    if (!rc) rc = cmfrec_hip_session_set_sideinfo(s, su.centred_or_null(), si.centred_or_null());
+    if (!rc && su.sz.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'U', su.sz.row, su.sz.col, su.sz.val, su.sz.nnz, su.sz.colmeans());
+    if (!rc && si.sz.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'I', si.sz.row, si.sz.col, si.sz.val, si.sz.nnz, si.sz.colmeans());
+    if (!rc && su.sparse()) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'U', su.row, su.col, su.val, su.nnz);
+    if (!rc && si.sparse()) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'I', si.row, si.col, si.val, si.nnz);
+    return rc;
+}
+
+// dense side information with NaN: the per-attribute rules of the dense C / D update (DenseNanSide::rules); kc: the width of C / D
+int hand_nan_rules(cmfrec_hip_session *s, const SideInput &side, int which, int_t kc, bool scale_lam, bool use_cg)
+{
+    if (side.nan.na_col.empty() || !side.sparse()) return 0;
+    std::vector<unsigned char> mask; std::vector<real_t> mult;
+    side.nan.rules(kc, scale_lam, mask, mult);
+    int rc = 0;
+    if (use_cg) rc = cmfrec_hip_session_set_closed_form_rows(s, which, mask.data());
+    if (!rc && !mult.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, which, mult.data());
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -880,68 +720,23 @@ int_t fit_collective_implicit_als(
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
     if (k_main && nnz == 0) return fail(verbose, "Cannot pass 'k_main' without X data.");
     if (nnz == 0) return fail(verbose, "cmfrec_hip: the implicit model needs at least one entry of X.");
-    // sparse side information whose absent entries are zeros -> the dense route on the zero-filled matrix (ZeroFilledSide), or, past
-    // its size limit on a single device, the same route on the triplets (SparseZerosSide)
-    ZeroFilledSide zfU, zfI;
-    SparseZerosSide szU, szI;
+    // side information, stage 1 (NA_as_zero_U / _I) and stage 2 (NaN in a dense matrix), U before I: SideInput, fit_inputs.hpp
+    SideInput su = user_side(U, m_u, p, U_row, U_col, U_sp, nnz_U, U_colmeans), si = item_side(II, n_i, q, I_row, I_col, I_sp, nnz_I, I_colmeans);
     const bool sparse_zeros_ok = !sharded_fit_wanted(devices_from_env());
-    const bool naz_U = NA_as_zero_U && U == nullptr && nnz_U > 0, naz_I = NA_as_zero_I && II == nullptr && nnz_I > 0;
-    std::vector<int_t> zero_rows_A, zero_rows_B;
-    if (naz_U) {
-        zero_rows_A = rows_without_data(m, ixA, nnz, U_row, nnz_U);
-        int e = zfU.build(m, m_u, p, U_row, U_col, U_sp, nnz_U);
-        if (e == 3 && sparse_zeros_ok && (e = szU.take(m, m_u, p, U_row, U_col, U_sp, nnz_U, U_colmeans)) == 4)
-            return fail(verbose, "cmfrec_hip: NA_as_zero_U beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of U is not implemented.");
-        if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_U with more rows of U than X is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_U on several devices runs on the zero-filled dense matrix (rows of X x p), which is larger than "
-                                               "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
-                                             : "cmfrec_hip: U index out of range.");
-        if (!szU.on) U = zfU.dense.data();
-        m_u = m; nnz_U = 0; U_row = U_col = nullptr; U_sp = nullptr;
-    }
-    if (naz_I) {
-        zero_rows_B = rows_without_data(n, ixB, nnz, I_row, nnz_I);
-        int e = zfI.build(n, n_i, q, I_row, I_col, I_sp, nnz_I);
-        if (e == 3 && sparse_zeros_ok && (e = szI.take(n, n_i, q, I_row, I_col, I_sp, nnz_I, I_colmeans)) == 4)
-            return fail(verbose, "cmfrec_hip: NA_as_zero_I beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of I is not implemented.");
-        if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_I with more rows of I than X has columns is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_I on several devices runs on the zero-filled dense matrix (columns of X x q), which is larger than "
-                                               "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
-                                             : "cmfrec_hip: I index out of range.");
-        if (!szI.on) II = zfI.dense.data();
-        n_i = n; nnz_I = 0; I_row = I_col = nullptr; I_sp = nullptr;
-    }
-    // dense side information with NaN -> the sparse route on its centred present entries
-    DenseNanSide nanU, nanI;
-    const bool hadU = (U != nullptr) || szU.on;
-    bool nan_side = false;
-    if (U && m_u > 0 && p > 0 && nanU.convert(U, m_u, p, U_colmeans)) {
-        U = nullptr; U_row = nanU.row.data(); U_col = nanU.col.data(); U_sp = nanU.val.data(); nnz_U = nanU.val.size(); nan_side = true;
-    } else if (U == nullptr && nnz_U > 0 && U_row && U_col && U_sp) {
-        bool ok = true;
-        for (size_t e = 0; e < nnz_U && ok; e++) ok = (U_col[e] >= 0 && U_col[e] < p);
-        if (ok) sparse_colmeans(U_col, U_sp, nnz_U, p, U_colmeans);
-    }
-    if (II && n_i > 0 && q > 0 && nanI.convert(II, n_i, q, I_colmeans)) {
-        II = nullptr; I_row = nanI.row.data(); I_col = nanI.col.data(); I_sp = nanI.val.data(); nnz_I = nanI.val.size(); nan_side = true;
-    } else if (II == nullptr && nnz_I > 0 && I_row && I_col && I_sp) {
-        bool ok = true;
-        for (size_t e = 0; e < nnz_I && ok; e++) ok = (I_col[e] >= 0 && I_col[e] < q);
-        if (ok) sparse_colmeans(I_col, I_sp, nnz_I, q, I_colmeans);
-    }
-    if (nan_side && nnz_U == 0 && nanU.row.empty() && hadU && U == nullptr)
-        return fail(verbose, "cmfrec_hip: U has no present entries.");
+    std::string refusal = su.zero_fill(NA_as_zero_U, m, ixA, nnz, sparse_zeros_ok);
+    if (refusal.empty()) refusal = si.zero_fill(NA_as_zero_I, n, ixB, nnz, sparse_zeros_ok);
+    if (!refusal.empty()) return fail(verbose, refusal);
+    su.take_nan(); si.take_nan();
+    const bool nan_side = su.nan_side || si.nan_side;
+    // (asymmetry, kept: only U is refused for having nothing left; an I without a present entry counts as no I)
+    if (su.nothing_present(nan_side)) return fail(verbose, "cmfrec_hip: U has no present entries.");
     // side information: dense or sparse COO (missing = absent).  Sparse: rows within X.
-    const bool spU = (U == nullptr && nnz_U > 0), spI = (II == nullptr && nnz_I > 0);
-    if ((spU && (m_u > m || !U_row || !U_col || !U_sp)) || (spI && (n_i > n || !I_row || !I_col || !I_sp)))
+    if (su.bad_triplets(m) || si.bad_triplets(n))
         return fail(verbose, "cmfrec_hip: sparse side information must be COO triplets with rows inside X.");
-    if (U == nullptr && !spU && !szU.on) { m_u = 0; p = 0; }
-    if (II == nullptr && !spI && !szI.on) { n_i = 0; q = 0; }
-    for (size_t e = 0; spU && e < nnz_U; e++)
-        if (U_row[e] < 0 || U_row[e] >= m_u || U_col[e] < 0 || U_col[e] >= p) return fail(verbose, "cmfrec_hip: U index out of range.");
-    for (size_t e = 0; spI && e < nnz_I; e++)
-        if (I_row[e] < 0 || I_row[e] >= n_i || I_col[e] < 0 || I_col[e] >= q) return fail(verbose, "cmfrec_hip: I index out of range.");
-    if ((l1_lam != 0 || l1_lam_unique) && (((U || nnz_U) && m_u > m) || ((II || nnz_I) && n_i > n)))
+    su.drop_if_absent(); si.drop_if_absent();
+    if (su.index_out_of_range()) return fail(verbose, su.index_message());
+    if (si.index_out_of_range()) return fail(verbose, si.index_message());
+    if ((l1_lam != 0 || l1_lam_unique) && (su.beyond(m) || si.beyond(n)))
         return fail(verbose, "cmfrec_hip: L1 together with side information beyond X is not implemented.");
     if (nonneg || nonneg_C || nonneg_D || l1_lam != 0 || l1_lam_unique) use_cg = false;    // collective.c:9568-9571 (any of them, unlike the explicit model)
     // For rows with few missing values the reference corrects a precomputed Gramian instead of summing the present entries
@@ -979,28 +774,17 @@ int_t fit_collective_implicit_als(
     }
     tm.lap("log transform");
 
-    // ---- side information: column means + centering, common.c:4938-4997 (only when the means are asked for) ----
-    std::vector<real_t> Uc, Ic;
-    auto center_cols = [](const real_t *M, int rows, int cols, real_t *means, std::vector<real_t> &out) {
-        out.assign(M, M + (size_t)rows * cols);
-        if (means == nullptr) return;
-        for (int c = 0; c < cols; c++) means[c] = 0;
-        for (int r = 0; r < rows; r++) for (int c = 0; c < cols; c++) means[c] += M[(size_t)r * cols + c];
-        for (int c = 0; c < cols; c++) means[c] /= (double)rows;
-        for (int r = 0; r < rows; r++) for (int c = 0; c < cols; c++) out[(size_t)r * cols + c] -= means[c];
-    };
-    if (U) center_cols(U, m_u, p, U_colmeans, Uc);
-    if (II) center_cols(II, n_i, q, I_colmeans, Ic);
+    su.center(); si.center();
 
     const int k_totA = k_user + k + k_main, k_totB = k_item + k + k_main;
-    const int_t m_max = std::max(m, m_u), n_max = std::max(n, n_i);     // rows of A / B (collective.c:9437-9440)
+    const int_t m_max = std::max(m, su.rows), n_max = std::max(n, si.rows);     // rows of A / B (collective.c:9437-9440)
     if (reset_values) {                                                  // :9750-9774
-        const bool fill_B = (II != nullptr || spI || szI.on);
+        const bool fill_B = si.present();
         cmfrng::random_parallel<real_t>(A, (size_t)m_max * k_totA, fill_B ? B : nullptr, fill_B ? (size_t)n_max * k_totB : 0, seed, false);
         if (use_cg) {
             if (!fill_B) memset(B, 0, (size_t)n_max * k_totB * sizeof(real_t));
-            if (U || spU || szU.on) memset(C, 0, (size_t)p * (k_user + k) * sizeof(real_t));
-            if (II || spI || szI.on) memset(D, 0, (size_t)q * (k_item + k) * sizeof(real_t));
+            if (su.present()) memset(C, 0, (size_t)su.cols * (k_user + k) * sizeof(real_t));
+            if (si.present()) memset(D, 0, (size_t)si.cols * (k_item + k) * sizeof(real_t));
         }
         // Cholesky: start values that are never read (the C / D / B steps run first) are left as passed, like the reference
     }
@@ -1012,15 +796,25 @@ int_t fit_collective_implicit_als(
     mdl.implicit = 1; mdl.m = m_max; mdl.n = n_max; mdl.m_x = m; mdl.n_x = n;
     mdl.k = k; mdl.k_main = k_main; mdl.k_user = k_user; mdl.k_item = k_item;
     mdl.use_cg = use_cg; mdl.max_cg_steps = max_cg_steps; mdl.precondition_cg = precondition_cg; mdl.lam = lam;
-    mdl.p = p; mdl.q = q; mdl.m_u = m_u; mdl.n_i = n_i; mdl.w_user = w_user; mdl.w_item = w_item;
+    mdl.p = su.cols; mdl.q = si.cols; mdl.m_u = su.rows; mdl.n_i = si.rows; mdl.w_user = w_user; mdl.w_item = w_item;
     mdl.row_begin = 0; mdl.row_end = m_max; mdl.col_begin = 0; mdl.col_end = n_max;
+    // the matrices for predictions, single device and shards alike (collective.c:10056-10115; also after an interrupt, :10034-10043)
+    // (a monitored fit that returns an earlier iterate than niter - 1 returns one whose last A-step was not the Cholesky pass; a
+    //  sharded fit has no monitor, check_monitor)
+    auto epilogue = [&](cmfrec_hip_session *s) {
+        const int last_chol = (!use_cg || (finalize_chol && niter > 0 && (!mon.on || mon.returned == niter - 1))) ? 1 : 0;
+        const int rc2 = cmfrec_hip_session_precompute(s, last_chol, 0, precomputedBtB, nullptr, su.had_dense ? precomputedBeTBe : nullptr,
+                                                      su.had_dense ? precomputedBeTBeChol : nullptr, nullptr, nullptr);
+        if (su.naz && !rc2) fill_CtUbias(precomputedCtUbias, C, su.colmeans, su.cols, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
+        return rc2;
+    };
     // device selection without touching the signature: CMFREC_HIP_DEVICES (one ordinal: that device; several: row-block shards)
     const std::vector<int> devs = devices_from_env();
     // Sharded: the plain model and the one with DENSE side information (C / D by partial sums + all-reduce, multi_sideinfo_step),
     // all solvers, constraints and penalties; sparse side information and side information beyond the shape of X keep to the
     // first listed device.
-    const bool multi_ok = sharded_fit_wanted(devs) && !spU && !spI && !szU.on && !szI.on && m_u <= m && n_i <= n && m >= (int_t)devs.size() &&
-                          n >= (int_t)devs.size() && zero_rows_A.empty() && zero_rows_B.empty();
+    const bool multi_ok = sharded_fit_wanted(devs) && !su.sparse() && !si.sparse() && !su.sz.on && !si.sz.on && su.rows <= m && si.rows <= n &&
+                          m >= (int_t)devs.size() && n >= (int_t)devs.size() && su.zero_rows.empty() && si.zero_rows.empty();
     if (devs.size() > 1 && !multi_ok && verbose)
         printf("cmfrec_hip: CMFREC_HIP_DEVICES lists %d devices; this configuration (sparse side information / side information beyond X) "
                "runs on the first\n", (int)devs.size());
@@ -1028,9 +822,10 @@ int_t fit_collective_implicit_als(
         MultiDev md;
         int rc_loop = build_shards(md, devs, mdl, m_max, n_max, ixA, ixB, apply_log_transf ? Xs.data() : X, nnz, (real_t)0, alpha,
                                    [&](cmfrec_hip_session *sd, int d) {
-            int rc2 = set_sideinfo_shard(md, sd, d, U ? Uc.data() : nullptr, m_u, p, II ? Ic.data() : nullptr, n_i, q);
+            int rc2 = set_sideinfo_shard(md, sd, d, su.centred_or_null(), su.rows, su.cols, si.centred_or_null(), si.rows, si.cols);
             if (!rc2 && (nonneg || nonneg_C || nonneg_D)) rc2 = cmfrec_hip_session_set_nonneg(sd, nonneg, nonneg_C, nonneg_D, (int)max_cd_steps);
             if (!rc2 && l1_lam != 0) rc2 = cmfrec_hip_session_set_l1(sd, l1_lam, (int)max_cd_steps);
+            // (the shards always pass lam6, the single device below only when lam_unique / l1_lam_unique was given: left apart)
             if (!rc2) rc2 = cmfrec_hip_session_set_lam_unique(sd, lam6, l1_lam_unique ? l16 : nullptr, (int)max_cd_steps);
             if (!rc2) rc2 = cmfrec_hip_session_set_factors(sd, A, B, nullptr, nullptr, C, D);
             return rc2;
@@ -1041,39 +836,22 @@ int_t fit_collective_implicit_als(
             int rc2 = cmfrec_hip_session_get_factors(s0, A, B, nullptr, nullptr, C, D);
             if (rc2) rc_loop = rc2;
         }
-        if ((rc_loop == 0 || rc_loop == 3) && s0 && precompute_for_predictions) {
-            const int last_chol = (!use_cg || (finalize_chol && niter > 0)) ? 1 : 0;
-            int rc2 = cmfrec_hip_session_precompute(s0, last_chol, 0, precomputedBtB, nullptr, hadU ? precomputedBeTBe : nullptr,
-                                                    hadU ? precomputedBeTBeChol : nullptr, nullptr, nullptr);
-            if (rc2) rc_loop = rc2;
-            if (naz_U && !rc2) fill_CtUbias(precomputedCtUbias, C, U_colmeans, p, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
-        }
+        if ((rc_loop == 0 || rc_loop == 3) && s0 && precompute_for_predictions)
+            if (const int rc2 = epilogue(s0)) rc_loop = rc2;
         if (verbose && rc_loop == 0) printf("ALS procedure terminated successfully\n");
         return rc_loop;
     }
-    cmfrec_hip_session *s = cmfrec_hip_session_create(&mdl, devs.empty() ? -1 : devs[0]);
-    if (!s) { if (verbose) fprintf(stderr, "%s\n", cmfrec_hip_last_error()); const int ec = cmfrec_hip_last_error_code(); return ec ? ec : 1; }
+    int rc = 0;
+    cmfrec_hip_session *s = create_session(mdl, devs.empty() ? -1 : devs[0], verbose, rc);
+    if (!s) return rc;
     tm.lap("session create");
     // X := alpha * X and COO -> CSR + CSC happen on the device (coo_device.hpp), same entry order as helpers.c:1375-1491
-    int rc = cmfrec_hip_session_set_X_coo(s, ixA, ixB, apply_log_transf ? Xs.data() : X, nnz, (real_t)0, alpha);
+    rc = cmfrec_hip_session_set_X_coo(s, ixA, ixB, apply_log_transf ? Xs.data() : X, nnz, (real_t)0, alpha);
     std::vector<real_t>().swap(Xs);
     tm.lap("set_X_coo (upload, sort, bins)");
-    if (!rc && !zero_rows_A.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'A', zero_rows_A.data(), (int)zero_rows_A.size());
-    if (!rc && !zero_rows_B.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'B', zero_rows_B.data(), (int)zero_rows_B.size());
-    if (!rc) rc = cmfrec_hip_session_set_sideinfo(s, U ? Uc.data() : nullptr, II ? Ic.data() : nullptr);
-    if (!rc && szU.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'U', szU.row, szU.col, szU.val, szU.nnz, szU.colmeans());
-    if (!rc && szI.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'I', szI.row, szI.col, szI.val, szI.nnz, szI.colmeans());
-    if (!rc && spU) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'U', U_row, U_col, U_sp, nnz_U);
-    if (!rc && spI) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'I', I_row, I_col, I_sp, nnz_I);
-    // dense side information with NaN: the per-attribute rules of the dense C / D update (DenseNanSide::rules)
-    for (int side = 0; side < 2 && !rc; side++) {
-        const DenseNanSide &ns = side ? nanI : nanU;
-        if (ns.na_col.empty() || !(side ? spI : spU)) continue;
-        std::vector<unsigned char> mask; std::vector<real_t> mult;
-        ns.rules((side ? k_item : k_user) + k, false, mask, mult);
-        if (use_cg) rc = cmfrec_hip_session_set_closed_form_rows(s, side ? 'D' : 'C', mask.data());
-        if (!rc && !mult.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, side ? 'D' : 'C', mult.data());
-    }
+    if (!rc) rc = hand_sides_to_session(s, su, si);
+    if (!rc) rc = hand_nan_rules(s, su, 'C', k_user + k, false, use_cg);
+    if (!rc) rc = hand_nan_rules(s, si, 'D', k_item + k, false, use_cg);
     if (!rc && (nonneg || nonneg_C || nonneg_D)) rc = cmfrec_hip_session_set_nonneg(s, nonneg, nonneg_C, nonneg_D, (int)max_cd_steps);
     if (!rc && l1_lam != 0) rc = cmfrec_hip_session_set_l1(s, l1_lam, (int)max_cd_steps);
     if (!rc && (lam_unique || l1_lam_unique))
@@ -1090,14 +868,9 @@ int_t fit_collective_implicit_als(
         if (rc2) rc_loop = rc2;
     }
     tm.lap("get_factors");
-    if ((rc_loop == 0 || rc_loop == 3) && precompute_for_predictions) {   // collective.c:10056-10115 (also after an interrupt, :10034-10043)
+    if ((rc_loop == 0 || rc_loop == 3) && precompute_for_predictions) {
         if (verbose) { printf("Finishing precomputed matrices..."); fflush(stdout); }
-        // (a monitored fit that returns an earlier iterate than niter - 1 returns one whose last A-step was not the Cholesky pass)
-        const int last_chol = (!use_cg || (finalize_chol && niter > 0 && (!mon.on || mon.returned == niter - 1))) ? 1 : 0;
-        int rc2 = cmfrec_hip_session_precompute(s, last_chol, 0, precomputedBtB, nullptr, hadU ? precomputedBeTBe : nullptr,
-                                                hadU ? precomputedBeTBeChol : nullptr, nullptr, nullptr);
-        if (rc2) rc_loop = rc2;
-        if (naz_U && !rc2) fill_CtUbias(precomputedCtUbias, C, U_colmeans, p, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
+        if (const int rc2 = epilogue(s)) rc_loop = rc2;
         if (verbose) printf("  done\n");
         tm.lap("precompute epilogue");
     }
@@ -1132,37 +905,13 @@ int_t fit_collective_explicit_als(
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
     if (k_main && Xfull == nullptr && nnz == 0) return fail(verbose, "Cannot pass 'k_main' without X data.");
-    // sparse side information whose absent entries are zeros -> the dense route on the zero-filled matrix (ZeroFilledSide), or, past
-    // its size limit on a single device, the same route on the triplets (SparseZerosSide)
-    ZeroFilledSide zfU, zfI;
-    SparseZerosSide szU, szI;
+    // side information, stage 1 (NA_as_zero_U / _I), U before I: SideInput, fit_inputs.hpp.  The dense-X and NA_as_zero_X checks below
+    // read what it left; stage 2 (NaN in a dense matrix) follows them.
+    SideInput su = user_side(U, m_u, p, U_row, U_col, U_sp, nnz_U, U_colmeans), si = item_side(II, n_i, q, I_row, I_col, I_sp, nnz_I, I_colmeans);
     const bool sparse_zeros_ok = !sharded_fit_wanted(devices_from_env());
-    const bool naz_U = NA_as_zero_U && U == nullptr && nnz_U > 0, naz_I = NA_as_zero_I && II == nullptr && nnz_I > 0;
-    std::vector<int_t> zero_rows_A, zero_rows_B;
-    if (naz_U) {
-        zero_rows_A = rows_without_data(m, ixA, nnz, U_row, nnz_U);
-        int e = zfU.build(m, m_u, p, U_row, U_col, U_sp, nnz_U);
-        if (e == 3 && sparse_zeros_ok && (e = szU.take(m, m_u, p, U_row, U_col, U_sp, nnz_U, U_colmeans)) == 4)
-            return fail(verbose, "cmfrec_hip: NA_as_zero_U beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of U is not implemented.");
-        if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_U with more rows of U than X is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_U on several devices runs on the zero-filled dense matrix (rows of X x p), which is larger than "
-                                               "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
-                                             : "cmfrec_hip: U index out of range.");
-        if (!szU.on) U = zfU.dense.data();
-        m_u = m; nnz_U = 0; U_row = U_col = nullptr; U_sp = nullptr;
-    }
-    if (naz_I) {
-        zero_rows_B = rows_without_data(n, ixB, nnz, I_row, nnz_I);
-        int e = zfI.build(n, n_i, q, I_row, I_col, I_sp, nnz_I);
-        if (e == 3 && sparse_zeros_ok && (e = szI.take(n, n_i, q, I_row, I_col, I_sp, nnz_I, I_colmeans)) == 4)
-            return fail(verbose, "cmfrec_hip: NA_as_zero_I beyond CMFREC_HIP_ZEROFILL_MAX_GB: NaN among the values of I is not implemented.");
-        if (e) return fail(verbose, e == 2 ? "cmfrec_hip: NA_as_zero_I with more rows of I than X has columns is not implemented."
-                                    : e == 3 ? "cmfrec_hip: NA_as_zero_I on several devices runs on the zero-filled dense matrix (columns of X x q), which is larger than "
-                                               "CMFREC_HIP_ZEROFILL_MAX_GB (default 8) here: not implemented at this size."
-                                             : "cmfrec_hip: I index out of range.");
-        if (!szI.on) II = zfI.dense.data();
-        n_i = n; nnz_I = 0; I_row = I_col = nullptr; I_sp = nullptr;
-    }
+    std::string refusal = su.zero_fill(NA_as_zero_U, m, ixA, nnz, sparse_zeros_ok);
+    if (refusal.empty()) refusal = si.zero_fill(NA_as_zero_I, n, ixB, nnz, sparse_zeros_ok);
+    if (!refusal.empty()) return fail(verbose, refusal);
     // Dense X: the rows of the present entries go through the same row kernels as a sparse X (a row's system is the sum over
     // its present entries either way: factors_closed_form, common.c:762-1075; factors_explicit_cg_dense, :1615-1749).  What the
     // reference's dense cases add is the CHOICE of solver (optimizeA Cases 1-2, common.c:2787-3116), followed here per
@@ -1184,7 +933,7 @@ int_t fit_collective_explicit_als(
     // information is dense or missing-as-zero (:5121-5130), the solver asked for otherwise.  The side without side information keeps
     // optimizeA's rules above.  Side information on exactly the rows / columns of X (the rows beyond it would take optimizeA's dense
     // cases on a sub-block, :4832-5099), complete (no NaN), no weights.
-    const bool dense_side_A = Xfull && (U != nullptr || nnz_U > 0 || szU.on), dense_side_B = Xfull && (II != nullptr || nnz_I > 0 || szI.on);
+    const bool dense_side_A = Xfull && su.present(), dense_side_B = Xfull && si.present();
     const bool had_dense_X = Xfull != nullptr;
     if (Xfull) {
         if (add_implicit_features || NA_as_zero_X)
@@ -1193,7 +942,7 @@ int_t fit_collective_explicit_als(
         //  dense weights, either solver, both precisions -- so that combination has nothing to be pinned against)
         if ((dense_side_A || dense_side_B) && (weight || NA_as_zero_U || NA_as_zero_I))
             return fail(verbose, "cmfrec_hip: dense X with side information: not together with observation weights or NA_as_zero_U / _I.");
-        if ((dense_side_A && m_u != m) || (dense_side_B && n_i != n))
+        if ((dense_side_A && su.rows != m) || (dense_side_B && si.rows != n))
             return fail(verbose, "cmfrec_hip: dense X with side information: U / I must have exactly the rows / columns of X.");
         if (m <= 0 || n <= 0) return fail(verbose, "cmfrec_hip: invalid dimensions.");
         dx.convert(Xfull, weight, m, n);
@@ -1236,8 +985,8 @@ int_t fit_collective_explicit_als(
             bool mixA = false, mixB = false;
             dense_chol_A = dx.full || dx.near_row || case2_chol(dx.na_row, n, fewA, mixA);
             dense_chol_B = dx.full || dx.near_col || case2_chol(dx.na_col, m, fewB, mixB);
-            if (dense_side_A) { dense_chol_A = (dx.full || dx.near_row) && U != nullptr; mixA = false; }
-            if (dense_side_B) { dense_chol_B = (dx.full || dx.near_col) && II != nullptr; mixB = false; }
+            if (dense_side_A) { dense_chol_A = (dx.full || dx.near_row) && su.dense != nullptr; mixA = false; }
+            if (dense_side_B) { dense_chol_B = (dx.full || dx.near_col) && si.dense != nullptr; mixB = false; }
             // a half-step with rows of both kinds under use_cg: the rows that miss few entries are marked for the closed form
             // (cmfrec_hip_session_set_closed_form_rows), the update runs both solvers
             if (use_cg && !nonneg && l1_lam == 0 && !l1_lam_unique) {
@@ -1255,7 +1004,7 @@ int_t fit_collective_explicit_als(
         return fail(verbose, "cmfrec_hip: NA_as_zero_X is implemented for the model without nonneg / L1 and scale_bias_const.");
     // the matrices for predictions (round 5): for the model without side information -- B_plus_bias, BtB, TransBtBinvBt as ever, plus
     // BtXbias, the constant every new row's right-hand side receives (collective.c:8938-8986)
-    if (NA_as_zero_X && precompute_for_predictions && (U || II || nnz_U || nnz_I || szU.on || szI.on || add_implicit_features))
+    if (NA_as_zero_X && precompute_for_predictions && (su.present() || si.present() || add_implicit_features))
         return fail(verbose, "cmfrec_hip: NA_as_zero_X with precompute_for_predictions: the model without side information and implicit features.");
     // ... with implicit features (round 5): the model without side information and weights, closed form (optimizeA_collective's
     // general branch on a matrix all rows share, collective.c:8612 / :8783 -> :1534-1846)
@@ -1265,10 +1014,10 @@ int_t fit_collective_explicit_als(
     // ... with SPARSE side information (round 5): row by row on the shared B^T B plus the rank-1 terms of the row's own attributes
     // (collective_closed_form_block with prefer_BtB, collective.c:1534-1846) -- closed form, side information on exactly the rows /
     // columns of X, no weights
-    if (NA_as_zero_X && ((U == nullptr && nnz_U) || (II == nullptr && nnz_I))) {
+    if (NA_as_zero_X && (su.sparse() || si.sparse())) {
         if (NA_as_zero_U || NA_as_zero_I)
             return fail(verbose, "cmfrec_hip: NA_as_zero_X with sparse side information: not together with NA_as_zero_U / _I.");
-        if ((U == nullptr && nnz_U && m_u != m) || (II == nullptr && nnz_I && n_i != n))
+        if ((su.sparse() && su.rows != m) || (si.sparse() && si.rows != n))
             return fail(verbose, "cmfrec_hip: NA_as_zero_X with side information: U / I must have exactly the rows / columns of X.");
     }
     // ... with observation weights (round 5): optimizeA Case 4's NA_as_zero + weight branches (common.c:3209-3302, :846-907,
@@ -1283,40 +1032,25 @@ int_t fit_collective_explicit_als(
         if (use_cg && !precondition_cg && k + k_main + 1 > 64)
             return fail(verbose, "cmfrec_hip: NA_as_zero_X with observation weights under CG: k + k_main + bias <= 64 (precondition_cg takes more).");
     }
-    if (NA_as_zero_X && (U || II)) {
+    if (NA_as_zero_X && (su.dense || si.dense)) {
         // (use_cg is accepted: with a factorised shared block matrix the reference takes the closed form whatever the solver asked for)
-        if ((U && m_u != m) || (II && n_i != n))
+        if ((su.dense && su.rows != m) || (si.dense && si.rows != n))
             return fail(verbose, "cmfrec_hip: NA_as_zero_X with side information: U / I must have exactly the rows / columns of X.");
-        for (size_t e = 0; U && e < (size_t)m_u * (size_t)p; e++)
-            if (std::isnan(U[e])) return fail(verbose, "cmfrec_hip: NA_as_zero_X with side information: NaN in U is not implemented.");
-        for (size_t e = 0; II && e < (size_t)n_i * (size_t)q; e++)
-            if (std::isnan(II[e])) return fail(verbose, "cmfrec_hip: NA_as_zero_X with side information: NaN in I is not implemented.");
+        for (size_t e = 0; su.dense && e < (size_t)su.rows * (size_t)su.cols; e++)
+            if (std::isnan(su.dense[e])) return fail(verbose, "cmfrec_hip: NA_as_zero_X with side information: NaN in U is not implemented.");
+        for (size_t e = 0; si.dense && e < (size_t)si.rows * (size_t)si.cols; e++)
+            if (std::isnan(si.dense[e])) return fail(verbose, "cmfrec_hip: NA_as_zero_X with side information: NaN in I is not implemented.");
     }
-    // dense side information with NaN -> the sparse route on its centred present entries
-    DenseNanSide nanU, nanI;
-    const bool hadU = (U != nullptr) || szU.on;
-    bool nan_side = false;
-    if (U && m_u > 0 && p > 0 && nanU.convert(U, m_u, p, U_colmeans)) {
-        U = nullptr; U_row = nanU.row.data(); U_col = nanU.col.data(); U_sp = nanU.val.data(); nnz_U = nanU.val.size(); nan_side = true;
-    } else if (U == nullptr && nnz_U > 0 && U_row && U_col && U_sp) {
-        bool ok = true;
-        for (size_t e = 0; e < nnz_U && ok; e++) ok = (U_col[e] >= 0 && U_col[e] < p);
-        if (ok) sparse_colmeans(U_col, U_sp, nnz_U, p, U_colmeans);
-    }
-    if (II && n_i > 0 && q > 0 && nanI.convert(II, n_i, q, I_colmeans)) {
-        II = nullptr; I_row = nanI.row.data(); I_col = nanI.col.data(); I_sp = nanI.val.data(); nnz_I = nanI.val.size(); nan_side = true;
-    } else if (II == nullptr && nnz_I > 0 && I_row && I_col && I_sp) {
-        bool ok = true;
-        for (size_t e = 0; e < nnz_I && ok; e++) ok = (I_col[e] >= 0 && I_col[e] < q);
-        if (ok) sparse_colmeans(I_col, I_sp, nnz_I, q, I_colmeans);
-    }
-    if (nan_side && nnz_U == 0 && nanU.row.empty() && hadU && U == nullptr)
-        return fail(verbose, "cmfrec_hip: U has no present entries.");
+    // stage 2 of the intake: dense side information with NaN -> the sparse route on its centred present entries
+    su.take_nan(); si.take_nan();
+    const bool nan_side = su.nan_side || si.nan_side;
+    // (asymmetry, kept: only U is refused for having nothing left; an I without a present entry counts as no I)
+    if (su.nothing_present(nan_side)) return fail(verbose, "cmfrec_hip: U has no present entries.");
     // implicit features (Ai, Bi on the binary "was observed" matrix): closed-form solves, dense, sparse (round 6, fixture g32) or no
     // side information inside the shape of X, prediction matrices not produced
     if (add_implicit_features) {
         if (!Ai || !Bi) return fail(verbose, "cmfrec_hip: add_implicit_features needs the Ai and Bi outputs.");
-        if (((U || nnz_U) && m_u > m) || ((II || nnz_I) && n_i > n))
+        if (su.beyond(m) || si.beyond(n))
             return fail(verbose, "cmfrec_hip: implicit features with side information beyond X are not implemented.");
         if (precompute_for_predictions)
             return fail(verbose, "cmfrec_hip: implicit features: precompute_for_predictions is not implemented.");
@@ -1327,14 +1061,12 @@ int_t fit_collective_explicit_als(
         if (!(w_implicit > 0)) return fail(verbose, "cmfrec_hip: w_implicit must be positive.");
     }
     // side information: dense (no NaN) or sparse COO (missing = absent).  Sparse: Cholesky updates only, rows within X.
-    const bool spU = (U == nullptr && nnz_U > 0), spI = (II == nullptr && nnz_I > 0);
-    if ((spU && (m_u > m || !U_row || !U_col || !U_sp)) || (spI && (n_i > n || !I_row || !I_col || !I_sp)))
+    if (su.bad_triplets(m) || si.bad_triplets(n))
         return fail(verbose, "cmfrec_hip: sparse side information must be COO triplets with rows inside X.");
-    for (size_t e = 0; spU && e < nnz_U; e++)
-        if (U_row[e] < 0 || U_row[e] >= m_u || U_col[e] < 0 || U_col[e] >= p) return fail(verbose, "cmfrec_hip: U index out of range.");
-    for (size_t e = 0; spI && e < nnz_I; e++)
-        if (I_row[e] < 0 || I_row[e] >= n_i || I_col[e] < 0 || I_col[e] >= q) return fail(verbose, "cmfrec_hip: I index out of range.");
-    if ((l1_lam != 0 || l1_lam_unique) && (((U || nnz_U) && m_u > m) || ((II || nnz_I) && n_i > n)))
+    su.drop_if_absent(); si.drop_if_absent();
+    if (su.index_out_of_range()) return fail(verbose, su.index_message());
+    if (si.index_out_of_range()) return fail(verbose, si.index_message());
+    if ((l1_lam != 0 || l1_lam_unique) && (su.beyond(m) || si.beyond(n)))
         return fail(verbose, "cmfrec_hip: L1 together with side information beyond X is not implemented.");
     if (nonneg || l1_lam != 0 || l1_lam_unique) use_cg = false;           // collective.c:7474-7479
     // For rows with few missing values the reference corrects a precomputed Gramian instead of summing the present entries
@@ -1356,7 +1088,7 @@ int_t fit_collective_explicit_als(
     // themselves (collective.c:1636-1653 beside :1673-1699; block CG :2187-2208 beside :2292-2298) -- fixture g31.
     // (weights + sparse side information + scale_lam_sideinfo: the reference's multipliers add `U_csr_p[row+1] - U_csr[row]` -- a VALUE of
     //  U where its row pointer is meant, collective.c:8087, :8106 -- so there is no meaningful number to agree with: refused)
-    if (weight && scale_lam_sideinfo && (spU || spI))
+    if (weight && scale_lam_sideinfo && (su.sparse() || si.sparse()))
         return fail(verbose, "cmfrec_hip: observation weights with sparse side information under scale_lam_sideinfo are not implemented "
                              "(the reference's lambda multipliers for this combination read a value of U / I in place of a row pointer).");
     // (round 6, fixture g38: with implicit features too -- the weighted row solvers with the implicit-features term, whose own
@@ -1365,8 +1097,6 @@ int_t fit_collective_explicit_als(
                    (scale_bias_const && scale_lam && (user_bias || item_bias))))
         return fail(verbose, "cmfrec_hip: observation weights together with NaN side information / scale_lam_sideinfo / "
                              "scale_bias_const are not implemented.");
-    if (U == nullptr && !spU && !szU.on) { m_u = 0; p = 0; }
-    if (II == nullptr && !spI && !szI.on) { n_i = 0; q = 0; }
     if (m <= 0 || n <= 0 || nnz == 0) return fail(verbose, "cmfrec_hip: invalid dimensions.");
     for (size_t e = 0; e < nnz; e++)
         if (ixA[e] < 0 || ixA[e] >= m || ixB[e] < 0 || ixB[e] >= n) return fail(verbose, "cmfrec_hip: X index out of range.");
@@ -1386,7 +1116,7 @@ int_t fit_collective_explicit_als(
     // counted under scale_lam_sideinfo) -- instead of row by row (collective.c:7555-7556, :8026-8048, :8071-8160)
     if (!scale_lam || !has_bias) scale_bias_const = false;
     if (scale_bias_const) {
-        if (add_implicit_features || spU || spI || nan_side)
+        if (add_implicit_features || su.sparse() || si.sparse() || nan_side)
             return fail(verbose, "cmfrec_hip: scale_bias_const with implicit features / sparse or NaN side information is not implemented.");
         if (item_bias && !user_bias && !use_cg)
             return fail(verbose, "cmfrec_hip: scale_bias_const with only an item bias and the Cholesky solver: the reference leaves "
@@ -1402,95 +1132,26 @@ int_t fit_collective_explicit_als(
             }
             return (real_t)wmean;
         };
-        if (user_bias) { *scaling_biasA = mean_count(ixA, m, (U || szU.on) ? p : 0, m_u); lam6[0] *= *scaling_biasA; l16[0] *= *scaling_biasA; }
-        if (item_bias) { *scaling_biasB = mean_count(ixB, n, (II || szI.on) ? q : 0, n_i); lam6[1] *= *scaling_biasB; l16[1] *= *scaling_biasB; }
+        if (user_bias) { *scaling_biasA = mean_count(ixA, m, (su.dense || su.sz.on) ? su.cols : 0, su.rows); lam6[0] *= *scaling_biasA; l16[0] *= *scaling_biasA; }
+        if (item_bias) { *scaling_biasB = mean_count(ixB, n, (si.dense || si.sz.on) ? si.cols : 0, si.rows); lam6[1] *= *scaling_biasB; l16[1] *= *scaling_biasB; }
     }
     const int k_totA = k_user + k + k_main, k_totB = k_item + k + k_main;
-    const int_t m_max = std::max(m, m_u), n_max = std::max(n, n_i);      // rows of A / B (collective.c:7332-7335)
+    const int_t m_max = std::max(m, su.rows), n_max = std::max(n, si.rows);      // rows of A / B (collective.c:7332-7335)
 
     // ---- global mean, common.c:3494-3524 + :3603 (nthreads selects running mean vs sum/cnt); the
     //      subtraction itself happens on the device while the CSR / CSC are built ----
     PhaseTimer tm;
-    real_t gm = 0;
-    if (center && NA_as_zero_X && weight) {
-        // weighted mean of the entries (common.c:3558-3584; with 8 threads or more the unweighted sum over the sum of the weights,
-        // quirk Q13), then DIVIDED by the weights' share of all cells, wsum / (wsum + m n - nnz), as the reference does
-        // (:3590-3594; the sum of the weights there is a compensated sum, helpers.c:1691-1707)
-        double xsum = 0, wsum = 2.220446049250313e-16;
-        if (nthreads >= 8) {
-            wsum = 0;
-            for (size_t e = 0; e < nnz; e++) { xsum += (double)X[e]; wsum += (double)weight[e]; }
-            gm = (real_t)(xsum / wsum);
-        } else {
-            for (size_t e = 0; e < nnz; e++) { wsum += (double)weight[e]; xsum += (((double)X[e] - xsum) * (double)weight[e]) / wsum; }
-            gm = (real_t)xsum;
-        }
-        double err = 0, res = 0;
-        for (size_t e = 0; e < nnz; e++) { const double diff = (double)weight[e] - err; const double temp = res + diff; err = (temp - res) - diff; res = temp; }
-        const long double wl = (long double)res;
-        gm = (real_t)((long double)gm / (wl / (wl + ((long double)m * (long double)n - (long double)nnz))));
-        if (std::fabs(gm) < std::sqrt(EPS_T)) gm = 0;
-    } else if (center && NA_as_zero_X) {
-        // mean over all m x n cells: the mean of the entries x nnz / (m n) (common.c:3494-3523); the stored values stay as
-        // they are (:3600-3607), the mean enters every right-hand side instead (collective.c:8573-8600, :8756-8787)
-        double xsum = 0;
-        if (nthreads >= 8) {
-            for (size_t e = 0; e < nnz; e++) xsum += X[e];
-            gm = (real_t)(xsum / (double)nnz);
-        } else {
-            size_t cnt = 0;
-            for (size_t e = 0; e < nnz; e++) xsum += (X[e] - xsum) / (double)(++cnt);
-            gm = (real_t)xsum;
-        }
-        gm = (real_t)((long double)gm * ((long double)nnz / ((long double)m * (long double)n)));
-        if (std::fabs(gm) < std::sqrt(EPS_T)) gm = 0;
-    } else if (center && weight) {
-        // weighted running mean, common.c:3574-3584.  With 8 threads or more the reference divides the UNWEIGHTED sum of X by
-        // the sum of the weights (:3561-3571) -- not a mean, but the number a caller with nthreads >= 8 receives (Python:
-        // nthreads = -1 on a host of 8 cores or more), so it is reproduced (fixture g23).
-        double xsum = 0, wsum = 2.220446049250313e-16;
-        if (nthreads >= 8) {
-            wsum = 0;
-            for (size_t e = 0; e < nnz; e++) { xsum += (double)X[e]; wsum += (double)weight[e]; }
-            xsum = (double)(real_t)(xsum / wsum);
-        } else
-            for (size_t e = 0; e < nnz; e++) { wsum += (double)weight[e]; xsum += (((double)X[e] - xsum) * (double)weight[e]) / wsum; }
-        gm = (real_t)xsum;
-        if (nonneg) gm = std::max(gm, (real_t)0);                         // :3604-3605
-        if (std::fabs(gm) < std::sqrt(EPS_T)) gm = 0;
-    } else if (center) {
-        double xsum = 0;
-        if (nthreads >= 8) {
-            for (size_t e = 0; e < nnz; e++) xsum += X[e];
-            gm = (real_t)(xsum / (double)nnz);
-        } else {
-            size_t cnt = 0;
-            for (size_t e = 0; e < nnz; e++) xsum += (X[e] - xsum) / (double)(++cnt);
-            gm = (real_t)xsum;
-        }
-        if (nonneg) gm = std::max(gm, (real_t)0);                         // common.c:3604-3605
-        if (std::fabs(gm) < std::sqrt(EPS_T)) gm = 0;
-    }
+    const real_t gm = center ? global_mean(X, weight, nnz, m, n, nthreads, NA_as_zero_X, nonneg) : (real_t)0;      // fit_inputs.hpp
     *glob_mean = gm;
     tm.lap("global mean");
 
     // ---- side information: column means + centering, common.c:4938-4997 ----
-    std::vector<real_t> Uc, Ic;
-    auto center_cols = [](const real_t *M, int rows, int cols, real_t *means, std::vector<real_t> &out) {
-        out.assign(M, M + (size_t)rows * cols);
-        if (means == nullptr) return;                                     // no centring asked for (common.c:4938)
-        for (int c = 0; c < cols; c++) means[c] = 0;
-        for (int r = 0; r < rows; r++) for (int c = 0; c < cols; c++) means[c] += M[(size_t)r * cols + c];
-        for (int c = 0; c < cols; c++) means[c] /= (double)rows;
-        for (int r = 0; r < rows; r++) for (int c = 0; c < cols; c++) out[(size_t)r * cols + c] -= means[c];
-    };
-    if (U) center_cols(U, m_u, p, U_colmeans, Uc);
-    if (II) center_cols(II, n_i, q, I_colmeans, Ic);
+    su.center(); si.center();
 
     tm.lap("side info centring");
     // ---- factor start values, collective.c:8241-8274 ----
     if (reset_values) {
-        const bool fill_B = (II != nullptr || spI || szI.on || add_implicit_features);
+        const bool fill_B = (si.present() || add_implicit_features);
         cmfrng::random_parallel<real_t>(A, (size_t)m_max * k_totA, fill_B ? B : nullptr, fill_B ? (size_t)n_max * k_totB : 0, seed, true);
         if (nonneg) {                                                     // :8256-8263: non-negative start values
             for (size_t e = 0; e < (size_t)m_max * k_totA; e++) A[e] = std::fabs(A[e]);
@@ -1498,8 +1159,8 @@ int_t fit_collective_explicit_als(
         }
         if (use_cg) {
             if (!fill_B) memset(B, 0, (size_t)n_max * k_totB * sizeof(real_t));
-            if (U || spU || szU.on) memset(C, 0, (size_t)p * (k_user + k) * sizeof(real_t));
-            if (II || spI || szI.on) memset(D, 0, (size_t)q * (k_item + k) * sizeof(real_t));
+            if (su.present()) memset(C, 0, (size_t)su.cols * (k_user + k) * sizeof(real_t));
+            if (si.present()) memset(D, 0, (size_t)si.cols * (k_item + k) * sizeof(real_t));
         }
     }
 
@@ -1517,7 +1178,7 @@ int_t fit_collective_explicit_als(
     mdl.implicit = 0; mdl.m = m_max; mdl.n = n_max; mdl.m_x = m; mdl.n_x = n;
     mdl.k = k; mdl.k_main = k_main; mdl.k_user = k_user; mdl.k_item = k_item;
     mdl.user_bias = user_bias; mdl.item_bias = item_bias; mdl.scale_lam = scale_lam; mdl.scale_lam_sideinfo = scale_lam_sideinfo;
-    mdl.use_cg = use_cg; mdl.max_cg_steps = max_cg_steps; mdl.precondition_cg = precondition_cg; mdl.p = p; mdl.q = q; mdl.m_u = m_u; mdl.n_i = n_i;
+    mdl.use_cg = use_cg; mdl.max_cg_steps = max_cg_steps; mdl.precondition_cg = precondition_cg; mdl.p = su.cols; mdl.q = si.cols; mdl.m_u = su.rows; mdl.n_i = si.rows;
     mdl.lam = lam; mdl.w_user = w_user; mdl.w_item = w_item;
     mdl.row_begin = 0; mdl.row_end = m_max; mdl.col_begin = 0; mdl.col_end = n_max;
     const std::vector<int> devs = devices_from_env();                  // CMFREC_HIP_DEVICES: one ordinal = that device, several = row-block shards
@@ -1527,33 +1188,62 @@ int_t fit_collective_explicit_als(
     // sweeps alternate over all rows and all columns, common.c:4410-4909), then handed to every shard.
     // (a dense X keeps to one device: its half-steps follow the reference's per-half-step choice of solver, dense_chol_A / _B,
     // and its empty rows are zeroed afterwards -- neither is part of multi_loop)
-    const bool multi_ok = sharded_fit_wanted(devs) && !spU && !spI && !szU.on && !szI.on && m_u <= m && n_i <= n && !add_implicit_features && !NA_as_zero_X &&
-                          !weight && dx.na_row.empty() && m >= (int_t)devs.size() && n >= (int_t)devs.size() && zero_rows_A.empty() &&
-                          zero_rows_B.empty();
+    const bool multi_ok = sharded_fit_wanted(devs) && !su.sparse() && !si.sparse() && !su.sz.on && !si.sz.on && su.rows <= m && si.rows <= n &&
+                          !add_implicit_features && !NA_as_zero_X && !weight && dx.na_row.empty() && m >= (int_t)devs.size() && n >= (int_t)devs.size() &&
+                          su.zero_rows.empty() && si.zero_rows.empty();
     if (devs.size() > 1 && !multi_ok && verbose)
         printf("cmfrec_hip: CMFREC_HIP_DEVICES lists %d devices; this configuration (sparse side information / side information beyond X / "
                "weights / implicit features / NA_as_zero / dense X) runs on the first\n", (int)devs.size());
+    // the penalties and constraints of a session: the temporary bias session, every shard, the single device
+    auto configure = [&](cmfrec_hip_session *sd) {
+        int rc2 = 0;
+        if (nonneg || nonneg_C || nonneg_D) rc2 = cmfrec_hip_session_set_nonneg(sd, nonneg, nonneg_C, nonneg_D, (int)max_cd_steps);
+        if (!rc2 && l1_lam != 0) rc2 = cmfrec_hip_session_set_l1(sd, l1_lam, (int)max_cd_steps);
+        if (!rc2 && (lam_unique || l1_lam_unique || scale_bias_const))
+            rc2 = cmfrec_hip_session_set_lam_unique(sd, (lam_unique || scale_bias_const) ? lam6 : nullptr,
+                                                    (l1_lam_unique || (scale_bias_const && l1_lam != 0)) ? l16 : nullptr, (int)max_cd_steps);
+        if (!rc2 && scale_bias_const) rc2 = cmfrec_hip_session_set_scale_bias_const(sd, 1);
+        return rc2;
+    };
+    // the biases' lambdas for their start values, clipped like common.c:4449-4452 (collective.c:8178, :8197, :8218-8219)
+    const real_t lam_u = std::fabs(lam6[0]) < EPS_T ? EPS_T : lam6[0], lam_i = std::fabs(lam6[1]) < EPS_T ? EPS_T : lam6[1];
+    // the matrices for predictions, single device and shards alike (collective.c:8936-9249)
+    auto epilogue = [&](cmfrec_hip_session *s) {
+        const int last_chol = (!use_cg || (finalize_chol && niter > 0)) ? 1 : 0;
+        const int rc2 = cmfrec_hip_session_precompute(s, last_chol, include_all_X ? 1 : 0, precomputedBtB, precomputedTransBtBinvBt, nullptr,
+                                                      su.had_dense ? precomputedBeTBeChol : nullptr, su.had_dense ? precomputedCtCw : nullptr,
+                                                      su.had_dense ? precomputedTransCtCinvCt : nullptr);
+        if (rc2) return rc2;
+        if (su.naz) fill_CtUbias(precomputedCtUbias, C, su.colmeans, su.cols, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
+        if (NA_as_zero_X && precomputedBtXbias != nullptr) {               // (never on the shards: multi_ok excludes NA_as_zero_X)
+            // minus the sum over the items of (their bias + the mean) x their factors, the bias column as 1 (collective.c:8938-8986)
+            const int_t kp = k + k_main + (user_bias ? 1 : 0);
+            std::vector<double> acc((size_t)kp, 0.);
+            if (item_bias || center)
+                for (int_t c = 0; c < n; c++) {
+                    const double coef = -((item_bias ? (double)biasB[c] : 0.) + (double)gm);
+                    const real_t *b = B + (size_t)c * k_totB + k_item;
+                    for (int_t f = 0; f < k + k_main; f++) acc[(size_t)f] += coef * (double)b[f];
+                    if (user_bias) acc[(size_t)(kp - 1)] += coef;
+                }
+            for (int_t f = 0; f < kp; f++) precomputedBtXbias[f] = (real_t)acc[(size_t)f];
+        }
+        if (user_bias && B_plus_bias) {                                   // append_ones_last_col, :8908-8920
+            for (int_t c = 0; c < n_max; c++) {
+                memcpy(B_plus_bias + (size_t)c * (k_totB + 1), B + (size_t)c * k_totB, (size_t)k_totB * sizeof(real_t));
+                B_plus_bias[(size_t)c * (k_totB + 1) + k_totB] = 1;
+            }
+        }
+        return 0;
+    };
     if (multi_ok) {
-        auto configure = [&](cmfrec_hip_session *sd) {
-            int rc2 = 0;
-            if (nonneg || nonneg_C || nonneg_D) rc2 = cmfrec_hip_session_set_nonneg(sd, nonneg, nonneg_C, nonneg_D, (int)max_cd_steps);
-            if (!rc2 && l1_lam != 0) rc2 = cmfrec_hip_session_set_l1(sd, l1_lam, (int)max_cd_steps);
-            if (!rc2 && (lam_unique || l1_lam_unique || scale_bias_const))
-                rc2 = cmfrec_hip_session_set_lam_unique(sd, (lam_unique || scale_bias_const) ? lam6 : nullptr,
-                                                        (l1_lam_unique || (scale_bias_const && l1_lam != 0)) ? l16 : nullptr, (int)max_cd_steps);
-            if (!rc2 && scale_bias_const) rc2 = cmfrec_hip_session_set_scale_bias_const(sd, 1);
-            return rc2;
-        };
         int rc = 0;
         if (has_bias && reset_values) {
-            cmfrec_hip_session *t = cmfrec_hip_session_create(&mdl, devs[0]);
-            if (!t) { if (verbose) fprintf(stderr, "%s\n", cmfrec_hip_last_error()); const int ec = cmfrec_hip_last_error_code(); return ec ? ec : 1; }
+            cmfrec_hip_session *t = create_session(mdl, devs[0], verbose, rc);
+            if (!t) return rc;
             rc = cmfrec_hip_session_set_X_coo_weighted(t, ixA, ixB, X, nullptr, nnz, gm, (real_t)1);
             if (!rc) rc = configure(t);          // (the sweeps need the attribute COUNTS under scale_lam_sideinfo, mdl.p / mdl.q, not U / I)
             if (!rc) rc = cmfrec_hip_session_set_factors(t, A, B, nullptr, nullptr, nullptr, nullptr);
-            real_t lam_u = lam6[0], lam_i = lam6[1];                      // collective.c:8178, :8197, :8218-8219
-            if (std::fabs(lam_u) < EPS_T) lam_u = EPS_T;
-            if (std::fabs(lam_i) < EPS_T) lam_i = EPS_T;
             if (!rc) rc = cmfrec_hip_session_init_biases(t, lam_u, lam_i);
             if (!rc) rc = cmfrec_hip_session_get_factors(t, nullptr, nullptr, biasA, biasB, nullptr, nullptr);
             cmfrec_hip_session_destroy(t);
@@ -1561,7 +1251,7 @@ int_t fit_collective_explicit_als(
         }
         MultiDev md;
         if (!rc) rc = build_shards(md, devs, mdl, m_max, n_max, ixA, ixB, X, nnz, gm, (real_t)1, [&](cmfrec_hip_session *sd, int d) {
-            int rc2 = set_sideinfo_shard(md, sd, d, U ? Uc.data() : nullptr, m_u, p, II ? Ic.data() : nullptr, n_i, q);
+            int rc2 = set_sideinfo_shard(md, sd, d, su.centred_or_null(), su.rows, su.cols, si.centred_or_null(), si.rows, si.cols);
             if (!rc2) rc2 = configure(sd);
             if (!rc2) rc2 = cmfrec_hip_session_set_factors(sd, A, B, has_bias ? biasA : nullptr, has_bias ? biasB : nullptr, C, D);
             return rc2;
@@ -1572,54 +1262,25 @@ int_t fit_collective_explicit_als(
             const int rc2 = cmfrec_hip_session_get_factors(s0, A, B, biasA, biasB, C, D);
             if (rc2) rc_loop = rc2;
         }
-        if ((rc_loop == 0 || rc_loop == 3) && s0 && precompute_for_predictions) {   // collective.c:8936-9249
-            const int last_chol = (!use_cg || (finalize_chol && niter > 0)) ? 1 : 0;
-            int rc2 = cmfrec_hip_session_precompute(s0, last_chol, include_all_X ? 1 : 0, precomputedBtB, precomputedTransBtBinvBt, nullptr,
-                                                    hadU ? precomputedBeTBeChol : nullptr, hadU ? precomputedCtCw : nullptr,
-                                                    hadU ? precomputedTransCtCinvCt : nullptr);
-            if (rc2) rc_loop = rc2;
-            if (naz_U && !rc2) fill_CtUbias(precomputedCtUbias, C, U_colmeans, p, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
-            if (!rc2 && user_bias && B_plus_bias) {                           // append_ones_last_col, :8908-8920
-                for (int_t c = 0; c < n_max; c++) {
-                    memcpy(B_plus_bias + (size_t)c * (k_totB + 1), B + (size_t)c * k_totB, (size_t)k_totB * sizeof(real_t));
-                    B_plus_bias[(size_t)c * (k_totB + 1) + k_totB] = 1;
-                }
-            }
-        }
+        if ((rc_loop == 0 || rc_loop == 3) && s0 && precompute_for_predictions)
+            if (const int rc2 = epilogue(s0)) rc_loop = rc2;
         if (verbose && rc_loop == 0) printf("ALS procedure terminated successfully\n");
         return rc_loop;
     }
-    cmfrec_hip_session *s = cmfrec_hip_session_create(&mdl, devs.empty() ? -1 : devs[0]);
-    if (!s) { if (verbose) fprintf(stderr, "%s\n", cmfrec_hip_last_error()); const int ec = cmfrec_hip_last_error_code(); return ec ? ec : 1; }
+    int rc = 0;
+    cmfrec_hip_session *s = create_session(mdl, devs.empty() ? -1 : devs[0], verbose, rc);
+    if (!s) return rc;
     tm.lap("start values + session");
     // X - mean, COO -> CSR + CSC and the bias start values are computed on the device (coo_device.hpp)
-    int rc = cmfrec_hip_session_set_X_coo_weighted(s, ixA, ixB, X, weight, nnz, NA_as_zero_X ? (real_t)0 : gm, (real_t)1);
+    rc = cmfrec_hip_session_set_X_coo_weighted(s, ixA, ixB, X, weight, nnz, NA_as_zero_X ? (real_t)0 : gm, (real_t)1);
     if (!rc && NA_as_zero_X) rc = cmfrec_hip_session_set_NA_as_zero_X(s, 1, center ? 1 : 0, gm);
     tm.lap("set_X_coo (upload, sort, bins)");
     if (!rc && !dense_cf_A.empty()) rc = cmfrec_hip_session_set_closed_form_rows(s, 'A', dense_cf_A.data());
     if (!rc && !dense_cf_B.empty()) rc = cmfrec_hip_session_set_closed_form_rows(s, 'B', dense_cf_B.data());
-    if (!rc && !zero_rows_A.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'A', zero_rows_A.data(), (int)zero_rows_A.size());
-    if (!rc && !zero_rows_B.empty()) rc = cmfrec_hip_session_set_zero_rows(s, 'B', zero_rows_B.data(), (int)zero_rows_B.size());
-    if (!rc) rc = cmfrec_hip_session_set_sideinfo(s, U ? Uc.data() : nullptr, II ? Ic.data() : nullptr);
-    if (!rc && szU.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'U', szU.row, szU.col, szU.val, szU.nnz, szU.colmeans());
-    if (!rc && szI.on) rc = cmfrec_hip_session_set_sideinfo_sparse_zeros(s, 'I', szI.row, szI.col, szI.val, szI.nnz, szI.colmeans());
-    if (!rc && spU) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'U', U_row, U_col, U_sp, nnz_U);
-    if (!rc && spI) rc = cmfrec_hip_session_set_sideinfo_sparse(s, 'I', I_row, I_col, I_sp, nnz_I);
-    // dense side information with NaN: the per-attribute rules of the dense C / D update (DenseNanSide::rules)
-    for (int side = 0; side < 2 && !rc; side++) {
-        const DenseNanSide &ns = side ? nanI : nanU;
-        if (ns.na_col.empty() || !(side ? spI : spU)) continue;
-        std::vector<unsigned char> mask; std::vector<real_t> mult;
-        ns.rules((side ? k_item : k_user) + k, (scale_lam || scale_lam_sideinfo), mask, mult);
-        if (use_cg) rc = cmfrec_hip_session_set_closed_form_rows(s, side ? 'D' : 'C', mask.data());
-        if (!rc && !mult.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, side ? 'D' : 'C', mult.data());
-    }
-    if (!rc && (nonneg || nonneg_C || nonneg_D)) rc = cmfrec_hip_session_set_nonneg(s, nonneg, nonneg_C, nonneg_D, (int)max_cd_steps);
-    if (!rc && l1_lam != 0) rc = cmfrec_hip_session_set_l1(s, l1_lam, (int)max_cd_steps);
-    if (!rc && (lam_unique || l1_lam_unique || scale_bias_const))
-        rc = cmfrec_hip_session_set_lam_unique(s, (lam_unique || scale_bias_const) ? lam6 : nullptr,
-                                               (l1_lam_unique || (scale_bias_const && l1_lam != 0)) ? l16 : nullptr, (int)max_cd_steps);
-    if (!rc && scale_bias_const) rc = cmfrec_hip_session_set_scale_bias_const(s, 1);
+    if (!rc) rc = hand_sides_to_session(s, su, si);
+    if (!rc) rc = hand_nan_rules(s, su, 'C', k_user + k, scale_lam, use_cg);
+    if (!rc) rc = hand_nan_rules(s, si, 'D', k_item + k, scale_lam, use_cg);
+    if (!rc) rc = configure(s);
     if (!rc) rc = cmfrec_hip_session_set_factors(s, A, B, reset_values ? nullptr : biasA, reset_values ? nullptr : biasB, C, D);
     // Ai / Bi need no start values: their first update is a closed-form solve (collective.c:8236-8240)
     if (!rc && add_implicit_features) rc = cmfrec_hip_session_set_implicit_features(s, w_implicit, nullptr, nullptr);
@@ -1628,9 +1289,6 @@ int_t fit_collective_explicit_als(
     if (!rc && has_bias && reset_values && NA_as_zero_X) {
         // bias start values, missing-as-zero branches (common.c:4207-4237 one-sided; :4453-4476, :4693-4710, :4849-4868
         // two-sided): O(nnz) running means per row and column, computed here on the host and handed over
-        real_t lam_u = lam6[0], lam_i = lam6[1];
-        if (std::fabs(lam_u) < EPS_T) lam_u = EPS_T;
-        if (std::fabs(lam_i) < EPS_T) lam_i = EPS_T;
         auto scaled_means = [&](const int_t *ix, int_t rows, int_t other) {       // running mean of the row's entries (COO order) x cnt / other
             std::vector<double> mean((size_t)rows, 0.); std::vector<size_t> cnt((size_t)rows, 0);
             for (size_t e = 0; e < nnz; e++) { const size_t r = (size_t)ix[e]; mean[r] += ((double)X[e] - mean[r]) / (double)(++cnt[r]); }
@@ -1676,12 +1334,8 @@ int_t fit_collective_explicit_als(
             rc = cmfrec_hip_session_set_factors(s, nullptr, nullptr, user_bias ? biasA : nullptr, item_bias ? biasB : nullptr, nullptr, nullptr);
         }
     } else
-    if (!rc && has_bias && reset_values) {                                // common.c:4410-4909; lambdas clipped like :4449-4452
-        real_t lam_u = lam6[0], lam_i = lam6[1];                          // collective.c:8178, :8197, :8218-8219
-        if (std::fabs(lam_u) < EPS_T) lam_u = EPS_T;
-        if (std::fabs(lam_i) < EPS_T) lam_i = EPS_T;
+    if (!rc && has_bias && reset_values)                                  // common.c:4410-4909
         rc = cmfrec_hip_session_init_biases(s, lam_u, lam_i);
-    }
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("bias init");
     // dense X under scale_lam: the rows' lambda multipliers (n for a row that misses few entries, its present entries otherwise)
@@ -1702,33 +1356,9 @@ int_t fit_collective_explicit_als(
         if (item_bias) for (int_t c = n; c < n_max; c++) biasB[c] = 0;
         if (niter > 0) zero_empty_dense();
     }
-    if ((rc_loop == 0 || rc_loop == 3) && precompute_for_predictions) {   // collective.c:8936-9249
+    if ((rc_loop == 0 || rc_loop == 3) && precompute_for_predictions) {
         if (verbose) { printf("Finishing precomputed matrices..."); fflush(stdout); }
-        const int last_chol = (!use_cg || (finalize_chol && niter > 0)) ? 1 : 0;
-        int rc2 = cmfrec_hip_session_precompute(s, last_chol, include_all_X ? 1 : 0, precomputedBtB, precomputedTransBtBinvBt, nullptr,
-                                                hadU ? precomputedBeTBeChol : nullptr, hadU ? precomputedCtCw : nullptr,
-                                                hadU ? precomputedTransCtCinvCt : nullptr);
-        if (rc2) rc_loop = rc2;
-        if (naz_U && !rc2) fill_CtUbias(precomputedCtUbias, C, U_colmeans, p, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
-        if (!rc2 && NA_as_zero_X && precomputedBtXbias != nullptr) {
-            // minus the sum over the items of (their bias + the mean) x their factors, the bias column as 1 (collective.c:8938-8986)
-            const int_t kp = k + k_main + (user_bias ? 1 : 0);
-            std::vector<double> acc((size_t)kp, 0.);
-            if (item_bias || center)
-                for (int_t c = 0; c < n; c++) {
-                    const double coef = -((item_bias ? (double)biasB[c] : 0.) + (double)gm);
-                    const real_t *b = B + (size_t)c * k_totB + k_item;
-                    for (int_t f = 0; f < k + k_main; f++) acc[(size_t)f] += coef * (double)b[f];
-                    if (user_bias) acc[(size_t)(kp - 1)] += coef;
-                }
-            for (int_t f = 0; f < kp; f++) precomputedBtXbias[f] = (real_t)acc[(size_t)f];
-        }
-        if (!rc2 && user_bias && B_plus_bias) {                           // append_ones_last_col, :8908-8920
-            for (int_t c = 0; c < n_max; c++) {
-                memcpy(B_plus_bias + (size_t)c * (k_totB + 1), B + (size_t)c * k_totB, (size_t)k_totB * sizeof(real_t));
-                B_plus_bias[(size_t)c * (k_totB + 1) + k_totB] = 1;
-            }
-        }
+        if (const int rc2 = epilogue(s)) rc_loop = rc2;
         if (verbose) printf("  done\n");
     }
     cmfrec_hip_session_destroy(s);
