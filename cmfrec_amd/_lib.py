@@ -52,6 +52,15 @@ class NewRowsModelF(C.Structure):
     _fields_ = _newrows_model_fields(C.c_float)
 
 
+class NewRowsModelEx(C.Structure):
+    """``cmfrec_hip_newrows_model_ex``: the model followed by the two missing-as-zero options, double precision."""
+    _fields_ = [("base", NewRowsModel), ("NA_as_zero_X", C.c_int32), ("NA_as_zero_U", C.c_int32)]
+
+
+class NewRowsModelExF(C.Structure):
+    _fields_ = [("base", NewRowsModelF), ("NA_as_zero_X", C.c_int32), ("NA_as_zero_U", C.c_int32)]
+
+
 class NewRowsBatch(C.Structure):
     """``cmfrec_hip_newrows_batch``: pointers and counts only, the same layout in both precisions."""
     _fields_ = [("m", C.c_int32), ("m_u", C.c_int32), ("U", C.c_void_p),
@@ -106,6 +115,10 @@ def newrows_model_mirror(dtype):
     return NewRowsModel if np.dtype(dtype) == np.float64 else NewRowsModelF
 
 
+def newrows_model_ex_mirror(dtype):
+    return NewRowsModelEx if np.dtype(dtype) == np.float64 else NewRowsModelExF
+
+
 EXPORTED = [
     "fit_collective_implicit_als", "fit_collective_explicit_als",
     "factors_collective_explicit_multiple", "factors_collective_implicit_multiple", "cmfrec_hip_factors_multiple", "cmfrec_hip_factors_multiple_l1", "cmfrec_hip_factors_multiple_ex",
@@ -116,7 +129,7 @@ EXPORTED = [
     "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
     "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
     "cmfrec_hip_rankset_create", "cmfrec_hip_rankset_destroy", "cmfrec_hip_ranker_metrics", "cmfrec_hip_session_ranking",
-    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy",
+    "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy", "cmfrec_hip_factors_multiple_naz", "cmfrec_hip_sizeof_newrows_model_ex", "cmfrec_hip_newrows_create_ex", "cmfrec_hip_newrows_naz_launch_waves",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
     "cmfrec_hip_session_set_sideinfo", "cmfrec_hip_session_set_sideinfo_local", "cmfrec_hip_session_sideinfo_partial", "cmfrec_hip_session_sideinfo_finish", "cmfrec_hip_session_set_nonneg", "cmfrec_hip_session_set_l1", "cmfrec_hip_session_set_lam_unique", "cmfrec_hip_session_set_scale_bias_const", "cmfrec_hip_session_set_NA_as_zero_X", "cmfrec_hip_session_set_zero_rows", "cmfrec_hip_session_set_closed_form_rows", "cmfrec_hip_session_set_lambda_multipliers", "cmfrec_hip_session_set_implicit_features", "cmfrec_hip_session_get_implicit_features", "cmfrec_hip_session_set_sideinfo_sparse", "cmfrec_hip_session_set_sideinfo_sparse_zeros", "cmfrec_hip_side_zeros_products", "cmfrec_hip_session_update", "cmfrec_hip_session_iterate",
@@ -173,6 +186,11 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_newrows_create.restype = C.c_void_p
     lib.cmfrec_hip_newrows_create.argtypes = [C.POINTER(nrm), C.c_int]
     lib.cmfrec_hip_newrows_factors.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p]
+    nrx = newrows_model_ex_mirror(dtype)
+    lib.cmfrec_hip_newrows_naz_launch_waves.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.cmfrec_hip_newrows_create_ex.restype = C.c_void_p
+    lib.cmfrec_hip_newrows_create_ex.argtypes = [C.POINTER(nrx), C.c_int]
+    lib.cmfrec_hip_factors_multiple_naz.argtypes = [C.POINTER(nrx), C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p]
     lib.cmfrec_hip_newrows_topN.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cmfrec_hip_newrows_topN_candidates.argtypes = [C.c_void_p, C.POINTER(NewRowsBatch), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -227,6 +245,9 @@ def load(dtype=np.float64):
     if lib.cmfrec_hip_sizeof_model() != C.sizeof(mirror):
         raise RuntimeError("cmfrec_amd: the ctypes mirror of cmfrec_hip_model (%d bytes) does not match the library (%d)"
                            % (C.sizeof(mirror), lib.cmfrec_hip_sizeof_model()))
+    if lib.cmfrec_hip_sizeof_newrows_model_ex() != C.sizeof(nrx):
+        raise RuntimeError("cmfrec_amd: the ctypes mirror of cmfrec_hip_newrows_model_ex (%d bytes) does not match the library (%d)"
+                           % (C.sizeof(nrx), lib.cmfrec_hip_sizeof_newrows_model_ex()))
     if lib.cmfrec_hip_sizeof_newrows_model() != C.sizeof(nrm):
         raise RuntimeError("cmfrec_amd: the ctypes mirror of cmfrec_hip_newrows_model (%d bytes) does not match the library (%d)"
                            % (C.sizeof(nrm), lib.cmfrec_hip_sizeof_newrows_model()))

@@ -74,6 +74,7 @@ struct Switches {
     int cg_teams = 0;               // CMFREC_HIP_CG_TEAMS: at most that many teams (rounded up to whole workgroups) in a launch of the dynamically scheduled CG row kernels, so that a small problem gives a team several rows (test hook; 0: by occupancy)
     int newrows_block_rows = 0;     // CMFREC_HIP_NEWROWS_BLOCK_ROWS: rows per device block of a dense batch of new rows (test hook; 0: by the 1 GB budget)
     int predict_block = 0;          // CMFREC_HIP_PREDICT_BLOCK: pairs per upload / launch / download block of the pair scorer (test hook; 0: 2^24)
+    int naz_waves = 0;              // CMFREC_HIP_NAZ_WAVES: at most that many wavefronts (rounded up to whole workgroups) in a launch of the NA_as_zero right-hand-side kernel of new rows (newrows_naz_kernels.hpp), so that one wavefront takes many rows in turn (test hook; 0: by occupancy)
     void reload()
     {
         auto str = [](const char *n) -> const char * { const char *v = getenv(n); return (v != nullptr && v[0] != 0) ? v : nullptr; };
@@ -104,6 +105,7 @@ struct Switches {
         cg_teams = num("CMFREC_HIP_CG_TEAMS", 0);
         newrows_block_rows = num("CMFREC_HIP_NEWROWS_BLOCK_ROWS", 0);
         predict_block = num("CMFREC_HIP_PREDICT_BLOCK", 0);
+        naz_waves = num("CMFREC_HIP_NAZ_WAVES", 0);
     }
 };
 inline Switches &switches_mut() { static Switches sw; static bool first = (sw.reload(), true); (void)first; return sw; }

@@ -1382,6 +1382,13 @@ static int unsupported_multiple(const char *what)
     return 2;
 }
 
+// the refusals of the missing-as-zero models of the new-rows handle
+static int unsupported_naz(const char *what)
+{
+    cmfhip::g_last_error = std::string("cmfrec_hip_newrows: ") + what + " is not supported";
+    return 2;
+}
+
 }  // extern "C"
 
 // ---- the handle: a model of new rows resident on the device (cmfrec_hip_newrows_*, include/cmfrec_hip.h) ---------------------
@@ -1389,6 +1396,7 @@ static int unsupported_multiple(const char *what)
 // their batch half (factors / topN); the drop-in functions themselves are create, factors, destroy.
 struct cmfrec_hip_newrows {
     cmfrec_hip_newrows_model mdl;              // the scalars; its pointers are cleared after create
+    bool naz_X = false, naz_U = false;         // the missing-as-zero options (cmfrec_hip_newrows_create_ex)
     cmfhip::NewRowsState *state = nullptr;
     cmfrec_hip_ranker *ranker = nullptr;       // made by the first topN call
     cmfhip::PairScorer *scorer = nullptr;      // made by the first predict call
@@ -1409,12 +1417,13 @@ namespace {
 
 // Model half of factors_collective_explicit_multiple (factors_collective_explicit_single, collective.c:10611-10630;
 // collective_factors_warm, :3694-3713) and of factors_collective_implicit_multiple (collective_factors_warm_implicit, :4000-4004).
-int newrows_model_side(const cmfrec_hip_newrows_model &m, cmfhip::NewRowsModelArgs &M, int_t *n_sparse)
+int newrows_model_side(const cmfrec_hip_newrows_model &m, cmfhip::NewRowsModelArgs &M, int_t *n_sparse, bool naz_X = false, bool naz_U = false)
 {
     const bool side = m.C != nullptr && m.p > 0;
     M.B = m.B; M.C = side ? m.C : nullptr; M.p = side ? m.p : 0; M.U_colmeans = side ? m.U_colmeans : nullptr;
     M.k = m.k; M.k_user = m.k_user; M.k_item = m.k_item; M.k_main = m.k_main;
     M.nonneg = m.nonneg != 0;
+    if (m.implicit && (naz_X || naz_U)) return unsupported_naz("NA_as_zero of the implicit model");
     if (m.implicit) {
         // L1 penalty: rows with observations keep the l1_lam of the call (collective_factors_warm_implicit rescales lam and w_user by
         // w_main only, :4000-4004).
@@ -1436,6 +1445,12 @@ int newrows_model_side(const cmfrec_hip_newrows_model &m, cmfhip::NewRowsModelAr
     }
     const bool Bi = m.add_implicit_features != 0;
     if (Bi && !m.Bi) return unsupported_multiple("add_implicit_features without Bi");
+    // missing-as-zero models: what the handle does not solve under either option
+    const bool naz = naz_X || naz_U;
+    if (naz && m.nonneg) return unsupported_naz("NA_as_zero together with non-negativity");
+    if (naz && (m.l1_lam != 0 || m.l1_lam_unique != nullptr)) return unsupported_naz("NA_as_zero together with an L1 penalty");
+    if (naz && Bi) return unsupported_naz("NA_as_zero together with implicit features");
+    if (naz && m.scale_bias_const) return unsupported_naz("NA_as_zero together with scale_bias_const");
     const bool ub = m.user_bias != 0;
     // factors_collective_explicit_single, collective.c:10611-10630
     real_t lam = m.lam, l1_lam = m.l1_lam, lam_bias = m.lam, l1_lam_bias = m.l1_lam, w_user = m.w_user, w_implicit = m.w_implicit;
@@ -1461,6 +1476,7 @@ int newrows_model_side(const cmfrec_hip_newrows_model &m, cmfhip::NewRowsModelAr
     *n_sparse = (more && !Bi) ? m.n_max : m.n;
     M.n = more ? m.n_max : m.n;
     M.biasB = m.biasB; M.user_bias = ub;
+    M.NA_as_zero_X = naz_X; M.NA_as_zero_U = naz_U; M.glob_mean = m.glob_mean; M.n_x = m.n;
     M.lam = lam; M.lam_bias = lam_bias; M.lam_x = lam; M.w_user = w_user;
     M.scale_lam = m.scale_lam != 0; M.scale_lam_sideinfo = m.scale_lam_sideinfo != 0; M.scale_bias_const = scale_bias_const;
     M.l1_lam = l1_lam; M.l1_lam_bias = l1_lam_bias;
@@ -1494,7 +1510,9 @@ int newrows_batch_side(const cmfrec_hip_newrows &h, const cmfrec_hip_newrows_bat
     if (U == nullptr && !spU) m_u = 0;
     if (std::max(mx, m_u) <= 0) return 1;                                       // rows out: max(m, m_u), collective.c:11210
     if (mx <= 0) { Xfull = nullptr; weight = nullptr; }
-    if (U) for (size_t e = 0; e < (size_t)m_u * (size_t)m.p; e++) if (std::isnan(U[e])) return unsupported_multiple("missing values in U");
+    if (U) for (size_t e = 0; e < (size_t)m_u * (size_t)m.p; e++) if (std::isnan(U[e]))
+        return (h.naz_X || h.naz_U) ? unsupported_naz("NA_as_zero together with missing values in a dense U")
+                                                  : unsupported_multiple("missing values in U");
     const bool side = U != nullptr || spU;
     if (!m.implicit) {
         // The block solver's weighted right-hand side of sparse X is the NA_as_zero one, w x - (w - 1)(glob_mean + biasB), applied
@@ -1523,7 +1541,8 @@ int newrows_batch_side(const cmfrec_hip_newrows &h, const cmfrec_hip_newrows_bat
             if (m.alpha != 1) for (size_t e = 0; e < nz; e++) vals_tmp[e] *= m.alpha;                      // :4006-4016
             vals = vals_tmp.data();
         }
-    } else if (m.glob_mean != 0 && nz) {
+    } else if (m.glob_mean != 0 && nz && !h.naz_X) {
+        // (under NA_as_zero_X the mean is part of every cell's target: it enters through the constant BtXbias, session.hip)
         vals_tmp.assign(vals, vals + nz);
         for (size_t e = 0; e < nz; e++) vals_tmp[e] -= m.glob_mean;
         vals = vals_tmp.data();
@@ -1571,7 +1590,13 @@ extern "C" {
 
 int cmfrec_hip_sizeof_newrows_model(void) { return (int)sizeof(cmfrec_hip_newrows_model); }
 
-cmfrec_hip_newrows *cmfrec_hip_newrows_create(const cmfrec_hip_newrows_model *model, int device)
+int cmfrec_hip_sizeof_newrows_model_ex(void) { return (int)sizeof(cmfrec_hip_newrows_model_ex); }
+
+}  // extern "C"
+
+namespace {
+
+cmfrec_hip_newrows *newrows_create(const cmfrec_hip_newrows_model *model, bool naz_X, bool naz_U, int device)
 {
     cmfrec_hip_newrows *h = nullptr;
     const int rc = cmfhip::guarded([&]() {
@@ -1581,9 +1606,10 @@ cmfrec_hip_newrows *cmfrec_hip_newrows_create(const cmfrec_hip_newrows_model *mo
         }
         cmfhip::NewRowsModelArgs M;
         int_t n_sparse = 0;
-        if (int mrc = newrows_model_side(*model, M, &n_sparse)) return mrc;
+        if (int mrc = newrows_model_side(*model, M, &n_sparse, naz_X, naz_U)) return mrc;
         h = new cmfrec_hip_newrows();
         h->mdl = *model;
+        h->naz_X = naz_X; h->naz_U = naz_U;
         h->n_sparse = n_sparse;
         h->has_C = M.C != nullptr; h->has_biasB = M.biasB != nullptr; h->has_Bi = M.Bi != nullptr; h->has_means = M.U_colmeans != nullptr;
         int src = 0;
@@ -1599,6 +1625,20 @@ cmfrec_hip_newrows *cmfrec_hip_newrows_create(const cmfrec_hip_newrows_model *mo
         return nullptr;
     }
     return h;
+}
+
+}  // namespace
+
+extern "C" {
+
+cmfrec_hip_newrows *cmfrec_hip_newrows_create(const cmfrec_hip_newrows_model *model, int device)
+{
+    return newrows_create(model, false, false, device);
+}
+
+cmfrec_hip_newrows *cmfrec_hip_newrows_create_ex(const cmfrec_hip_newrows_model_ex *model, int device)
+{
+    return newrows_create(model ? &model->base : nullptr, model && model->NA_as_zero_X != 0, model && model->NA_as_zero_U != 0, device);
 }
 
 int cmfrec_hip_newrows_factors(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, real_t *A, real_t *biasA)
@@ -1765,6 +1805,32 @@ int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double
 void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h)
 {
     delete h;
+}
+
+int cmfrec_hip_newrows_naz_launch_waves(cmfrec_hip_newrows *h, int *waves)
+{
+    if (h == nullptr || h->state == nullptr || waves == nullptr) {
+        cmfhip::g_last_error = "cmfrec_hip_newrows_naz_launch_waves: invalid arguments";
+        return 2;
+    }
+    *waves = cmfhip::newrows_state_naz_waves(h->state);
+    return 0;
+}
+
+int cmfrec_hip_factors_multiple_naz(const cmfrec_hip_newrows_model_ex *model, const cmfrec_hip_newrows_batch *batch, real_t *A, real_t *biasA)
+{
+    if (model == nullptr || batch == nullptr) {
+        cmfhip::g_last_error = "cmfrec_hip_factors_multiple_naz: invalid arguments";
+        return 2;
+    }
+    cmfrec_hip_newrows *h = cmfrec_hip_newrows_create_ex(model, -1);
+    if (h == nullptr) {
+        const int ec = cmfrec_hip_last_error_code();
+        return ec > 3 ? 1 : (ec ? ec : 1);
+    }
+    const int rc = cmfrec_hip_newrows_factors(h, batch, A, biasA);
+    cmfrec_hip_newrows_destroy(h);
+    return rc;
 }
 
 }  // extern "C"

@@ -30,6 +30,11 @@ struct NewRowsModelArgs {
     const real_t *BiTBi_pre = nullptr;
     const real_t *TransBtBinvBt_pre = nullptr; // [n_TB, k + k_main (+ 1)]
     int_t n_TB = 0;
+    // missing-as-zero models: an absent entry of a sparse X / of a sparse U is a zero.  glob_mean and
+    // n_x (the items that carry a bias: the rest of B's rows count with the mean only) enter the constant of the right-hand sides.
+    bool NA_as_zero_X = false, NA_as_zero_U = false;
+    real_t glob_mean = 0;
+    int_t n_x = 0;
 };
 
 // The batch side: everything that depends on X, U, the weights or Xfull.
@@ -70,6 +75,15 @@ int newrows_state_solve_ms(NewRowsState *s, double *ms);
 // HIP-event time of the fill kernel over the blocks of the last impute call.
 int newrows_state_impute(NewRowsState *s, const NewRowsBatchArgs &bt, real_t *Xout, real_t *A, real_t *biasA, bool *solved);
 double newrows_state_fill_ms(const NewRowsState *s);
+// the wavefronts of the last launch of the missing-as-zero right-hand-side kernel (0: none yet; what CMFREC_HIP_NAZ_WAVES caps)
+int newrows_state_naz_waves(const NewRowsState *s);
+
+// newrows_naz_tu.hip: the kernels of newrows_naz_kernels.hpp behind plain functions (the one unit that instantiates them)
+template <typename T> struct NazRhsParams;
+int naz_launch_rhs(hipStream_t st, int num_cus, const NazRhsParams<real_t> &P, int max_waves);     // the wavefronts of the task launch
+void naz_launch_pad_rows(hipStream_t st, const real_t *src, size_t lds, int off, int cols, real_t scale, int ones_col, real_t *dst, size_t ldd,
+                         size_t rows);
+void naz_launch_weight_corrections(hipStream_t st, const real_t *w, size_t nnz, real_t *g, real_t *z);
 
 // topn_tu.hip: a ranker over items that are on the device already (packed copy, ldb = topnw_kp(k)), and a ranking call on
 // device factors with device exclusion lists -- cmfrec_hip_ranker_topN without its uploads.  The caller has synchronised the

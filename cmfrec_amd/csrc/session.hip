@@ -13,6 +13,7 @@
 #include "side_zeros_kernels.hpp"
 #include "impute_kernels.hpp"
 #include "newrows.hpp"
+#include "newrows_naz_kernels.hpp"
 #include <dlfcn.h>
 #include <functional>
 #include <limits>
@@ -2831,6 +2832,26 @@ struct NewRowsState {
     bool xb_resident = false;
     hipEvent_t ev2 = nullptr, ev3 = nullptr;
     double fill_ms = 0;
+    // missing-as-zero models (newrows_run_naz): the padded operand copies of the right-hand-side kernel, B^T B with the ones column
+    // and no diagonal, the constant rows [CtUbias | BtXbias] of the rows with / without side information -- built by create -- and
+    // the shared matrices with their inverses, each built by the first batch that needs it
+    struct NazInverse {
+        DevBuf<real_t> M, R, Linv, Minv;
+        int k = 0;
+        bool built = false;
+    };
+    bool naz = false, naz_has_cst = false;
+    int kx = 0;
+    size_t ldBx = 0, ldCw = 0;
+    DevBuf<real_t> dBx, dCw, dBtB, dc_side, dc_plain, dc_u;   // [kt] each: [CtUbias | BtXbias], [0 | BtXbias], [CtUbias | 0]
+    int naz_last_waves = 0;
+    NazInverse inv_side, inv_plain, inv_cold;
+    real_t inv_side_mult = 0;                  // the lambda multiplier inv_side was built with (dense U under scale_lam_sideinfo: n + p)
+    DevBuf<real_t> drhs, dtmp, dres, dg, dz, dpart, dUC, dcold2;
+    DevBuf<NazTask> dtasks;
+    DevBuf<NazFinishRow> dfin;
+    std::vector<NazTask> tasks;
+    std::vector<NazFinishRow> fin;
     ~NewRowsState()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -2856,6 +2877,265 @@ static int newrows_form_check(bool implicit, bool Bi, const NewRowsBatchArgs &bt
     if (implicit && (bt.weight || bt.Xfull || bt.weight_full || Bi)) return bad("observation weights, dense X and implicit features belong to the explicit model");
     if (bt.Xfull && (bt.nnz > 0 || bt.Xcsr_p)) return bad("X given both as a dense and as a sparse matrix");
     if ((bt.weight_full && !bt.Xfull) || (bt.weight && bt.Xfull)) return bad("the weights must have the form of X (weight with sparse X, weight_full with Xfull)");
+    return 0;
+}
+
+// ---- missing-as-zero models: NA_as_zero_X / NA_as_zero_U of a batch of new rows -----------------------
+// Per row, with every one of the n cells counted (an absent one a zero of weight 1, its target -glob_mean - biasB_j) and an
+// absent attribute of a sparse U a zero minus its column mean:
+//     M   = blockdiag(0, B~^T B~) + w_user C^T C + diag(lam mult)          B~ = [B | 1] with a user bias
+//     rhs = [CtUbias | BtXbias] + sum_X coef_j B~_j (+) sum_U u_c w_user C_c,   BtXbias = -sum_all (glob_mean + biasB_j) B~_j,
+//     CtUbias = -w_user C^T colmeans
+// Without observation weights M is the same for every row: the batch is newrows_naz_kernels.hpp's gather-sum and one product
+// with the inverse the model keeps.  With weights a row adds sum_obs (w_j - 1) b_j b_j^T: the row Cholesky kernel on the base B~^T B~.
+// The model side, once per handle: the padded copies, B~^T B~, the constants.
+static void newrows_naz_model_side(NewRowsState &S)
+{
+    const NewRowsModelArgs &M = S.M;
+    DeviceInfo &dev = S.dev;
+    hipStream_t st = dev.stream;
+    const int ub = S.ub, kk = S.kk, kc = S.kc, kt = S.kt, n = M.n, kx = kk + ub;
+    S.naz = true; S.kx = kx;
+    S.ldBx = naz_padded_ld<real_t>(kx);
+    S.dBx.alloc((size_t)n * S.ldBx);
+    naz_launch_pad_rows(st, S.dB.ptr, S.ldB, M.k_item, kk, (real_t)1, ub ? kk : -1, S.dBx.ptr, S.ldBx, (size_t)n);
+    if (S.have_C) {
+        S.ldCw = naz_padded_ld<real_t>(kc);
+        S.dCw.alloc((size_t)M.p * S.ldCw);
+        naz_launch_pad_rows(st, S.dC.ptr, (size_t)kc, 0, kc, M.w_user, -1, S.dCw.ptr, S.ldCw, (size_t)M.p);
+    }
+    S.dc_side.alloc((size_t)kt); S.dc_plain.alloc((size_t)kt); S.dc_u.alloc((size_t)kt);
+    HIP_CHECK(hipMemsetAsync(S.dc_side.ptr, 0, (size_t)kt * sizeof(real_t), st));
+    HIP_CHECK(hipMemsetAsync(S.dc_u.ptr, 0, (size_t)kt * sizeof(real_t), st));
+    HIP_CHECK(hipMemsetAsync(S.dc_plain.ptr, 0, (size_t)kt * sizeof(real_t), st));
+    if (M.NA_as_zero_X) {
+        const real_t *Bx = S.dB.ptr + M.k_item;
+        S.dBtB.alloc((size_t)kx * kx);
+        launch_gram(dev, S.gws, Bx, S.ldB, n, kx, S.dBtB.ptr, (real_t)1, (real_t)0);
+        // BtXbias: the items that carry a bias, then the items beyond them with the mean alone (include_all_X)
+        S.naz_has_cst = M.glob_mean != (real_t)0 || S.dbias.ptr != nullptr;
+        if (S.naz_has_cst) {
+            const int n_b = std::max(0, std::min<int>(M.n_x > 0 ? M.n_x : n, n));
+            const int nb1 = (n_b + COLSUM_ROWS - 1) / COLSUM_ROWS, nb2 = (n - n_b + COLSUM_ROWS - 1) / COLSUM_ROWS;
+            DevBuf<real_t> part;
+            part.alloc((size_t)std::max(nb1 + nb2, 1) * kx);
+            if (nb1 > 0)
+                hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb1), dim3(256), 0, st, Bx, S.ldB, n_b, kx, S.dbias.ptr, M.glob_mean,
+                                   part.ptr);
+            if (nb2 > 0)
+                hipLaunchKernelGGL(weighted_colsum_partial_kernel<real_t>, dim3(nb2), dim3(256), 0, st, Bx + (size_t)n_b * S.ldB, S.ldB, n - n_b, kx,
+                                   (const real_t *)nullptr, M.glob_mean, part.ptr + (size_t)nb1 * kx);
+            hipLaunchKernelGGL(colsum_finish_kernel<real_t>, grid1d(kx), dim3(256), 0, st, part.ptr, nb1 + nb2, kx, (real_t)-1, S.dc_plain.ptr + M.k_user);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(S.dc_side.ptr + M.k_user, S.dc_plain.ptr + M.k_user, (size_t)kx * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));   // part goes away
+        }
+    }
+    if (M.NA_as_zero_U && S.have_C && S.have_means) {
+        // CtUbias = -w_user C^T colmeans, added onto the first k_user + k columns of the rows with side information
+        DevBuf<real_t> ctu;
+        ctu.alloc((size_t)kc);
+        launch_gemm<false>(dev, 1, kc, M.p, -M.w_user, S.dmeans.ptr, (size_t)M.p, S.dC.ptr, (size_t)kc, ctu.ptr, (size_t)kc);
+        hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)kc), dim3(256), 0, st, S.dc_side.ptr, (size_t)kt, (size_t)1, kc, ctu.ptr);
+        hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)kc), dim3(256), 0, st, S.dc_u.ptr, (size_t)kt, (size_t)1, kc, ctu.ptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+}
+
+// I.M [k, k] holds a symmetric positive definite matrix: its inverse through the library's own potrf / trtri, kept in I.Minv
+static void newrows_naz_invert(DeviceInfo &dev, NewRowsState::NazInverse &I, int k)
+{
+    hipStream_t st = dev.stream;
+    const size_t kk2 = (size_t)k * k;
+    I.R.alloc(kk2); I.Linv.alloc(kk2); I.Minv.alloc(kk2);
+    HIP_CHECK(hipMemcpyAsync(I.R.ptr, I.M.ptr, kk2 * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(potrf_upper_kernel<real_t>, dim3(1), dim3(256), 0, st, I.R.ptr, k);
+    HIP_CHECK(hipGetLastError());
+    launch_trtri(dev, I.R.ptr, k, I.Linv.ptr);
+    launch_gemm<true>(dev, k, k, k, (real_t)1, I.Linv.ptr, (size_t)k, I.Linv.ptr, (size_t)k, I.Minv.ptr, (size_t)k);
+    I.k = k; I.built = true;
+}
+
+// out[rows, k] (ld = ldo) = rhs[rows, k] M^-1: the product with the explicit inverse and one step of refinement with the matrix
+// itself, x1 = x0 + (b - x0 M) M^-1, which brings the error of the product (cond(M) eps) back to that of two triangular solves
+static void newrows_naz_apply(NewRowsState &S, const NewRowsState::NazInverse &I, const real_t *rhs, size_t ldr, int rows, real_t *out, size_t ldo)
+{
+    if (rows <= 0) return;
+    DeviceInfo &dev = S.dev;
+    const int k = I.k;
+    S.dtmp.alloc_at_least((size_t)rows * k); S.dres.alloc_at_least((size_t)rows * k);
+    launch_gemm<false>(dev, rows, k, k, (real_t)1, rhs, ldr, I.Minv.ptr, (size_t)k, out, ldo);
+    launch_gemm<false>(dev, rows, k, k, (real_t)1, out, ldo, I.M.ptr, (size_t)k, S.dres.ptr, (size_t)k);
+    hipLaunchKernelGGL(residual_rows_kernel<real_t>, grid1d((size_t)rows * k), dim3(256), 0, dev.stream, S.dres.ptr, (size_t)k, rhs, ldr, (size_t)rows, k);
+    launch_gemm<false>(dev, rows, k, k, (real_t)1, S.dres.ptr, (size_t)k, I.Minv.ptr, (size_t)k, S.dtmp.ptr, (size_t)k);
+    hipLaunchKernelGGL(add_rows_kernel<real_t>, grid1d((size_t)rows * k), dim3(256), 0, dev.stream, out, ldo, S.dtmp.ptr, (size_t)k, (size_t)rows, k);
+    HIP_CHECK(hipGetLastError());
+}
+
+// the task list of the right-hand-side kernel from the rows' lengths (host), uploaded into S.dtasks / S.dfin; returns the slots
+static size_t newrows_naz_tasks(NewRowsState &S, int rows, const std::vector<size_t> *lenX, const std::vector<size_t> *lenU, int rows_u)
+{
+    S.tasks.clear(); S.fin.clear();
+    size_t slots = 0;
+    for (int r = 0; r < rows; r++) {
+        const int nx = lenX ? (int)(((*lenX)[r] + NAZ_SEG - 1) / NAZ_SEG) : 0;
+        const int nu = (lenU && r < rows_u) ? (int)(((*lenU)[r] + NAZ_SEG - 1) / NAZ_SEG) : 0;
+        const int tot = nx + nu;
+        if (tot == 0) continue;
+        const bool direct = tot == 1;
+        const int slot0 = (int)slots;
+        for (int sg = 0; sg < nx; sg++) S.tasks.push_back(NazTask{r, direct ? 2 : 0, sg, slot0 + sg});
+        for (int sg = 0; sg < nu; sg++) S.tasks.push_back(NazTask{r, 1 | (direct ? 2 : 0), sg, slot0 + nx + sg});
+        if (!direct) { S.fin.push_back(NazFinishRow{r, slot0, nx, nu}); slots += (size_t)tot; }
+    }
+    hipStream_t st = S.dev.stream;
+    if (!S.tasks.empty()) S.dtasks.upload(S.tasks.data(), S.tasks.size(), st);
+    if (!S.fin.empty()) S.dfin.upload(S.fin.data(), S.fin.size(), st);
+    return slots;
+}
+
+// The batch side.  Xs / Us: the shards newrows_state_run has built (Us: sparse U, or empty); lenX / lenU: the rows' lengths on the
+// host; m_u / p: as newrows_state_run has reduced them (0 without side information in the batch); dense: dU holds the centred
+// dense U.  naz_x: NA_as_zero_X applies to this batch (a sparse X).  Leaves the factors in S.dA.
+static int newrows_run_naz(NewRowsState &S, SparseShard &Xs, SparseShard &Us, const std::vector<size_t> &lenX, const std::vector<size_t> &lenU,
+                           int m_max, int m_u, int p, bool spU, bool naz_x)
+{
+    const NewRowsModelArgs &M = S.M;
+    auto bad = [](const char *what) { g_last_error = std::string("cmfrec_hip_factors_multiple: ") + what; return 2; };
+    DeviceInfo &dev = S.dev;
+    hipStream_t st = dev.stream;
+    const int ub = S.ub, kc = S.kc, kt = S.kt, kx = S.kx, k_user = M.k_user, n = M.n;
+    const size_t ldA = S.ldA, ldB = S.ldB;
+    const bool scaled = M.scale_lam || M.scale_lam_sideinfo;
+    const real_t lam = M.lam, lam_bias = M.lam_bias;
+    const int max_waves = switches().naz_waves;
+    const bool side = p > 0 && m_u > 0;
+    NazRhsParams<real_t> P;
+    P.Bx = S.dBx.ptr; P.ldbx = S.ldBx; P.kx = kx; P.koff_x = k_user;
+    P.biasB = S.dbias.ptr; P.glob_mean = M.glob_mean;
+    // The constant of a row: BtXbias belongs to a sparse X under NA_as_zero_X, CtUbias to a sparse U under NA_as_zero_U -- a dense
+    // U is centred before it is multiplied and knows no absent entry, and an ordinary X (or a dense Xfull) has no constant
+    const bool ctu = spU && M.NA_as_zero_U;
+    P.c_side = naz_x ? (ctu ? S.dc_side.ptr : S.dc_plain.ptr) : (ctu ? S.dc_u.ptr : nullptr);
+    P.c_plain = naz_x ? S.dc_plain.ptr : nullptr;
+    P.rows_side = side ? std::min(m_u, m_max) : 0;
+    P.n_bias = (int)(M.n_x > 0 ? M.n_x : M.n);
+    P.kt = kt; P.rows = m_max;
+    P.gwidth = std::max(kx, S.have_C ? kc : 0);
+    if (spU) { P.up = Us.p.ptr; P.ui = Us.i.ptr; P.uv = Us.v.ptr; P.Cw = S.dCw.ptr; P.ldcw = S.ldCw; P.kc = kc; }
+    auto run_rhs = [&](bool with_x, real_t *rhs, size_t ld) {
+        if (with_x) { P.xp = Xs.p.ptr; P.xi = Xs.i.ptr; P.xv = Xs.v.ptr; P.xw = Xs.weighted() ? Xs.w.ptr : nullptr; }
+        const size_t slots = newrows_naz_tasks(S, m_max, with_x ? &lenX : nullptr, spU ? &lenU : nullptr, m_u);
+        P.ldp = (size_t)std::max(kx, kc);
+        S.dpart.alloc_at_least(std::max<size_t>(slots, 1) * P.ldp);
+        P.partial = S.dpart.ptr;
+        P.tasks = S.dtasks.ptr; P.ntasks = (int)S.tasks.size(); P.fin = S.dfin.ptr; P.nfin = (int)S.fin.size();
+        P.rhs = rhs; P.ld = ld;
+        poison_lds(st, dev.num_cus);              // test hook (the kernel has no LDS: nothing may depend on it)
+        S.naz_last_waves = naz_launch_rhs(st, dev.num_cus, P, max_waves);
+    };
+    auto ensure_CtC = [&]() {
+        if (S.ctc_built) return;
+        S.dCtC.alloc((size_t)kc * kc);
+        launch_gram(dev, S.gws, S.dC.ptr, (size_t)kc, p, kc, S.dCtC.ptr, M.w_user, (real_t)0);
+        S.ctc_built = true;
+    };
+    if (!naz_x) {
+        // NA_as_zero_U with an ordinary X: the rows with entries through the collective row solver with the shared w_user C^T C as
+        // its side block and the right-hand sides of the side block from the kernel's second source + CtUbias; the rows without
+        // any entry ("cold") share w_user C^T C + lam I
+        ensure_CtC();
+        run_rhs(false, S.dA.ptr, ldA);
+        if (!S.inv_cold.built) {
+            S.inv_cold.M.alloc((size_t)kc * kc);
+            HIP_CHECK(hipMemcpyAsync(S.inv_cold.M.ptr, S.dCtC.ptr, (size_t)kc * kc * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(add_diag_kernel<real_t>, dim3((kc + 255) / 256), dim3(256), 0, st, S.inv_cold.M.ptr, kc, 0, kc, lam);
+            newrows_naz_invert(dev, S.inv_cold, kc);
+        }
+        S.dcold.alloc_at_least((size_t)m_u * kc); S.dcold2.alloc_at_least((size_t)m_u * kc);
+        HIP_CHECK(hipMemcpy2DAsync(S.dcold.ptr, (size_t)kc * sizeof(real_t), S.dA.ptr, ldA * sizeof(real_t), (size_t)kc * sizeof(real_t), (size_t)m_u,
+                                   hipMemcpyDeviceToDevice, st));
+        newrows_naz_apply(S, S.inv_cold, S.dcold.ptr, (size_t)kc, m_u, S.dcold2.ptr, (size_t)kc);
+        CholCall c{S.dA.ptr, ldA, S.dB.ptr + M.k_item, ldB, kt, k_user, S.dbias.ptr, S.dCtC.ptr, kc, m_u, p, lam, lam_bias, M.scale_lam, false,
+                   M.scale_bias_const, CHOL_COLLECTIVE};
+        if (int rc = launch_chol(dev, c, &Xs)) return rc;
+        hipLaunchKernelGGL(cold_select_kernel<real_t>, dim3(m_u), dim3(64), 0, st, S.dA.ptr, ldA, kt, kc, S.dcold2.ptr, Xs.p.ptr, m_u);
+        HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    if (Xs.weighted()) {
+        // observation weights, no side information: every row's matrix is B~^T B~ + sum_obs (w_j - 1) b_j b_j^T + lam mult, mult =
+        // sum of the row's weights + its absent cells.  The right-hand sides are the kernel's (its per-entry coefficients); the row
+        // Cholesky kernel adds the corrections onto the base matrix and solves in place.
+        if (side) return bad("NA_as_zero_X with observation weights together with side information is not supported");
+        run_rhs(true, S.dA.ptr, ldA);
+        S.dg.alloc_at_least(Xs.nnz); S.dz.alloc_at_least(Xs.nnz);
+        naz_launch_weight_corrections(st, Xs.w.ptr, Xs.nnz, S.dg.ptr, S.dz.ptr);
+        Xs.wsum_naz.alloc_at_least((size_t)m_max);
+        hipLaunchKernelGGL(naz_wsum_kernel<real_t>, grid1d((size_t)m_max), dim3(256), 0, st, Xs.p.ptr, Xs.w.ptr, m_max, n, Xs.wsum_naz.ptr);
+        HIP_CHECK(hipGetLastError());
+        CholCall c{S.dA.ptr + k_user, ldA, S.dB.ptr + M.k_item, ldB, kx, 0, nullptr, S.dBtB.ptr, 0, 0, 0, lam, lam_bias, scaled, false,
+                   M.scale_bias_const, CHOL_NAZ_W};
+        c.values_override = S.dz.ptr; c.weights_override = S.dg.ptr; c.rhs_prefilled_all = true; c.all_rows = S.naz_has_cst;
+        if (int rc = launch_chol(dev, c, &Xs)) return rc;
+        if (scaled && !S.naz_has_cst) {
+            hipLaunchKernelGGL(zero_weightless_rows_kernel<real_t>, dim3(m_max), dim3(64), 0, st, Xs.p.ptr, Xs.wsum_naz.ptr, m_max, 0,
+                               std::numeric_limits<real_t>::epsilon(), S.dA.ptr, ldA, kt);
+            HIP_CHECK(hipGetLastError());
+        }
+        return 0;
+    }
+    // the shared-matrix route
+    if (side && !spU && m_u != m_max)
+        return bad("NA_as_zero_X with dense U: side information on exactly the rows of the batch (m_u == m)");
+    if (side && spU && !M.NA_as_zero_U)
+        return bad("NA_as_zero_X with a sparse U whose absent entries are missing is not supported (NA_as_zero_U)");
+    const int rows_side = P.rows_side;
+    auto diag = [&](real_t *Gd, real_t mult, bool keep_last) {         // Gd [kx, kx] = B~^T B~ + lam mult I, the last unknown's own lambda
+        HIP_CHECK(hipMemcpyAsync(Gd, S.dBtB.ptr, (size_t)kx * kx * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(add_diag_kernel<real_t>, dim3((kx + 255) / 256), dim3(256), 0, st, Gd, kx, 0, kx, lam * mult);
+        const real_t last = (ub ? lam_bias : lam) * (keep_last ? (real_t)1 : mult);
+        if (last != lam * mult) hipLaunchKernelGGL(add_diag_kernel<real_t>, dim3(1), dim3(64), 0, st, Gd, kx, kx - 1, kx, last - lam * mult);
+    };
+    const real_t mult_side = (M.scale_lam_sideinfo && !spU) ? (real_t)(n + p) : (scaled ? (real_t)n : (real_t)1);
+    if (rows_side > 0 && (!S.inv_side.built || S.inv_side_mult != mult_side)) {
+        ensure_CtC();
+        const real_t mult = mult_side;
+        DevBuf<real_t> Gd;
+        Gd.alloc((size_t)kx * kx);
+        diag(Gd.ptr, mult, false);
+        S.inv_side.M.alloc((size_t)kt * kt);
+        hipLaunchKernelGGL(naz_block_matrix_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, Gd.ptr, kx, S.dCtC.ptr, kc, k_user, lam * mult,
+                           S.inv_side.M.ptr);
+        HIP_CHECK(hipGetLastError());
+        newrows_naz_invert(dev, S.inv_side, kt);
+        S.inv_side_mult = mult_side;
+        HIP_CHECK(hipStreamSynchronize(st));       // Gd goes away
+    }
+    if (rows_side < m_max && !S.inv_plain.built) {
+        const real_t mult = scaled ? (real_t)n : (real_t)1;
+        DevBuf<real_t> Gd;
+        Gd.alloc((size_t)kx * kx);
+        diag(Gd.ptr, mult, M.scale_bias_const);
+        S.inv_plain.M.alloc((size_t)kt * kt);
+        hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, st, Gd.ptr, kx, k_user, lam * mult, S.inv_plain.M.ptr);
+        HIP_CHECK(hipGetLastError());
+        newrows_naz_invert(dev, S.inv_plain, kt);
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    S.drhs.alloc_at_least((size_t)m_max * kt);
+    run_rhs(true, S.drhs.ptr, (size_t)kt);
+    if (side && !spU) {
+        // dense U (centred already) joins the right-hand sides as U (w_user C)
+        S.dUC.alloc_at_least((size_t)m_u * kc);
+        launch_gemm<false>(dev, m_u, kc, p, M.w_user, S.dU.ptr, (size_t)p, S.dC.ptr, (size_t)kc, S.dUC.ptr, (size_t)kc);
+        hipLaunchKernelGGL(add_cols_scaled_kernel<real_t>, grid1d((size_t)m_u * kc), dim3(256), 0, st, S.drhs.ptr, (size_t)kt, 0, S.dUC.ptr, kc, (real_t)1,
+                           (size_t)m_u);
+        HIP_CHECK(hipGetLastError());
+    }
+    newrows_naz_apply(S, S.inv_side, S.drhs.ptr, (size_t)kt, rows_side, S.dA.ptr, ldA);
+    newrows_naz_apply(S, S.inv_plain, S.drhs.ptr + (size_t)rows_side * kt, (size_t)kt, m_max - rows_side, S.dA.ptr + (size_t)rows_side * ldA, ldA);
     return 0;
 }
 
@@ -2929,6 +3209,11 @@ NewRowsState *newrows_state_create(const NewRowsModelArgs &M, int device, int *r
         }
     }
     if (M.TransBtBinvBt_pre && M.n_TB > 0) { S.have_TB = true; S.dTB.upload(M.TransBtBinvBt_pre, (size_t)M.n_TB * S.kT, st); }
+    if (M.NA_as_zero_X || M.NA_as_zero_U) {
+        if (M.implicit || M.Bi || M.nonneg || l1on) return bad("NA_as_zero belongs to the explicit model without implicit features, nonneg or an L1 penalty");
+        if (kt > (sizeof(real_t) == 8 ? 256 : 272)) return bad("NA_as_zero: at most 256 (double) / 272 (single precision) unknowns per row");
+        newrows_naz_model_side(S);
+    }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventCreate(&S.ev0));
     HIP_CHECK(hipEventCreate(&S.ev1));
@@ -3000,11 +3285,21 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
     if (!(p > 0 && (U || spU))) { p = 0; m_u = 0; }
     // index validation on the host, before anything reaches the device (the fit entry points do the same,
     // fit.hip): a row id outside [0, m_x) or an item id outside [0, n) would corrupt device memory silently
+    // (the missing-as-zero routes want the rows' lengths on the host for their task list: counted in the same pass)
+    std::vector<size_t> lenX, lenU;
+    const bool want_len = S.naz && ((M.NA_as_zero_X && !Xfull) || (M.NA_as_zero_U && spU));
+    if (want_len) { lenX.assign((size_t)m_max, 0); lenU.assign((size_t)m_max, 0); }
     if (Xcsr_p) {
         const size_t nz = Xcsr_p[m_x];
         for (int r = 0; r < m_x; r++) if (Xcsr_p[r] > Xcsr_p[r + 1]) return bad("Xcsr_p is not non-decreasing");
         if (nz > 0 && (!bt.Xcsr_i || !bt.Xcsr)) return bad("Xcsr_i / Xcsr missing");
         for (size_t e = 0; e < nz; e++) if (bt.Xcsr_i[e] < 0 || bt.Xcsr_i[e] >= n) return bad("item index of X outside [0, n)");
+        if (want_len) for (int r = 0; r < m_x; r++) lenX[r] = Xcsr_p[r + 1] - Xcsr_p[r];
+    } else if (want_len) {
+        for (size_t e = 0; e < nnz; e++) {
+            if (ixA[e] < 0 || ixA[e] >= m_x || ixB[e] < 0 || ixB[e] >= n) return bad("row / item index of X outside [0, m_x) x [0, n)");
+            lenX[ixA[e]]++;
+        }
     } else {
         for (size_t e = 0; e < nnz; e++)
             if (ixA[e] < 0 || ixA[e] >= m_x || ixB[e] < 0 || ixB[e] >= n) return bad("row / item index of X outside [0, m_x) x [0, n)");
@@ -3015,9 +3310,12 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
             for (int r = 0; r < m_u; r++) if (U_csr_p[r] > U_csr_p[r + 1]) return bad("U_csr_p is not non-decreasing");
             if (nz > 0 && (!bt.U_csr_i || !bt.U_csr)) return bad("U_csr_i / U_csr missing");
             for (size_t e = 0; e < nz; e++) if (bt.U_csr_i[e] < 0 || bt.U_csr_i[e] >= p) return bad("attribute index of U outside [0, p)");
+            if (want_len) for (int r = 0; r < m_u; r++) lenU[r] = U_csr_p[r + 1] - U_csr_p[r];
         } else {
-            for (size_t e = 0; e < bt.nnz_U; e++)
+            for (size_t e = 0; e < bt.nnz_U; e++) {
                 if (bt.U_row[e] < 0 || bt.U_row[e] >= m_u || bt.U_col[e] < 0 || bt.U_col[e] >= p) return bad("row / attribute index of U outside [0, m_u) x [0, p)");
+                if (want_len) lenU[bt.U_row[e]]++;
+            }
         }
     }
     DeviceScope scope(S.dev.device);
@@ -3131,7 +3429,12 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
     const real_t *opp = S.dB.ptr + M.k_item;
     const real_t *bias_sub = S.dbias.ptr;
     int rc = 0;
-    if (implicit) {
+    // missing-as-zero models: a sparse X under NA_as_zero_X, a sparse U under NA_as_zero_U (a dense Xfull ignores the first, as
+    // the reference does, collective.c:3621-3632; a dense U knows no absent entry)
+    const bool naz_x = S.naz && M.NA_as_zero_X && !Xfull, naz_u = S.naz && M.NA_as_zero_U && spU && m_u > 0;
+    if (naz_x || naz_u) {
+        rc = newrows_run_naz(S, Xs, Us, lenX, lenU, m_max, m_u, p, spU, naz_x);
+    } else if (implicit) {
         if (p == 0) {
             CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk, 0, nullptr, S.dG.ptr, 0, 0, 0, lam, lam, false, false, false,
                        CHOL_IMPLICIT};
@@ -3222,7 +3525,7 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
     }
     HIP_CHECK(hipGetLastError());
     if (rc) return rc;
-    if (!implicit && Xs.weighted() && (scale_lam || scale_lam_sideinfo)) {
+    if (!implicit && !naz_x && Xs.weighted() && (scale_lam || scale_lam_sideinfo)) {
         hipLaunchKernelGGL(zero_weightless_rows_kernel<real_t>, dim3(m_max), dim3(64), 0, st, Xs.p.ptr, Xs.wsum.ptr, m_max, p > 0 ? m_u : 0,
                            std::numeric_limits<real_t>::epsilon(), dA.ptr, ldA, kt);
         HIP_CHECK(hipGetLastError());
@@ -3305,6 +3608,7 @@ int newrows_state_impute(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *X
 }
 
 double newrows_state_fill_ms(const NewRowsState *s) { return s->fill_ms; }
+int newrows_state_naz_waves(const NewRowsState *s) { return s->naz_last_waves; }
 
 // ---- exclusion lists of the last batch's rows ---------------------------------------------------
 // row pointers of the union: the row's own entries, then the caller's list

@@ -705,6 +705,10 @@ class CMF(_Base):
         ``X``: a SciPy sparse matrix, a (row, col, val) triplet, or a dense array with NaN for the missing entries.  ``W``:
         observation weights in the form of ``X`` (a sparse ``W`` must have ``X``'s pattern).  A model fitted with
         ``add_implicit_features`` uses its ``Bi_``.  Returns ``A`` [max(m_x, m_u), k_user+k+k_main], or ``(A, bias)``."""
+        if self.NA_as_zero or self.NA_as_zero_user:
+            # the missing-as-zero models go through the new-rows handle, which knows the options (the drop-in call refuses them)
+            with self.new_users() as nu:
+                return nu.factors(X=X, U=U, W=W, return_bias=return_bias)
         b = _new_rows_batch(self, X, U, W, dense_ok=True)
         lam6 = None if self._lam6 is None else np.ascontiguousarray(self._lam6, self.dtype_)
         l16 = None if self._l16 is None else np.ascontiguousarray(self._l16, self.dtype_)

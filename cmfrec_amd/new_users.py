@@ -26,7 +26,8 @@ class NewUsers:
         self.dtype = dt = np.dtype(model.dtype_)
         self.implicit = not hasattr(model, "user_bias")
         self.lib = lib = _lib.load(dt)
-        m = _lib.newrows_model_mirror(dt)()
+        mx = _lib.newrows_model_ex_mirror(dt)()             # the model and, behind it, the two missing-as-zero options
+        m = mx.base
         keep = []                                           # the arrays behind the struct's pointers, alive until create returns
 
         def arr(a, dtype=dt):
@@ -62,6 +63,8 @@ class NewUsers:
             m.glob_mean = model.glob_mean_; m.lam = model.lambda_; m.l1_lam = model.l1_lambda
             m.scaling_biasA = model._scaling_biasA if model.scale_bias_const else 1.
             m.w_implicit = model.w_implicit; m.alpha = 1.; m.w_main_multiplier = 1.
+            # a model fitted with missing-as-zero options solves its new rows under the same model
+            mx.NA_as_zero_X = int(getattr(model, "NA_as_zero", False)); mx.NA_as_zero_U = int(getattr(model, "NA_as_zero_user", False))
             if lam6 is not None:
                 m.lam_unique = arr(lam6)
             if model._l16 is not None:
@@ -78,7 +81,7 @@ class NewUsers:
         self.n, self.p = n, p
         self.width = model.k_user + model.k + model.k_main
         self.has_bias = (not self.implicit) and bool(model.user_bias)
-        h = lib.cmfrec_hip_newrows_create(C.byref(m), C.c_int(device))
+        h = lib.cmfrec_hip_newrows_create_ex(C.byref(mx), C.c_int(device))
         if not h:
             _lib.check(lib.cmfrec_hip_last_error_code() or 4, lib, "NewUsers")
         self.handle = C.c_void_p(h)

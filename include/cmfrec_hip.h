@@ -705,6 +705,15 @@ void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
  * kernel_ms: HIP-event times of the most recent call -- its solve phase (uploads of the batch, shard build, row solves; 0 after
  *   an impute call that found no NaN) and, after a topN, the ranking kernel, after an impute, the fill kernel summed over the
  *   blocks, after a predict, the scoring kernel summed over the blocks (0 after a factors call); 2 before the first call.
+ * Missing-as-zero models (the explicit model; cmfrec_hip_newrows_model_ex and cmfrec_hip_newrows_create_ex below).  NA_as_zero_X: every one of
+ *   the n cells of a row of a SPARSE batch counts, an absent one as a zero of weight 1 with the target -glob_mean - biasB_j; a dense
+ *   Xfull batch ignores the field, as the reference does.  NA_as_zero_U: an absent attribute of a SPARSE U is a zero (minus its
+ *   column mean).  The handle builds B^T B, C^T C, BtXbias and CtUbias itself on the device (items beyond n, with include_all_X,
+ *   count with glob_mean only).  Without observation weights every row of such a batch shares one matrix: the batch is one
+ *   gather-sum over the triplets and one product with that matrix's inverse.  Refused with code 2 (per batch: the handle stays
+ *   usable): either field with nonneg, an L1 penalty, implicit features, scale_bias_const or the implicit model; NA_as_zero_X
+ *   with a sparse U whose absent entries are missing (NA_as_zero_U = 0), with weights together with side information, or with
+ *   dense U on other rows than the batch's (m_u != m).
  * Calls on one handle must not overlap; a handle belongs to the device it was made on. */
 typedef struct cmfrec_hip_newrows_model {
     int32_t implicit;
@@ -719,6 +728,12 @@ typedef struct cmfrec_hip_newrows_model {
     const real_t *lam_unique, *l1_lam_unique;            /* the reference's six values each, or NULL */
     const real_t *BtB, *TransBtBinvBt, *BiTBi, *TransCtCinvCt;
 } cmfrec_hip_newrows_model;
+/* The model with the missing-as-zero options behind it: `base` first, so the struct is cmfrec_hip_newrows_model with the two fields at
+ * its end; cmfrec_hip_newrows_model itself keeps its layout for the callers compiled against it.  0 / 0: cmfrec_hip_newrows_create. */
+typedef struct cmfrec_hip_newrows_model_ex {
+    cmfrec_hip_newrows_model base;
+    int32_t NA_as_zero_X, NA_as_zero_U;
+} cmfrec_hip_newrows_model_ex;
 typedef struct cmfrec_hip_newrows_batch {
     int32_t m, m_u;
     const real_t *U;
@@ -749,6 +764,15 @@ int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_b
                                size_t n_pairs, real_t *out, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms);
 void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h);
+/* One-shot form of a missing-as-zero batch: cmfrec_hip_newrows_create, one cmfrec_hip_newrows_factors, destroy -- the level-2
+ * call beside cmfrec_hip_factors_multiple_ex for models with NA_as_zero_X / NA_as_zero_U set.  The codes of factors.
+ * create_ex: cmfrec_hip_newrows_create with the two options; every other call of the handle is the same. */
+/* naz_launch_waves: the wavefronts of the most recent launch of the missing-as-zero right-hand-side kernel on this handle (0: none
+ * yet) -- what the test hook CMFREC_HIP_NAZ_WAVES caps (measurement and tests, like cmfrec_hip_evalset_launch_waves). */
+int cmfrec_hip_newrows_naz_launch_waves(cmfrec_hip_newrows *h, int *waves);
+int cmfrec_hip_sizeof_newrows_model_ex(void);
+cmfrec_hip_newrows *cmfrec_hip_newrows_create_ex(const cmfrec_hip_newrows_model_ex *model, int device);
+int cmfrec_hip_factors_multiple_naz(const cmfrec_hip_newrows_model_ex *model, const cmfrec_hip_newrows_batch *batch, real_t *A, real_t *biasA);
 
 /* Replaces impute_X_collective_explicit, /root/reference/src/cmfrec.h:2071-2103 (body src/collective.c:11351-11544; the Python class's
  * CMF.transform): the NaN of Xfull [m, n] replaced in place by the predictions from the factors of its rows -- the same
