@@ -5,7 +5,9 @@
 // Routing: k <= TOPN_KMAX (64) launches topn_kernel, the kernel of every release so far; beyond that -- or for every k under
 // CMFREC_HIP_TOPN=wide, a cross-check and A/B switch -- topn_wide_kernel (topn_wide_kernels.hpp).  A call with candidate lists
 // (cmfrec_hip_ranker_topN_candidates and its kin) launches topn_cand_kernel (topn_cand_kernels.hpp) for every k.  A rank call
-// (cmfrec_hip_ranker_ranks and its kin) launches topn_rank_kernel (topn_rank_kernels.hpp) for every k.
+// (cmfrec_hip_ranker_ranks and its kin) launches topn_rank_kernel (topn_rank_kernels.hpp) for every k.  A neighbour call
+// (cmfrec_hip_ranker_similar and its kin) launches topn_similar_kernel (topn_similar_kernels.hpp) for every k: the wide
+// kernel's body with the query tile gathered from the resident rows.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -14,11 +16,14 @@
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
+#include "topn_similar_kernels.hpp"
 #include "topn_cand_kernels.hpp"
 #include "topn_rank_kernels.hpp"
 #include "rank_metrics_kernels.hpp"
 
 using namespace cmfhip;
+
+namespace cmfhip { void poison_lds(hipStream_t st, int num_cus); }   // launch_cg.hip (launch.hpp): test hook, CMFREC_HIP_POISON_LDS=1
 
 struct cmfrec_hip_ranker {
     struct Device { int device = 0, num_cus = 256; hipStream_t stream = nullptr; } dev;
@@ -33,6 +38,9 @@ struct cmfrec_hip_ranker {
     DevBuf<int> ci, corder;                  // ... and the users by descending list length
     DevBuf<unsigned> next;                   // work counter of topn_cand_kernel
     DevBuf<int> pool;                        // per-user pool of a rank call (its held-out lists use cp / ci, its ranks ids)
+    DevBuf<real_t> rn;                       // inverse row norms of B: made by the first cosine call, resident from then on
+    bool has_rn = false;
+    DevBuf<int> qid;                         // query ids of a neighbour call
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the ranking kernel of the last call
     bool timed = false;
     int last_users = 0, last_grid = 0;       // users per workgroup and workgroups of that launch
@@ -53,13 +61,14 @@ constexpr const char *RANK_LIMITS = "needs k <= 272";
 // unless fewer finish the nu users in fewer or cheaper waves of workgroups.  A workgroup's time per item round is about
 // (nut + 1/2) -- its MFMAs and the item fetch they share -- times the workgroups that share its CU.
 // CMFREC_HIP_TOPN_TILES (test hook) asks for a number of tiles; it is clamped to what fits.
-int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu)
+// extra_per_tile: LDS bytes per user tile beyond topnw_lds_bytes (the neighbour kernel's ids and inverse norms).
+int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu, size_t extra_per_tile = 0)
 {
     const int forced = switches().topn_tiles;
     int best = 1, best_bpc = 1;
     double best_cost = 0;
     for (int nut = 1; nut <= TOPNW_MAX_NUT; nut++) {
-        const size_t smem = topnw_lds_bytes(nut, k, n_top, sizeof(real_t));
+        const size_t smem = topnw_lds_bytes(nut, k, n_top, sizeof(real_t)) + nut * extra_per_tile;
         if (smem > TOPNW_LDS_MAX) break;
         const int bpc = (int)std::min<size_t>(TOPNW_LDS_MAX / smem, (size_t)(2048 / TOPNW_TH));
         const long tiles = ((long)nu + 16 * nut - 1) / (16 * nut), slots = (long)num_cus * bpc;
@@ -80,6 +89,40 @@ int launch_wide(const cmfrec_hip_ranker::Device &dev, const TopnWideParams<real_
     const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
     hipLaunchKernelGGL((topn_wide_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
     return grid;
+}
+
+template <int NUT, int METRIC>
+int launch_similar(const cmfrec_hip_ranker::Device &dev, const TopnSimilarParams<real_t> &P, int blocks_per_cu)
+{
+    const size_t smem = topns_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
+    HIP_CHECK(hipFuncSetAttribute((const void *)topn_similar_kernel<real_t, NUT, METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
+    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
+    hipLaunchKernelGGL((topn_similar_kernel<real_t, NUT, METRIC>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
+    return grid;
+}
+
+template <int METRIC>
+int launch_similar_tiles(const cmfrec_hip_ranker::Device &dev, const TopnSimilarParams<real_t> &P, int nut, int blocks_per_cu)
+{
+    switch (nut) {
+    case 1: return launch_similar<1, METRIC>(dev, P, blocks_per_cu);
+    case 2: return launch_similar<2, METRIC>(dev, P, blocks_per_cu);
+    case 3: return launch_similar<3, METRIC>(dev, P, blocks_per_cu);
+    default: return launch_similar<4, METRIC>(dev, P, blocks_per_cu);
+    }
+}
+
+// the inverse norms of the ranker's rows, made on its stream the first time they are asked for (the caller holds the DeviceScope)
+void ensure_inverse_norms(cmfrec_hip_ranker *r)
+{
+    if (r->has_rn) return;
+    r->rn.alloc_at_least((size_t)r->n);
+    const int rows = TOPNS_NORM_TH / 4;
+    hipLaunchKernelGGL(row_rnorm_kernel<real_t>, dim3((unsigned)((r->n + rows - 1) / rows)), dim3(TOPNS_NORM_TH), 0, r->dev.stream, r->B.ptr,
+                       r->ldb, r->n, (int)r->ldb, r->rn.ptr);
+    HIP_CHECK(hipGetLastError());
+    r->has_rn = true;
 }
 
 // User tiles per workgroup and slice length of the rank kernel (DESIGN.md "Ranks of held-out items"): the longest held-out list
@@ -428,6 +471,7 @@ int rankset_run_on_factors(cmfrec_hip_ranker **owned, cmfrec_hip_rankset *set, c
     } else {
         DeviceScope scope(device);
         upload_columns(r->B.ptr, r->ldb, dB, ldB, (size_t)n, (size_t)kk, r->dev.stream);
+        r->has_rn = false;                                   // (norms of the rows that were)
         if (dbiasB) r->bias.upload(dbiasB, (size_t)n, r->dev.stream);
     }
     memset(out, 0, sizeof *out);
@@ -645,6 +689,84 @@ int cmfrec_hip_ranker_metrics(cmfrec_hip_ranker *r, const real_t *A, size_t lda,
     });
 }
 
+int cmfrec_hip_ranker_similar(cmfrec_hip_ranker *r, const int_t *query_ids, int_t nq, int metric, const size_t excl_p[], const int_t excl_i[],
+                              int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    const char *fn = "cmfrec_hip_ranker_similar";
+    return guarded([&]() {
+        if (r == nullptr || nq < 0 || n_top <= 0 || (nq > 0 && (!query_ids || !out_ids))) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if (metric != TOPNS_DOT && metric != TOPNS_COSINE) {
+            g_last_error = std::string(fn) + ": metric must be 0 (dot product) or 1 (cosine), got " + std::to_string(metric);
+            return 2;
+        }
+        if (int rc = check_n_top(fn, n_top, r->n)) return rc;
+        for (int_t q = 0; q < nq; q++)
+            if (query_ids[q] < 0 || query_ids[q] >= r->n) {
+                g_last_error = std::string(fn) + ": query id " + std::to_string(query_ids[q]) + " (entry " + std::to_string(q) +
+                               ") is not a row of the ranker's " + std::to_string(r->n);
+                return 2;
+            }
+        if (excl_p != nullptr) {
+            bool bad = false;
+            for (int_t q = 0; !bad && q < nq; q++) bad = excl_p[q] > excl_p[q + 1];
+            if (bad || (excl_p[nq] > 0 && excl_i == nullptr)) {
+                g_last_error = std::string(fn) + ": invalid arguments (the exclusion lists are not a CSR over the queries)";
+                return 2;
+            }
+        }
+        if (nq == 0) return 0;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        r->qid.upload(query_ids, (size_t)nq, dev.stream);
+        if (excl_p) {
+            r->ep.upload(excl_p, (size_t)nq + 1, dev.stream);
+            r->ei.alloc_at_least(std::max<size_t>(excl_p[nq], 1));
+            if (excl_p[nq] > 0) r->ei.upload(excl_i, excl_p[nq], dev.stream);
+        }
+        if (metric == TOPNS_COSINE) ensure_inverse_norms(r);             // outside the timed interval
+        r->ids.alloc_at_least((size_t)nq * n_top);
+        if (out_scores) r->sc.alloc_at_least((size_t)nq * n_top);
+        TopnSimilarParams<real_t> P;
+        P.query_ids = r->qid.ptr; P.nu = nq; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
+        P.rn = metric == TOPNS_COSINE ? r->rn.ptr : nullptr;
+        P.excl_p = excl_p ? r->ep.ptr : nullptr; P.excl_i = excl_p ? r->ei.ptr : nullptr;
+        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+        int bpc = 1;
+        const int nut = pick_user_tiles(nq, r->k, n_top, dev.num_cus, &bpc, 16 * (sizeof(real_t) + sizeof(int)));
+        poison_lds(dev.stream, dev.num_cus);                             // (the policy's LDS too is written before it is read)
+        HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+        r->last_grid = metric == TOPNS_COSINE ? launch_similar_tiles<TOPNS_COSINE>(dev, P, nut, bpc) : launch_similar_tiles<TOPNS_DOT>(dev, P, nut, bpc);
+        r->last_users = 16 * nut;
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
+        r->timed = true;
+        r->ids.download(out_ids, (size_t)nq * n_top, dev.stream);
+        if (out_scores) r->sc.download(out_scores, (size_t)nq * n_top, dev.stream);
+        HIP_CHECK(hipStreamSynchronize(dev.stream));
+        return 0;
+    });
+}
+
+int cmfrec_hip_ranker_inverse_norms(cmfrec_hip_ranker *r, real_t *out)
+{
+    return guarded([&]() {
+        if (r == nullptr || out == nullptr) {
+            g_last_error = "cmfrec_hip_ranker_inverse_norms: invalid arguments";
+            return 2;
+        }
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        ensure_inverse_norms(r);
+        r->rn.download(out, (size_t)r->n, r->dev.stream);
+        HIP_CHECK(hipStreamSynchronize(r->dev.stream));
+        return 0;
+    });
+}
+
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms)
 {
     return guarded([&]() {
@@ -710,6 +832,24 @@ int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, cons
     cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
     if (r == nullptr) return g_last_rc;
     const int rc = cmfrec_hip_ranker_topN_candidates(r, A, lda, nu, cand_p, cand_i, excl_p, excl_i, n_top, out_ids, out_scores);
+    cmfrec_hip_ranker_destroy(r);
+    return rc;
+}
+
+int cmfrec_hip_similar_batch(const real_t *B, size_t ldb, int_t n, int_t k, const int_t *query_ids, int_t nq, int metric, const size_t excl_p[],
+                             const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    if (n <= 0 || k <= 0 || nq < 0 || n_top <= 0 || !B) {
+        g_last_error = "cmfrec_hip_similar_batch: invalid arguments";
+        return 2;
+    }
+    if (k > TOPNW_KMAX || n_top > TOPN_NMAX || n_top > n) {
+        g_last_error = std::string("cmfrec_hip_similar_batch: ") + LIMITS;
+        return 2;
+    }
+    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, nullptr, -1);
+    if (r == nullptr) return g_last_rc;
+    const int rc = cmfrec_hip_ranker_similar(r, query_ids, nq, metric, excl_p, excl_i, n_top, out_ids, out_scores);
     cmfrec_hip_ranker_destroy(r);
     return rc;
 }

@@ -62,9 +62,32 @@ struct TopnWideParams {
     int *out_ids; T *out_scores;             // [nu, n_top]; out_scores may be null
 };
 
-template <typename T, int NUT>
-__global__ void __launch_bounds__(TOPNW_TH)
-topn_wide_kernel(const TopnWideParams<T> P)
+// What topn_wide_body leaves to its caller (topn_wide_kernel below, topn_similar_kernel in topn_similar_kernels.hpp): where the
+// user tile comes from, what turns an accumulator into a score, and one more reason to skip a pair.  Everything is resolved at
+// compile time; `xs` is the policy's own LDS behind the body's (extra bytes: the host adds them to topnw_lds_bytes).
+//   Params                         the fields the body reads: nu, B, ldb, n, k, excl_p, excl_i, n_top, out_ids, out_scores
+//   fill_users(P, As, xs, ...)     As [UT][KS] <- the tile's factors, zero beyond k and beyond the tile's nu_t users (all threads,
+//                                  in front of the body's barrier); xs <- whatever score / self_pair read
+//   item_value(P, item, live)      per lane and round: what the score needs of the lane's item
+//   score(acc, iv, xs, UT, u)      the score of user u of the tile against that item
+//   self_pair(xs, UT, u, item)     true: the pair is skipped, ahead of the exclusion list
+template <typename T>
+struct TopnWidePolicy {
+    using Params = TopnWideParams<T>;
+    static __device__ __forceinline__ void fill_users(const Params &P, T *As, unsigned char *, int u0, int nu_t, int UT, int KS, int tid)
+    {
+        for (int e = tid; e < UT * KS; e += TOPNW_TH) {
+            const int u = e / KS, f = e % KS;
+            As[e] = (u < nu_t && f < P.k) ? P.A[(size_t)(u0 + u) * P.lda + f] : T(0);
+        }
+    }
+    static __device__ __forceinline__ T item_value(const Params &P, int item, bool live) { return (P.biasB != nullptr && live) ? P.biasB[item] : T(0); }
+    static __device__ __forceinline__ T score(T acc, T bias, const unsigned char *, int, int) { return acc + bias; }
+    static __device__ __forceinline__ bool self_pair(const unsigned char *, int, int, int) { return false; }
+};
+
+template <typename T, int NUT, typename POL>
+__device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
 {
     using Acc = MfmaAcc<T>;
     using vec = typename Acc::vec;
@@ -83,6 +106,7 @@ topn_wide_kernel(const TopnWideParams<T> P)
     int *sid = reinterpret_cast<int *>(thr + UT);                   // [UT][LS]
     int *cnt = sid + UT * LS;                                       // [UT] candidates offered since the last merge
     int *flag = cnt + UT;                                           // [2] "a lane still holds a candidate", alternating
+    unsigned char *xs = reinterpret_cast<unsigned char *>(flag + 2);   // the policy's own (8-byte aligned: UT * LS + UT + 2 ints)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 15, grp = lane >> 4;
     const T NEG = -INFINITY;
@@ -91,10 +115,7 @@ topn_wide_kernel(const TopnWideParams<T> P)
     for (int u0 = blockIdx.x * UT; u0 < P.nu; u0 += gridDim.x * UT) {
         const int nu_t = min(UT, P.nu - u0);
         __syncthreads();
-        for (int e = tid; e < UT * KS; e += TOPNW_TH) {
-            const int u = e / KS, f = e % KS;
-            As[e] = (u < nu_t && f < k) ? P.A[(size_t)(u0 + u) * P.lda + f] : T(0);
-        }
+        POL::fill_users(P, As, xs, u0, nu_t, UT, KS, tid);
         for (int e = tid; e < UT * LS; e += TOPNW_TH) { ssc[e] = NEG; sid[e] = 0x7fffffff; }
         if (tid < UT) { cnt[tid] = 0; thr[tid] = NEG; }
         __syncthreads();
@@ -109,7 +130,7 @@ topn_wide_kernel(const TopnWideParams<T> P)
         for (int c0 = 0; c0 < P.n; c0 += TOPNW_ITEMS) {
             const int item = c0 + 16 * wave + col;
             const bool live = item < P.n;
-            const T bias = (P.biasB != nullptr && live) ? P.biasB[item] : T(0);
+            const auto iv = POL::item_value(P, item, live);
             vec acc[NUT];
 #pragma unroll
             for (int t = 0; t < NUT; t++) acc[t] = vec{0, 0, 0, 0};
@@ -143,8 +164,8 @@ topn_wide_kernel(const TopnWideParams<T> P)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int u = 16 * t + Acc::row_of(lane, r);
-                    acc[t][r] += bias;
-                    if (live && u < nu_t && acc[t][r] >= thr[u]) {               // NaN never enters
+                    acc[t][r] = POL::score(acc[t][r], iv, xs, UT, u);
+                    if (live && u < nu_t && acc[t][r] >= thr[u] && !POL::self_pair(xs, UT, u, item)) {   // NaN never enters
                         bool skip = false;
                         if (P.excl_p != nullptr) {                               // sorted list of the user: binary search
                             const size_t end = P.excl_p[u0 + u + 1];
@@ -240,6 +261,13 @@ topn_wide_kernel(const TopnWideParams<T> P)
             if (P.out_scores != nullptr) P.out_scores[(size_t)(u0 + u) * ntop + j] = sv;
         }
     }
+}
+
+template <typename T, int NUT>
+__global__ void __launch_bounds__(TOPNW_TH)
+topn_wide_kernel(const TopnWideParams<T> P)
+{
+    topn_wide_body<T, NUT, TopnWidePolicy<T>>(P);
 }
 
 }  // namespace cmfhip

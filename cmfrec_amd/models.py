@@ -99,6 +99,11 @@ class ModelRanker:
         users, A, excl = _topN_inputs(self._model, users, exclude)
         return self._ranker.ranks(A, heldout, exclude=excl)
 
+    def similar_items(self, items, n=10, metric="cosine", exclude=None):
+        """(ids, scores) as ``Ranker.similar``: the neighbours of the model's items ``items`` among its items, from the resident
+        ``B_[:, k_item:]``; the item bias plays no part.  ``exclude``: CSR over the queries, further items to skip."""
+        return self._ranker.similar(items, n=n, metric=metric, exclude=exclude)
+
     def kernel_ms(self):
         return self._ranker.kernel_ms()
 
@@ -110,6 +115,25 @@ class ModelRanker:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _similar(factors, first, ids, n, metric, what):
+    """Shared body of ``similar_items`` / ``similar_users``: a ranker over the scored columns of one factor matrix, made for the
+    call."""
+    from .ops import _similar_args
+    from .rank import Ranker
+    _similar_args(ids, factors.shape[0], metric, what)       # (refused before anything is uploaded)
+    with Ranker(np.ascontiguousarray(factors[:, first:])) as r:
+        return r.similar(ids, n=n, metric=metric)
+
+
+_SIMILAR_ITEMS_DOC = """(ids [len(items), n] int32, scores): the items most like each of ``items`` by ``metric`` = "cosine" or "dot" over
+        ``B_[:, k_item:]`` -- the columns the scores use; a bias plays no part --, descending, ties by lower id, the item itself
+        left out (``Ranker.similar``).  A ranker made for the call: to ask several times, hold ``ranker()`` and call its
+        ``similar_items``."""
+_SIMILAR_USERS_DOC = """(ids [len(users), n] int32, scores): the users most like each of ``users`` by ``metric`` = "cosine" or "dot" over
+        ``A_[:, k_user:]`` -- the columns the scores use --, descending, ties by lower id, the user itself left out
+        (``Ranker.similar`` on a ranker over the user factors, made for the call)."""
 
 
 def _ranks(self, users, heldout, exclude, biasB):
@@ -506,6 +530,14 @@ class CMF_implicit(_Base):
         """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch."""
         return ModelRanker(self, None)
 
+    def similar_items(self, items, n=10, metric="cosine"):
+        return _similar(self.B_, self.k_item, items, n, metric, "similar_items")
+    similar_items.__doc__ = _SIMILAR_ITEMS_DOC
+
+    def similar_users(self, users, n=10, metric="cosine"):
+        return _similar(self.A_, self.k_user, users, n, metric, "similar_users")
+    similar_users.__doc__ = _SIMILAR_USERS_DOC
+
     def scorer(self):
         """A ``cmfrec_amd.Scorer`` over this model: both factor matrices go to the device once, then ``.predict(user, item)``
         per batch of pairs (NaN for a pair outside the model).  The caller closes it; a refit needs a new one."""
@@ -793,6 +825,14 @@ class CMF(_Base):
         """A ``ModelRanker`` over this model's item factors and item bias: upload them once, then ``.topN(users, n, exclude)``
         per batch, with the scores of ``topN_batch``."""
         return ModelRanker(self, self.item_bias_ if self.item_bias else None)
+
+    def similar_items(self, items, n=10, metric="cosine"):
+        return _similar(self.B_, self.k_item, items, n, metric, "similar_items")
+    similar_items.__doc__ = _SIMILAR_ITEMS_DOC
+
+    def similar_users(self, users, n=10, metric="cosine"):
+        return _similar(self.A_, self.k_user, users, n, metric, "similar_users")
+    similar_users.__doc__ = _SIMILAR_USERS_DOC
 
     def scorer(self):
         """A ``cmfrec_amd.Scorer`` over this model: both factor matrices, the biases and the global mean go to the device once,

@@ -299,6 +299,49 @@ def ranks_batch(A, B, heldout, biasB=None, exclude=None):
     return hp.astype(np.int64), hi, ranks, pool
 
 
+SIMILAR_METRICS = {"dot": 0, "cosine": 1}     # the `metric` of cmfrec_hip_ranker_similar
+
+
+def _similar_args(ids, n_rows, metric, what):
+    """(ids int32 [nq], metric code) of a neighbour call, checked without a device: the ids 1-D integers in [0, n_rows), the
+    metric one of SIMILAR_METRICS."""
+    if not isinstance(metric, str) or metric not in SIMILAR_METRICS:
+        raise ValueError("%s: metric must be 'cosine' or 'dot', got %r" % (what, metric))
+    ids = np.asarray(ids)
+    if ids.ndim != 1:
+        raise ValueError("%s: ids must be a 1-D array of row ids, got %d-D" % (what, ids.ndim))
+    if len(ids) and not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError("%s: ids must be integers, got %s" % (what, ids.dtype))
+    if len(ids) and (ids.min() < 0 or ids.max() >= n_rows):
+        raise ValueError("%s: ids must be in [0, %d), got %d .. %d" % (what, n_rows, ids.min(), ids.max()))
+    return np.ascontiguousarray(ids, np.int32), SIMILAR_METRICS[metric]
+
+
+def similar_batch(B, ids, n_top=10, metric="cosine", exclude=None):
+    """Neighbours of the rows ``ids`` of ``B`` [n, k] among the rows of ``B``: (ids [nq, n_top] int32, scores [nq, n_top]) by
+    ``metric`` = "cosine" (B_q . B_i / (|B_q| |B_i|)) or "dot" (B_q . B_i), descending, ties by lower id, the query itself left
+    out, -1 / -inf where fewer than ``n_top`` rows remain.  A zero row (or one with a NaN) has no cosine and is nobody's
+    neighbour.  ``exclude``: (indptr, indices) CSR over the queries or a SciPy CSR matrix, further rows to skip per query.
+    Every width the library fits (k <= 272), n_top <= min(128, n).  B is uploaded on every call: to ask several times, hold
+    a ``cmfrec_amd.Ranker`` and call its ``similar``."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.dtype.type not in (np.float64, np.float32):
+        raise ValueError("similar_batch: B must be a 2-D float64 or float32 array, got %d-D %s" % (B.ndim, B.dtype))
+    q, code = _similar_args(ids, B.shape[0], metric, "similar_batch")
+    if exclude is not None and _is_csr(exclude):
+        exclude = (exclude.indptr, exclude.indices)
+    ep, ei = _sorted_exclude(exclude, len(q))
+    B = np.ascontiguousarray(B)
+    lib = _lib.load(B.dtype)
+    n, k = B.shape
+    n_top = int(n_top)
+    out = np.empty((len(q), n_top), np.int32); sc = np.empty((len(q), n_top), B.dtype)
+    rc = lib.cmfrec_hip_similar_batch(_lib.ptr(B), C.c_size_t(k), C.c_int(n), C.c_int(k), _lib.ptr(q), C.c_int(len(q)), C.c_int(code),
+                                      _lib.ptr(ep), _lib.ptr(ei), C.c_int(n_top), _lib.ptr(out), _lib.ptr(sc))
+    _lib.check(rc, lib, "similar_batch")
+    return out, sc
+
+
 DENSE_OPS = {"gemm": 0, "gemm_ta": 1, "gram": 2, "potrf": 3, "trtri": 4, "potrs_rows": 5}
 
 

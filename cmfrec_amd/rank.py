@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _heldout_lists, _is_csr, _sorted_exclude, _sorted_include
+from .ops import _heldout_lists, _is_csr, _similar_args, _sorted_exclude, _sorted_include
 
 
 def check_rankset(users, heldout, exclude):
@@ -190,9 +190,34 @@ class Ranker:
         out = (rec.as_dict(),) + ((pu,) if per_user else ()) + ((rk,) if return_ranks else ())
         return out[0] if len(out) == 1 else out
 
+    def similar(self, ids, n=10, metric="cosine", exclude=None):
+        """(ids [nq, n] int32, scores [nq, n]): the neighbours of the ranker's own rows ``ids`` among its rows, by ``metric`` =
+        "cosine" (B_q . B_i / (|B_q| |B_i|)) or "dot" (B_q . B_i; the bias plays no part in either), descending, ties by lower
+        id, the query itself left out, -1 / -inf where fewer than ``n`` rows remain.  Only the ids go to the device.  A zero row
+        (or one with a NaN) has no cosine: it is nobody's neighbour and has none.  ``exclude``: (indptr, indices) CSR over the
+        queries or a SciPy CSR matrix, further rows to skip per query."""
+        q, code = _similar_args(ids, self.n, metric, "Ranker.similar")
+        if exclude is not None and _is_csr(exclude):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, len(q))
+        h = self._live()
+        n = int(n)
+        out = np.empty((len(q), n), np.int32); sc = np.empty((len(q), n), self.dtype)
+        rc = self.lib.cmfrec_hip_ranker_similar(h, _lib.ptr(q), C.c_int(len(q)), C.c_int(code), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
+                                                _lib.ptr(out), _lib.ptr(sc))
+        _lib.check(rc, self.lib, "Ranker.similar")
+        return out, sc
+
+    def inverse_norms(self):
+        """[n]: 1 / |B_i| of every row as the cosine scores use it (made on the device by the first call that needs it, resident
+        from then on); NaN for a row whose sum of squares is zero, NaN or infinite."""
+        rn = np.empty(self.n, self.dtype)
+        _lib.check(self.lib.cmfrec_hip_ranker_inverse_norms(self._live(), _lib.ptr(rn)), self.lib, "Ranker.inverse_norms")
+        return rn
+
     def kernel_ms(self):
-        """HIP-event time (ms) of the ranking kernel of the most recent ``topN`` or ``ranks`` call (of ``ranks``: the whole rank
-        kernel, its threshold and exclusion steps included)."""
+        """HIP-event time (ms) of the ranking kernel of the most recent ``topN``, ``ranks`` or ``similar`` call (of ``ranks``: the
+        whole rank kernel, its threshold and exclusion steps included; of ``similar``: without the norm kernel)."""
         ms = C.c_double(0)
         _lib.check(self.lib.cmfrec_hip_ranker_kernel_ms(self._live(), C.byref(ms)), self.lib, "Ranker.kernel_ms")
         return ms.value

@@ -654,6 +654,25 @@ int cmfrec_hip_ranks_batch(const real_t *A, size_t lda, int_t nu, const real_t *
                            const real_t *biasB, const size_t held_p[], const int_t held_i[],
                            const size_t excl_p[], const int_t excl_i[],
                            int_t *out_rank, real_t *out_scores, int_t *out_pool);
+/* Neighbours of the ranker's own rows ("items like this item"; a ranker over the user factors: "users like this user").
+ * query_ids [nq]: rows of the ranker's matrix, each in [0, n); only the ids are uploaded, the query tile is gathered from the
+ * resident rows.  metric: 0 = dot product, score(q, i) = B_q . B_i -- without the bias, even when the ranker holds one;
+ * 1 = cosine, score(q, i) = ((B_q . B_i) * rn[i]) * rn[q], two multiplications in that order, rn[i] = 1 / sqrt(sum_f B[i, f]^2)
+ * (IEEE square root and division, made by the first cosine call of a ranker and resident from then on; inverse_norms downloads
+ * them).  A row whose sum of squares is zero, NaN or infinite has rn = NaN: it is nobody's neighbour and, as a query, has none.
+ * The query itself is skipped; excl_p / excl_i (optional): further exclusion lists, CSR over the nq queries, each ascending, as
+ * in ranker_topN.  Order, ties (lower id first), -1 / -inf filling and limits are those of ranker_topN.  Every k <= 272 runs the
+ * MFMA kernel's body (topn_similar_kernels.hpp).  Code 2 with a message, decided on the host with the outputs untouched: a
+ * query id outside [0, n) or query_ids == NULL, a metric other than 0 / 1, exclusion lists that are not a CSR, k > 272 or
+ * n_top > min(128, n).  nq == 0: code 0, nothing written.  kernel_ms / launch_shape report the neighbour kernel after such a
+ * call (the norm kernel is outside the timed interval).  Neighbour, top-N, candidate and rank calls may be interleaved on one
+ * handle.  cmfrec_hip_similar_batch is create (without a bias), one such call, destroy. */
+int cmfrec_hip_ranker_similar(cmfrec_hip_ranker *r, const int_t *query_ids, int_t nq, int metric,
+                              const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                              int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_similar_batch(const real_t *B, size_t ldb, int_t n, int_t k, const int_t *query_ids, int_t nq, int metric,
+                             const size_t excl_p[], const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_ranker_inverse_norms(cmfrec_hip_ranker *r, real_t *out);
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
