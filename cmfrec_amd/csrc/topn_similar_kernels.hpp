@@ -102,10 +102,11 @@ struct TopnSimilarPolicy {
     }
     static __device__ __forceinline__ T score(T acc, T rni, const unsigned char *xs, int, int u) { return (acc * rni) * reinterpret_cast<const T *>(xs)[u]; }
     static __device__ __forceinline__ T score(T acc, None, const unsigned char *, int, int) { return acc; }
-    static __device__ __forceinline__ bool self_pair(const unsigned char *xs, int UT, int u, int item)
+    static __device__ __forceinline__ bool admit(const unsigned char *xs, int UT, int u, int item, T)
     {
-        return reinterpret_cast<const int *>(reinterpret_cast<const T *>(xs) + UT)[u] == item;
+        return reinterpret_cast<const int *>(reinterpret_cast<const T *>(xs) + UT)[u] != item;
     }
+    static __device__ __forceinline__ size_t out_stride(const Params &P) { return (size_t)P.n_top; }
 };
 
 template <typename T, int NUT, int METRIC>

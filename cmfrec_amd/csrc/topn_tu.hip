@@ -7,7 +7,9 @@
 // (cmfrec_hip_ranker_topN_candidates and its kin) launches topn_cand_kernel (topn_cand_kernels.hpp) for every k.  A rank call
 // (cmfrec_hip_ranker_ranks and its kin) launches topn_rank_kernel (topn_rank_kernels.hpp) for every k.  A neighbour call
 // (cmfrec_hip_ranker_similar and its kin) launches topn_similar_kernel (topn_similar_kernels.hpp) for every k: the wide
-// kernel's body with the query tile gathered from the resident rows.
+// kernel's body with the query tile gathered from the resident rows.  A deep or next-page call (cmfrec_hip_ranker_topN_deep /
+// _topN_after) launches topn_after_kernel (topn_after_kernels.hpp) for every k, once per page: the wide kernel's body behind a
+// per-user cursor.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -17,6 +19,7 @@
 #include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
 #include "topn_similar_kernels.hpp"
+#include "topn_after_kernels.hpp"
 #include "topn_cand_kernels.hpp"
 #include "topn_rank_kernels.hpp"
 #include "rank_metrics_kernels.hpp"
@@ -41,6 +44,9 @@ struct cmfrec_hip_ranker {
     DevBuf<real_t> rn;                       // inverse row norms of B: made by the first cosine call, resident from then on
     bool has_rn = false;
     DevBuf<int> qid;                         // query ids of a neighbour call
+    DevBuf<real_t> cur_s;                    // the caller's cursors of a next-page call
+    DevBuf<int> cur_i;
+    int last_pages = 0, last_page_len = 0;   // launches and page length of the last deep call
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the ranking kernel of the last call
     bool timed = false;
     int last_users = 0, last_grid = 0;       // users per workgroup and workgroups of that launch
@@ -56,6 +62,7 @@ namespace {
 
 constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
 constexpr const char *RANK_LIMITS = "needs k <= 272";
+constexpr const char *DEEP_LIMITS = "needs k <= 272 and 1 <= n_top <= n";
 
 // User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
 // unless fewer finish the nu users in fewer or cheaper waves of workgroups.  A workgroup's time per item round is about
@@ -99,6 +106,17 @@ int launch_similar(const cmfrec_hip_ranker::Device &dev, const TopnSimilarParams
     const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
     const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
     hipLaunchKernelGGL((topn_similar_kernel<real_t, NUT, METRIC>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
+    return grid;
+}
+
+template <int NUT>
+int launch_after(const cmfrec_hip_ranker::Device &dev, const TopnAfterParams<real_t> &P, int blocks_per_cu)
+{
+    const size_t smem = topna_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
+    HIP_CHECK(hipFuncSetAttribute((const void *)topn_after_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
+    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
+    hipLaunchKernelGGL((topn_after_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
     return grid;
 }
 
@@ -233,6 +251,72 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
     r->ids.download(out_ids, (size_t)nu * n_top, dev.stream);
     if (out_scores) r->sc.download(out_scores, (size_t)nu * n_top, dev.stream);
     HIP_CHECK(hipStreamSynchronize(dev.stream));
+    return 0;
+}
+
+// Page length of a deep list (DESIGN.md "Deep lists and next pages"): 128, the list size the wide kernel has been measured at,
+// and longer only where a longer page was measured at least 10 % faster at n_top = 500 and 1000 -- double precision 256 around
+// k = 128 and 512 around k = 256, single precision 256 around k = 272; the ranges' ends lie midway between the measured widths.
+// A list that one page of 128 holds runs as that page.  CMFREC_HIP_TOPN_PAGE (test hook, 1 .. TOPNA_PAGE_MAX, read per call) asks
+// for any other length; the length is cut down to what one user tile fits beside the factors.  The result does not depend on it.
+int default_page_len(int k)
+{
+    if (sizeof(real_t) == 8) return k >= 192 ? 512 : (k >= 96 ? 256 : 128);
+    return k >= 192 ? 256 : 128;
+}
+
+int pick_page_len(int k, int_t n_top)
+{
+    const char *v = getenv("CMFREC_HIP_TOPN_PAGE");
+    const int asked = (v != nullptr && v[0] != 0) ? atoi(v) : 0;
+    int len = (asked >= 1 && asked <= TOPNA_PAGE_MAX) ? asked : (n_top <= 128 ? 128 : default_page_len(k));
+    while (len > 32 && topna_lds_bytes(1, k, len, sizeof(real_t)) > TOPNW_LDS_MAX) len = topnw_np(len) / 2;
+    return (int)std::min<int_t>(len, n_top);
+}
+
+// The n_top best of nu users behind their cursors, in pages of page_len on topn_after_kernel, for every k (the register-resident
+// topn_kernel of k <= 64 rounds otherwise, and a cursor compares bits).  The whole [nu, n_top] result lives in r->ids / r->sc;
+// page p is one launch that writes the columns [p * page_len, ...) and reads its cursors from the column in front of them -- no
+// host round trip between the pages, one download at the end.  The first page's cursors: dcur_s / dcur_i [nu], or null (every
+// user starts at the top).  The timing events enclose all the pages.  Returns the launches in *pages.
+// (the caller holds the DeviceScope and has checked the limits; the factors and exclusion lists are on the device)
+int rank_device_deep(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
+                     int page_len, const real_t *dcur_s, const int *dcur_i, int_t *out_ids, real_t *out_scores, int *pages)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    const size_t cells = (size_t)nu * (size_t)n_top;
+    r->ids.alloc_at_least(cells);
+    r->sc.alloc_at_least(cells);                                         // (the next page's cursors, wanted by the caller or not)
+    TopnAfterParams<real_t> P;
+    P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
+    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+    P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+    P.out_ld = (size_t)n_top;
+    poison_lds(dev.stream, dev.num_cus);                                 // (the policy's LDS too is written before it is read)
+    HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    int launches = 0;
+    for (int_t first = 0; first < n_top; first += page_len, launches++) {
+        P.n_top = (int)std::min<int_t>(page_len, n_top - first);
+        P.out_ids = r->ids.ptr + first; P.out_scores = r->sc.ptr + first;
+        if (first == 0) { P.cur_scores = dcur_s; P.cur_ids = dcur_s ? dcur_i : nullptr; P.cur_ld = 1; }
+        else { P.cur_scores = r->sc.ptr + first - 1; P.cur_ids = r->ids.ptr + first - 1; P.cur_ld = (size_t)n_top; }
+        int bpc = 1;
+        const int nut = pick_user_tiles(nu, r->k, P.n_top, dev.num_cus, &bpc, topna_extra_bytes(sizeof(real_t)));
+        switch (nut) {
+        case 1: r->last_grid = launch_after<1>(dev, P, bpc); break;
+        case 2: r->last_grid = launch_after<2>(dev, P, bpc); break;
+        case 3: r->last_grid = launch_after<3>(dev, P, bpc); break;
+        default: r->last_grid = launch_after<4>(dev, P, bpc); break;
+        }
+        r->last_users = 16 * nut;
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
+    r->timed = true;
+    r->ids.download(out_ids, cells, dev.stream);
+    if (out_scores) r->sc.download(out_scores, cells, dev.stream);
+    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    if (pages) *pages = launches;
     return 0;
 }
 
@@ -576,6 +660,82 @@ int cmfrec_hip_ranker_topN_candidates(cmfrec_hip_ranker *r, const real_t *A, siz
     });
 }
 
+int cmfrec_hip_ranker_topN_deep(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t excl_p[], const int_t excl_i[],
+                                int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    const char *fn = "cmfrec_hip_ranker_topN_deep";
+    return guarded([&]() {
+        if (r != nullptr && (n_top < 1 || n_top > r->n)) {
+            g_last_error = std::string(fn) + ": " + DEEP_LIMITS;
+            return 2;
+        }
+        if (r == nullptr || nu <= 0 || !A || !out_ids || lda < (size_t)r->k || (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        const int k = r->k;
+        r->A.alloc_at_least((size_t)nu * k);
+        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        if (excl_p) {
+            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
+            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
+            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
+        }
+        const int len = pick_page_len(k, n_top);
+        int pages = 0;
+        if (int rc = rank_device_deep(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, len, nullptr,
+                                      nullptr, out_ids, out_scores, &pages))
+            return rc;
+        r->last_pages = pages; r->last_page_len = len;
+        return 0;
+    });
+}
+
+int cmfrec_hip_ranker_topN_after(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t excl_p[], const int_t excl_i[],
+                                 const int_t *after_ids, const real_t *after_scores, int_t n_top, int_t *out_ids, real_t *out_scores)
+{
+    const char *fn = "cmfrec_hip_ranker_topN_after";
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || n_top <= 0 || !A || !out_ids || lda < (size_t)r->k || (after_ids == nullptr) != (after_scores == nullptr) ||
+            (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if (int rc = check_n_top(fn, n_top, r->n)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        const int k = r->k;
+        r->A.alloc_at_least((size_t)nu * k);
+        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        if (excl_p) {
+            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
+            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
+            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
+        }
+        if (after_ids) {
+            r->cur_s.upload(after_scores, (size_t)nu, dev.stream);
+            r->cur_i.upload(after_ids, (size_t)nu, dev.stream);
+        }
+        return rank_device_deep(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, (int)n_top,
+                                after_ids ? r->cur_s.ptr : nullptr, after_ids ? r->cur_i.ptr : nullptr, out_ids, out_scores, nullptr);
+    });
+}
+
+int cmfrec_hip_ranker_pages(cmfrec_hip_ranker *r, int *pages, int *page_len)
+{
+    if (r == nullptr || r->last_pages == 0) {
+        g_last_error = "cmfrec_hip_ranker_pages: no deep ranking call on this handle yet";
+        return 2;
+    }
+    if (pages) *pages = r->last_pages;
+    if (page_len) *page_len = r->last_page_len;
+    return 0;
+}
+
 int cmfrec_hip_ranker_ranks(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t held_p[], const int_t held_i[],
                             const size_t excl_p[], const int_t excl_i[], int_t *out_rank, real_t *out_scores, int_t *out_pool)
 {
@@ -813,6 +973,29 @@ int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B
     cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
     if (r == nullptr) return g_last_rc;
     const int rc = cmfrec_hip_ranker_topN(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
+    cmfrec_hip_ranker_destroy(r);
+    return rc;
+}
+
+int cmfrec_hip_topN_deep_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                               const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                               int_t *out_ids, real_t *out_scores)
+{
+    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B) {
+        g_last_error = "cmfrec_hip_topN_deep_batch: invalid arguments";
+        return 2;
+    }
+    if (k > TOPNW_KMAX || n_top < 1 || n_top > n) {
+        g_last_error = std::string("cmfrec_hip_topN_deep_batch: ") + DEEP_LIMITS;
+        return 2;
+    }
+    if (!out_ids) {
+        g_last_error = "cmfrec_hip_topN_deep_batch: invalid arguments";
+        return 2;
+    }
+    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
+    if (r == nullptr) return g_last_rc;
+    const int rc = cmfrec_hip_ranker_topN_deep(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
     cmfrec_hip_ranker_destroy(r);
     return rc;
 }

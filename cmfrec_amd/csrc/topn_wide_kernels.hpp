@@ -62,15 +62,18 @@ struct TopnWideParams {
     int *out_ids; T *out_scores;             // [nu, n_top]; out_scores may be null
 };
 
-// What topn_wide_body leaves to its caller (topn_wide_kernel below, topn_similar_kernel in topn_similar_kernels.hpp): where the
+// What topn_wide_body leaves to its caller (topn_wide_kernel below, topn_similar_kernel in topn_similar_kernels.hpp,
+// topn_after_kernel in topn_after_kernels.hpp): where the
 // user tile comes from, what turns an accumulator into a score, and one more reason to skip a pair.  Everything is resolved at
 // compile time; `xs` is the policy's own LDS behind the body's (extra bytes: the host adds them to topnw_lds_bytes).
 //   Params                         the fields the body reads: nu, B, ldb, n, k, excl_p, excl_i, n_top, out_ids, out_scores
 //   fill_users(P, As, xs, ...)     As [UT][KS] <- the tile's factors, zero beyond k and beyond the tile's nu_t users (all threads,
-//                                  in front of the body's barrier); xs <- whatever score / self_pair read
+//                                  in front of the body's barrier); xs <- whatever score / admit read
 //   item_value(P, item, live)      per lane and round: what the score needs of the lane's item
 //   score(acc, iv, xs, UT, u)      the score of user u of the tile against that item
-//   self_pair(xs, UT, u, item)     true: the pair is skipped, ahead of the exclusion list
+//   admit(xs, UT, u, item, score)  false: the pair is skipped -- asked once per pair, ahead of the exclusion list, not again
+//                                  when a candidate is offered a second time
+//   out_stride(P)                  elements between two users' rows of out_ids / out_scores
 template <typename T>
 struct TopnWidePolicy {
     using Params = TopnWideParams<T>;
@@ -83,7 +86,8 @@ struct TopnWidePolicy {
     }
     static __device__ __forceinline__ T item_value(const Params &P, int item, bool live) { return (P.biasB != nullptr && live) ? P.biasB[item] : T(0); }
     static __device__ __forceinline__ T score(T acc, T bias, const unsigned char *, int, int) { return acc + bias; }
-    static __device__ __forceinline__ bool self_pair(const unsigned char *, int, int, int) { return false; }
+    static __device__ __forceinline__ bool admit(const unsigned char *, int, int, int, T) { return true; }
+    static __device__ __forceinline__ size_t out_stride(const Params &P) { return (size_t)P.n_top; }
 };
 
 template <typename T, int NUT, typename POL>
@@ -165,7 +169,7 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
                 for (int r = 0; r < 4; r++) {
                     const int u = 16 * t + Acc::row_of(lane, r);
                     acc[t][r] = POL::score(acc[t][r], iv, xs, UT, u);
-                    if (live && u < nu_t && acc[t][r] >= thr[u] && !POL::self_pair(xs, UT, u, item)) {   // NaN never enters
+                    if (live && u < nu_t && acc[t][r] >= thr[u] && POL::admit(xs, UT, u, item, acc[t][r])) {   // NaN never enters
                         bool skip = false;
                         if (P.excl_p != nullptr) {                               // sorted list of the user: binary search
                             const size_t end = P.excl_p[u0 + u + 1];
@@ -254,11 +258,12 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
                 __syncthreads();
             } while (more);
         }
+        const size_t ldo = POL::out_stride(P);
         for (int e = tid; e < nu_t * ntop; e += TOPNW_TH) {
             const int u = e / ntop, j = e % ntop;
             const T sv = ssc[u * LS + j];
-            P.out_ids[(size_t)(u0 + u) * ntop + j] = (sv == NEG) ? -1 : sid[u * LS + j];
-            if (P.out_scores != nullptr) P.out_scores[(size_t)(u0 + u) * ntop + j] = sv;
+            P.out_ids[(size_t)(u0 + u) * ldo + j] = (sv == NEG) ? -1 : sid[u * LS + j];
+            if (P.out_scores != nullptr) P.out_scores[(size_t)(u0 + u) * ldo + j] = sv;
         }
     }
 }

@@ -73,6 +73,21 @@ def _topN(self, users, n, exclude, biasB, include=None):
     return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl, include=include)
 
 
+def _topN_deep(self, users, n, exclude, biasB):
+    """Shared body of ``CMF.topN_deep`` / ``CMF_implicit.topN_deep``."""
+    from . import ops
+    _, A, excl = _topN_inputs(self, users, exclude)
+    B = np.ascontiguousarray(self.B_[:, self.k_item:])
+    return ops.topN_deep_batch(A, B, n, biasB=biasB, exclude=excl)
+
+
+_TOPN_DEEP_DOC = """``topN_batch`` without its limit of 128: (ids [len(users), n] int32, scores) for any ``1 <= n <= items``, built on the
+        device in pages that each admit only what lies strictly behind the page before (``ops.topN_deep_batch``); ``users`` and
+        ``exclude`` as in ``topN_batch``.  The scores are exactly what the ranker returns, A_u . B_i (+ the item bias): the global
+        mean and the user bias ``topN_batch`` adds are left out (they do not change the order).  To ask for several batches, or
+        for one page after another, hold ``ranker()`` and call its ``topN_deep`` / ``topN_after``."""
+
+
 class ModelRanker:
     """What ``CMF.ranker()`` / ``CMF_implicit.ranker()`` return: the fitted model's item factors (and item bias) held on the
     device by a ``cmfrec_amd.Ranker``; ``topN(users, n, exclude, include)`` takes user ids of the fitted model and returns what the
@@ -91,6 +106,24 @@ class ModelRanker:
         else:
             ids, sc = self._ranker.topN(A, n=n, exclude=excl, include=include)
         return ids, self._model._finish_scores(users, sc)
+
+    def topN_deep(self, users, n, exclude=None):
+        """(ids, scores) for user ids of the fitted model and any ``1 <= n <= items`` (``Ranker.topN_deep``: pages chained on the
+        device).  The scores are the ranker's own, A_u . B_i (+ item bias), exactly as it returns them -- without the global
+        mean and the user bias ``topN`` adds, which do not change the order: their bits are what ``topN_after`` takes as a cursor."""
+        _, A, excl = _topN_inputs(self._model, users, exclude)
+        return self._ranker.topN_deep(A, n, exclude=excl)
+
+    def topN_after(self, users, after_ids, after_scores, n=10, exclude=None):
+        """The next ``n`` items of every user strictly behind its cursor (``Ranker.topN_after``), typically ``ids[:, -1]`` /
+        ``scores[:, -1]`` of the previous ``topN_after`` / ``topN_deep`` call for the same users; both None: the first page.
+        Scores as ``topN_deep`` returns them."""
+        _, A, excl = _topN_inputs(self._model, users, exclude)
+        return self._ranker.topN_after(A, after_ids, after_scores, n=n, exclude=excl)
+
+    def pages(self):
+        """(launches, page length) of the most recent ``topN_deep`` call."""
+        return self._ranker.pages()
 
     def ranks(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool) as ``Ranker.ranks`` for user ids of the fitted model: ``heldout`` = (indptr, indices) CSR
@@ -501,6 +534,10 @@ class CMF_implicit(_Base):
         SciPy CSR matrix of that many rows, or one 1-D array shared by all: each user is ranked over its own list only."""
         return _topN(self, users, n, exclude, None, include)
 
+    def topN_deep(self, users, n, exclude=None):
+        return _topN_deep(self, users, n, exclude, None)
+    topN_deep.__doc__ = _TOPN_DEEP_DOC
+
     def ranks_batch(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by A_u . B_i, counted
         on the GPU (``ops.ranks_batch``).  ``heldout``: (indptr, indices) CSR over the users OF THIS CALL or a SciPy CSR matrix
@@ -786,6 +823,10 @@ class CMF(_Base):
         one 1-D array shared by all: each user is ranked over its own list only."""
         ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None, include)
         return ids, self._finish_scores(np.atleast_1d(np.asarray(users, np.int64)), sc)
+
+    def topN_deep(self, users, n, exclude=None):
+        return _topN_deep(self, users, n, exclude, self.item_bias_ if self.item_bias else None)
+    topN_deep.__doc__ = _TOPN_DEEP_DOC
 
     def ranks_batch(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by

@@ -258,6 +258,46 @@ def topN_batch(A, B, n_top=10, biasB=None, exclude=None, include=None):
     return ids, sc
 
 
+def topN_deep_batch(A, B, n_top, biasB=None, exclude=None):
+    """``topN_batch`` without the limit of 128: (ids [nu, n_top] int32, scores [nu, n_top]) for any ``1 <= n_top <= items``,
+    k <= 272, built on the device in pages (``Ranker.topN_deep``); every k runs the MFMA kernel.  B is uploaded on every call:
+    to rank several batches against the same items, hold a ``cmfrec_amd.Ranker``."""
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B, A.dtype)
+    lib, R = _prep(A, B)
+    nu, lda = A.shape
+    n, ldb = B.shape
+    n_top = int(n_top)
+    ids = np.empty((nu, max(n_top, 0)), np.int32); sc = np.empty((nu, max(n_top, 0)), A.dtype)
+    bs = None if biasB is None else np.ascontiguousarray(biasB, A.dtype)
+    if exclude is not None and _is_csr(exclude):
+        exclude = (exclude.indptr, exclude.indices)
+    ep, ei = _sorted_exclude(exclude, nu)
+    rc = lib.cmfrec_hip_topN_deep_batch(_lib.ptr(A), C.c_size_t(lda), C.c_int(nu), _lib.ptr(B), C.c_size_t(ldb), C.c_int(n),
+                                        C.c_int(lda), _lib.ptr(bs), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n_top), _lib.ptr(ids),
+                                        _lib.ptr(sc))
+    _lib.check(rc, lib, "topN_deep_batch")
+    return ids, sc
+
+
+def after_cursor(after_ids, after_scores, nu, dtype, what):
+    """(ids int32 [nu], scores [nu] of ``dtype``) of a next-page call, checked without a device; (None, None) for the first
+    page.  One without the other, or anything but one entry per user, is a ValueError."""
+    if after_ids is None and after_scores is None:
+        return None, None
+    if after_ids is None or after_scores is None:
+        raise ValueError("%s: after_ids and after_scores come together (both None: the first page)" % what)
+    ai = np.asarray(after_ids); asc = np.asarray(after_scores)
+    if ai.shape != (nu,) or asc.shape != (nu,):
+        raise ValueError("%s: after_ids and after_scores must have one entry per user (%d), got shapes %s and %s"
+                         % (what, nu, ai.shape, asc.shape))
+    if not np.issubdtype(ai.dtype, np.integer):
+        raise ValueError("%s: after_ids must be integers, got %s" % (what, ai.dtype))
+    if asc.dtype != np.dtype(dtype):
+        raise ValueError("%s: after_scores is %s, the ranker's items are %s (a converted score is another cursor)"
+                         % (what, asc.dtype, np.dtype(dtype)))
+    return np.ascontiguousarray(ai, np.int32), np.ascontiguousarray(asc)
+
+
 def _heldout_lists(heldout, nu, what):
     """The held-out lists of a rank call through ``_sorted_include`` (ascending, unique, ids outside int32 -> -1)."""
     if heldout is None:

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _heldout_lists, _is_csr, _similar_args, _sorted_exclude, _sorted_include
+from .ops import _heldout_lists, _is_csr, _similar_args, _sorted_exclude, _sorted_include, after_cursor
 
 
 def check_rankset(users, heldout, exclude):
@@ -135,6 +135,59 @@ class Ranker:
                                              _lib.ptr(ids), _lib.ptr(sc))
         _lib.check(rc, self.lib, "Ranker.topN")
         return ids, sc
+
+    def _users(self, A, what):
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[1] != self.k:
+            raise ValueError("%s: A must be [users, %d], got shape %s" % (what, self.k, A.shape))
+        if A.dtype != self.dtype:
+            raise ValueError("%s: A is %s, the ranker's items are %s" % (what, A.dtype, self.dtype))
+        return np.ascontiguousarray(A)
+
+    def topN_deep(self, A, n, exclude=None):
+        """(ids [nu, n] int32, scores [nu, n]) as ``topN`` for any ``1 <= n <= items``: the list is built on the device in pages
+        of up to 512 positions, each page one pass of the MFMA kernel that admits only what lies strictly behind the previous
+        page's last (score, id); the result does not depend on the page length.  Every k runs the MFMA kernel, so the scores
+        have the bits of ``ranks`` (and of ``topN`` for k > 64 or under ``CMFREC_HIP_TOPN=wide``)."""
+        h = self._live()
+        A = self._users(A, "Ranker.topN_deep")
+        nu = A.shape[0]
+        n = int(n)
+        if exclude is not None and _is_csr(exclude):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, nu)
+        ids = np.empty((nu, max(n, 0)), np.int32); sc = np.empty((nu, max(n, 0)), self.dtype)
+        rc = self.lib.cmfrec_hip_ranker_topN_deep(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
+                                                  _lib.ptr(ids), _lib.ptr(sc))
+        _lib.check(rc, self.lib, "Ranker.topN_deep")
+        return ids, sc
+
+    def topN_after(self, A, after_ids, after_scores, n=10, exclude=None):
+        """The next page: (ids [nu, n], scores [nu, n]), the ``n <= min(128, items)`` best items of every user strictly behind its
+        cursor ``(after_scores[u], after_ids[u])`` in the order of ``topN`` -- typically the last column of the previous page,
+        ``ids[:, -1]`` / ``scores[:, -1]``.  Both None: the first page.  A user whose previous page ended in -1 / -inf gets
+        -1 / -inf throughout.  The cursor's item need not be rankable any more (it may be excluded now).  The cursor compares
+        score bits: it must come from ``topN_after``, ``topN_deep``, ``ranks`` or the MFMA ``topN`` (k > 64, or
+        ``CMFREC_HIP_TOPN=wide``); with a score of the default k <= 64 kernel a near tie may repeat or skip a neighbour."""
+        h = self._live()
+        A = self._users(A, "Ranker.topN_after")
+        nu = A.shape[0]
+        ai, asc = after_cursor(after_ids, after_scores, nu, self.dtype, "Ranker.topN_after")
+        n = int(n)
+        if exclude is not None and _is_csr(exclude):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, nu)
+        ids = np.empty((nu, max(n, 0)), np.int32); sc = np.empty((nu, max(n, 0)), self.dtype)
+        rc = self.lib.cmfrec_hip_ranker_topN_after(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(ep), _lib.ptr(ei), _lib.ptr(ai),
+                                                   _lib.ptr(asc), C.c_int(n), _lib.ptr(ids), _lib.ptr(sc))
+        _lib.check(rc, self.lib, "Ranker.topN_after")
+        return ids, sc
+
+    def pages(self):
+        """(launches, page length) of the most recent ``topN_deep`` call."""
+        p, l = C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.cmfrec_hip_ranker_pages(self._live(), C.byref(p), C.byref(l)), self.lib, "Ranker.pages")
+        return p.value, l.value
 
     def ranks(self, A, heldout, exclude=None, return_scores=False):
         """(indptr, items, ranks, pool) for the rows of ``A`` and their held-out lists, as ``ops.ranks_batch``: ``ranks[j]`` is

@@ -672,6 +672,36 @@ int cmfrec_hip_ranker_similar(cmfrec_hip_ranker *r, const int_t *query_ids, int_
                               int_t *out_ids, real_t *out_scores);
 int cmfrec_hip_similar_batch(const real_t *B, size_t ldb, int_t n, int_t k, const int_t *query_ids, int_t nq, int metric,
                              const size_t excl_p[], const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores);
+/* Deep lists and next pages: top-N without the limit of 128, and "items 21-40" without ranking the first 20 again.
+ * topN_deep: the n_top best of every user for any 1 <= n_top <= n (k <= 272 as everywhere; otherwise code 2, "needs k <= 272 and
+ * 1 <= n_top <= n", before anything touches the device).  Order, tie rule (lower id first), -1 / -inf filling, exclusion lists, NaN
+ * rule and out_scores == NULL are those of cmfrec_hip_ranker_topN.  The [nu, n_top] result is built on the device in pages: page p
+ * is one pass of the MFMA kernel's body (topn_after_kernels.hpp) that admits only the pairs strictly behind the last (score, id) of
+ * page p - 1 in the total order, read from the result itself -- no host round trip between the pages, one download at the end.  The
+ * result does not depend on the page length (128 by default; CMFREC_HIP_TOPN_PAGE = 1 .. 512 is a test hook).  Every k runs the MFMA
+ * kernel: a score has the bits cmfrec_hip_ranker_ranks and the MFMA top-N kernel give the pair, so for n_top <= 128 the result is
+ * that of cmfrec_hip_ranker_topN for k > 64 (for every k under CMFREC_HIP_TOPN=wide) bit for bit.  kernel_ms: the interval around
+ * all the pages; launch_shape: the last page's.  pages: the launches and the page length of the most recent topN_deep call on the
+ * handle (code 2 before the first).  cmfrec_hip_topN_deep_batch is create, one topN_deep call, destroy.
+ * topN_after: the next n_top <= min(128, n) items of every user strictly behind its cursor (after_scores[u], after_ids[u]) --
+ * [nu] each, typically the last column of the previous page; both NULL: the first page (one without the other: code 2).  A cursor
+ * of (+inf, -1) starts at the top; the (-inf, -1) an exhausted user's page ends with gives -1 / -inf throughout; so does a NaN
+ * cursor score.  The cursor's item need not be rankable: it may have been excluded since.  The cursor compares score bits, so the
+ * scores must come from this route: topN_after, topN_deep, ranker_ranks, or ranker_topN on the MFMA kernel (k > 64, or
+ * CMFREC_HIP_TOPN=wide).  The default kernel of k <= 64 rounds a score differently in the last bits: with a cursor from it, an item
+ * that nearly ties with the cursor's may be returned again or left out.
+ * Deep, next-page, top-N, candidate, rank and neighbour calls may be interleaved on one handle. */
+int cmfrec_hip_ranker_topN_deep(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                                const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                                int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_ranker_topN_after(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                                 const size_t excl_p[], const int_t excl_i[],
+                                 const int_t *after_ids, const real_t *after_scores, int_t n_top,
+                                 int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_topN_deep_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                               const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
+                               int_t *out_ids, real_t *out_scores);
+int cmfrec_hip_ranker_pages(cmfrec_hip_ranker *r, int *pages, int *page_len);
 int cmfrec_hip_ranker_inverse_norms(cmfrec_hip_ranker *r, real_t *out);
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
