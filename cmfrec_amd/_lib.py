@@ -127,6 +127,7 @@ EXPORTED = [
     "cmfrec_hip_ranker_create", "cmfrec_hip_ranker_topN", "cmfrec_hip_ranker_topN_candidates", "cmfrec_hip_topN_candidates_batch", "cmfrec_hip_ranker_ranks", "cmfrec_hip_ranks_batch", "cmfrec_hip_ranker_kernel_ms", "cmfrec_hip_ranker_launch_shape", "cmfrec_hip_ranker_destroy",
     "cmfrec_hip_ranker_similar", "cmfrec_hip_similar_batch", "cmfrec_hip_ranker_inverse_norms",
     "cmfrec_hip_ranker_topN_deep", "cmfrec_hip_ranker_topN_after", "cmfrec_hip_topN_deep_batch", "cmfrec_hip_ranker_pages",
+    "cmfrec_hip_ranker_set_split", "cmfrec_hip_ranker_slices", "cmfrec_hip_topn_split_plan", "cmfrec_hip_newrows_set_split",
     "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
     "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
     "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
@@ -193,6 +194,10 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_topN_deep_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
         [C.c_int, C.c_void_p, C.c_void_p]
     lib.cmfrec_hip_ranker_pages.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.cmfrec_hip_ranker_set_split.argtypes = [C.c_void_p, C.c_int]
+    lib.cmfrec_hip_ranker_slices.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.cmfrec_hip_topn_split_plan.argtypes = [C.c_int] * 5 + [C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.cmfrec_hip_newrows_set_split.argtypes = [C.c_void_p, C.c_int]
     nrm = newrows_model_mirror(dtype)
     lib.cmfrec_hip_newrows_create.restype = C.c_void_p
     lib.cmfrec_hip_newrows_create.argtypes = [C.POINTER(nrm), C.c_int]

@@ -1399,6 +1399,7 @@ struct cmfrec_hip_newrows {
     bool naz_X = false, naz_U = false;         // the missing-as-zero options (cmfrec_hip_newrows_create_ex)
     cmfhip::NewRowsState *state = nullptr;
     cmfrec_hip_ranker *ranker = nullptr;       // made by the first topN call
+    int split = -1;                            // cmfrec_hip_newrows_set_split: handed to the ranker when it is made
     cmfhip::PairScorer *scorer = nullptr;      // made by the first predict call
     bool has_C = false, has_biasB = false, has_Bi = false, has_means = false;
     int_t n_sparse = 0;                        // rows of B a sparse batch may index (n_max with include_all_X), n: a dense one
@@ -1671,6 +1672,7 @@ int cmfrec_hip_newrows_topN(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batc
         if (h->ranker == nullptr) {
             h->ranker = cmfhip::ranker_create_from_device(v.dB + h->mdl.k_item, v.ldB, v.n, kr, v.dbiasB, v.device);
             if (h->ranker == nullptr) return cmfhip::g_last_rc ? cmfhip::g_last_rc : 4;
+            (void)cmfrec_hip_ranker_set_split(h->ranker, h->split);
         }
         const size_t *dp = nullptr;
         const int *di = nullptr;
@@ -1700,6 +1702,7 @@ int cmfrec_hip_newrows_topN_candidates(cmfrec_hip_newrows *h, const cmfrec_hip_n
         if (h->ranker == nullptr) {
             h->ranker = cmfhip::ranker_create_from_device(v.dB + h->mdl.k_item, v.ldB, v.n, kr, v.dbiasB, v.device);
             if (h->ranker == nullptr) return cmfhip::g_last_rc ? cmfhip::g_last_rc : 4;
+            (void)cmfrec_hip_ranker_set_split(h->ranker, h->split);
         }
         const size_t *dp = nullptr;
         const int *di = nullptr;
@@ -1730,6 +1733,7 @@ int cmfrec_hip_newrows_ranks(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_bat
         if (h->ranker == nullptr) {
             h->ranker = cmfhip::ranker_create_from_device(v.dB + h->mdl.k_item, v.ldB, v.n, kr, v.dbiasB, v.device);
             if (h->ranker == nullptr) return cmfhip::g_last_rc ? cmfhip::g_last_rc : 4;
+            (void)cmfrec_hip_ranker_set_split(h->ranker, h->split);
         }
         const size_t *dp = nullptr;
         const int *di = nullptr;
@@ -1782,6 +1786,16 @@ int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_b
     // (a batch without rows leaves newrows_solve before it clears what the call before left: what the last call was is set here)
     if (rc == 0) { h->called = true; h->ranked = false; h->imputed = false; h->predicted = true; if (empty) h->solved = false; }
     return rc > 3 ? 1 : rc;
+}
+
+int cmfrec_hip_newrows_set_split(cmfrec_hip_newrows *h, int slices)
+{
+    if (h == nullptr || slices < -1) {
+        cmfhip::g_last_error = "cmfrec_hip_newrows_set_split: invalid arguments (-1: off, 0: the planner's choice, >= 1: that many slices)";
+        return 2;
+    }
+    h->split = slices;
+    return h->ranker ? cmfrec_hip_ranker_set_split(h->ranker, slices) : 0;
 }
 
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms)

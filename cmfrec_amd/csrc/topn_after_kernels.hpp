@@ -70,6 +70,8 @@ struct TopnAfterPolicy {
         return topn_before(cs[u], reinterpret_cast<const int *>(cs + UT)[u], s, item);
     }
     static __device__ __forceinline__ size_t out_stride(const Params &P) { return P.out_ld; }
+    static __device__ __forceinline__ int item_begin(const Params &) { return 0; }
+    static __device__ __forceinline__ int item_end(const Params &P) { return P.n; }
 };
 
 template <typename T, int NUT>

@@ -107,6 +107,8 @@ struct TopnSimilarPolicy {
         return reinterpret_cast<const int *>(reinterpret_cast<const T *>(xs) + UT)[u] != item;
     }
     static __device__ __forceinline__ size_t out_stride(const Params &P) { return (size_t)P.n_top; }
+    static __device__ __forceinline__ int item_begin(const Params &) { return 0; }
+    static __device__ __forceinline__ int item_end(const Params &P) { return P.n; }
 };
 
 template <typename T, int NUT, int METRIC>

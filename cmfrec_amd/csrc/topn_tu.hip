@@ -9,7 +9,9 @@
 // (cmfrec_hip_ranker_similar and its kin) launches topn_similar_kernel (topn_similar_kernels.hpp) for every k: the wide
 // kernel's body with the query tile gathered from the resident rows.  A deep or next-page call (cmfrec_hip_ranker_topN_deep /
 // _topN_after) launches topn_after_kernel (topn_after_kernels.hpp) for every k, once per page: the wide kernel's body behind a
-// per-user cursor.
+// per-user cursor.  A ranker whose split setting is on (cmfrec_hip_ranker_set_split) sends the full ranking, for every k, to the MFMA
+// arithmetic: topn_wide_kernel itself where the planner (cmfrec_hip_topn_split_plan) leaves the items whole, else
+// topn_split_kernel over slices of the items and topn_split_merge_kernel behind it (topn_split_kernels.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,6 +20,7 @@
 #include "device_base.hpp"
 #include "newrows.hpp"
 #include "topn_wide_kernels.hpp"
+#include "topn_split_kernels.hpp"
 #include "topn_similar_kernels.hpp"
 #include "topn_after_kernels.hpp"
 #include "topn_cand_kernels.hpp"
@@ -50,6 +53,10 @@ struct cmfrec_hip_ranker {
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the ranking kernel of the last call
     bool timed = false;
     int last_users = 0, last_grid = 0;       // users per workgroup and workgroups of that launch
+    int split = -1;                          // cmfrec_hip_ranker_set_split: -1 off, 0 the planner's choice, >= 1 that many slices
+    int last_slices = 1;                     // item slices of the last ranking launch
+    DevBuf<real_t> part_sc;                  // the slices' lists of a split call: [slices][nu][n_top]
+    DevBuf<int> part_id;
     ~cmfrec_hip_ranker()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -69,13 +76,13 @@ constexpr const char *DEEP_LIMITS = "needs k <= 272 and 1 <= n_top <= n";
 // (nut + 1/2) -- its MFMAs and the item fetch they share -- times the workgroups that share its CU.
 // CMFREC_HIP_TOPN_TILES (test hook) asks for a number of tiles; it is clamped to what fits.
 // extra_per_tile: LDS bytes per user tile beyond topnw_lds_bytes (the neighbour kernel's ids and inverse norms).
-int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu, size_t extra_per_tile = 0)
+int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu, size_t extra_per_tile = 0, size_t sizeof_real = sizeof(real_t))
 {
     const int forced = switches().topn_tiles;
     int best = 1, best_bpc = 1;
     double best_cost = 0;
     for (int nut = 1; nut <= TOPNW_MAX_NUT; nut++) {
-        const size_t smem = topnw_lds_bytes(nut, k, n_top, sizeof(real_t)) + nut * extra_per_tile;
+        const size_t smem = topnw_lds_bytes(nut, k, n_top, sizeof_real) + nut * extra_per_tile;
         if (smem > TOPNW_LDS_MAX) break;
         const int bpc = (int)std::min<size_t>(TOPNW_LDS_MAX / smem, (size_t)(2048 / TOPNW_TH));
         const long tiles = ((long)nu + 16 * nut - 1) / (16 * nut), slots = (long)num_cus * bpc;
@@ -96,6 +103,48 @@ int launch_wide(const cmfrec_hip_ranker::Device &dev, const TopnWideParams<real_
     const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
     hipLaunchKernelGGL((topn_wide_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
     return grid;
+}
+
+// Item slices of a full ranking: the user tiles of pick_user_tiles fill `tiles` of the device's
+// num_cus * blocks_per_cu workgroup slots; while slots stay empty the items are cut so that tiles * slices fills them, but never
+// into slices of fewer than TOPNSP_MIN_ROUNDS rounds of TOPNW_ITEMS items -- below that the slice pass costs what it saves (the
+// user tile is loaded, every slice's list is written, merged and read again).  requested >= 1 asks for that many slices and is
+// held to the rounds there are and to TOPNSP_MAX_SLICES.  The slices are equal but for the last: slice_items = rounds per slice
+// * TOPNW_ITEMS, slices = what that leaves non-empty.
+// PROVISIONAL: TOPNSP_MIN_ROUNDS and the use of every LDS-limited slot are to be set from tools/bench_topn_split.py's table.
+constexpr long TOPNSP_MIN_ROUNDS = 4;
+
+void plan_split(int nu, int n, int k, int n_top, int num_cus, size_t sizeof_real, int requested, int *slices, int *slice_items)
+{
+    const long rounds = std::max<long>(1, ((long)n + TOPNW_ITEMS - 1) / TOPNW_ITEMS);
+    long want = requested;
+    if (requested <= 0) {
+        int bpc = 1;
+        const int nut = pick_user_tiles(nu, k, n_top, num_cus, &bpc, 0, sizeof_real);
+        const long tiles = ((long)nu + 16 * nut - 1) / (16 * nut), slots = (long)num_cus * bpc;
+        want = tiles >= slots ? 1 : std::min(slots / tiles, std::max<long>(1, rounds / TOPNSP_MIN_ROUNDS));
+    }
+    want = std::max<long>(1, std::min<long>(want, std::min<long>(rounds, TOPNSP_MAX_SLICES)));
+    const long per = (rounds + want - 1) / want;
+    *slices = (int)((rounds + per - 1) / per);
+    *slice_items = (int)std::min<long>(per * TOPNW_ITEMS, ((long)0x7fffffff / TOPNW_ITEMS) * TOPNW_ITEMS);
+}
+
+// the slice pass and the merge of a split ranking: P.out_ids / P.out_scores are the scratch, `out` the call's result
+template <int NUT>
+int launch_split(const cmfrec_hip_ranker::Device &dev, const TopnSplitParams<real_t> &P, int blocks_per_cu, int slices,
+                 const TopnMergeParams<real_t> &M)
+{
+    const size_t smem = topnw_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
+    HIP_CHECK(hipFuncSetAttribute((const void *)topn_split_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
+    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
+    hipLaunchKernelGGL((topn_split_kernel<real_t, NUT>), dim3(grid, slices), dim3(TOPNW_TH), smem, dev.stream, P);
+    HIP_CHECK(hipGetLastError());
+    const int nw = topnsp_merge_waves(slices);
+    hipLaunchKernelGGL(topn_split_merge_kernel<real_t>, dim3(P.nu), dim3(64 * nw), topnsp_merge_lds_bytes(nw, P.n_top, sizeof(real_t)),
+                       dev.stream, M);
+    return grid * slices;
 }
 
 template <int NUT, int METRIC>
@@ -207,6 +256,15 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
         r->next.alloc_at_least(1);
         HIP_CHECK(hipMemsetAsync(r->next.ptr, 0, sizeof(unsigned), dev.stream));
     }
+    // a split ranker: the full ranking of every k on the MFMA arithmetic, over as many item slices as the planner gives it
+    const bool split = dcand_p == nullptr && r->split >= 0;
+    int slices = 1, slice_items = 0;
+    if (split) plan_split(nu, r->n, k, n_top, dev.num_cus, sizeof(real_t), r->split, &slices, &slice_items);
+    if (slices > 1) {
+        r->part_sc.alloc_at_least((size_t)slices * (size_t)nu * (size_t)n_top);
+        r->part_id.alloc_at_least((size_t)slices * (size_t)nu * (size_t)n_top);
+    }
+    r->last_slices = slices;
     HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
     if (dcand_p) {
         TopnCandParams<real_t> P;
@@ -218,7 +276,26 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
         P.next = r->next.ptr; P.order = r->corder.ptr;
         r->last_grid = launch_topn_cand(dev.stream, dev.num_cus, P, switches().topn_cand_waves);
         r->last_users = TOPNC_NW;
-    } else if (k <= TOPN_KMAX && !switches().topn_wide) {
+    } else if (slices > 1) {
+        TopnSplitParams<real_t> P;
+        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
+        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+        P.n_top = n_top; P.out_ids = r->part_id.ptr; P.out_scores = r->part_sc.ptr;
+        P.slice_items = slice_items; P.s0 = P.s1 = 0;
+        TopnMergeParams<real_t> M;
+        M.part_scores = r->part_sc.ptr; M.part_ids = r->part_id.ptr; M.slices = slices; M.nu = nu; M.n_top = n_top;
+        M.out_ids = r->ids.ptr; M.out_scores = out_scores ? r->sc.ptr : nullptr;
+        int bpc = 1;
+        const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
+        switch (nut) {
+        case 1: r->last_grid = launch_split<1>(dev, P, bpc, slices, M); break;
+        case 2: r->last_grid = launch_split<2>(dev, P, bpc, slices, M); break;
+        case 3: r->last_grid = launch_split<3>(dev, P, bpc, slices, M); break;
+        default: r->last_grid = launch_split<4>(dev, P, bpc, slices, M); break;
+        }
+        r->last_users = 16 * nut;
+    } else if (k <= TOPN_KMAX && !switches().topn_wide && !split) {
         TopnParams<real_t> P;
         P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
         P.biasB = r->has_bias ? r->bias.ptr : nullptr;
@@ -313,6 +390,7 @@ int rank_device_deep(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t n
     }
     HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
     r->timed = true;
+    r->last_slices = 1;
     r->ids.download(out_ids, cells, dev.stream);
     if (out_scores) r->sc.download(out_scores, cells, dev.stream);
     HIP_CHECK(hipStreamSynchronize(dev.stream));
@@ -399,6 +477,7 @@ int ranks_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, s
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
     r->timed = true;
+    r->last_slices = 1;
     if (stay) return 0;
     r->ids.download(out_rank, total, dev.stream);
     if (out_scores) r->sc.download(out_scores, total, dev.stream);
@@ -904,6 +983,7 @@ int cmfrec_hip_ranker_similar(cmfrec_hip_ranker *r, const int_t *query_ids, int_
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
         r->timed = true;
+        r->last_slices = 1;
         r->ids.download(out_ids, (size_t)nq * n_top, dev.stream);
         if (out_scores) r->sc.download(out_scores, (size_t)nq * n_top, dev.stream);
         HIP_CHECK(hipStreamSynchronize(dev.stream));
@@ -940,6 +1020,38 @@ int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms)
         *ms = (double)t;
         return 0;
     });
+}
+
+int cmfrec_hip_ranker_set_split(cmfrec_hip_ranker *r, int slices)
+{
+    if (r == nullptr || slices < -1) {
+        g_last_error = "cmfrec_hip_ranker_set_split: invalid arguments (-1: off, 0: the planner's choice, >= 1: that many slices)";
+        return 2;
+    }
+    r->split = slices;
+    return 0;
+}
+
+int cmfrec_hip_ranker_slices(cmfrec_hip_ranker *r, int *slices)
+{
+    if (r == nullptr || slices == nullptr || !r->timed) {
+        g_last_error = "cmfrec_hip_ranker_slices: no ranking call on this handle yet";
+        return 2;
+    }
+    *slices = r->last_slices;
+    return 0;
+}
+
+int cmfrec_hip_topn_split_plan(int_t nu, int_t n, int_t k, int_t n_top, int num_cus, size_t sizeof_real, int requested, int *slices,
+                               int *slice_items)
+{
+    if (nu <= 0 || n <= 0 || k <= 0 || k > TOPNW_KMAX || n_top <= 0 || n_top > TOPN_NMAX || n_top > n || num_cus <= 0 ||
+        (sizeof_real != 4 && sizeof_real != 8) || requested < 0 || slices == nullptr || slice_items == nullptr) {
+        g_last_error = std::string("cmfrec_hip_topn_split_plan: invalid arguments (") + LIMITS + "; sizeof_real 4 or 8; requested >= 0)";
+        return 2;
+    }
+    plan_split(nu, n, k, n_top, num_cus, sizeof_real, requested, slices, slice_items);
+    return 0;
 }
 
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups)

@@ -74,6 +74,8 @@ struct TopnWideParams {
 //   admit(xs, UT, u, item, score)  false: the pair is skipped -- asked once per pair, ahead of the exclusion list, not again
 //                                  when a candidate is offered a second time
 //   out_stride(P)                  elements between two users' rows of out_ids / out_scores
+//   item_begin(P), item_end(P)     the items [begin, end) the workgroup ranks: 0 and P.n, but for a slice of the items
+//                                  (topn_split_kernels.hpp) -- begin a multiple of TOPNW_ITEMS, so the rows keep their lanes
 template <typename T>
 struct TopnWidePolicy {
     using Params = TopnWideParams<T>;
@@ -88,6 +90,8 @@ struct TopnWidePolicy {
     static __device__ __forceinline__ T score(T acc, T bias, const unsigned char *, int, int) { return acc + bias; }
     static __device__ __forceinline__ bool admit(const unsigned char *, int, int, int, T) { return true; }
     static __device__ __forceinline__ size_t out_stride(const Params &P) { return (size_t)P.n_top; }
+    static __device__ __forceinline__ int item_begin(const Params &) { return 0; }
+    static __device__ __forceinline__ int item_end(const Params &P) { return P.n; }
 };
 
 template <typename T, int NUT, typename POL>
@@ -113,6 +117,7 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
     unsigned char *xs = reinterpret_cast<unsigned char *>(flag + 2);   // the policy's own (8-byte aligned: UT * LS + UT + 2 ints)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 15, grp = lane >> 4;
+    const int i0 = POL::item_begin(P), i1 = POL::item_end(P);       // the items of this workgroup's pass
     const T NEG = -INFINITY;
     int turn = 0;                                                   // merges so far (uniform): which flag is live
     if (tid < 2) flag[tid] = 0;
@@ -127,13 +132,13 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
         // the item rows arrive through a ring of PF loads in flight per lane: a chunk's load is issued PF chunks ahead, and the
         // first PF of the NEXT round before this round's filter and merge, so those overlap the fetch
         auto item_row = [&](int c0) { return P.B + (size_t)min(c0 + 16 * wave + col, P.n - 1) * P.ldb + grp * V; };
-        const T *brow = item_row(0);
+        const T *brow = item_row(i0);
         ldv bq[PF];
 #pragma unroll
         for (int p = 0; p < PF; p++) bq[p] = *reinterpret_cast<const ldv *>(brow + min(p, nchunk - 1) * CH);
-        for (int c0 = 0; c0 < P.n; c0 += TOPNW_ITEMS) {
+        for (int c0 = i0; c0 < i1; c0 += TOPNW_ITEMS) {
             const int item = c0 + 16 * wave + col;
-            const bool live = item < P.n;
+            const bool live = item < i1;
             const auto iv = POL::item_value(P, item, live);
             vec acc[NUT];
 #pragma unroll

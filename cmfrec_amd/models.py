@@ -47,6 +47,12 @@ class _Base:
     def _lib(self):
         return _lib.load(self.dtype_), _lib.real(self.dtype_)
 
+    def close(self):
+        """Releases the resident handles the one-user methods (``topN``, ``topN_warm``, ...) keep on the model; the next such
+        call makes new ones.  ``fit()`` calls it, and so does garbage collection."""
+        from . import one_user
+        one_user.release(self)
+
 
 def _topN_inputs(self, users, exclude):
     """(user ids, their factors, their exclusion lists) of a ranking call on a fitted model."""
@@ -93,11 +99,11 @@ class ModelRanker:
     device by a ``cmfrec_amd.Ranker``; ``topN(users, n, exclude, include)`` takes user ids of the fitted model and returns what the
     model's ``topN_batch`` returns.  The caller closes it (``close()`` or a ``with`` block); a refit needs a new one."""
 
-    def __init__(self, model, biasB):
+    def __init__(self, model, biasB, split=None):
         from .rank import Ranker
         self._model = model
         self._ranker = Ranker(np.ascontiguousarray(model.B_[:, model.k_item:]),
-                              None if biasB is None else np.ascontiguousarray(biasB, model.B_.dtype))
+                              None if biasB is None else np.ascontiguousarray(biasB, model.B_.dtype), split=split)
 
     def topN(self, users, n=10, exclude=None, include=None):
         users, A, excl = _topN_inputs(self._model, users, exclude)
@@ -139,6 +145,10 @@ class ModelRanker:
 
     def kernel_ms(self):
         return self._ranker.kernel_ms()
+
+    def slices(self):
+        """Item slices of the most recent ranking launch (``Ranker.slices``)."""
+        return self._ranker.slices()
 
     def close(self):
         self._ranker.close()
@@ -435,6 +445,7 @@ class CMF_implicit(_Base):
         information without missing values, or SciPy sparse matrices (missing = absent).
         ``validation``: a ``cmfrec_amd.Validation`` -- a held-out set evaluated on the device while fitting, early stopping and the
         best iterate (default metric "ndcg" at ``k=10``, the training items left out of every ranking)."""
+        self.close()                                # the one-user handles hold the factors of the fit that was
         row, col, val, m, n = _coo_triplet(X, shape)
         lib, R = self._lib()
         dt = self.dtype_
@@ -599,6 +610,47 @@ class CMF_implicit(_Base):
         with self.new_users() as nu:
             return nu.predict(X=X, U=U, row=row, item=item)
 
+    # ---- the reference's one-user interface (cmfrec_amd/one_user.py): batches of one on two resident handles, a ModelRanker and
+    # a NewUsers with split="auto", made by the first call and released by fit() / close().  Every k is scored by the MFMA
+    # kernel: for k <= 64 the scores agree with topN_batch up to rounding, not in bits.
+    def topN(self, user, n=10, include=None, exclude=None, output_score=False):
+        """The ``n`` best items of one user of the fit (reference ``CMF_implicit.topN``): ids [n], or ``(ids, scores)`` with
+        ``output_score``.  Nothing is excluded unless ``exclude`` (item ids) says so; ``include`` (item ids) ranks over those
+        items only; the two together raise ``ValueError``.  ``topN_batch([user], ...)`` row 0 from a resident ranker."""
+        from . import one_user
+        return one_user.topN(self, user, n, include, exclude, output_score)
+
+    def topN_warm(self, n=10, X_col=None, X_val=None, U=None, U_col=None, U_val=None, include=None, exclude=None, output_score=False):
+        """The ``n`` best items of a new user from its interactions ``X_col`` / ``X_val`` (and attributes ``U``, or ``U_col`` /
+        ``U_val``), reference ``CMF_implicit.topN_warm``: ``topN_new_batch`` of one row with ``exclude_seen=False``."""
+        from . import one_user
+        return one_user.topN_new(self, n, None, X_col, X_val, None, U, None, U_col, U_val, include, exclude, output_score, True)
+
+    def topN_cold(self, n=10, U=None, U_col=None, U_val=None, include=None, exclude=None, output_score=False):
+        """The ``n`` best items of a new user from its attributes alone (reference ``CMF_implicit.topN_cold``)."""
+        from . import one_user
+        return one_user.topN_new(self, n, None, None, None, None, U, None, U_col, U_val, include, exclude, output_score, False)
+
+    def factors_warm(self, X_col, X_val, U=None, U_col=None, U_val=None):
+        """The factors [k_user + k + k_main] of a new user (reference ``CMF_implicit.factors_warm``): ``factors_multiple`` row 0."""
+        from . import one_user
+        return one_user.factors_new(self, None, X_col, X_val, None, U, None, U_col, U_val, False, True)
+
+    def factors_cold(self, U=None, U_col=None, U_val=None):
+        """The factors of a new user from its attributes alone (reference ``CMF_implicit.factors_cold``)."""
+        from . import one_user
+        return one_user.factors_new(self, None, None, None, None, U, None, U_col, U_val, False, False)
+
+    def predict_warm(self, items, X_col, X_val, U=None, U_col=None, U_val=None):
+        """The scores [len(items)] of a new user for ``items`` (reference ``CMF_implicit.predict_warm``)."""
+        from . import one_user
+        return one_user.predict_new(self, items, None, X_col, X_val, None, U, None, U_col, U_val, True)
+
+    def predict_cold(self, items, U=None, U_col=None, U_val=None):
+        """The scores [len(items)] of a new user for ``items`` from its attributes alone (reference ``CMF_implicit.predict_cold``)."""
+        from . import one_user
+        return one_user.predict_new(self, items, None, None, None, None, U, None, U_col, U_val, False)
+
     def predict(self, user, item):
         """A_u . B_i for paired user / item ids (reference predict_multiple, common.c:5066-5106).  NumPy on the host;
         ``predict_batch`` scores the pairs on the device."""
@@ -661,6 +713,7 @@ class CMF(_Base):
         ``CMF.fit(X, ..., W=...)``, cmfrec/__init__.py:3066; an array(nnz,) for sparse ``X``, an array(m, n) for dense ``X``).
         ``validation``: a ``cmfrec_amd.Validation`` -- a held-out set evaluated on the device while fitting (default metric
         "rmse"), early stopping and the best iterate; the model then has ``validation_history_``, ``best_iteration_``, ``n_iter_``."""
+        self.close()                                # the one-user handles hold the factors of the fit that was
         lib, R = self._lib()
         dt = self.dtype_
         Xfull = None
@@ -904,6 +957,51 @@ class CMF(_Base):
         ``predict_new``; C function predict_X_new_collective_explicit): one ``new_users()`` handle made, used and closed."""
         with self.new_users() as nu:
             return nu.predict(X=X, U=U, W=W, row=row, item=item)
+
+    # ---- the reference's one-user interface (cmfrec_amd/one_user.py): batches of one on two resident handles, a ModelRanker and
+    # a NewUsers with split="auto", made by the first call and released by fit() / close().  Every k is scored by the MFMA
+    # kernel: for k <= 64 the scores agree with topN_batch up to rounding, not in bits.
+    def topN(self, user, n=10, include=None, exclude=None, output_score=False):
+        """The ``n`` best items of one user of the fit (reference ``CMF.topN``): ids [n], or ``(ids, scores)`` with
+        ``output_score`` -- the scores of ``topN_batch``, global mean and biases included.  Nothing is excluded unless ``exclude``
+        (item ids) says so; ``include`` (item ids) ranks over those items only; the two together raise ``ValueError``.
+        ``topN_batch([user], ...)`` row 0 from a resident ranker."""
+        from . import one_user
+        return one_user.topN(self, user, n, include, exclude, output_score)
+
+    def topN_warm(self, n=10, X=None, X_col=None, X_val=None, W=None, U=None, U_bin=None, U_col=None, U_val=None, include=None,
+                  exclude=None, output_score=False):
+        """The ``n`` best items of a new user from its ratings -- ``X`` [items] dense with NaN, or ``X_col`` / ``X_val`` -- weights
+        ``W`` in the same form, attributes ``U`` [p] or ``U_col`` / ``U_val`` (reference ``CMF.topN_warm``): ``topN_new_batch`` of
+        one row with ``exclude_seen=False``.  ``U_bin`` raises ``ValueError``: the reference takes it with L-BFGS only."""
+        from . import one_user
+        return one_user.topN_new(self, n, X, X_col, X_val, W, U, U_bin, U_col, U_val, include, exclude, output_score, True)
+
+    def topN_cold(self, n=10, U=None, U_bin=None, U_col=None, U_val=None, include=None, exclude=None, output_score=False):
+        """The ``n`` best items of a new user from its attributes alone (reference ``CMF.topN_cold``)."""
+        from . import one_user
+        return one_user.topN_new(self, n, None, None, None, None, U, U_bin, U_col, U_val, include, exclude, output_score, False)
+
+    def factors_warm(self, X=None, X_col=None, X_val=None, W=None, U=None, U_bin=None, U_col=None, U_val=None, return_bias=False):
+        """The factors [k_user + k + k_main] of a new user, with ``return_bias`` ``(factors, bias)`` (reference
+        ``CMF.factors_warm``): ``factors_multiple`` row 0."""
+        from . import one_user
+        return one_user.factors_new(self, X, X_col, X_val, W, U, U_bin, U_col, U_val, return_bias, True)
+
+    def factors_cold(self, U=None, U_bin=None, U_col=None, U_val=None):
+        """The factors of a new user from its attributes alone (reference ``CMF.factors_cold``)."""
+        from . import one_user
+        return one_user.factors_new(self, None, None, None, None, U, U_bin, U_col, U_val, False, False)
+
+    def predict_warm(self, items, X=None, X_col=None, X_val=None, W=None, U=None, U_bin=None, U_col=None, U_val=None):
+        """The predictions [len(items)] of a new user for ``items`` (reference ``CMF.predict_warm``)."""
+        from . import one_user
+        return one_user.predict_new(self, items, X, X_col, X_val, W, U, U_bin, U_col, U_val, True)
+
+    def predict_cold(self, items, U=None, U_bin=None, U_col=None, U_val=None):
+        """The predictions [len(items)] of a new user for ``items`` from its attributes alone (reference ``CMF.predict_cold``)."""
+        from . import one_user
+        return one_user.predict_new(self, items, None, None, None, None, U, U_bin, U_col, U_val, False)
 
     def predict(self, user, item):
         """glob_mean + biasA[u] + biasB[i] + A_u . B_i (reference predict_multiple, common.c:5098-5106).  NumPy on the host;

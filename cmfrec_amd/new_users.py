@@ -16,10 +16,13 @@ def _has(M):
 
 class NewUsers:
     """What ``CMF.new_users()`` / ``CMF_implicit.new_users()`` return.  The caller owns the handle: ``close()`` it, or use it as a
-    context manager; a refit needs a new one.  Calls on one handle must not overlap."""
+    context manager; a refit needs a new one.  Calls on one handle must not overlap.
+    ``split``: None, ``"auto"`` or a number of slices, as ``Ranker`` takes it -- for the full ranking of ``topN`` (without ``include``)."""
 
-    def __init__(self, model, device=-1):
+    def __init__(self, model, device=-1, split=None):
+        from .rank import split_code
         self.handle = None
+        code = split_code(split, "NewUsers: split")
         if not getattr(model, "is_fitted_", False):
             raise ValueError("NewUsers: the model is not fitted")
         self._model = model
@@ -85,6 +88,9 @@ class NewUsers:
         if not h:
             _lib.check(lib.cmfrec_hip_last_error_code() or 4, lib, "NewUsers")
         self.handle = C.c_void_p(h)
+        self.split = split
+        if code != -1:
+            _lib.check(lib.cmfrec_hip_newrows_set_split(self.handle, C.c_int(code)), lib, "NewUsers")
 
     def _live(self):
         if not getattr(self, "handle", None):

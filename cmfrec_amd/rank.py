@@ -72,13 +72,44 @@ class RankSet:
             pass
 
 
-class Ranker:
-    """``Ranker(B, biasB=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype or None.
-    ``topN(A, n=10, exclude=None, include=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns the handle:
-    ``close()`` it, or use it as a context manager."""
+def split_code(split, what="split"):
+    """The C code of a ``split`` setting: None -> -1 (off), "auto" -> 0 (the planner chooses), an int >= 1 -> that many slices."""
+    if split is None:
+        return -1
+    if isinstance(split, str):
+        if split == "auto":
+            return 0
+        raise ValueError("%s must be None, \"auto\" or a number of slices >= 1, got %r" % (what, split))
+    if isinstance(split, (bool, float)) or int(split) != split or int(split) < 1:
+        raise ValueError("%s must be None, \"auto\" or a number of slices >= 1, got %r" % (what, split))
+    return int(split)
 
-    def __init__(self, B, biasB=None, device=-1):
+
+def split_plan(nu, n, k, n_top, num_cus=256, dtype=np.float64, requested=0):
+    """(slices, slice_items) of ``cmfrec_hip_topn_split_plan``: how a full ranking of ``nu`` users over ``n`` items would be cut
+    on a device of ``num_cus`` compute units; ``requested`` = 0 to let the planner choose, >= 1 to ask for that many slices.
+    Host arithmetic only: no device is needed."""
+    lib = _lib.load(dtype)
+    s, si = C.c_int(0), C.c_int(0)
+    rc = lib.cmfrec_hip_topn_split_plan(int(nu), int(n), int(k), int(n_top), int(num_cus), C.c_size_t(np.dtype(dtype).itemsize),
+                                        int(requested), C.byref(s), C.byref(si))
+    _lib.check(rc, lib, "split_plan")
+    return s.value, si.value
+
+
+class Ranker:
+    """``Ranker(B, biasB=None, device=-1, split=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype
+    or None.  ``topN(A, n=10, exclude=None, include=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns
+    the handle: ``close()`` it, or use it as a context manager.
+    ``split``: None (the default, every call as it always was), ``"auto"`` or a number of slices: the full ranking of ``topN``
+    (without ``include``) cuts the items into slices across the device and merges the slices' lists -- what makes a request of a
+    few users use more than one compute unit.  With it on, every k is scored by the MFMA kernel: ids and scores are those of
+    ``CMFREC_HIP_TOPN=wide`` bit for bit, whatever the number of slices; for k <= 64 they agree with the default kernel up to
+    rounding.  ``include``, ``topN_deep`` / ``topN_after``, ``ranks``, ``metrics`` and ``similar`` ignore the setting."""
+
+    def __init__(self, B, biasB=None, device=-1, split=None):
         self.handle = None
+        code = split_code(split, "Ranker: split")
         B = np.asarray(B)
         if B.ndim != 2:
             raise ValueError("Ranker: B must be 2-D [items, factors], got %d-D" % B.ndim)
@@ -102,6 +133,26 @@ class Ranker:
         if not h:
             _lib.check(self.lib.cmfrec_hip_last_error_code() or 4, self.lib, "Ranker")
         self.handle = C.c_void_p(h)
+        self._split = None
+        if code != -1:
+            self.split = split
+
+    @property
+    def split(self):
+        """None, "auto" or the number of slices asked for (``cmfrec_hip_ranker_set_split``); assignable."""
+        return self._split
+
+    @split.setter
+    def split(self, value):
+        code = split_code(value, "Ranker: split")
+        _lib.check(self.lib.cmfrec_hip_ranker_set_split(self._live(), C.c_int(code)), self.lib, "Ranker.split")
+        self._split = value
+
+    def slices(self):
+        """Item slices of the most recent ranking launch: 1 when it was not split."""
+        s = C.c_int(0)
+        _lib.check(self.lib.cmfrec_hip_ranker_slices(self._live(), C.byref(s)), self.lib, "Ranker.slices")
+        return s.value
 
     def _live(self):
         if not getattr(self, "handle", None):
@@ -270,7 +321,8 @@ class Ranker:
 
     def kernel_ms(self):
         """HIP-event time (ms) of the ranking kernel of the most recent ``topN``, ``ranks`` or ``similar`` call (of ``ranks``: the
-        whole rank kernel, its threshold and exclusion steps included; of ``similar``: without the norm kernel)."""
+        whole rank kernel, its threshold and exclusion steps included; of ``similar``: without the norm kernel; of a split ``topN``:
+        the slice pass and the merge)."""
         ms = C.c_double(0)
         _lib.check(self.lib.cmfrec_hip_ranker_kernel_ms(self._live(), C.byref(ms)), self.lib, "Ranker.kernel_ms")
         return ms.value

@@ -705,6 +705,30 @@ int cmfrec_hip_ranker_pages(cmfrec_hip_ranker *r, int *pages, int *page_len);
 int cmfrec_hip_ranker_inverse_norms(cmfrec_hip_ranker *r, real_t *out);
 int cmfrec_hip_ranker_kernel_ms(cmfrec_hip_ranker *r, double *ms);
 int cmfrec_hip_ranker_launch_shape(cmfrec_hip_ranker *r, int *users_per_workgroup, int *workgroups);
+
+/* The full ranking of a few users across the whole device.  The MFMA ranking kernel gives a whole pass
+ * over the items to the workgroup that owns a tile of 16..64 users, so a request of one user runs on one compute unit.  With the
+ * split setting on, the items of a full ranking are cut into slices, every (user tile, slice) is a workgroup of its own, and a
+ * second kernel on the same stream merges the slices' lists per user.
+ * set_split: slices = -1 off (the default: exactly the launches of a handle that never heard of it), 0 = the number
+ * cmfrec_hip_topn_split_plan chooses per call, >= 1 = that many, held to what the planner allows.  The setting affects the full
+ * ranking only: cmfrec_hip_ranker_topN without candidates and cmfrec_hip_newrows_topN.  Candidate lists, topN_deep / topN_after,
+ * ranks, metrics and similar ignore it.  With the setting on, EVERY k takes the MFMA arithmetic, also k <= 64: ids and scores are
+ * bit for bit those of the unsplit MFMA kernel (CMFREC_HIP_TOPN=wide for k <= 64) whatever the number of slices; against the
+ * register-resident kernel of k <= 64 the scores agree up to rounding.  Limits and return codes as cmfrec_hip_ranker_topN.
+ * slices: the item slices of the most recent ranking launch on the handle, 1 when it was not split (return code 2 before the
+ * first call).  cmfrec_hip_ranker_kernel_ms spans the slice pass and the merge; cmfrec_hip_ranker_launch_shape's workgroups are
+ * those of the slice pass (user-tile workgroups times slices).
+ * cmfrec_hip_newrows_set_split: the same setting for the ranker inside a new-rows handle, made now or later.
+ * cmfrec_hip_topn_split_plan: the planner, host arithmetic only (no device is touched): for nu users, n items, k factors and lists
+ * of n_top on a device of num_cus compute units and elements of sizeof_real bytes (4 or 8), requested = 0 to choose or >= 1 to
+ * ask: *slices >= 1 and *slice_items, a multiple of 128 with slices * slice_items >= n > (slices - 1) * slice_items.  It splits
+ * only while the user tiles alone leave workgroup slots of the device empty, and never into slices shorter than a measured
+ * minimum.  Return code 2 for arguments outside cmfrec_hip_ranker_topN's limits. */
+int cmfrec_hip_ranker_set_split(cmfrec_hip_ranker *r, int slices);
+int cmfrec_hip_ranker_slices(cmfrec_hip_ranker *r, int *slices);
+int cmfrec_hip_topn_split_plan(int_t nu, int_t n, int_t k, int_t n_top, int num_cus, size_t sizeof_real, int requested,
+                               int *slices, int *slice_items);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
 
 /* New rows against a model that stays on the device: factors and top-N of users who were not part of the fit, batch after
@@ -812,6 +836,7 @@ int cmfrec_hip_newrows_impute(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_ba
 int cmfrec_hip_newrows_predict(cmfrec_hip_newrows *h, const cmfrec_hip_newrows_batch *batch, const int_t *row, const int_t *col,
                                size_t n_pairs, real_t *out, real_t *A, real_t *biasA);
 int cmfrec_hip_newrows_kernel_ms(cmfrec_hip_newrows *h, double *solve_ms, double *rank_ms);
+int cmfrec_hip_newrows_set_split(cmfrec_hip_newrows *h, int slices);   /* see cmfrec_hip_ranker_set_split */
 void cmfrec_hip_newrows_destroy(cmfrec_hip_newrows *h);
 /* One-shot form of a missing-as-zero batch: cmfrec_hip_newrows_create, one cmfrec_hip_newrows_factors, destroy -- the level-2
  * call beside cmfrec_hip_factors_multiple_ex for models with NA_as_zero_X / NA_as_zero_U set.  The codes of factors.
