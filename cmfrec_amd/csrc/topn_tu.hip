@@ -11,7 +11,10 @@
 // _topN_after) launches topn_after_kernel (topn_after_kernels.hpp) for every k, once per page: the wide kernel's body behind a
 // per-user cursor.  A ranker whose split setting is on (cmfrec_hip_ranker_set_split) sends the full ranking, for every k, to the MFMA
 // arithmetic: topn_wide_kernel itself where the planner (cmfrec_hip_topn_split_plan) leaves the items whole, else
-// topn_split_kernel over slices of the items and topn_split_merge_kernel behind it (topn_split_kernels.hpp).
+// topn_split_kernel over slices of the items and topn_split_merge_kernel behind it (topn_split_kernels.hpp).  A ranker whose filter
+// is on (cmfrec_hip_ranker_set_filter) sends cmfrec_hip_ranker_topN of n_top <= 64 through topn_filter_kernel (topn_filter_kernels.hpp,
+// launched from topn_filter_tu.hip), topn_filter_refine_kernel over the shortlists -- with the arithmetic of the kernel the call
+// would run unfiltered -- and topn_filter_certify_kernel; the users that are not certified take the route above in a second batch.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -25,6 +28,7 @@
 #include "topn_after_kernels.hpp"
 #include "topn_cand_kernels.hpp"
 #include "topn_rank_kernels.hpp"
+#include "topn_filter.hpp"
 #include "rank_metrics_kernels.hpp"
 
 using namespace cmfhip;
@@ -57,8 +61,18 @@ struct cmfrec_hip_ranker {
     int last_slices = 1;                     // item slices of the last ranking launch
     DevBuf<real_t> part_sc;                  // the slices' lists of a split call: [slices][nu][n_top]
     DevBuf<int> part_id;
+    int filter = 0;                          // cmfrec_hip_ranker_set_filter: 0 off, 1 the half-precision filter
+    TopnFilterImage fimg;                    // the image of B, built when the filter is switched on
+    DevBuf<int> f_short, f_state, f_cert;    // shortlists [nu][m], per-user state and certificate of a filtered call
+    DevBuf<float> f_tau, f_keys;
+    int fs_users = 0, fs_filtered = 0, fs_certified = 0;   // of the last cmfrec_hip_ranker_topN
+    bool fs_valid = false;
+    hipEvent_t fev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the filter, the refinement and the certificate
+    float f_ms[3] = {0, 0, 0};
     ~cmfrec_hip_ranker()
     {
+        for (hipEvent_t e : fev)
+            if (e) (void)hipEventDestroy(e);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (dev.stream) (void)hipStreamDestroy(dev.stream);
@@ -328,6 +342,76 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
     r->ids.download(out_ids, (size_t)nu * n_top, dev.stream);
     if (out_scores) r->sc.download(out_scores, (size_t)nu * n_top, dev.stream);
     HIP_CHECK(hipStreamSynchronize(dev.stream));
+    return 0;
+}
+
+// the image of the ranker's items, built on first use and again after the items changed; false: the filter cannot run on them
+bool ensure_filter_image(cmfrec_hip_ranker *r)
+{
+    if (!r->fimg.ready)
+        topn_filter_build_image(r->dev.stream, r->dev.num_cus, r->B.ptr, r->ldb, r->n, r->k, r->has_bias ? r->bias.ptr : nullptr, r->fimg);
+    return r->fimg.usable;
+}
+
+// shortlist length of a filtered call: topnf_m; CMFREC_HIP_TOPN_FILTER_M (test hook, 32 .. 128, read per call) forces it
+int filter_m(int_t n_top)
+{
+    const char *v = getenv("CMFREC_HIP_TOPN_FILTER_M");
+    return topnf_m((int)n_top, (v != nullptr && v[0] != 0) ? atoi(v) : 0);
+}
+
+TopnFilterParams<real_t> filter_params(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, int m)
+{
+    TopnFilterParams<real_t> P;
+    P.A = dA; P.lda = lda; P.nu = nu; P.Bh = r->fimg.Bh.ptr; P.n = r->n; P.k = r->k;
+    P.nb = r->fimg.nb.ptr; P.db = r->fimg.db.ptr; P.sb = r->fimg.sb;
+    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+    P.excl_p = nullptr; P.excl_i = nullptr; P.m = m;
+    P.short_ids = nullptr; P.tau = nullptr; P.state = nullptr; P.keys = nullptr;
+    return P;
+}
+
+// The filtered ranking of nu users whose factors dA [nu, lda] and exclusion lists are on the device:
+// topn_filter_kernel leaves a shortlist of m ids and the bound tau per user, topn_filter_refine_kernel ranks the shortlists with
+// the scores of the kernel rank_device would launch for this ranker (the same routing), topn_filter_certify_kernel compares.  ids / scores come down for every user, certified [nu] says whose are final.
+int rank_device_filtered(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
+                         int_t *out_ids, real_t *out_scores, int *certified)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    const int m = filter_m(n_top);
+    const size_t cells = (size_t)nu * (size_t)n_top;
+    r->ids.alloc_at_least(cells);
+    r->sc.alloc_at_least(cells);
+    r->f_short.alloc_at_least((size_t)nu * (size_t)m);
+    r->f_state.alloc_at_least((size_t)nu);
+    r->f_cert.alloc_at_least((size_t)nu);
+    r->f_tau.alloc_at_least((size_t)nu);
+    for (hipEvent_t &e : r->fev)
+        if (!e) HIP_CHECK(hipEventCreate(&e));
+    TopnFilterParams<real_t> F = filter_params(r, dA, lda, nu, m);
+    F.excl_p = dexcl_p; F.excl_i = dexcl_p ? dexcl_i : nullptr;
+    F.short_ids = r->f_short.ptr; F.tau = r->f_tau.ptr; F.state = r->f_state.ptr;
+    HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    HIP_CHECK(hipEventRecord(r->fev[0], dev.stream));
+    r->last_grid = topn_filter_launch(dev.stream, dev.num_cus, F, switches().topn_tiles, &r->last_users);
+    HIP_CHECK(hipEventRecord(r->fev[1], dev.stream));
+    TopnRefineParams<real_t> P;
+    P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
+    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+    P.short_ids = r->f_short.ptr; P.m = m;
+    P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = r->sc.ptr;
+    topn_filter_refine(dev.stream, dev.num_cus, P, !(r->k <= TOPN_KMAX && !switches().topn_wide));
+    HIP_CHECK(hipEventRecord(r->fev[2], dev.stream));
+    topn_filter_certify(dev.stream, r->sc.ptr, nu, n_top, r->f_tau.ptr, r->f_state.ptr, r->f_cert.ptr);
+    HIP_CHECK(hipEventRecord(r->fev[3], dev.stream));
+    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
+    r->timed = true;
+    r->last_slices = 1;
+    r->ids.download(out_ids, cells, dev.stream);
+    if (out_scores) r->sc.download(out_scores, cells, dev.stream);
+    r->f_cert.download(certified, (size_t)nu, dev.stream);
+    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    for (int s = 0; s < 3; s++) HIP_CHECK(hipEventElapsedTime(&r->f_ms[s], r->fev[s], r->fev[s + 1]));
     return 0;
 }
 
@@ -635,6 +719,7 @@ int rankset_run_on_factors(cmfrec_hip_ranker **owned, cmfrec_hip_rankset *set, c
         DeviceScope scope(device);
         upload_columns(r->B.ptr, r->ldb, dB, ldB, (size_t)n, (size_t)kk, r->dev.stream);
         r->has_rn = false;                                   // (norms of the rows that were)
+        r->fimg.ready = false;                               // (and their image)
         if (dbiasB) r->bias.upload(dbiasB, (size_t)n, r->dev.stream);
     }
     memset(out, 0, sizeof *out);
@@ -707,7 +792,116 @@ int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, in
             r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
             if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
         }
-        return rank_device(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids, out_scores);
+        r->fs_valid = true; r->fs_users = nu; r->fs_filtered = 0; r->fs_certified = 0;
+        // the filter: n_top <= 64 of a ranker that is not split and whose items have an image; everything else as it always was
+        if (r->filter != 1 || n_top > TOPNF_NTOP_MAX || r->split >= 0 || !ensure_filter_image(r))
+            return rank_device(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids, out_scores);
+        std::vector<int> cert((size_t)nu);
+        if (int rc = rank_device_filtered(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids,
+                                          out_scores, cert.data()))
+            return rc;
+        // the users without a certificate: one batch on the exact route, their rows scattered into the result
+        std::vector<int_t> rest;
+        for (int_t u = 0; u < nu; u++)
+            if (!cert[u]) rest.push_back(u);
+        r->fs_filtered = nu; r->fs_certified = nu - (int)rest.size();
+        if (rest.empty()) return 0;
+        const size_t nr = rest.size();
+        std::vector<real_t> Ar(nr * (size_t)k), sr(out_scores ? nr * (size_t)n_top : 0);
+        std::vector<int_t> ir(nr * (size_t)n_top), xi;
+        std::vector<size_t> xp(excl_p ? nr + 1 : 0, 0);
+        for (size_t j = 0; j < nr; j++) {
+            const int_t u = rest[j];
+            memcpy(&Ar[j * (size_t)k], A + (size_t)u * lda, (size_t)k * sizeof(real_t));
+            if (excl_p) {
+                xi.insert(xi.end(), excl_i + excl_p[u], excl_i + excl_p[u + 1]);
+                xp[j + 1] = xi.size();
+            }
+        }
+        upload_columns(r->A.ptr, (size_t)k, Ar.data(), (size_t)k, nr, (size_t)k, dev.stream);
+        if (excl_p) {
+            r->ep.upload(xp.data(), nr + 1, dev.stream);
+            if (!xi.empty()) r->ei.upload(xi.data(), xi.size(), dev.stream);
+        }
+        if (int rc = rank_device(r, r->A.ptr, (size_t)k, (int_t)nr, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, ir.data(),
+                                 out_scores ? sr.data() : nullptr))
+            return rc;                                       // (rank_device has waited for the stream: the vectors may go)
+        for (size_t j = 0; j < nr; j++) {
+            memcpy(out_ids + (size_t)rest[j] * n_top, &ir[j * (size_t)n_top], (size_t)n_top * sizeof(int_t));
+            if (out_scores) memcpy(out_scores + (size_t)rest[j] * n_top, &sr[j * (size_t)n_top], (size_t)n_top * sizeof(real_t));
+        }
+        return 0;
+    });
+}
+
+int cmfrec_hip_ranker_set_filter(cmfrec_hip_ranker *r, int mode)
+{
+    return guarded([&]() {
+        if (r == nullptr || (mode != 0 && mode != 1)) {
+            g_last_error = "cmfrec_hip_ranker_set_filter: invalid arguments (0: off, 1: the half-precision filter)";
+            return 2;
+        }
+        DeviceScope scope(r->dev.device);
+        r->filter = mode;
+        if (mode == 0) r->fimg.release();
+        else (void)ensure_filter_image(r);
+        return 0;
+    });
+}
+
+int cmfrec_hip_ranker_filter_stats(cmfrec_hip_ranker *r, int *users, int *filtered, int *certified)
+{
+    if (r == nullptr || !r->fs_valid) {
+        g_last_error = "cmfrec_hip_ranker_filter_stats: no cmfrec_hip_ranker_topN call on this handle yet";
+        return 2;
+    }
+    if (users) *users = r->fs_users;
+    if (filtered) *filtered = r->fs_filtered;
+    if (certified) *certified = r->fs_certified;
+    return 0;
+}
+
+int cmfrec_hip_ranker_filter_ms(cmfrec_hip_ranker *r, double ms[4])
+{
+    if (r == nullptr || ms == nullptr || r->filter != 1 || !r->fimg.ready) {
+        g_last_error = "cmfrec_hip_ranker_filter_ms: the filter of this handle is off";
+        return 2;
+    }
+    ms[0] = r->fimg.usable ? r->fimg.build_ms : 0.0;
+    for (int s = 0; s < 3; s++) ms[s + 1] = r->fs_filtered > 0 ? r->f_ms[s] : 0.0;
+    return 0;
+}
+
+int cmfrec_hip_ranker_filter_keys(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, float *keys_out)
+{
+    const char *fn = "cmfrec_hip_ranker_filter_keys";
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || !A || !keys_out || lda < (size_t)r->k) {
+            g_last_error = std::string(fn) + ": invalid arguments";
+            return 2;
+        }
+        if ((size_t)nu * (size_t)r->n > ((size_t)1 << 20)) {
+            g_last_error = std::string(fn) + ": a probe for small shapes, needs nu * n <= 2^20";
+            return 2;
+        }
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        if (r->filter != 1 || !ensure_filter_image(r)) {
+            g_last_error = std::string(fn) + ": the filter of this handle is off, or its items have no image";
+            return 2;
+        }
+        const cmfrec_hip_ranker::Device &dev = r->dev;
+        const int k = r->k;
+        const size_t cells = (size_t)nu * (size_t)r->n;
+        r->A.alloc_at_least((size_t)nu * k);
+        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        r->f_keys.alloc_at_least(cells);
+        TopnFilterParams<real_t> F = filter_params(r, r->A.ptr, (size_t)k, nu, TOPNF_M_MIN);
+        F.keys = r->f_keys.ptr;
+        topn_filter_launch_keys(dev.stream, dev.num_cus, F);
+        r->f_keys.download(keys_out, cells, dev.stream);
+        HIP_CHECK(hipStreamSynchronize(dev.stream));
+        return 0;
     });
 }
 

@@ -69,11 +69,13 @@ def _topN_inputs(self, users, exclude):
     return users, A, excl
 
 
-def _topN(self, users, n, exclude, biasB, include=None):
+def _topN(self, users, n, exclude, biasB, include=None, filter=None):
     """Shared body of ``CMF.topN_batch`` / ``CMF_implicit.topN_batch``."""
     from . import ops
     _, A, excl = _topN_inputs(self, users, exclude)
     B = np.ascontiguousarray(self.B_[:, self.k_item:])
+    if filter is not None:
+        return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl, include=include, filter=filter)
     if include is None:
         return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl)
     return ops.topN_batch(A, B, n_top=n, biasB=biasB, exclude=excl, include=include)
@@ -99,11 +101,15 @@ class ModelRanker:
     device by a ``cmfrec_amd.Ranker``; ``topN(users, n, exclude, include)`` takes user ids of the fitted model and returns what the
     model's ``topN_batch`` returns.  The caller closes it (``close()`` or a ``with`` block); a refit needs a new one."""
 
-    def __init__(self, model, biasB, split=None):
+    def __init__(self, model, biasB, split=None, filter=None):
         from .rank import Ranker
         self._model = model
         self._ranker = Ranker(np.ascontiguousarray(model.B_[:, model.k_item:]),
-                              None if biasB is None else np.ascontiguousarray(biasB, model.B_.dtype), split=split)
+                              None if biasB is None else np.ascontiguousarray(biasB, model.B_.dtype), split=split, filter=filter)
+
+    def filter_stats(self):
+        """``Ranker.filter_stats`` of the most recent ``topN``."""
+        return self._ranker.filter_stats()
 
     def topN(self, users, n=10, exclude=None, include=None):
         users, A, excl = _topN_inputs(self._model, users, exclude)
@@ -538,12 +544,13 @@ class CMF_implicit(_Base):
         _lib.check(rc, lib, "factors_collective_implicit_multiple")
         return A
 
-    def topN_batch(self, users, n=10, exclude=None, include=None):
+    def topN_batch(self, users, n=10, exclude=None, include=None, filter=None):
         """Top-``n`` item ids and scores (A_u . B_i) for a batch of users, ranked on the GPU; ``exclude``: CSR of items
         to skip per user (e.g. the training matrix).  Batch form of the reference's ``topN`` (common.c:5127-5380).
         ``include``: candidate lists -- (indptr, indices) CSR over the users OF THIS CALL (one list per entry of ``users``), a
-        SciPy CSR matrix of that many rows, or one 1-D array shared by all: each user is ranked over its own list only."""
-        return _topN(self, users, n, exclude, None, include)
+        SciPy CSR matrix of that many rows, or one 1-D array shared by all: each user is ranked over its own list only.
+        ``filter``: None or ``"fp16"``, the certified half-precision filter of ``cmfrec_amd.Ranker`` (the same exact list)."""
+        return _topN(self, users, n, exclude, None, include, filter)
 
     def topN_deep(self, users, n, exclude=None):
         return _topN_deep(self, users, n, exclude, None)
@@ -574,9 +581,10 @@ class CMF_implicit(_Base):
         rows of the batch, as ``NewUsers.topN`` takes them."""
         return _topN_new_batch(self, X, U, None, n, exclude_seen, exclude, include)
 
-    def ranker(self):
-        """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch."""
-        return ModelRanker(self, None)
+    def ranker(self, filter=None):
+        """A ``ModelRanker`` over this model's item factors: upload them once, then ``.topN(users, n, exclude)`` per batch.
+        ``filter``: None or ``"fp16"``, as ``cmfrec_amd.Ranker`` takes it."""
+        return ModelRanker(self, None, filter=filter)
 
     def similar_items(self, items, n=10, metric="cosine"):
         return _similar(self.B_, self.k_item, items, n, metric, "similar_items")
@@ -868,13 +876,14 @@ class CMF(_Base):
             return A, biasA
         return A
 
-    def topN_batch(self, users, n=10, exclude=None, include=None):
-        """Top-``n`` item ids and scores for a batch of users, ranked on the GPU by A_u . B_i + item_bias[i] (the user
+    def topN_batch(self, users, n=10, exclude=None, include=None, filter=None):
+        """``filter``: None or ``"fp16"``, the certified half-precision filter of ``cmfrec_amd.Ranker`` (the same exact list).
+        Top-``n`` item ids and scores for a batch of users, ranked on the GPU by A_u . B_i + item_bias[i] (the user
         bias and the global mean do not change the order; the reference adds them to the scores, common.c:5339-5345,
         and so does this method).  ``exclude``: CSR of items to skip per user.  ``include``: candidate lists -- (indptr,
         indices) CSR over the users OF THIS CALL (one list per entry of ``users``), a SciPy CSR matrix of that many rows, or
         one 1-D array shared by all: each user is ranked over its own list only."""
-        ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None, include)
+        ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None, include, filter)
         return ids, self._finish_scores(np.atleast_1d(np.asarray(users, np.int64)), sc)
 
     def topN_deep(self, users, n, exclude=None):
@@ -915,10 +924,10 @@ class CMF(_Base):
         with self.new_users() as nu:
             return nu.impute(X, U=U, W=W)
 
-    def ranker(self):
+    def ranker(self, filter=None):
         """A ``ModelRanker`` over this model's item factors and item bias: upload them once, then ``.topN(users, n, exclude)``
-        per batch, with the scores of ``topN_batch``."""
-        return ModelRanker(self, self.item_bias_ if self.item_bias else None)
+        per batch, with the scores of ``topN_batch``.  ``filter``: None or ``"fp16"``, as ``cmfrec_amd.Ranker`` takes it."""
+        return ModelRanker(self, self.item_bias_ if self.item_bias else None, filter=filter)
 
     def similar_items(self, items, n=10, metric="cosine"):
         return _similar(self.B_, self.k_item, items, n, metric, "similar_items")

@@ -229,14 +229,25 @@ def _sorted_include(include, nu):
     return ep, np.ascontiguousarray((key & 0xffffffff) - 1, np.int32)
 
 
-def topN_batch(A, B, n_top=10, biasB=None, exclude=None, include=None):
+def topN_batch(A, B, n_top=10, biasB=None, exclude=None, include=None, filter=None):
     """Top-N item ids (and scores) for every row of ``A``: score = A_u . B_i (+ biasB[i]), descending, ties by lower
     id; ``exclude`` = (indptr, indices) CSR of items to skip per user (sorted here).  Batch counterpart of the
     reference's per-user ``topN`` (src/common.c:5127-5380).  Every width the library fits (k <= 272), n_top <= min(128, n).
     ``include``: candidate lists -- (indptr, indices) CSR over the rows of ``A``, a SciPy CSR matrix, or one 1-D array shared by
     every user (sorted and de-duplicated here): each user is ranked over its own list only, with the result the full ranking
     gives when every other item is excluded (the reference's ``include_ix``, batched); ``exclude`` may come along.
+    ``filter``: None or ``"fp16"`` -- the certified half-precision filter of ``Ranker(filter=)``, its image built for this one
+    call (the full ranking only: not with ``include``).
     B is uploaded on every call: to rank several batches against the same items, hold a ``cmfrec_amd.Ranker``."""
+    if filter is not None:
+        from .rank import Ranker, filter_code
+        filter_code(filter, "topN_batch: filter")
+        if include is not None:
+            raise ValueError("topN_batch: filter and include do not go together")
+        A = np.ascontiguousarray(A)
+        bs = None if biasB is None else np.ascontiguousarray(biasB, A.dtype)
+        with Ranker(np.ascontiguousarray(B, A.dtype), bs, filter=filter) as r:
+            return r.topN(A, n=n_top, exclude=exclude)
     A = np.ascontiguousarray(A); B = np.ascontiguousarray(B, A.dtype)
     lib, R = _prep(A, B)
     nu, lda = A.shape

@@ -97,19 +97,47 @@ def split_plan(nu, n, k, n_top, num_cus=256, dtype=np.float64, requested=0):
     return s.value, si.value
 
 
+FILTER_NTOP_MAX = 64        # longer lists take the exact route (TOPNF_NTOP_MAX)
+
+
+def filter_code(filter, what="filter"):
+    """The C code of a ``filter`` setting: None -> 0 (off), "fp16" -> 1."""
+    if filter is None:
+        return 0
+    if isinstance(filter, str) and filter == "fp16":
+        return 1
+    raise ValueError("%s must be None or \"fp16\", got %r" % (what, filter))
+
+
+def filter_shortlist(n_top, forced=0):
+    """Shortlist length M of a filtered ranking of ``n_top``: max(32, pow2(2 n_top)), at most 128; ``forced`` (32 .. 128, what
+    ``CMFREC_HIP_TOPN_FILTER_M`` asks for) rounds up to a power of two instead, never below ``n_top``.  The host rule of ``topnf_m``."""
+    want = max(int(forced), int(n_top)) if 32 <= int(forced) <= 128 else 2 * int(n_top)
+    m = 32
+    while m < want and m < 128:
+        m *= 2
+    return m
+
+
 class Ranker:
-    """``Ranker(B, biasB=None, device=-1, split=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype
+    """``Ranker(B, biasB=None, device=-1, split=None, filter=None)``: B [n, k] item factors (float64 or float32), ``biasB`` [n] of the same dtype
     or None.  ``topN(A, n=10, exclude=None, include=None)`` ranks the rows of A [nu, k] like ``ops.topN_batch``.  The caller owns
     the handle: ``close()`` it, or use it as a context manager.
     ``split``: None (the default, every call as it always was), ``"auto"`` or a number of slices: the full ranking of ``topN``
     (without ``include``) cuts the items into slices across the device and merges the slices' lists -- what makes a request of a
     few users use more than one compute unit.  With it on, every k is scored by the MFMA kernel: ids and scores are those of
     ``CMFREC_HIP_TOPN=wide`` bit for bit, whatever the number of slices; for k <= 64 they agree with the default kernel up to
-    rounding.  ``include``, ``topN_deep`` / ``topN_after``, ``ranks``, ``metrics`` and ``similar`` ignore the setting."""
+    rounding.  ``include``, ``topN_deep`` / ``topN_after``, ``ranks``, ``metrics`` and ``similar`` ignore the setting.
+    ``filter``: None (the default: nothing changes, nothing is built) or ``"fp16"``: ``topN`` of ``n <= 64`` (without ``include``,
+    without ``split``) scores every pair on the fp16 matrix instruction against a half-precision image of ``B`` built once, keeps
+    a shortlist per user under an error bound the kernel computes, ranks the shortlists in the working precision and certifies
+    each user's list as the exact one; the users it cannot certify are ranked by the unfiltered route.  The result is the exact
+    top-N either way; ``filter_stats()`` tells how the last call went."""
 
-    def __init__(self, B, biasB=None, device=-1, split=None):
+    def __init__(self, B, biasB=None, device=-1, split=None, filter=None):
         self.handle = None
         code = split_code(split, "Ranker: split")
+        fcode = filter_code(filter, "Ranker: filter")
         B = np.asarray(B)
         if B.ndim != 2:
             raise ValueError("Ranker: B must be 2-D [items, factors], got %d-D" % B.ndim)
@@ -136,6 +164,44 @@ class Ranker:
         self._split = None
         if code != -1:
             self.split = split
+        self._filter = None
+        if fcode != 0:
+            self.filter = filter
+
+    @property
+    def filter(self):
+        """None or "fp16" (``cmfrec_hip_ranker_set_filter``); assignable: "fp16" builds the half-precision image, None releases it."""
+        return self._filter
+
+    @filter.setter
+    def filter(self, value):
+        code = filter_code(value, "Ranker: filter")
+        _lib.check(self.lib.cmfrec_hip_ranker_set_filter(self._live(), C.c_int(code)), self.lib, "Ranker.filter")
+        self._filter = value
+
+    def filter_stats(self):
+        """{"users", "filtered", "certified"} of the most recent ``topN`` without ``include``: ``filtered`` is 0 when the call took
+        the exact route (filter off, ``n`` > 64, ``split`` on, or items without an image), else the users of the call;
+        ``users - certified`` of them were ranked again by the exact route."""
+        u, f, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.cmfrec_hip_ranker_filter_stats(self._live(), C.byref(u), C.byref(f), C.byref(c)), self.lib, "Ranker.filter_stats")
+        return {"users": u.value, "filtered": f.value, "certified": c.value}
+
+    def filter_ms(self):
+        """HIP-event times (ms): {"image", "filter", "refine", "certify"} -- the image build and the three kernels of the most
+        recent filtered ``topN``."""
+        ms = (C.c_double * 4)()
+        _lib.check(self.lib.cmfrec_hip_ranker_filter_ms(self._live(), ms), self.lib, "Ranker.filter_ms")
+        return dict(zip(("image", "filter", "refine", "certify"), ms[:]))
+
+    def filter_keys(self, A):
+        """[nu, n] float32: the key of every pair as the filter kernel forms it -- half-precision score + bias + error bound, never
+        below the exact score.  A probe for small shapes (nu * n <= 2^20); the filter must be on."""
+        A = self._users(A, "Ranker.filter_keys")
+        keys = np.empty((A.shape[0], self.n), np.float32)
+        rc = self.lib.cmfrec_hip_ranker_filter_keys(self._live(), _lib.ptr(A), C.c_size_t(self.k), C.c_int(A.shape[0]), _lib.ptr(keys))
+        _lib.check(rc, self.lib, "Ranker.filter_keys")
+        return keys
 
     @property
     def split(self):

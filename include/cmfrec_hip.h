@@ -729,6 +729,28 @@ int cmfrec_hip_ranker_set_split(cmfrec_hip_ranker *r, int slices);
 int cmfrec_hip_ranker_slices(cmfrec_hip_ranker *r, int *slices);
 int cmfrec_hip_topn_split_plan(int_t nu, int_t n, int_t k, int_t n_top, int num_cus, size_t sizeof_real, int requested,
                                int *slices, int *slice_items);
+
+/* Exact top-N through a certified half-precision filter.  With the filter on, cmfrec_hip_ranker_topN of
+ * n_top <= 64 scores every pair on the fp16 matrix instruction against a half-precision image of the items, keeps per user the
+ * M = max(32, pow2(2 n_top)) <= 128 best KEYS -- a key is the half-precision score plus a bound the kernel computes on its distance
+ * from the exact score, so no item outside the shortlist scores above the M-th key --, ranks the shortlists in the working
+ * precision and certifies a user when its n_top-th exact score lies strictly above that key (or fewer than M items could be
+ * ranked).  The users without a certificate are ranked by the route the call takes with the filter off, in one batch.  The caller
+ * gets the exact list either way: the shortlists are scored with the arithmetic of the kernel the call runs with the filter
+ * off, so a certified user's ids and scores are those of the unfiltered call, bit for bit.
+ * set_filter: mode 0 = off (the default: exactly the launches of a handle that never heard of it; releases the image), 1 = fp16
+ * (builds the image: one pass over the items).  Items with a non-finite entry, or one of 2^41 and more in magnitude, get no
+ * image: every call then takes the exact route.  n_top > 64, a handle whose split setting is on, candidate lists, topN_deep /
+ * topN_after, ranks, metrics, similar and the new-rows handle are not filtered.
+ * filter_stats: of the most recent cmfrec_hip_ranker_topN -- its users, how many of them went through the filter (0: the call took
+ * the exact route) and how many were certified.  Return code 2 before the first call.
+ * filter_ms: HIP-event times -- ms[0] the image build, ms[1..3] filter, refinement and certificate of the most recent filtered call.
+ * filter_keys: a probe for small shapes (nu * n <= 2^20, filter on): keys_out [nu, n] <- the float32 key of every pair, from the
+ * filter kernel's own product and bound (no exclusion; NaN for a user row that the filter skips). */
+int cmfrec_hip_ranker_set_filter(cmfrec_hip_ranker *r, int mode);
+int cmfrec_hip_ranker_filter_stats(cmfrec_hip_ranker *r, int *users, int *filtered, int *certified);
+int cmfrec_hip_ranker_filter_ms(cmfrec_hip_ranker *r, double ms[4]);
+int cmfrec_hip_ranker_filter_keys(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, float *keys_out);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
 
 /* New rows against a model that stays on the device: factors and top-N of users who were not part of the fit, batch after
