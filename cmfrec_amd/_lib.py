@@ -105,6 +105,24 @@ class FitMonitor(C.Structure):
                 ("best_iter", C.POINTER(C.c_int))]
 
 
+class ObjectiveRecord(C.Structure):
+    """``cmfrec_hip_objective`` (include/cmfrec_hip.h): the same layout in both precisions."""
+    _fields_ = [("n", C.c_uint64), ("sum_w", C.c_double), ("data", C.c_double), ("normA", C.c_double * 4), ("normbiasA", C.c_double * 2),
+                ("normB", C.c_double * 4), ("normbiasB", C.c_double * 2), ("allpairs", C.c_double)]
+
+    def as_dict(self):
+        out = {"n": int(self.n), "sum_w": float(self.sum_w), "data": float(self.data), "allpairs": float(self.allpairs)}
+        for name in ("normA", "normbiasA", "normB", "normbiasB"):
+            out[name] = np.array(getattr(self, name)[:], np.float64)
+        return out
+
+
+class FitObjective(C.Structure):
+    """``cmfrec_hip_fit_objective`` (include/cmfrec_hip.h): the same layout in both precisions."""
+    _fields_ = [("every", C.c_int), ("tol", C.c_double), ("values", C.POINTER(C.c_double)), ("records", C.POINTER(ObjectiveRecord)),
+                ("iters_run", C.POINTER(C.c_int))]
+
+
 class EarlyStop(C.Structure):
     """``cmfrec_hip_early_stop``: the state of ``cmfrec_hip_early_stop_step``."""
     _fields_ = [("every", C.c_int), ("patience", C.c_int), ("higher_is_better", C.c_int), ("min_delta", C.c_double),
@@ -133,6 +151,7 @@ EXPORTED = [
     "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
     "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
     "cmfrec_hip_rankset_create", "cmfrec_hip_rankset_destroy", "cmfrec_hip_ranker_metrics", "cmfrec_hip_session_ranking",
+    "cmfrec_hip_session_objective", "cmfrec_hip_objective_value", "cmfrec_hip_fit_set_objective",
     "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy", "cmfrec_hip_factors_multiple_naz", "cmfrec_hip_sizeof_newrows_model_ex", "cmfrec_hip_newrows_create_ex", "cmfrec_hip_newrows_naz_launch_waves",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
@@ -252,6 +271,10 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_ranker_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.POINTER(RankRecord),
                                               C.c_void_p, C.c_void_p]
     lib.cmfrec_hip_session_ranking.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RankRecord)]
+    lib.cmfrec_hip_session_objective.argtypes = [C.c_void_p, C.POINTER(ObjectiveRecord)]
+    lib.cmfrec_hip_objective_value.restype = C.c_double
+    lib.cmfrec_hip_objective_value.argtypes = [C.POINTER(ObjectiveRecord), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int]
+    lib.cmfrec_hip_fit_set_objective.argtypes = [C.POINTER(FitObjective)]
     lib.cmfrec_hip_early_stop_step.argtypes = [C.POINTER(EarlyStop), C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.cmfrec_hip_pair_errors.argtypes = lib.cmfrec_hip_score_pairs.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Errors)]
     for name in EXPORTED_OTHER[1:]:

@@ -121,6 +121,37 @@ int check_monitor(const FitMonitor &mon, const char *fn, int_t m, int_t n, int_t
     if (rc && verbose) fprintf(stderr, "%s\n", cmfhip::g_last_error.c_str());
     return rc;
 }
+// ---- the objective while fitting (cmfrec_hip_fit_set_objective, include/cmfrec_hip.h) ---------------------------------
+// Waits per thread for the next fit call, as the monitor does; take_objective() empties the slot on every path out of a fit.
+struct FitObjective {
+    bool on = false;
+    cmfrec_hip_fit_objective o;
+    double lam6[6] = {0, 0, 0, 0, 0, 0}, w_main = 1;   // what cmfrec_hip_objective_value takes, set once the fit knows them
+    int scale_lam = 0, scale_bias_const = 0;
+    int ran = 0;                 // run_loop: the iterations that ran
+};
+thread_local FitObjective g_objective;
+FitObjective take_objective()
+{
+    FitObjective out = g_objective;
+    g_objective = FitObjective();
+    return out;
+}
+// the refusals before the fit writes to any output: 0 or 2.  unsupported: what of the call's model cmfrec_hip_session_objective
+// would refuse (the fit functions name it from their arguments), or null
+int check_objective(const FitObjective &obj, const FitMonitor &mon, const char *fn, int_t kk, int_t niter, const char *unsupported, bool verbose)
+{
+    if (!obj.on) return 0;
+    const std::string name(fn);
+    if (niter < 1) return refuse_monitor(verbose, name + ": an objective needs niter >= 1");
+    if (mon.on) return refuse_monitor(verbose, name + ": an objective and a monitor do not go together");
+    if (sharded_fit_wanted(devices_from_env()))
+        return refuse_monitor(verbose, name + ": an objective needs a fit on one device (CMFREC_HIP_DEVICES names several, or "
+                                              "CMFREC_HIP_SHARDED is set)");
+    if (unsupported != nullptr) return refuse_monitor(verbose, name + ": the objective is not implemented for " + unsupported);
+    if (kk < 1 || kk > 272) return refuse_monitor(verbose, name + ": the objective needs 1 <= k + k_main <= 272");
+    return 0;
+}
 double watched_value(const cmfrec_hip_errors &r, int metric)
 {
     const double sw = r.sum_w[0] + r.sum_w[1];
@@ -143,7 +174,7 @@ const char *watched_name(int metric)
 // all or nearly all complete: optimizeA Case 1, common.c:2787-2993)
 // mon: the held-out set is evaluated between the iterations, and the loop may end early and go back to its best iterate
 int run_loop(cmfrec_hip_session *s, const cmfrec_hip_model &mdl, int niter, bool finalize_chol, bool verbose, bool implicit_feats = false,
-             bool chol_A = false, bool chol_B = false, FitMonitor *mon = nullptr)
+             bool chol_A = false, bool chol_B = false, FitMonitor *mon = nullptr, FitObjective *obj = nullptr)
 {
     cmfrec_hip_early_stop es;
     memset(&es, 0, sizeof es);
@@ -156,8 +187,15 @@ int run_loop(cmfrec_hip_session *s, const cmfrec_hip_model &mdl, int niter, bool
         if (mon->m.records) memset(mon->m.records, 0, (size_t)niter * sizeof(cmfrec_hip_errors));
         if (mon->m.rank_records) memset(mon->m.rank_records, 0, (size_t)niter * sizeof(cmfrec_hip_rank_record));
     }
+    double obj_prev = std::nan("");
+    if (obj) {
+        for (int it = 0; it < niter && obj->o.values; it++) obj->o.values[it] = std::nan("");
+        if (obj->o.records) memset(obj->o.records, 0, (size_t)niter * sizeof(cmfrec_hip_objective));
+        es.every = obj->o.every;
+    }
     // what the monitor reports however the loop ends; the best iterate comes back when the loop ended on a later one
     auto finish = [&](int rc) {
+        if (obj) { obj->ran = ran; if (obj->o.iters_run) *obj->o.iters_run = ran; }
         if (!mon) return rc;
         if (mon->m.iters_run) *mon->m.iters_run = ran;
         if (mon->m.best_iter) *mon->m.best_iter = es.best_iter;
@@ -196,6 +234,20 @@ int run_loop(cmfrec_hip_session *s, const cmfrec_hip_model &mdl, int niter, bool
         if ((rc = cmfrec_hip_session_after_gather(s, 'A'))) return finish(rc);
         if (verbose) { cmfrec_hip_session_sync(s); printf(" done\n\tCompleted ALS iteration %2d\n\n", it + 1); fflush(stdout); }
         ran = it + 1;
+        if (obj && cmfrec_hip_early_stop_step(&es, it, niter, nullptr)) {
+            cmfrec_hip_objective rec;
+            if ((rc = cmfrec_hip_session_objective(s, &rec))) return finish(rc);
+            const double value = cmfrec_hip_objective_value(&rec, obj->lam6, obj->w_main, obj->scale_lam, obj->scale_bias_const);
+            if (obj->o.records) obj->o.records[it] = rec;
+            if (obj->o.values) obj->o.values[it] = value;
+            if (verbose) { printf("\tObjective after iteration %2d: %.10g\n\n", it + 1, value); fflush(stdout); }
+            const bool stop = obj->o.tol > 0 && !std::isnan(obj_prev) && obj_prev - value <= obj->o.tol * std::fabs(obj_prev);
+            obj_prev = value;
+            if (stop) {
+                if (verbose) { printf("\tStopping: the objective moved by no more than tol\n\n"); fflush(stdout); }
+                break;
+            }
+        }
         if (mon && cmfrec_hip_early_stop_step(&es, it, niter, nullptr)) {
             double value;
             if (mon->m.rankset != nullptr) {
@@ -668,6 +720,14 @@ int cmfrec_hip_fit_set_monitor(const cmfrec_hip_fit_monitor *monitor)
     return 0;
 }
 
+/* the objective while fitting (include/cmfrec_hip.h): handed to this thread's next fit call */
+int cmfrec_hip_fit_set_objective(const cmfrec_hip_fit_objective *objective)
+{
+    g_objective = FitObjective();
+    if (objective != nullptr) { g_objective.on = true; g_objective.o = *objective; }
+    return 0;
+}
+
 /* the rule of the monitor, host only: which iterations are evaluated, what improves, when to stop */
 int cmfrec_hip_early_stop_step(cmfrec_hip_early_stop *st, int iter, int niter, const double *value)
 {
@@ -714,7 +774,12 @@ int_t fit_collective_implicit_als(
 
     (void)nthreads;
     FitMonitor mon = take_monitor();
+    FitObjective obj = take_objective();
     if (const int rc_mon = check_monitor(mon, "fit_collective_implicit_als", m, n, k + k_main, niter, verbose)) return rc_mon;
+    {
+        const char *unsupported = (U || II || nnz_U || nnz_I || k_user || k_item) ? "side information" : (l1_lam != 0 || l1_lam_unique) ? "an L1 penalty" : nullptr;
+        if (const int rc_obj = check_objective(obj, mon, "fit_collective_implicit_als", k + k_main, niter, unsupported, verbose)) return rc_obj;
+    }
     // collective.c:9406-9435
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
@@ -759,6 +824,8 @@ int_t fit_collective_implicit_als(
     // per-matrix penalties: entries 2..5 = A, B, C, D (the bias slots are unused by this model, collective.c:9793-9809)
     real_t lam6[6], l16[6];
     for (int e = 0; e < 6; e++) { lam6[e] = lam_unique ? lam_unique[e] : lam; l16[e] = l1_lam_unique ? l1_lam_unique[e] : l1_lam; }
+    for (int e = 0; e < 6; e++) obj.lam6[e] = (e >= 2) ? (double)lam6[e] : 0.;
+    obj.w_main = (double)w_main;
     if (w_main != (real_t)1) {                                            // collective.c:9786-9811
         lam /= w_main; l1_lam /= w_main; w_user /= w_main; w_item /= w_main;
         for (int e = 2; e < 6; e++) { lam6[e] /= w_main; l16[e] /= w_main; }
@@ -802,7 +869,7 @@ int_t fit_collective_implicit_als(
     // (a monitored fit that returns an earlier iterate than niter - 1 returns one whose last A-step was not the Cholesky pass; a
     //  sharded fit has no monitor, check_monitor)
     auto epilogue = [&](cmfrec_hip_session *s) {
-        const int last_chol = (!use_cg || (finalize_chol && niter > 0 && (!mon.on || mon.returned == niter - 1))) ? 1 : 0;
+        const int last_chol = (!use_cg || (finalize_chol && niter > 0 && (!mon.on || mon.returned == niter - 1) && (!obj.on || obj.ran == niter))) ? 1 : 0;
         const int rc2 = cmfrec_hip_session_precompute(s, last_chol, 0, precomputedBtB, nullptr, su.had_dense ? precomputedBeTBe : nullptr,
                                                       su.had_dense ? precomputedBeTBeChol : nullptr, nullptr, nullptr);
         if (su.naz && !rc2) fill_CtUbias(precomputedCtUbias, C, su.colmeans, su.cols, k_user + k, w_user);   // collective.c:9244-9252, :10115-10123
@@ -860,7 +927,7 @@ int_t fit_collective_implicit_als(
     if (verbose && !rc) { printf("Starting ALS optimization routine\n\n"); fflush(stdout); }
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("set_factors");
-    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, false, false, false, mon.on ? &mon : nullptr);
+    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, false, false, false, mon.on ? &mon : nullptr, obj.on ? &obj : nullptr);
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("ALS iterations");
     if (rc_loop == 0 || rc_loop == 3) {
@@ -900,7 +967,13 @@ int_t fit_collective_explicit_als(
     (void)max_cd_steps;
     (void)precomputedBiTBi;        // with add_implicit_features the prediction matrices are not produced here
     FitMonitor mon = take_monitor();
+    FitObjective obj = take_objective();
     if (const int rc_mon = check_monitor(mon, "fit_collective_explicit_als", m, n, k + k_main, niter, verbose)) return rc_mon;
+    {
+        const char *unsupported = (U || II || nnz_U || nnz_I || k_user || k_item) ? "side information" : add_implicit_features ? "implicit features"
+                                  : NA_as_zero_X ? "NA_as_zero_X" : Xfull ? "a dense X" : (l1_lam != 0 || l1_lam_unique) ? "an L1 penalty" : nullptr;
+        if (const int rc_obj = check_objective(obj, mon, "fit_collective_explicit_als", k + k_main, niter, unsupported, verbose)) return rc_obj;
+    }
     // collective.c:7308-7329
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
     if (k_item && II == nullptr && nnz_I == 0) return fail(verbose, "Cannot pass 'k_item' without I data.");
@@ -1343,7 +1416,13 @@ int_t fit_collective_explicit_als(
     if (!rc && !dense_mult_B.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, 'B', dense_mult_B.data());
     if (verbose && !rc) { printf("Starting ALS optimization routine\n\n"); fflush(stdout); }
     mon.glob_mean = gm;
-    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, add_implicit_features, dense_chol_A, dense_chol_B, mon.on ? &mon : nullptr);
+    // the penalties in the caller's units, as the row solvers see them: lam6 x w_main, the biases' with scaling_biasA / _biasB inside
+    for (int e = 0; e < 6; e++) obj.lam6[e] = (double)lam6[e] * (double)w_main;
+    if (!user_bias) obj.lam6[0] = 0;
+    if (!item_bias) obj.lam6[1] = 0;
+    obj.w_main = (double)w_main; obj.scale_lam = scale_lam ? 1 : 0; obj.scale_bias_const = scale_bias_const ? 1 : 0;
+    int rc_loop = rc ? rc : run_loop(s, mdl, niter, finalize_chol, verbose, add_implicit_features, dense_chol_A, dense_chol_B, mon.on ? &mon : nullptr,
+                                          obj.on ? &obj : nullptr);
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("ALS iterations");
     if (rc_loop == 0 || rc_loop == 3) {

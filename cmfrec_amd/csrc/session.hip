@@ -14,6 +14,7 @@
 #include "impute_kernels.hpp"
 #include "newrows.hpp"
 #include "newrows_naz_kernels.hpp"
+#include "objective.hpp"
 #include <dlfcn.h>
 #include <functional>
 #include <limits>
@@ -142,6 +143,7 @@ struct cmfrec_hip_session {
     DevBuf<real_t> snap[8];
     bool has_snapshot = false;
     cmfrec_hip_ranker *ranker = nullptr;  // cmfrec_hip_session_ranking: the session's own ranker, refreshed from B where it lives
+    ObjectiveWorkspace *objective_ws = nullptr;   // cmfrec_hip_session_objective: work items, records and Gramian partials (objective_tu.hip)
     std::vector<EventPair> evA, evB;     // whole half-steps
     BinTimers binA, binB;                // row-update kernel launches per nnz bin
 
@@ -158,6 +160,7 @@ struct cmfrec_hip_session {
         binA.clear(); binB.clear();
         for (auto e : partEv) (void)hipEventDestroy(e);
         if (ranker) cmfrec_hip_ranker_destroy(ranker);
+        objective_workspace_destroy(objective_ws);
     }
 };
 
@@ -2112,6 +2115,45 @@ int cmfrec_hip_session_ranking(cmfrec_hip_session *s, cmfrec_hip_rankset *set, i
         HIP_CHECK(hipStreamSynchronize(s->dev.stream));          // the ranker has a stream of its own
         return rankset_run_on_factors(&s->ranker, set, fn, s->dev.device, s->A.ptr + m.k_user, s->ldA, m.m, s->B.ptr + m.k_item, s->ldB, m.n,
                                       m.k + m.k_main, (!m.implicit && m.item_bias) ? s->biasB.ptr : nullptr, k_at, out);
+    });
+}
+
+// the components of the training objective of the current factors (objective_tu.hip, objective_run): one pass over the resident CSR
+// of X, the factors and the biases where they are, behind the updates queued on the session's stream; writes nothing of the model's
+int cmfrec_hip_session_objective(cmfrec_hip_session *s, cmfrec_hip_objective *out)
+{
+    const std::string fn = "cmfrec_hip_session_objective";
+    return guarded([&]() {
+        if (s == nullptr || out == nullptr) {
+            g_last_error = fn + ": invalid arguments";
+            return 2;
+        }
+        const cmfrec_hip_model &m = s->mdl;
+        const char *why = nullptr;
+        if (m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n || s->side_local) why = "needs a session that owns all rows";
+        else if (m.p > 0 || m.q > 0 || m.k_user > 0 || m.k_item > 0 || s->sparseU || s->sparseI || s->zerosU.on() || s->zerosI.on() ||
+                 s->U.ptr != nullptr || s->II.ptr != nullptr)
+            why = "side information is not part of the objective yet";
+        else if (s->implicit_feats) why = "implicit features are not part of the objective yet";
+        else if (s->naz_X) why = "NA_as_zero_X is not implemented";
+        else if (s->l1_lam != (real_t)0 || std::any_of(s->l16, s->l16 + 6, [](real_t v) { return v != (real_t)0; })) why = "an L1 penalty is not implemented";
+        else if (m.k + m.k_main < 1 || m.k + m.k_main > 272) why = "1 <= k + k_main <= 272";
+        else if (s->Xr.nrows != m.m || s->Xc.nrows != m.n || s->Xr.nnz != s->Xc.nnz) why = "set X first (both orientations, all rows)";
+        if (why != nullptr) {
+            g_last_error = fn + ": " + why;
+            return 2;
+        }
+        HIP_CHECK(hipSetDevice(s->dev.device));
+        const bool implicit = m.implicit != 0;
+        ObjectiveCall c;
+        c.device = s->dev.device; c.num_cus = s->dev.num_cus; c.stream = s->dev.stream; c.implicit = implicit; c.kk = m.k + m.k_main;
+        c.A = s->A.ptr; c.ldA = s->ldA; c.m = m.m; c.k_user = m.k_user; c.biasA = (!implicit && m.user_bias) ? s->biasA.ptr : nullptr;
+        c.B = s->B.ptr; c.ldB = s->ldB; c.n = m.n; c.k_item = m.k_item; c.biasB = (!implicit && m.item_bias) ? s->biasB.ptr : nullptr;
+        c.nnz = s->Xr.nnz; c.csr_p = s->Xr.p.ptr; c.csr_i = s->Xr.i.ptr; c.csr_v = s->Xr.v.ptr;
+        c.csr_w = s->Xr.weighted() ? s->Xr.w.ptr : nullptr;
+        c.wsum_rows = s->Xr.weighted() ? s->Xr.wsum.ptr : nullptr;
+        c.csc_p = s->Xc.p.ptr; c.wsum_cols = s->Xc.weighted() ? s->Xc.wsum.ptr : nullptr;
+        return objective_run(s->objective_ws, c, out);
     });
 }
 

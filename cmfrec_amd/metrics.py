@@ -98,6 +98,26 @@ def error_metrics(rec, include_fallback=True):
     return out
 
 
+def objective_from_record(rec, lambda_=0., w_main=1., scale_lam=False, scale_bias_const=False, scaling_biasA=1., scaling_biasB=1.,
+                          w_main_multiplier=1.):
+    """The training objective from its components (``AlsSession.objective``, a fit's ``objective_history_``):
+
+        0.5 w (data + allpairs) + 0.5 (lam_A normA + lam_B normB + lam_biasA normbiasA + lam_biasB normbiasB)
+
+    ``lambda_``: one number, or the six of ``lam_unique`` (user bias, item bias, A, B, C, D), as the model was given them;
+    ``w`` = ``w_main`` x ``w_main_multiplier`` (the implicit model's ``adjust_weight``).  Under ``scale_lam`` the sums whose rows
+    are multiplied by their entry counts (weight sums) are taken; under ``scale_bias_const`` the biases keep the plain sums and
+    their lambdas are multiplied by ``scaling_biasA`` / ``scaling_biasB``.  It is the function whose minimiser over one row is
+    what the closed-form half-step solves.  Pure NumPy."""
+    lam = np.broadcast_to(np.asarray(lambda_, np.float64), (6,)) if np.ndim(lambda_) == 0 else np.asarray(lambda_, np.float64).reshape(6)
+    s = 1 if scale_lam else 0
+    sb = 1 if (scale_lam and not scale_bias_const) else 0
+    lam_bA = lam[0] * (scaling_biasA if (scale_lam and scale_bias_const) else 1.)
+    lam_bB = lam[1] * (scaling_biasB if (scale_lam and scale_bias_const) else 1.)
+    penalty = lam[2] * rec["normA"][s] + lam[3] * rec["normB"][s] + lam_bA * rec["normbiasA"][sb] + lam_bB * rec["normbiasB"][sb]
+    return float(0.5 * w_main * w_main_multiplier * (rec["data"] + rec["allpairs"]) + 0.5 * penalty)
+
+
 def mean_from_record(rec):
     """What ``mean_metrics(ranking_metrics(...))`` returns, from the record of a reduction on the device (``Ranker.metrics``,
     ``AlsSession.ranking``): per metric ``sum / count`` over the users that count (NaN where none does), and ``users``."""

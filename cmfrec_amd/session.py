@@ -279,6 +279,17 @@ class AlsSession:
         _lib.check(rc, self.lib, "AlsSession.ranking")
         return rec.as_dict()
 
+    def objective(self):
+        """The components of the training objective of the session's current factors (``cmfrec_hip_objective``) as a dict: one
+        pass over the resident X, the factors and the biases on the device, behind the updates queued on the session's stream;
+        ``metrics.objective_from_record`` composes the number.  Nothing in the session changes.  Refused (``RuntimeError``, code
+        2): a session that does not own all rows, side information, implicit features, NA_as_zero_X, an L1 penalty."""
+        if not self.handle:
+            raise RuntimeError("AlsSession: the handle is closed")
+        rec = _lib.ObjectiveRecord()
+        _lib.check(self.lib.cmfrec_hip_session_objective(self.handle, C.byref(rec)), self.lib, "AlsSession.objective")
+        return rec.as_dict()
+
     def snapshot(self):
         """Keeps a second copy of the factors as they are now -- everything ``get_factors`` and ``get_implicit_features`` return --
         on the device (allocated on first use; device-to-device copies on the session's stream).  A later snapshot replaces it."""

@@ -111,6 +111,47 @@ class Validation:
         return users.astype(np.int32), take(held), excl
 
 
+class Objective:
+    """The training objective while fitting, for ``CMF.fit(..., objective=)`` / ``CMF_implicit.fit(..., objective=)``: evaluated on
+    the device after every ``every``-th iteration and after the last one (``cmfrec_hip_fit_set_objective``).  ``tol``: the fit
+    stops once an evaluation is below the one before it by no more than ``tol`` times that one's magnitude; None: watch only.
+    After the fit the model has ``objective_history_`` -- one dict per evaluated iteration: ``iteration``, ``objective`` and the
+    components of ``AlsSession.objective`` -- and ``n_iter_``.  Not together with ``validation=``; the models
+    ``AlsSession.objective`` refuses (side information, implicit features, NA_as_zero, dense X, L1) are refused before the fit."""
+
+    def __init__(self, every=1, tol=None):
+        self.every = int(every)
+        self.tol = None if tol is None else float(tol)
+
+    def _begin(self, lib, niter):
+        return _ObjectiveWatch(self, lib, int(niter))
+
+
+class _ObjectiveWatch:
+    def __init__(self, o, lib, niter):
+        self.lib, self.niter = lib, niter
+        self.values = (C.c_double * max(niter, 1))()
+        self.records = (_lib.ObjectiveRecord * max(niter, 1))()
+        self.iters_run = C.c_int(0)
+        self.objective = _lib.FitObjective(every=o.every, tol=o.tol or 0., values=self.values, records=self.records,
+                                           iters_run=C.pointer(self.iters_run))
+        lib.cmfrec_hip_fit_set_objective(C.byref(self.objective))
+
+    def close(self):
+        self.lib.cmfrec_hip_fit_set_objective(None)
+
+    def results(self):
+        """(objective_history_, n_iter_)"""
+        history = []
+        for it in range(min(self.niter, self.iters_run.value)):
+            if not math.isnan(self.values[it]):
+                entry = self.records[it].as_dict()
+                entry["iteration"] = it
+                entry["objective"] = float(self.values[it])
+                history.append(entry)
+        return history, int(self.iters_run.value)
+
+
 class _Watch:
     """One monitored fit: the resident set, the monitor's output arrays and what becomes of them."""
 

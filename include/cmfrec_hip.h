@@ -1085,6 +1085,56 @@ int cmfrec_hip_ranker_metrics(cmfrec_hip_ranker *r, const real_t *A, size_t lda,
 int cmfrec_hip_session_ranking(cmfrec_hip_session *s, cmfrec_hip_rankset *set, int k_at, cmfrec_hip_rank_record *out);
 int cmfrec_hip_early_stop_step(cmfrec_hip_early_stop *st, int iter, int niter, const double *value);
 
+/* The training objective of the factors as they are on the device (objective_kernels.hpp).  The device
+ * returns components, the host composes the number.  With s_ij = a_i . b_j over the k + k_main columns both sides share and v_ij
+ * the value as the session stores it (centred; alpha x for the implicit model):
+ *   n, sum_w    the stored entries and the sum of their observation weights (n without weights, and for the implicit model)
+ *   data        explicit:  sum over the stored entries of w_ij (v_ij - biasA_i - biasB_j - s_ij)^2
+ *               implicit:  sum over the stored entries of (1 + v_ij) (1 - s_ij)^2 - s_ij^2
+ *   allpairs    implicit:  sum over ALL m x n pairs of s_ij^2 = <A^T A, B^T B>, both Gramians rebuilt in double precision on every
+ *               call; 0 for the explicit model.  The implicit data term is data + allpairs.
+ *   normA [4]   sum over the rows of A of ||row||^2 over all its columns; the same with every row times lambda's multiplier under
+ *               scale_lam (the row's entries or weight sum, 1 for a row without entries); the two sums for the last column alone
+ *   normbiasA [2]  sum of biasA_i^2, and with the multipliers; zeros for a model without that bias
+ *   normB, normbiasB  the same for B and the item bias, the multipliers from the column orientation
+ * The sums are carried in double and added in an order that depends on the device and the launch, not on the run: the same call
+ * returns the same bytes (no atomics).  session_objective waits for the updates queued on the session's stream and changes nothing
+ * in the session.  Refused with 2 and a message, `out` untouched: a session that does not own all rows, X not set, side
+ * information of any kind, implicit features, NA_as_zero_X, an L1 penalty, k + k_main < 1 or > 272.
+ * CMFREC_HIP_OBJ_SEGMENT / CMFREC_HIP_OBJ_WAVES (test hooks, read per call): the entries per work item of a long row (2048), and
+ * at most that many wavefronts, rounded up to whole workgroups, in the row launch.
+ * objective_value, host only:  0.5 w_main (data + allpairs) + 0.5 (lam6[2] normA + lam6[3] normB + lam6[0] normbiasA + lam6[1]
+ * normbiasB), lam6 in the reference's lam_unique order and the caller's units (before the division by w_main), the scaled sums
+ * under scale_lam -- the biases' unscaled ones under scale_bias_const, whose lam6[0] / [1] then carry scaling_biasA / _biasB.  It is
+ * the function whose minimiser over one row is what the closed-form half-step solves. */
+typedef struct cmfrec_hip_objective {
+    uint64_t n;
+    double sum_w, data;
+    double normA[4], normbiasA[2], normB[4], normbiasB[2];
+    double allpairs;
+} cmfrec_hip_objective;
+int cmfrec_hip_session_objective(cmfrec_hip_session *s, cmfrec_hip_objective *out);
+double cmfrec_hip_objective_value(const cmfrec_hip_objective *rec, const double *lam6, double w_main, int scale_lam, int scale_bias_const);
+/* The objective while fitting: handed over like the monitor, per thread, consumed by the next fit_collective_*_als call on that
+ * thread whatever it returns; NULL clears it.  A fit without one runs exactly as before.
+ *   every      evaluate after iterations every, 2 every, ... (1-based) and after the last one; < 1 counts as 1
+ *   tol        after an evaluation f_t that has an earlier one f_p, the fit stops when f_p - f_t <= tol |f_p|; <= 0: watch only
+ *   values     [niter] out, optional: the objective per iteration, NaN where not evaluated or not run
+ *   records    [niter] out, optional: the components per evaluated iteration (the others are zeroed)
+ *   iters_run  out, optional: the iterations that ran
+ * A fit that stops before iteration niter - 1 does not add the finalize_chol pass.  Refused with 2 and a message, before the fit
+ * writes to any of its outputs: niter < 1; an objective together with a monitor; CMFREC_HIP_DEVICES naming several devices or
+ * CMFREC_HIP_SHARDED=1; a model cmfrec_hip_session_objective refuses (side information, k_user / k_item, implicit features,
+ * NA_as_zero_X, a dense X, an L1 penalty, k + k_main > 272). */
+typedef struct cmfrec_hip_fit_objective {
+    int every;
+    double tol;
+    double *values;
+    cmfrec_hip_objective *records;
+    int *iters_run;
+} cmfrec_hip_fit_objective;
+int cmfrec_hip_fit_set_objective(const cmfrec_hip_fit_objective *objective);
+
 /* Replace predict_X_old_collective_explicit / _implicit and predict_X_new_collective_explicit / _implicit of the reference's
  * src/cmfrec.h (bodies src/collective.c:11797-12069 over predict_multiple, src/common.c:5066-5110) -- the same positional
  * parameters, the same return codes; nthreads is accepted and ignored.
