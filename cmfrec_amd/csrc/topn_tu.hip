@@ -69,6 +69,7 @@ struct cmfrec_hip_ranker {
     bool fs_valid = false;
     hipEvent_t fev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the filter, the refinement and the certificate
     float f_ms[3] = {0, 0, 0};
+    const real_t *item_bias() const { return has_bias ? bias.ptr : nullptr; }
     ~cmfrec_hip_ranker()
     {
         for (hipEvent_t e : fev)
@@ -108,14 +109,30 @@ int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu, s
     return best;
 }
 
-template <int NUT>
-int launch_wide(const cmfrec_hip_ranker::Device &dev, const TopnWideParams<real_t> &P, int blocks_per_cu)
+// the run-time tile count as a compile-time one: f(std::integral_constant<int, NUT>) for NUT = nut
+template <class F>
+int with_tiles(int nut, F &&f)
 {
-    const size_t smem = topnw_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
-    HIP_CHECK(hipFuncSetAttribute((const void *)topn_wide_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
+    static_assert(TOPNW_MAX_NUT == 4, "one case per tile count");
+    switch (nut) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    default: return f(std::integral_constant<int, 4>());
+    }
+}
+
+// One launch of a kernel that takes nut user tiles per workgroup and smem bytes of LDS: a workgroup per tile group of P.nu users,
+// at most blocks_per_cu per CU, times grid_y (the item slices of the split kernel).  Returns the grid's first dimension.
+template <class Params>
+int launch_tiled(const cmfrec_hip_ranker::Device &dev, void (*kernel)(Params), int nut, size_t smem, const Params &P, int blocks_per_cu,
+                 int grid_y = 1)
+{
+    HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int tiles = (P.nu + 16 * nut - 1) / (16 * nut);
     const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
-    hipLaunchKernelGGL((topn_wide_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
+    hipLaunchKernelGGL(kernel, dim3(grid, grid_y), dim3(TOPNW_TH), smem, dev.stream, P);
+    HIP_CHECK(hipGetLastError());
     return grid;
 }
 
@@ -142,56 +159,6 @@ void plan_split(int nu, int n, int k, int n_top, int num_cus, size_t sizeof_real
     const long per = (rounds + want - 1) / want;
     *slices = (int)((rounds + per - 1) / per);
     *slice_items = (int)std::min<long>(per * TOPNW_ITEMS, ((long)0x7fffffff / TOPNW_ITEMS) * TOPNW_ITEMS);
-}
-
-// the slice pass and the merge of a split ranking: P.out_ids / P.out_scores are the scratch, `out` the call's result
-template <int NUT>
-int launch_split(const cmfrec_hip_ranker::Device &dev, const TopnSplitParams<real_t> &P, int blocks_per_cu, int slices,
-                 const TopnMergeParams<real_t> &M)
-{
-    const size_t smem = topnw_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
-    HIP_CHECK(hipFuncSetAttribute((const void *)topn_split_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
-    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
-    hipLaunchKernelGGL((topn_split_kernel<real_t, NUT>), dim3(grid, slices), dim3(TOPNW_TH), smem, dev.stream, P);
-    HIP_CHECK(hipGetLastError());
-    const int nw = topnsp_merge_waves(slices);
-    hipLaunchKernelGGL(topn_split_merge_kernel<real_t>, dim3(P.nu), dim3(64 * nw), topnsp_merge_lds_bytes(nw, P.n_top, sizeof(real_t)),
-                       dev.stream, M);
-    return grid * slices;
-}
-
-template <int NUT, int METRIC>
-int launch_similar(const cmfrec_hip_ranker::Device &dev, const TopnSimilarParams<real_t> &P, int blocks_per_cu)
-{
-    const size_t smem = topns_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
-    HIP_CHECK(hipFuncSetAttribute((const void *)topn_similar_kernel<real_t, NUT, METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
-    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
-    hipLaunchKernelGGL((topn_similar_kernel<real_t, NUT, METRIC>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
-    return grid;
-}
-
-template <int NUT>
-int launch_after(const cmfrec_hip_ranker::Device &dev, const TopnAfterParams<real_t> &P, int blocks_per_cu)
-{
-    const size_t smem = topna_lds_bytes(NUT, P.k, P.n_top, sizeof(real_t));
-    HIP_CHECK(hipFuncSetAttribute((const void *)topn_after_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
-    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
-    hipLaunchKernelGGL((topn_after_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
-    return grid;
-}
-
-template <int METRIC>
-int launch_similar_tiles(const cmfrec_hip_ranker::Device &dev, const TopnSimilarParams<real_t> &P, int nut, int blocks_per_cu)
-{
-    switch (nut) {
-    case 1: return launch_similar<1, METRIC>(dev, P, blocks_per_cu);
-    case 2: return launch_similar<2, METRIC>(dev, P, blocks_per_cu);
-    case 3: return launch_similar<3, METRIC>(dev, P, blocks_per_cu);
-    default: return launch_similar<4, METRIC>(dev, P, blocks_per_cu);
-    }
 }
 
 // the inverse norms of the ranker's rows, made on its stream the first time they are asked for (the caller holds the DeviceScope)
@@ -236,36 +203,121 @@ int pick_rank_shape(int nu, int k, size_t max_held, int num_cus, int *ts, int *t
     return best;
 }
 
-template <int NUT>
-int launch_rank(const cmfrec_hip_ranker::Device &dev, const TopnRankParams<real_t> &P, int blocks_per_cu)
+int refuse(const char *fn, const std::string &why)
 {
-    const size_t smem = topnr_lds_bytes(NUT, P.k, P.tsp, sizeof(real_t));
-    HIP_CHECK(hipFuncSetAttribute((const void *)topn_rank_kernel<real_t, NUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int tiles = (P.nu + 16 * NUT - 1) / (16 * NUT);
-    const int grid = std::min(tiles, dev.num_cus * blocks_per_cu);
-    hipLaunchKernelGGL((topn_rank_kernel<real_t, NUT>), dim3(grid), dim3(TOPNW_TH), smem, dev.stream, P);
-    return grid;
+    g_last_error = std::string(fn) + ": " + why;
+    return 2;
 }
 
 int check_n_top(const char *fn, int_t n_top, int_t n)
 {
-    if (n_top > TOPN_NMAX || n_top > n) {
-        g_last_error = std::string(fn) + ": " + LIMITS;
-        return 2;
-    }
-    return 0;
+    return (n_top > TOPN_NMAX || n_top > n) ? refuse(fn, LIMITS) : 0;
 }
 
-// the ranking of nu users whose factors dA [nu, lda] and exclusion lists are on the device already: the launch, the timing
-// events and the download of cmfrec_hip_ranker_topN (the caller holds the DeviceScope and has checked the limits)
+// what every call over a batch of users refuses as "invalid arguments": no handle, no users, factors narrower than the model,
+// exclusion offsets that promise indices that are not there (the order of an exclusion list is the caller's business)
+bool bad_users(const cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t *excl_p = nullptr, const int_t *excl_i = nullptr)
+{
+    return r == nullptr || nu <= 0 || !A || lda < (size_t)r->k || (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0);
+}
+
+// lists over `count` users or queries are a CSR: offsets that do not decrease, indices where there is an entry; *longest = the
+// longest list
+bool csr_ok(const size_t *p, const int_t *i, int_t count, size_t *longest = nullptr)
+{
+    if (p == nullptr) return false;
+    size_t len = 0;
+    for (int_t u = 0; u < count; u++) {
+        if (p[u] > p[u + 1]) return false;
+        len = std::max(len, p[u + 1] - p[u]);
+    }
+    if (longest) *longest = len;
+    return p[count] == 0 || i != nullptr;
+}
+
+void upload_csr(DevBuf<size_t> &dp, DevBuf<int> &di, const size_t *p, const int_t *i, int_t count, hipStream_t st)
+{
+    dp.upload(p, (size_t)count + 1, st);
+    di.alloc_at_least(std::max<size_t>(p[count], 1));
+    if (p[count] > 0) di.upload(i, p[count], st);
+}
+
+// the users of a call, on the device: factors dA [nu, lda] (null in a neighbour call, whose users are rows of B) and their
+// exclusion lists, both null where the call has none
+struct RankUsers {
+    const real_t *dA; size_t lda; int_t nu;
+    const size_t *excl_p; const int *excl_i;
+};
+
+// the factors of a call's users from the host (or wherever A is) into r->A, packed
+RankUsers stage_users(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu)
+{
+    const size_t k = (size_t)r->k;
+    r->A.alloc_at_least((size_t)nu * k);
+    upload_columns(r->A.ptr, k, A, lda, (size_t)nu, k, r->dev.stream);
+    return RankUsers{r->A.ptr, k, nu, nullptr, nullptr};
+}
+
+// ... and their exclusion lists (host CSR over users.nu, or null) into r->ep / r->ei
+void stage_exclusions(cmfrec_hip_ranker *r, RankUsers &users, const size_t *excl_p, const int_t *excl_i)
+{
+    if (excl_p == nullptr) return;
+    upload_csr(r->ep, r->ei, excl_p, excl_i, users.nu, r->dev.stream);
+    users.excl_p = r->ep.ptr; users.excl_i = r->ei.ptr;
+}
+
+// The fields the kernels' parameter structs have in common, filled from the ranker and the call; a struct without one of the
+// groups (the neighbour kernel has no user factors, the refinement no exclusions) does not call that group's function.
+template <class P> void set_items(P &p, const cmfrec_hip_ranker *r) { p.B = r->B.ptr; p.ldb = r->ldb; p.n = r->n; p.k = r->k; }
+template <class P> void set_users(P &p, const RankUsers &u) { p.A = u.dA; p.lda = u.lda; p.nu = u.nu; }
+template <class P> void set_exclusions(P &p, const RankUsers &u) { p.excl_p = u.excl_p; p.excl_i = u.excl_p ? u.excl_i : nullptr; }
+template <class P> void set_lists(P &p, const cmfrec_hip_ranker *r, int_t n_top, bool want_scores)
+{
+    p.n_top = n_top; p.out_ids = r->ids.ptr; p.out_scores = want_scores ? r->sc.ptr : nullptr;
+}
+
+// the parameters of a kernel that scores the users against every item: all of the above but the lists
+template <class P>
+P ranking_params(const cmfrec_hip_ranker *r, const RankUsers &users)
+{
+    P p;
+    set_items(p, r); p.biasB = r->item_bias();
+    set_users(p, users); set_exclusions(p, users);
+    return p;
+}
+
+// the end of the interval that cmfrec_hip_ranker_kernel_ms reports, and what _launch_shape and _slices say of its last launch
+void end_timed(cmfrec_hip_ranker *r, int users_per_workgroup, int grid, int slices)
+{
+    HIP_CHECK(hipEventRecord(r->ev1, r->dev.stream));
+    r->timed = true;
+    r->last_users = users_per_workgroup; r->last_grid = grid; r->last_slices = slices;
+}
+
+// the call's result comes down and the stream is waited for.  more / out_more: a third array of the call (the pools of a rank
+// call, the certificates of a filtered one), null where there is none or the caller does not want it
+void download_and_wait(cmfrec_hip_ranker *r, size_t cells, int_t *out_ids, real_t *out_scores, const DevBuf<int> *more = nullptr,
+                       int *out_more = nullptr, size_t n_more = 0)
+{
+    hipStream_t st = r->dev.stream;
+    r->ids.download(out_ids, cells, st);
+    if (out_scores) r->sc.download(out_scores, cells, st);
+    if (out_more) more->download(out_more, n_more, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// the ranking of users who are on the device already: the launch, the timing events and the download of cmfrec_hip_ranker_topN
+// (the caller holds the DeviceScope and has checked the limits)
 // dcand_p != null: over each user's candidate list (device CSR) on topn_cand_kernel
-int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
-                int_t *out_ids, real_t *out_scores, const size_t *dcand_p = nullptr, const int *dcand_i = nullptr)
+int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t *out_ids, real_t *out_scores,
+                const size_t *dcand_p = nullptr, const int *dcand_i = nullptr)
 {
     const cmfrec_hip_ranker::Device &dev = r->dev;
     const int k = r->k;
-    r->ids.alloc_at_least((size_t)nu * n_top);
-    if (out_scores) r->sc.alloc_at_least((size_t)nu * n_top);
+    const int_t nu = users.nu;
+    const size_t cells = (size_t)nu * n_top;
+    r->ids.alloc_at_least(cells);
+    if (out_scores) r->sc.alloc_at_least(cells);
     if (dcand_p) {
         r->next.alloc_at_least(1);
         HIP_CHECK(hipMemsetAsync(r->next.ptr, 0, sizeof(unsigned), dev.stream));
@@ -275,73 +327,57 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
     int slices = 1, slice_items = 0;
     if (split) plan_split(nu, r->n, k, n_top, dev.num_cus, sizeof(real_t), r->split, &slices, &slice_items);
     if (slices > 1) {
-        r->part_sc.alloc_at_least((size_t)slices * (size_t)nu * (size_t)n_top);
-        r->part_id.alloc_at_least((size_t)slices * (size_t)nu * (size_t)n_top);
+        r->part_sc.alloc_at_least((size_t)slices * cells);
+        r->part_id.alloc_at_least((size_t)slices * cells);
     }
-    r->last_slices = slices;
     HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    int users_per_workgroup = 0, grid = 0;
     if (dcand_p) {
-        TopnCandParams<real_t> P;
-        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
-        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+        auto P = ranking_params<TopnCandParams<real_t>>(r, users);
+        set_lists(P, r, n_top, out_scores != nullptr);
         P.cand_p = dcand_p; P.cand_i = dcand_i;
-        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
-        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
         P.next = r->next.ptr; P.order = r->corder.ptr;
-        r->last_grid = launch_topn_cand(dev.stream, dev.num_cus, P, switches().topn_cand_waves);
-        r->last_users = TOPNC_NW;
+        grid = launch_topn_cand(dev.stream, dev.num_cus, P, switches().topn_cand_waves);
+        users_per_workgroup = TOPNC_NW;
     } else if (slices > 1) {
-        TopnSplitParams<real_t> P;
-        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
-        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+        // the slice pass writes every slice's list into the scratch, the merge makes the call's result of them
+        auto P = ranking_params<TopnSplitParams<real_t>>(r, users);
         P.n_top = n_top; P.out_ids = r->part_id.ptr; P.out_scores = r->part_sc.ptr;
         P.slice_items = slice_items; P.s0 = P.s1 = 0;
         TopnMergeParams<real_t> M;
-        M.part_scores = r->part_sc.ptr; M.part_ids = r->part_id.ptr; M.slices = slices; M.nu = nu; M.n_top = n_top;
-        M.out_ids = r->ids.ptr; M.out_scores = out_scores ? r->sc.ptr : nullptr;
+        M.part_scores = r->part_sc.ptr; M.part_ids = r->part_id.ptr; M.slices = slices; M.nu = nu;
+        set_lists(M, r, n_top, out_scores != nullptr);
         int bpc = 1;
         const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
-        switch (nut) {
-        case 1: r->last_grid = launch_split<1>(dev, P, bpc, slices, M); break;
-        case 2: r->last_grid = launch_split<2>(dev, P, bpc, slices, M); break;
-        case 3: r->last_grid = launch_split<3>(dev, P, bpc, slices, M); break;
-        default: r->last_grid = launch_split<4>(dev, P, bpc, slices, M); break;
-        }
-        r->last_users = 16 * nut;
+        grid = slices * with_tiles(nut, [&](auto t) {
+            const int tiles = launch_tiled(dev, topn_split_kernel<real_t, t()>, t(), topnw_lds_bytes(t(), k, n_top, sizeof(real_t)), P, bpc, slices);
+            const int nw = topnsp_merge_waves(slices);
+            hipLaunchKernelGGL(topn_split_merge_kernel<real_t>, dim3(nu), dim3(64 * nw), topnsp_merge_lds_bytes(nw, n_top, sizeof(real_t)),
+                               dev.stream, M);
+            return tiles;
+        });
+        users_per_workgroup = 16 * nut;
     } else if (k <= TOPN_KMAX && !switches().topn_wide && !split) {
-        TopnParams<real_t> P;
-        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
-        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
-        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+        auto P = ranking_params<TopnParams<real_t>>(r, users);
+        set_lists(P, r, n_top, out_scores != nullptr);
         const size_t smem = topn_lds_bytes(sizeof(real_t));
         HIP_CHECK(hipFuncSetAttribute((const void *)topn_kernel<real_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        const int tiles = (nu + TOPN_UT - 1) / TOPN_UT;
-        hipLaunchKernelGGL(topn_kernel<real_t>, dim3(std::min(tiles, dev.num_cus * 2)), dim3(TOPN_TH), smem, dev.stream, P);
-        r->last_users = TOPN_UT; r->last_grid = std::min(tiles, dev.num_cus * 2);
+        grid = std::min((nu + TOPN_UT - 1) / TOPN_UT, dev.num_cus * 2);
+        hipLaunchKernelGGL(topn_kernel<real_t>, dim3(grid), dim3(TOPN_TH), smem, dev.stream, P);
+        users_per_workgroup = TOPN_UT;
     } else {
-        TopnWideParams<real_t> P;
-        P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = k;
-        P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-        P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
-        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
+        auto P = ranking_params<TopnWideParams<real_t>>(r, users);
+        set_lists(P, r, n_top, out_scores != nullptr);
         int bpc = 1;
         const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
-        switch (nut) {
-        case 1: r->last_grid = launch_wide<1>(dev, P, bpc); break;
-        case 2: r->last_grid = launch_wide<2>(dev, P, bpc); break;
-        case 3: r->last_grid = launch_wide<3>(dev, P, bpc); break;
-        default: r->last_grid = launch_wide<4>(dev, P, bpc); break;
-        }
-        r->last_users = 16 * nut;
+        grid = with_tiles(nut, [&](auto t) {
+            return launch_tiled(dev, topn_wide_kernel<real_t, t()>, t(), topnw_lds_bytes(t(), k, n_top, sizeof(real_t)), P, bpc);
+        });
+        users_per_workgroup = 16 * nut;
     }
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
-    r->timed = true;
-    r->ids.download(out_ids, (size_t)nu * n_top, dev.stream);
-    if (out_scores) r->sc.download(out_scores, (size_t)nu * n_top, dev.stream);
-    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    end_timed(r, users_per_workgroup, grid, slices);
+    download_and_wait(r, cells, out_ids, out_scores);
     return 0;
 }
 
@@ -349,7 +385,7 @@ int rank_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, co
 bool ensure_filter_image(cmfrec_hip_ranker *r)
 {
     if (!r->fimg.ready)
-        topn_filter_build_image(r->dev.stream, r->dev.num_cus, r->B.ptr, r->ldb, r->n, r->k, r->has_bias ? r->bias.ptr : nullptr, r->fimg);
+        topn_filter_build_image(r->dev.stream, r->dev.num_cus, r->B.ptr, r->ldb, r->n, r->k, r->item_bias(), r->fimg);
     return r->fimg.usable;
 }
 
@@ -360,24 +396,26 @@ int filter_m(int_t n_top)
     return topnf_m((int)n_top, (v != nullptr && v[0] != 0) ? atoi(v) : 0);
 }
 
-TopnFilterParams<real_t> filter_params(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, int m)
+// the filter kernel's parameters over the image of the items; the outputs are the caller's to set
+TopnFilterParams<real_t> filter_params(cmfrec_hip_ranker *r, const RankUsers &users, int m)
 {
     TopnFilterParams<real_t> P;
-    P.A = dA; P.lda = lda; P.nu = nu; P.Bh = r->fimg.Bh.ptr; P.n = r->n; P.k = r->k;
+    set_users(P, users); set_exclusions(P, users);
+    P.Bh = r->fimg.Bh.ptr; P.n = r->n; P.k = r->k;
     P.nb = r->fimg.nb.ptr; P.db = r->fimg.db.ptr; P.sb = r->fimg.sb;
-    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-    P.excl_p = nullptr; P.excl_i = nullptr; P.m = m;
+    P.biasB = r->item_bias(); P.m = m;
     P.short_ids = nullptr; P.tau = nullptr; P.state = nullptr; P.keys = nullptr;
     return P;
 }
 
-// The filtered ranking of nu users whose factors dA [nu, lda] and exclusion lists are on the device:
-// topn_filter_kernel leaves a shortlist of m ids and the bound tau per user, topn_filter_refine_kernel ranks the shortlists with
-// the scores of the kernel rank_device would launch for this ranker (the same routing), topn_filter_certify_kernel compares.  ids / scores come down for every user, certified [nu] says whose are final.
-int rank_device_filtered(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
-                         int_t *out_ids, real_t *out_scores, int *certified)
+// The filtered ranking of users who are on the device: topn_filter_kernel leaves a shortlist of m ids
+// and the bound tau per user, topn_filter_refine_kernel ranks the shortlists with the scores of the kernel rank_device would
+// launch for this ranker (the same routing), topn_filter_certify_kernel compares.  ids / scores come down for every user,
+// certified [nu] says whose are final.
+int rank_device_filtered(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t *out_ids, real_t *out_scores, int *certified)
 {
     const cmfrec_hip_ranker::Device &dev = r->dev;
+    const int_t nu = users.nu;
     const int m = filter_m(n_top);
     const size_t cells = (size_t)nu * (size_t)n_top;
     r->ids.alloc_at_least(cells);
@@ -388,29 +426,24 @@ int rank_device_filtered(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int
     r->f_tau.alloc_at_least((size_t)nu);
     for (hipEvent_t &e : r->fev)
         if (!e) HIP_CHECK(hipEventCreate(&e));
-    TopnFilterParams<real_t> F = filter_params(r, dA, lda, nu, m);
-    F.excl_p = dexcl_p; F.excl_i = dexcl_p ? dexcl_i : nullptr;
+    TopnFilterParams<real_t> F = filter_params(r, users, m);
     F.short_ids = r->f_short.ptr; F.tau = r->f_tau.ptr; F.state = r->f_state.ptr;
     HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
     HIP_CHECK(hipEventRecord(r->fev[0], dev.stream));
-    r->last_grid = topn_filter_launch(dev.stream, dev.num_cus, F, switches().topn_tiles, &r->last_users);
+    int users_per_workgroup = 0;
+    const int grid = topn_filter_launch(dev.stream, dev.num_cus, F, switches().topn_tiles, &users_per_workgroup);
     HIP_CHECK(hipEventRecord(r->fev[1], dev.stream));
     TopnRefineParams<real_t> P;
-    P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
-    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+    set_items(P, r); P.biasB = r->item_bias();
+    set_users(P, users);
+    set_lists(P, r, n_top, true);
     P.short_ids = r->f_short.ptr; P.m = m;
-    P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = r->sc.ptr;
     topn_filter_refine(dev.stream, dev.num_cus, P, !(r->k <= TOPN_KMAX && !switches().topn_wide));
     HIP_CHECK(hipEventRecord(r->fev[2], dev.stream));
     topn_filter_certify(dev.stream, r->sc.ptr, nu, n_top, r->f_tau.ptr, r->f_state.ptr, r->f_cert.ptr);
     HIP_CHECK(hipEventRecord(r->fev[3], dev.stream));
-    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
-    r->timed = true;
-    r->last_slices = 1;
-    r->ids.download(out_ids, cells, dev.stream);
-    if (out_scores) r->sc.download(out_scores, cells, dev.stream);
-    r->f_cert.download(certified, (size_t)nu, dev.stream);
-    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    end_timed(r, users_per_workgroup, grid, 1);
+    download_and_wait(r, cells, out_ids, out_scores, &r->f_cert, certified, (size_t)nu);
     for (int s = 0; s < 3; s++) HIP_CHECK(hipEventElapsedTime(&r->f_ms[s], r->fev[s], r->fev[s + 1]));
     return 0;
 }
@@ -435,49 +468,37 @@ int pick_page_len(int k, int_t n_top)
     return (int)std::min<int_t>(len, n_top);
 }
 
-// The n_top best of nu users behind their cursors, in pages of page_len on topn_after_kernel, for every k (the register-resident
+// The n_top best of the users behind their cursors, in pages of page_len on topn_after_kernel, for every k (the register-resident
 // topn_kernel of k <= 64 rounds otherwise, and a cursor compares bits).  The whole [nu, n_top] result lives in r->ids / r->sc;
 // page p is one launch that writes the columns [p * page_len, ...) and reads its cursors from the column in front of them -- no
 // host round trip between the pages, one download at the end.  The first page's cursors: dcur_s / dcur_i [nu], or null (every
 // user starts at the top).  The timing events enclose all the pages.  Returns the launches in *pages.
-// (the caller holds the DeviceScope and has checked the limits; the factors and exclusion lists are on the device)
-int rank_device_deep(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, const size_t *dexcl_p, const int *dexcl_i, int_t n_top,
-                     int page_len, const real_t *dcur_s, const int *dcur_i, int_t *out_ids, real_t *out_scores, int *pages)
+// (the caller holds the DeviceScope and has checked the limits; the users are on the device)
+int rank_device_deep(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int page_len, const real_t *dcur_s, const int *dcur_i,
+                     int_t *out_ids, real_t *out_scores, int *pages)
 {
     const cmfrec_hip_ranker::Device &dev = r->dev;
-    const size_t cells = (size_t)nu * (size_t)n_top;
+    const size_t cells = (size_t)users.nu * (size_t)n_top;
     r->ids.alloc_at_least(cells);
     r->sc.alloc_at_least(cells);                                         // (the next page's cursors, wanted by the caller or not)
-    TopnAfterParams<real_t> P;
-    P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
-    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
-    P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
+    auto P = ranking_params<TopnAfterParams<real_t>>(r, users);
     P.out_ld = (size_t)n_top;
     poison_lds(dev.stream, dev.num_cus);                                 // (the policy's LDS too is written before it is read)
     HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
-    int launches = 0;
+    int launches = 0, nut = 1, grid = 0;
     for (int_t first = 0; first < n_top; first += page_len, launches++) {
         P.n_top = (int)std::min<int_t>(page_len, n_top - first);
         P.out_ids = r->ids.ptr + first; P.out_scores = r->sc.ptr + first;
         if (first == 0) { P.cur_scores = dcur_s; P.cur_ids = dcur_s ? dcur_i : nullptr; P.cur_ld = 1; }
         else { P.cur_scores = r->sc.ptr + first - 1; P.cur_ids = r->ids.ptr + first - 1; P.cur_ld = (size_t)n_top; }
         int bpc = 1;
-        const int nut = pick_user_tiles(nu, r->k, P.n_top, dev.num_cus, &bpc, topna_extra_bytes(sizeof(real_t)));
-        switch (nut) {
-        case 1: r->last_grid = launch_after<1>(dev, P, bpc); break;
-        case 2: r->last_grid = launch_after<2>(dev, P, bpc); break;
-        case 3: r->last_grid = launch_after<3>(dev, P, bpc); break;
-        default: r->last_grid = launch_after<4>(dev, P, bpc); break;
-        }
-        r->last_users = 16 * nut;
-        HIP_CHECK(hipGetLastError());
+        nut = pick_user_tiles(users.nu, r->k, P.n_top, dev.num_cus, &bpc, topna_extra_bytes(sizeof(real_t)));
+        grid = with_tiles(nut, [&](auto t) {
+            return launch_tiled(dev, topn_after_kernel<real_t, t()>, t(), topna_lds_bytes(t(), P.k, P.n_top, sizeof(real_t)), P, bpc);
+        });
     }
-    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
-    r->timed = true;
-    r->last_slices = 1;
-    r->ids.download(out_ids, cells, dev.stream);
-    if (out_scores) r->sc.download(out_scores, cells, dev.stream);
-    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    end_timed(r, 16 * nut, grid, 1);
+    download_and_wait(r, cells, out_ids, out_scores);
     if (pages) *pages = launches;
     return 0;
 }
@@ -485,21 +506,14 @@ int rank_device_deep(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t n
 // the candidate lists of a call (host CSR over the nu users) into the ranker's buffers; 2 with a message for lists that are not a CSR
 int upload_candidates(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size_t cand_p[], const int_t cand_i[])
 {
-    bool bad = cand_p == nullptr;
-    for (int_t u = 0; !bad && u < nu; u++) bad = cand_p[u] > cand_p[u + 1];
-    if (bad || (cand_p[nu] > 0 && cand_i == nullptr)) {
-        g_last_error = std::string(fn) + ": invalid arguments";
-        return 2;
-    }
+    if (!csr_ok(cand_p, cand_i, nu)) return refuse(fn, "invalid arguments");
     // the order the kernel hands the users out in: longest list first (a long list that starts last is the launch's tail)
     std::vector<int> order((size_t)nu);
     for (int_t u = 0; u < nu; u++) order[u] = u;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cand_p[a + 1] - cand_p[a] > cand_p[b + 1] - cand_p[b]; });
     r->corder.upload(order.data(), (size_t)nu, r->dev.stream);
     HIP_CHECK(hipStreamSynchronize(r->dev.stream));          // `order` goes away
-    r->cp.upload(cand_p, (size_t)nu + 1, r->dev.stream);
-    r->ci.alloc_at_least(std::max<size_t>(cand_p[nu], 1));
-    if (cand_p[nu] > 0) r->ci.upload(cand_i, cand_p[nu], r->dev.stream);
+    upload_csr(r->cp, r->ci, cand_p, cand_i, nu, r->dev.stream);
     return 0;
 }
 
@@ -507,67 +521,48 @@ int upload_candidates(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size
 // CSR; *max_held = the longest list
 int upload_held(cmfrec_hip_ranker *r, const char *fn, int_t nu, const size_t held_p[], const int_t held_i[], size_t *max_held)
 {
-    bool bad = held_p == nullptr;
-    size_t longest = 0;
-    for (int_t u = 0; !bad && u < nu; u++) {
-        bad = held_p[u] > held_p[u + 1];
-        if (!bad) longest = std::max(longest, held_p[u + 1] - held_p[u]);
-    }
-    if (bad || longest > (size_t)0x7fffffff || (held_p[nu] > held_p[0] && held_i == nullptr)) {
-        g_last_error = std::string(fn) + ": invalid arguments";
-        return 2;
-    }
-    r->cp.upload(held_p, (size_t)nu + 1, r->dev.stream);
-    r->ci.alloc_at_least(std::max<size_t>(held_p[nu], 1));
-    if (held_p[nu] > 0) r->ci.upload(held_i, held_p[nu], r->dev.stream);
-    *max_held = longest;
+    if (!csr_ok(held_p, held_i, nu, max_held) || *max_held > (size_t)0x7fffffff) return refuse(fn, "invalid arguments");
+    upload_csr(r->cp, r->ci, held_p, held_i, nu, r->dev.stream);
     return 0;
 }
 
-// the ranks of nu users whose factors dA [nu, lda], held-out lists (r->cp / r->ci, total entries) and exclusion lists are on the
-// device: the launch, the timing events (around topn_rank_kernel, whose threshold and exclusion steps are part of it) and the
-// download.  Nothing is written to the outputs before the kernel has run.
+// the ranks of users who are on the device, as are their held-out lists (total entries, the longest max_held): the launch, the
+// timing events (around topn_rank_kernel, whose threshold and exclusion steps are part of it) and the download.  Nothing is
+// written to the outputs before the kernel has run.
 // dheld_p / dheld_i: the held-out lists where they are (null: the ranker's own r->cp / r->ci, filled by upload_held).  stay: the
 // ranks and the pool stay on the device (r->ids, r->pool) for rank_metrics_kernel behind the launch; nothing is downloaded and
 // the stream is not waited for.
-int ranks_device(cmfrec_hip_ranker *r, const real_t *dA, size_t lda, int_t nu, size_t total, size_t max_held, const size_t *dexcl_p,
-                 const int *dexcl_i, int_t *out_rank, real_t *out_scores, int_t *out_pool, const size_t *dheld_p = nullptr,
-                 const int *dheld_i = nullptr, bool stay = false)
+int ranks_device(cmfrec_hip_ranker *r, const RankUsers &users, size_t total, size_t max_held, int_t *out_rank, real_t *out_scores,
+                 int_t *out_pool, const size_t *dheld_p = nullptr, const int *dheld_i = nullptr, bool stay = false)
 {
     const cmfrec_hip_ranker::Device &dev = r->dev;
     r->ids.alloc_at_least(std::max<size_t>(total, 1));
     if (out_scores) r->sc.alloc_at_least(std::max<size_t>(total, 1));
-    if (out_pool || stay) r->pool.alloc_at_least((size_t)nu);
-    TopnRankParams<real_t> P;
-    P.A = dA; P.lda = lda; P.nu = nu; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
-    P.biasB = r->has_bias ? r->bias.ptr : nullptr;
+    if (out_pool || stay) r->pool.alloc_at_least((size_t)users.nu);
+    auto P = ranking_params<TopnRankParams<real_t>>(r, users);
     P.held_p = dheld_p ? dheld_p : r->cp.ptr; P.held_i = dheld_p ? dheld_i : r->ci.ptr;
-    P.excl_p = dexcl_p; P.excl_i = dexcl_p ? dexcl_i : nullptr;
     P.out_rank = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr; P.out_pool = (out_pool || stay) ? r->pool.ptr : nullptr;
     int bpc = 1;
-    const int nut = pick_rank_shape(nu, r->k, max_held, dev.num_cus, &P.ts, &P.tsp, &bpc);
-    if (nut == 0) {
-        g_last_error = "cmfrec_hip_ranker_ranks: the model does not fit the rank kernel's LDS";
-        return 2;
-    }
+    const int nut = pick_rank_shape(users.nu, r->k, max_held, dev.num_cus, &P.ts, &P.tsp, &bpc);
+    if (nut == 0) return refuse("cmfrec_hip_ranker_ranks", "the model does not fit the rank kernel's LDS");
     HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
-    switch (nut) {
-    case 1: r->last_grid = launch_rank<1>(dev, P, bpc); break;
-    case 2: r->last_grid = launch_rank<2>(dev, P, bpc); break;
-    case 3: r->last_grid = launch_rank<3>(dev, P, bpc); break;
-    default: r->last_grid = launch_rank<4>(dev, P, bpc); break;
-    }
-    r->last_users = 16 * nut;
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
-    r->timed = true;
-    r->last_slices = 1;
-    if (stay) return 0;
-    r->ids.download(out_rank, total, dev.stream);
-    if (out_scores) r->sc.download(out_scores, total, dev.stream);
-    if (out_pool) r->pool.download(out_pool, (size_t)nu, dev.stream);
-    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    const int grid = with_tiles(nut, [&](auto t) {
+        return launch_tiled(dev, topn_rank_kernel<real_t, t()>, t(), topnr_lds_bytes(t(), P.k, P.tsp, sizeof(real_t)), P, bpc);
+    });
+    end_timed(r, 16 * nut, grid, 1);
+    if (!stay) download_and_wait(r, total, out_rank, out_scores, &r->pool, out_pool, (size_t)users.nu);
     return 0;
+}
+
+// a ranker of its own on the current device for one call
+template <class F>
+int with_ranker(const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB, F &&call)
+{
+    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
+    if (r == nullptr) return g_last_rc;
+    const int rc = call(r);
+    cmfrec_hip_ranker_destroy(r);
+    return rc;
 }
 
 }  // namespace
@@ -622,9 +617,8 @@ int rankset_run(cmfrec_hip_ranker *r, cmfrec_hip_rankset *set, const char *fn, c
         HIP_CHECK(hipStreamSynchronize(st));                 // the vectors go away
         set->table_k = k_at;
     }
-    if (int rc = ranks_device(r, dA, lda, set->nu, set->total, set->max_held, set->has_excl ? set->excl_p.ptr : nullptr,
-                              set->has_excl ? set->excl_i.ptr : nullptr, nullptr, nullptr, nullptr, set->held_p.ptr, set->held_i.ptr, true))
-        return rc;
+    const RankUsers users{dA, lda, set->nu, set->has_excl ? set->excl_p.ptr : nullptr, set->has_excl ? set->excl_i.ptr : nullptr};
+    if (int rc = ranks_device(r, users, set->total, set->max_held, nullptr, nullptr, nullptr, set->held_p.ptr, set->held_i.ptr, true)) return rc;
     const char *cap = getenv("CMFREC_HIP_RANKMETRIC_WAVES");            // test hook, read per call
     const int max_waves = (cap != nullptr && cap[0] != 0) ? atoi(cap) : 0;
     const size_t waves = rank_metrics_waves(set->nu, r->dev.num_cus, max_waves);
@@ -775,31 +769,21 @@ cmfrec_hip_ranker *cmfrec_hip_ranker_create(const real_t *B, size_t ldb, int_t n
 int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t excl_p[], const int_t excl_i[],
                            int_t n_top, int_t *out_ids, real_t *out_scores)
 {
+    const char *fn = "cmfrec_hip_ranker_topN";
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || n_top <= 0 || !A || !out_ids || lda < (size_t)r->k || (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
-            g_last_error = "cmfrec_hip_ranker_topN: invalid arguments";
-            return 2;
-        }
-        if (int rc = check_n_top("cmfrec_hip_ranker_topN", n_top, r->n)) return rc;
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || n_top <= 0 || !out_ids) return refuse(fn, "invalid arguments");
+        if (int rc = check_n_top(fn, n_top, r->n)) return rc;
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        const cmfrec_hip_ranker::Device &dev = r->dev;
-        const int k = r->k;
-        r->A.alloc_at_least((size_t)nu * k);
-        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
-        if (excl_p) {
-            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
-            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
-            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
-        }
+        const size_t k = (size_t)r->k;
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
         r->fs_valid = true; r->fs_users = nu; r->fs_filtered = 0; r->fs_certified = 0;
         // the filter: n_top <= 64 of a ranker that is not split and whose items have an image; everything else as it always was
         if (r->filter != 1 || n_top > TOPNF_NTOP_MAX || r->split >= 0 || !ensure_filter_image(r))
-            return rank_device(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids, out_scores);
+            return rank_device(r, users, n_top, out_ids, out_scores);
         std::vector<int> cert((size_t)nu);
-        if (int rc = rank_device_filtered(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids,
-                                          out_scores, cert.data()))
-            return rc;
+        if (int rc = rank_device_filtered(r, users, n_top, out_ids, out_scores, cert.data())) return rc;
         // the users without a certificate: one batch on the exact route, their rows scattered into the result
         std::vector<int_t> rest;
         for (int_t u = 0; u < nu; u++)
@@ -807,24 +791,20 @@ int cmfrec_hip_ranker_topN(cmfrec_hip_ranker *r, const real_t *A, size_t lda, in
         r->fs_filtered = nu; r->fs_certified = nu - (int)rest.size();
         if (rest.empty()) return 0;
         const size_t nr = rest.size();
-        std::vector<real_t> Ar(nr * (size_t)k), sr(out_scores ? nr * (size_t)n_top : 0);
+        std::vector<real_t> Ar(nr * k), sr(out_scores ? nr * (size_t)n_top : 0);
         std::vector<int_t> ir(nr * (size_t)n_top), xi;
         std::vector<size_t> xp(excl_p ? nr + 1 : 0, 0);
         for (size_t j = 0; j < nr; j++) {
             const int_t u = rest[j];
-            memcpy(&Ar[j * (size_t)k], A + (size_t)u * lda, (size_t)k * sizeof(real_t));
+            memcpy(&Ar[j * k], A + (size_t)u * lda, k * sizeof(real_t));
             if (excl_p) {
                 xi.insert(xi.end(), excl_i + excl_p[u], excl_i + excl_p[u + 1]);
                 xp[j + 1] = xi.size();
             }
         }
-        upload_columns(r->A.ptr, (size_t)k, Ar.data(), (size_t)k, nr, (size_t)k, dev.stream);
-        if (excl_p) {
-            r->ep.upload(xp.data(), nr + 1, dev.stream);
-            if (!xi.empty()) r->ei.upload(xi.data(), xi.size(), dev.stream);
-        }
-        if (int rc = rank_device(r, r->A.ptr, (size_t)k, (int_t)nr, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, ir.data(),
-                                 out_scores ? sr.data() : nullptr))
+        users = stage_users(r, Ar.data(), k, (int_t)nr);
+        stage_exclusions(r, users, excl_p ? xp.data() : nullptr, xi.data());
+        if (int rc = rank_device(r, users, n_top, ir.data(), out_scores ? sr.data() : nullptr))
             return rc;                                       // (rank_device has waited for the stream: the vectors may go)
         for (size_t j = 0; j < nr; j++) {
             memcpy(out_ids + (size_t)rest[j] * n_top, &ir[j * (size_t)n_top], (size_t)n_top * sizeof(int_t));
@@ -876,27 +856,16 @@ int cmfrec_hip_ranker_filter_keys(cmfrec_hip_ranker *r, const real_t *A, size_t 
 {
     const char *fn = "cmfrec_hip_ranker_filter_keys";
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || !A || !keys_out || lda < (size_t)r->k) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
-        if ((size_t)nu * (size_t)r->n > ((size_t)1 << 20)) {
-            g_last_error = std::string(fn) + ": a probe for small shapes, needs nu * n <= 2^20";
-            return 2;
-        }
+        if (bad_users(r, A, lda, nu) || !keys_out) return refuse(fn, "invalid arguments");
+        if ((size_t)nu * (size_t)r->n > ((size_t)1 << 20)) return refuse(fn, "a probe for small shapes, needs nu * n <= 2^20");
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        if (r->filter != 1 || !ensure_filter_image(r)) {
-            g_last_error = std::string(fn) + ": the filter of this handle is off, or its items have no image";
-            return 2;
-        }
+        if (r->filter != 1 || !ensure_filter_image(r)) return refuse(fn, "the filter of this handle is off, or its items have no image");
         const cmfrec_hip_ranker::Device &dev = r->dev;
-        const int k = r->k;
         const size_t cells = (size_t)nu * (size_t)r->n;
-        r->A.alloc_at_least((size_t)nu * k);
-        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
+        const RankUsers users = stage_users(r, A, lda, nu);
         r->f_keys.alloc_at_least(cells);
-        TopnFilterParams<real_t> F = filter_params(r, r->A.ptr, (size_t)k, nu, TOPNF_M_MIN);
+        TopnFilterParams<real_t> F = filter_params(r, users, TOPNF_M_MIN);
         F.keys = r->f_keys.ptr;
         topn_filter_launch_keys(dev.stream, dev.num_cus, F);
         r->f_keys.download(keys_out, cells, dev.stream);
@@ -910,26 +879,14 @@ int cmfrec_hip_ranker_topN_candidates(cmfrec_hip_ranker *r, const real_t *A, siz
 {
     const char *fn = "cmfrec_hip_ranker_topN_candidates";
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || n_top <= 0 || !A || !out_ids || !cand_p || lda < (size_t)r->k ||
-            (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || n_top <= 0 || !out_ids || !cand_p) return refuse(fn, "invalid arguments");
         if (int rc = check_n_top(fn, n_top, r->n)) return rc;
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        const cmfrec_hip_ranker::Device &dev = r->dev;
-        const int k = r->k;
         if (int rc = upload_candidates(r, fn, nu, cand_p, cand_i)) return rc;
-        r->A.alloc_at_least((size_t)nu * k);
-        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
-        if (excl_p) {
-            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
-            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
-            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
-        }
-        return rank_device(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, out_ids, out_scores,
-                           r->cp.ptr, r->ci.ptr);
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
+        return rank_device(r, users, n_top, out_ids, out_scores, r->cp.ptr, r->ci.ptr);
     });
 }
 
@@ -938,30 +895,15 @@ int cmfrec_hip_ranker_topN_deep(cmfrec_hip_ranker *r, const real_t *A, size_t ld
 {
     const char *fn = "cmfrec_hip_ranker_topN_deep";
     return guarded([&]() {
-        if (r != nullptr && (n_top < 1 || n_top > r->n)) {
-            g_last_error = std::string(fn) + ": " + DEEP_LIMITS;
-            return 2;
-        }
-        if (r == nullptr || nu <= 0 || !A || !out_ids || lda < (size_t)r->k || (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (r != nullptr && (n_top < 1 || n_top > r->n)) return refuse(fn, DEEP_LIMITS);
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || !out_ids) return refuse(fn, "invalid arguments");
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        const cmfrec_hip_ranker::Device &dev = r->dev;
-        const int k = r->k;
-        r->A.alloc_at_least((size_t)nu * k);
-        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
-        if (excl_p) {
-            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
-            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
-            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
-        }
-        const int len = pick_page_len(k, n_top);
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
+        const int len = pick_page_len(r->k, n_top);
         int pages = 0;
-        if (int rc = rank_device_deep(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, len, nullptr,
-                                      nullptr, out_ids, out_scores, &pages))
-            return rc;
+        if (int rc = rank_device_deep(r, users, n_top, len, nullptr, nullptr, out_ids, out_scores, &pages)) return rc;
         r->last_pages = pages; r->last_page_len = len;
         return 0;
     });
@@ -972,29 +914,19 @@ int cmfrec_hip_ranker_topN_after(cmfrec_hip_ranker *r, const real_t *A, size_t l
 {
     const char *fn = "cmfrec_hip_ranker_topN_after";
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || n_top <= 0 || !A || !out_ids || lda < (size_t)r->k || (after_ids == nullptr) != (after_scores == nullptr) ||
-            (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || n_top <= 0 || !out_ids || (after_ids == nullptr) != (after_scores == nullptr))
+            return refuse(fn, "invalid arguments");
         if (int rc = check_n_top(fn, n_top, r->n)) return rc;
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        const cmfrec_hip_ranker::Device &dev = r->dev;
-        const int k = r->k;
-        r->A.alloc_at_least((size_t)nu * k);
-        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
-        if (excl_p) {
-            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
-            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
-            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
-        }
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
         if (after_ids) {
-            r->cur_s.upload(after_scores, (size_t)nu, dev.stream);
-            r->cur_i.upload(after_ids, (size_t)nu, dev.stream);
+            r->cur_s.upload(after_scores, (size_t)nu, r->dev.stream);
+            r->cur_i.upload(after_ids, (size_t)nu, r->dev.stream);
         }
-        return rank_device_deep(r, r->A.ptr, (size_t)k, nu, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr, n_top, (int)n_top,
-                                after_ids ? r->cur_s.ptr : nullptr, after_ids ? r->cur_i.ptr : nullptr, out_ids, out_scores, nullptr);
+        return rank_device_deep(r, users, n_top, (int)n_top, after_ids ? r->cur_s.ptr : nullptr, after_ids ? r->cur_i.ptr : nullptr, out_ids,
+                                out_scores, nullptr);
     });
 }
 
@@ -1014,26 +946,14 @@ int cmfrec_hip_ranker_ranks(cmfrec_hip_ranker *r, const real_t *A, size_t lda, i
 {
     const char *fn = "cmfrec_hip_ranker_ranks";
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || !A || !held_p || lda < (size_t)r->k || (held_p[nu] > 0 && !out_rank) ||
-            (excl_p != nullptr && excl_i == nullptr && excl_p[nu] > 0)) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || !held_p || (held_p[nu] > 0 && !out_rank)) return refuse(fn, "invalid arguments");
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        const cmfrec_hip_ranker::Device &dev = r->dev;
-        const int k = r->k;
         size_t max_held = 0;
         if (int rc = upload_held(r, fn, nu, held_p, held_i, &max_held)) return rc;
-        r->A.alloc_at_least((size_t)nu * k);
-        upload_columns(r->A.ptr, (size_t)k, A, lda, (size_t)nu, (size_t)k, dev.stream);
-        if (excl_p) {
-            r->ep.upload(excl_p, (size_t)nu + 1, dev.stream);
-            r->ei.alloc_at_least(std::max<size_t>(excl_p[nu], 1));
-            if (excl_p[nu] > 0) r->ei.upload(excl_i, excl_p[nu], dev.stream);
-        }
-        return ranks_device(r, r->A.ptr, (size_t)k, nu, held_p[nu], max_held, excl_p ? r->ep.ptr : nullptr, excl_p ? r->ei.ptr : nullptr,
-                            out_rank, out_scores, out_pool);
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
+        return ranks_device(r, users, held_p[nu], max_held, out_rank, out_scores, out_pool);
     });
 }
 
@@ -1127,60 +1047,43 @@ int cmfrec_hip_ranker_similar(cmfrec_hip_ranker *r, const int_t *query_ids, int_
 {
     const char *fn = "cmfrec_hip_ranker_similar";
     return guarded([&]() {
-        if (r == nullptr || nq < 0 || n_top <= 0 || (nq > 0 && (!query_ids || !out_ids))) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
-        if (metric != TOPNS_DOT && metric != TOPNS_COSINE) {
-            g_last_error = std::string(fn) + ": metric must be 0 (dot product) or 1 (cosine), got " + std::to_string(metric);
-            return 2;
-        }
+        if (r == nullptr || nq < 0 || n_top <= 0 || (nq > 0 && (!query_ids || !out_ids))) return refuse(fn, "invalid arguments");
+        if (metric != TOPNS_DOT && metric != TOPNS_COSINE)
+            return refuse(fn, "metric must be 0 (dot product) or 1 (cosine), got " + std::to_string(metric));
         if (int rc = check_n_top(fn, n_top, r->n)) return rc;
         for (int_t q = 0; q < nq; q++)
-            if (query_ids[q] < 0 || query_ids[q] >= r->n) {
-                g_last_error = std::string(fn) + ": query id " + std::to_string(query_ids[q]) + " (entry " + std::to_string(q) +
-                               ") is not a row of the ranker's " + std::to_string(r->n);
-                return 2;
-            }
-        if (excl_p != nullptr) {
-            bool bad = false;
-            for (int_t q = 0; !bad && q < nq; q++) bad = excl_p[q] > excl_p[q + 1];
-            if (bad || (excl_p[nq] > 0 && excl_i == nullptr)) {
-                g_last_error = std::string(fn) + ": invalid arguments (the exclusion lists are not a CSR over the queries)";
-                return 2;
-            }
-        }
+            if (query_ids[q] < 0 || query_ids[q] >= r->n)
+                return refuse(fn, "query id " + std::to_string(query_ids[q]) + " (entry " + std::to_string(q) + ") is not a row of the ranker's " +
+                                      std::to_string(r->n));
+        if (excl_p != nullptr && !csr_ok(excl_p, excl_i, nq))
+            return refuse(fn, "invalid arguments (the exclusion lists are not a CSR over the queries)");
         if (nq == 0) return 0;
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
         const cmfrec_hip_ranker::Device &dev = r->dev;
         r->qid.upload(query_ids, (size_t)nq, dev.stream);
-        if (excl_p) {
-            r->ep.upload(excl_p, (size_t)nq + 1, dev.stream);
-            r->ei.alloc_at_least(std::max<size_t>(excl_p[nq], 1));
-            if (excl_p[nq] > 0) r->ei.upload(excl_i, excl_p[nq], dev.stream);
-        }
+        RankUsers queries{nullptr, 0, nq, nullptr, nullptr};
+        stage_exclusions(r, queries, excl_p, excl_i);
         if (metric == TOPNS_COSINE) ensure_inverse_norms(r);             // outside the timed interval
-        r->ids.alloc_at_least((size_t)nq * n_top);
-        if (out_scores) r->sc.alloc_at_least((size_t)nq * n_top);
+        const size_t cells = (size_t)nq * n_top;
+        r->ids.alloc_at_least(cells);
+        if (out_scores) r->sc.alloc_at_least(cells);
         TopnSimilarParams<real_t> P;
-        P.query_ids = r->qid.ptr; P.nu = nq; P.B = r->B.ptr; P.ldb = r->ldb; P.n = r->n; P.k = r->k;
+        set_items(P, r); set_exclusions(P, queries); set_lists(P, r, n_top, out_scores != nullptr);
+        P.query_ids = r->qid.ptr; P.nu = nq;
         P.rn = metric == TOPNS_COSINE ? r->rn.ptr : nullptr;
-        P.excl_p = excl_p ? r->ep.ptr : nullptr; P.excl_i = excl_p ? r->ei.ptr : nullptr;
-        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = out_scores ? r->sc.ptr : nullptr;
         int bpc = 1;
         const int nut = pick_user_tiles(nq, r->k, n_top, dev.num_cus, &bpc, 16 * (sizeof(real_t) + sizeof(int)));
         poison_lds(dev.stream, dev.num_cus);                             // (the policy's LDS too is written before it is read)
         HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
-        r->last_grid = metric == TOPNS_COSINE ? launch_similar_tiles<TOPNS_COSINE>(dev, P, nut, bpc) : launch_similar_tiles<TOPNS_DOT>(dev, P, nut, bpc);
-        r->last_users = 16 * nut;
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(r->ev1, dev.stream));
-        r->timed = true;
-        r->last_slices = 1;
-        r->ids.download(out_ids, (size_t)nq * n_top, dev.stream);
-        if (out_scores) r->sc.download(out_scores, (size_t)nq * n_top, dev.stream);
-        HIP_CHECK(hipStreamSynchronize(dev.stream));
+        auto launch = [&](auto m) {
+            return with_tiles(nut, [&](auto t) {
+                return launch_tiled(dev, topn_similar_kernel<real_t, t(), m()>, t(), topns_lds_bytes(t(), P.k, P.n_top, sizeof(real_t)), P, bpc);
+            });
+        };
+        const int grid = metric == TOPNS_COSINE ? launch(std::integral_constant<int, TOPNS_COSINE>()) : launch(std::integral_constant<int, TOPNS_DOT>());
+        end_timed(r, 16 * nut, grid, 1);
+        download_and_wait(r, cells, out_ids, out_scores);
         return 0;
     });
 }
@@ -1268,98 +1171,60 @@ int cmfrec_hip_topN_batch(const real_t *A, size_t lda, int_t nu, const real_t *B
                           const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
                           int_t *out_ids, real_t *out_scores)
 {
-    if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids) {
-        g_last_error = "cmfrec_hip_topN_batch: invalid arguments";
-        return 2;
-    }
-    if (k > TOPNW_KMAX || n_top > TOPN_NMAX || n_top > n) {
-        g_last_error = std::string("cmfrec_hip_topN_batch: ") + LIMITS;
-        return 2;
-    }
-    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
-    if (r == nullptr) return g_last_rc;
-    const int rc = cmfrec_hip_ranker_topN(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
-    cmfrec_hip_ranker_destroy(r);
-    return rc;
+    const char *fn = "cmfrec_hip_topN_batch";
+    if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids) return refuse(fn, "invalid arguments");
+    if (int rc = ranker_check_limits(fn, k, n_top, n)) return rc;
+    return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_topN(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
+    });
 }
 
 int cmfrec_hip_topN_deep_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
                                const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top,
                                int_t *out_ids, real_t *out_scores)
 {
-    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B) {
-        g_last_error = "cmfrec_hip_topN_deep_batch: invalid arguments";
-        return 2;
-    }
-    if (k > TOPNW_KMAX || n_top < 1 || n_top > n) {
-        g_last_error = std::string("cmfrec_hip_topN_deep_batch: ") + DEEP_LIMITS;
-        return 2;
-    }
-    if (!out_ids) {
-        g_last_error = "cmfrec_hip_topN_deep_batch: invalid arguments";
-        return 2;
-    }
-    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
-    if (r == nullptr) return g_last_rc;
-    const int rc = cmfrec_hip_ranker_topN_deep(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
-    cmfrec_hip_ranker_destroy(r);
-    return rc;
+    const char *fn = "cmfrec_hip_topN_deep_batch";
+    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B) return refuse(fn, "invalid arguments");
+    if (k > TOPNW_KMAX || n_top < 1 || n_top > n) return refuse(fn, DEEP_LIMITS);
+    if (!out_ids) return refuse(fn, "invalid arguments");
+    return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_topN_deep(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
+    });
 }
 
 int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
                                      const real_t *biasB, const size_t cand_p[], const int_t cand_i[], const size_t excl_p[],
                                      const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores)
 {
-    if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids || !cand_p) {
-        g_last_error = "cmfrec_hip_topN_candidates_batch: invalid arguments";
-        return 2;
-    }
-    if (k > TOPNW_KMAX || n_top > TOPN_NMAX || n_top > n) {
-        g_last_error = std::string("cmfrec_hip_topN_candidates_batch: ") + LIMITS;
-        return 2;
-    }
-    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
-    if (r == nullptr) return g_last_rc;
-    const int rc = cmfrec_hip_ranker_topN_candidates(r, A, lda, nu, cand_p, cand_i, excl_p, excl_i, n_top, out_ids, out_scores);
-    cmfrec_hip_ranker_destroy(r);
-    return rc;
+    const char *fn = "cmfrec_hip_topN_candidates_batch";
+    if (nu <= 0 || n <= 0 || k <= 0 || n_top <= 0 || !A || !B || !out_ids || !cand_p) return refuse(fn, "invalid arguments");
+    if (int rc = ranker_check_limits(fn, k, n_top, n)) return rc;
+    return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_topN_candidates(r, A, lda, nu, cand_p, cand_i, excl_p, excl_i, n_top, out_ids, out_scores);
+    });
 }
 
 int cmfrec_hip_similar_batch(const real_t *B, size_t ldb, int_t n, int_t k, const int_t *query_ids, int_t nq, int metric, const size_t excl_p[],
                              const int_t excl_i[], int_t n_top, int_t *out_ids, real_t *out_scores)
 {
-    if (n <= 0 || k <= 0 || nq < 0 || n_top <= 0 || !B) {
-        g_last_error = "cmfrec_hip_similar_batch: invalid arguments";
-        return 2;
-    }
-    if (k > TOPNW_KMAX || n_top > TOPN_NMAX || n_top > n) {
-        g_last_error = std::string("cmfrec_hip_similar_batch: ") + LIMITS;
-        return 2;
-    }
-    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, nullptr, -1);
-    if (r == nullptr) return g_last_rc;
-    const int rc = cmfrec_hip_ranker_similar(r, query_ids, nq, metric, excl_p, excl_i, n_top, out_ids, out_scores);
-    cmfrec_hip_ranker_destroy(r);
-    return rc;
+    const char *fn = "cmfrec_hip_similar_batch";
+    if (n <= 0 || k <= 0 || nq < 0 || n_top <= 0 || !B) return refuse(fn, "invalid arguments");
+    if (int rc = ranker_check_limits(fn, k, n_top, n)) return rc;
+    return with_ranker(B, ldb, n, k, nullptr, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_similar(r, query_ids, nq, metric, excl_p, excl_i, n_top, out_ids, out_scores);
+    });
 }
 
 int cmfrec_hip_ranks_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB,
                            const size_t held_p[], const int_t held_i[], const size_t excl_p[], const int_t excl_i[],
                            int_t *out_rank, real_t *out_scores, int_t *out_pool)
 {
-    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B || !held_p) {
-        g_last_error = "cmfrec_hip_ranks_batch: invalid arguments";
-        return 2;
-    }
-    if (k > TOPNW_KMAX) {
-        g_last_error = std::string("cmfrec_hip_ranks_batch: ") + RANK_LIMITS;
-        return 2;
-    }
-    cmfrec_hip_ranker *r = cmfrec_hip_ranker_create(B, ldb, n, k, biasB, -1);
-    if (r == nullptr) return g_last_rc;
-    const int rc = cmfrec_hip_ranker_ranks(r, A, lda, nu, held_p, held_i, excl_p, excl_i, out_rank, out_scores, out_pool);
-    cmfrec_hip_ranker_destroy(r);
-    return rc;
+    const char *fn = "cmfrec_hip_ranks_batch";
+    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B || !held_p) return refuse(fn, "invalid arguments");
+    if (k > TOPNW_KMAX) return refuse(fn, RANK_LIMITS);
+    return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_ranks(r, A, lda, nu, held_p, held_i, excl_p, excl_i, out_rank, out_scores, out_pool);
+    });
 }
 
 }  // extern "C"
@@ -1368,10 +1233,7 @@ namespace cmfhip {
 
 int ranker_check_limits(const char *fn, int_t k, int_t n_top, int_t n)
 {
-    if (k > TOPNW_KMAX || k <= 0) {
-        g_last_error = std::string(fn) + ": " + LIMITS;
-        return 2;
-    }
+    if (k > TOPNW_KMAX || k <= 0) return refuse(fn, LIMITS);
     return check_n_top(fn, n_top, n);
 }
 
@@ -1385,14 +1247,11 @@ int ranker_topN_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, s
                        const int *dexcl_i, int_t n_top, int_t *out_ids, real_t *out_scores)
 {
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || n_top <= 0 || !dA || !out_ids || lda < (size_t)r->k) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (bad_users(r, dA, lda, nu) || n_top <= 0 || !out_ids) return refuse(fn, "invalid arguments");
         if (int rc = check_n_top(fn, n_top, r->n)) return rc;
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
-        return rank_device(r, dA, lda, nu, dexcl_p, dexcl_i, n_top, out_ids, out_scores);
+        return rank_device(r, RankUsers{dA, lda, nu, dexcl_p, dexcl_i}, n_top, out_ids, out_scores);
     });
 }
 
@@ -1401,15 +1260,12 @@ int ranker_topN_candidates_device(cmfrec_hip_ranker *r, const char *fn, const re
                                   real_t *out_scores)
 {
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || n_top <= 0 || !dA || !out_ids || !cand_p || lda < (size_t)r->k) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (bad_users(r, dA, lda, nu) || n_top <= 0 || !out_ids || !cand_p) return refuse(fn, "invalid arguments");
         if (int rc = check_n_top(fn, n_top, r->n)) return rc;
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
         if (int rc = upload_candidates(r, fn, nu, cand_p, cand_i)) return rc;
-        return rank_device(r, dA, lda, nu, dexcl_p, dexcl_i, n_top, out_ids, out_scores, r->cp.ptr, r->ci.ptr);
+        return rank_device(r, RankUsers{dA, lda, nu, dexcl_p, dexcl_i}, n_top, out_ids, out_scores, r->cp.ptr, r->ci.ptr);
     });
 }
 
@@ -1418,16 +1274,14 @@ int ranker_ranks_device(cmfrec_hip_ranker *r, const char *fn, const real_t *dA, 
                         int_t *out_pool)
 {
     return guarded([&]() {
-        if (r == nullptr || nu <= 0 || !dA || !held_p || lda < (size_t)r->k || (held_p[nu] > 0 && !out_rank)) {
-            g_last_error = std::string(fn) + ": invalid arguments";
-            return 2;
-        }
+        if (bad_users(r, dA, lda, nu) || !held_p || (held_p[nu] > 0 && !out_rank)) return refuse(fn, "invalid arguments");
         DeviceScope scope(r->dev.device);
         switches_mut().reload();
         size_t max_held = 0;
         if (int rc = upload_held(r, fn, nu, held_p, held_i, &max_held)) return rc;
-        return ranks_device(r, dA, lda, nu, held_p[nu], max_held, dexcl_p, dexcl_i, out_rank, out_scores, out_pool);
+        return ranks_device(r, RankUsers{dA, lda, nu, dexcl_p, dexcl_i}, held_p[nu], max_held, out_rank, out_scores, out_pool);
     });
 }
 
 }  // namespace cmfhip
+

@@ -40,6 +40,77 @@ def test_one_handle_many_calls(dtype, k):
         assert np.array_equal(ids, ids1) and np.array_equal(sc, sc1)
 
 
+def mixed_problem(dtype, k, nu=37, n=300):
+    """make_problem with a cluster of forty near-equal item rows (apart by 2^-18 of themselves, 2^-14 in single precision: more than
+    the exact kernels' rounding, less than half precision sees).  A user who likes the cluster has it across positions 30 .. 33 of
+    its ranking, so a filtered call of n = 30 with a shortlist of 32 cannot certify that user."""
+    A, B, b, ep, ei = tr.make_problem(77 + k, dtype, nu, n, k)
+    step = 2.0 ** -18 if dtype is np.float64 else 2.0 ** -14
+    B[100:140] = (2 * B[100].astype(np.float64)[None, :] * (1 + np.arange(40)[:, None] * step)).astype(dtype)
+    b[100:140] = b[100]
+    return A, B, b, ep, ei
+
+
+# float64 k = 72: the wide kernel; k = 40: the register kernel in front of the deep and neighbour calls, which always take the tiled
+# one; nu = 37: three user tiles, the last one partial
+@pytest.mark.parametrize("dtype,k", [(np.float64, 72), (np.float64, 40), (np.float32, 257)], ids=lambda v: getattr(v, "__name__", str(v)))
+def test_one_handle_mixed_calls(monkeypatch, dtype, k):
+    """Calls of every kind on one handle, which share its buffers (factors, exclusion and candidate lists, ids, scores, cursors,
+    query ids): each result is bit-identical to the same call on a fresh handle."""
+    from cmfrec_amd import Ranker
+    monkeypatch.setenv("CMFREC_HIP_TOPN_FILTER_M", "32")    # (read by a filtered call only)
+    monkeypatch.setenv("CMFREC_HIP_TOPN_PAGE", "64")        # (by a deep call only: three pages at every width)
+    nu, n = 37, 300
+    A, B, b, ep, ei = mixed_problem(dtype, k, nu, n)
+    excl = (ep, ei)
+    S = tr.scores64(A, B, b)
+    for u in range(nu):
+        S[u, ei[int(ep[u]):int(ep[u + 1])]] = -np.inf
+    at = np.argsort(-S, axis=1, kind="stable")[:, 29:33]
+    assert np.any(np.all((at >= 100) & (at < 140), axis=1)), "the test's own inputs: no user has the cluster across positions 30 .. 33"
+    rng = np.random.default_rng(5)
+    held = (np.arange(0, 5 * nu + 1, 5), np.concatenate([rng.choice(n, 5, replace=False) for _ in range(nu)]))
+    queries = rng.choice(n, nu, replace=False)
+    first = {}
+
+    def remember(out):
+        first["ids"], first["sc"] = out
+        return out
+
+    def filtered(r):
+        out = r.topN(A, n=30, exclude=excl)
+        stats = r.filter_stats()
+        print("filtered step: %s k=%d %s" % (np.dtype(dtype).name, k, stats))
+        assert stats["filtered"] == nu and stats["certified"] < stats["filtered"], stats      # the remainder route has run
+        return out
+
+    # (settings of the handle, the call)
+    steps = [({}, lambda r: remember(r.topN(A, n=10, exclude=excl))),
+             ({}, lambda r: r.topN(A, n=10)),
+             ({}, lambda r: r.topN(A, n=10, include=np.arange(5, n, 2), exclude=excl)),
+             ({}, lambda r: r.ranks(A, held, exclude=excl, return_scores=True)),
+             ({}, lambda r: r.topN_deep(A, 150, exclude=excl)),
+             ({}, lambda r: r.topN_after(A, first["ids"][:, 9], first["sc"][:, 9], n=10, exclude=excl)),
+             ({}, lambda r: r.similar(queries, n=10, metric="cosine", exclude=excl)),
+             ({}, lambda r: r.similar(queries, n=10, metric="dot")),
+             (dict(split=3), lambda r: r.topN(A, n=10, exclude=excl)),
+             (dict(filter="fp16"), filtered),
+             ({}, lambda r: r.topN(A, n=10, exclude=excl))]
+    with Ranker(B, b) as one:
+        for j, (settings, call) in enumerate(steps):
+            one.split, one.filter = settings.get("split"), settings.get("filter")
+            got = call(one)
+            with Ranker(B, b, **settings) as fresh:
+                want = call(fresh)
+            assert len(got) == len(want)
+            for g, w in zip(got, want):
+                assert np.array_equal(g, w, equal_nan=True), "step %d" % (j + 1)
+            if j == 4:
+                assert one.pages() == (3, 64)
+            if j == 8:
+                assert one.slices() == 3
+
+
 def test_closed_handle_refuses():
     from cmfrec_amd import Ranker
     rng = np.random.default_rng(3)

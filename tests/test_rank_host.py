@@ -50,6 +50,8 @@ def test_limits_need_no_gpu():
         ops.topN_batch(np.zeros((4, 273)), np.zeros((300, 273)), n_top=5)
     with pytest.raises(RuntimeError, match=r"code 2.*n_top <= min\(128, n\)"):
         ops.topN_batch(np.zeros((4, 100)), np.zeros((300, 100)), n_top=129)
+    with pytest.raises(RuntimeError, match=r"code 2.*n_top <= min\(128, n\)"):
+        ops.topN_batch(np.zeros((4, 100)), np.zeros((20, 100)), n_top=21)
 
 
 def test_ranker_names_are_exported():

@@ -52,8 +52,10 @@ def test_c_refusals_before_the_device(dtype):
     nu, n = 3, 5
     hp = np.array([0, 1, 2, 3], np.uint64); hi = np.array([0, 1, 2], np.int32)
     ranks = np.full(3, 77, np.int32); sc = np.full(3, 5, dtype); pool = np.full(nu, 77, np.int32)
-    for k, held_p, what in ((273, hp, b"needs k <= 272"), (8, None, b"invalid arguments")):
-        A = np.zeros((nu, k), dtype); B = np.ones((n, k), dtype)
+    for k, held_p, null, what in ((273, hp, "", b"needs k <= 272"), (8, None, "", b"invalid arguments"), (8, hp, "A", b"invalid arguments"),
+                                  (8, hp, "B", b"invalid arguments")):
+        A = None if null == "A" else np.zeros((nu, k), dtype)
+        B = None if null == "B" else np.ones((n, k), dtype)
         rc = lib.cmfrec_hip_ranks_batch(_lib.ptr(A), k, nu, _lib.ptr(B), k, n, k, None, _lib.ptr(held_p), _lib.ptr(hi), None, None,
                                         _lib.ptr(ranks), _lib.ptr(sc), _lib.ptr(pool))
         assert rc == 2 and what in lib.cmfrec_hip_last_error()
