@@ -371,16 +371,23 @@ struct GramWorkspace {
 
 // ------------------------------------------------------------------------------------------
 // CG row updates
-struct CgCall {
-    real_t *A; size_t lda;
-    const real_t *B; size_t ldb;
-    int k;
-    const real_t *bias_sub;
-    const real_t *BtB;       // implicit only
+// lambda of a row's unknowns and of the last one (the bias; the same value where there is none)
+struct RowPenalty {
     real_t lam, lam_last;
-    bool scale_lam, scale_bias_const;
-    int max_cg_steps;
-    bool implicit;
+};
+
+// Built by explicit_rows / implicit_rows, which take what every launch of that model reads; everything else is an optional
+// member, set by name.  (No public constructor and not an aggregate: a description cannot be filled by position.)
+struct CgCall {
+    real_t *A = nullptr; size_t lda = 0;
+    const real_t *B = nullptr; size_t ldb = 0;
+    int k = 0;
+    const real_t *bias_sub = nullptr;
+    const real_t *BtB = nullptr;       // implicit only
+    real_t lam = 0, lam_last = 0;
+    bool scale_lam = false, scale_bias_const = false;
+    int max_cg_steps = 0;
+    bool implicit = false;
     bool precond = false;
     // block system with dense side information (A points at the first unknown, koff of them precede the X block)
     int koff = 0, kc = 0;
@@ -405,6 +412,32 @@ struct CgCall {
     const real_t *values_override = nullptr, *weights_override = nullptr;
     bool gx_all_rows = false;         // ... with the preconditioner (generic kernel): the rows without entries are part of the launch
     const real_t *wsum_override = nullptr;   // lambda's per-row multipliers under scale_lam instead of the rows' own counts / sums
+
+    // A [rows, lda] in and out, B [*, ldb] the opposing factors, k unknowns per row
+    static CgCall explicit_rows(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const real_t *bias_sub, RowPenalty pen,
+                                int max_cg_steps)
+    {
+        CgCall c;
+        c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.k = k; c.bias_sub = bias_sub;
+        c.lam = pen.lam; c.lam_last = pen.lam_last; c.max_cg_steps = max_cg_steps;
+        return c;
+    }
+    // ... BtB [k, k] the Gramian every row shares
+    static CgCall implicit_rows(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const real_t *BtB, RowPenalty pen,
+                                int max_cg_steps)
+    {
+        CgCall c = explicit_rows(A, lda, B, ldb, k, nullptr, pen, max_cg_steps);
+        c.BtB = BtB; c.implicit = true;
+        return c;
+    }
+    // sparse side information: the row's attributes (X2_) gather rows of C2_ [*, kc_], weight w
+    void set_second_source(const SparseShard &X2_, const real_t *C2_, int kc_, real_t w)
+    {
+        X2 = &X2_; C2 = C2_; kc = kc_; w_side = w;
+    }
+
+private:
+    CgCall() {}
 };
 
 enum class CgVariant { Auto, Generic };

@@ -46,15 +46,17 @@ void launch_gram_wave(dim3 grid, hipStream_t st, const CgParams<real_t> &P, cons
 hipError_t launch_chol_wg8(int num_cus, bool border, int waves_per_row, hipStream_t st, const CholParams<real_t> &W, const RowDesc *desc, const CholSlices<real_t> &SL);
 hipError_t launch_chol_parts_coop(int num_cus, bool border, int depth, hipStream_t st, const CholParams<real_t> &W, const RowDesc *desc, const CholSlices<real_t> &SL);
 
+// Built by the constructor named after its mode, which takes what every launch of that mode reads; everything else is an
+// optional member, set by name.  (No public constructor and not an aggregate: a description cannot be filled by position.)
 struct CholCall {
-    real_t *A; size_t lda;
-    const real_t *B; size_t ldb;
-    int kt, koff;
-    const real_t *bias_sub;
-    const real_t *Minit; int kc; int rows_with_u; int p_side;
-    real_t lam, lam_last;
-    bool scale_lam, scale_lam_sideinfo, scale_bias_const;
-    int mode;
+    real_t *A = nullptr; size_t lda = 0;
+    const real_t *B = nullptr; size_t ldb = 0;
+    int kt = 0, koff = 0;
+    const real_t *bias_sub = nullptr;
+    const real_t *Minit = nullptr; int kc = 0; int rows_with_u = 0; int p_side = 0;
+    real_t lam = 0, lam_last = 0;
+    bool scale_lam = false, scale_lam_sideinfo = false, scale_bias_const = false;
+    int mode = CHOL_EXPLICIT;
     const real_t *Mfull = nullptr;
     // second gather source (sparse side information): rows of B2[*, ldb2] selected by X2's entries, unknowns [0, kc2)
     const SparseShard *X2 = nullptr;
@@ -82,10 +84,78 @@ struct CholCall {
     // CG on the row's Gramian instead of the factorisation (gram_cg_wide_kernels.hpp): the producer build of the wave kernel runs
     // every row's rank-k update, gram_cg_wide_kernel takes the partials; the parameters of the CG (explicit model)
     const CgParams<real_t> *cg_wide = nullptr;
+
+    // A [rows, lda]: the right-hand sides in, the solutions out; M [k, k] the matrix of every row, diagonal included
+    static CholCall prefilled(real_t *A, size_t lda, int k, const real_t *M)
+    {
+        CholCall c = rows(CHOL_PREFILLED, A, lda, nullptr, 0, k, RowPenalty{0, 0});
+        c.Minit = M;
+        return c;
+    }
+    // A [rows, lda] in and out, B [*, ldb] the opposing factors gathered through X, k unknowns per row
+    static CholCall explicit_rows(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const real_t *bias_sub, RowPenalty pen)
+    {
+        CholCall c = rows(CHOL_EXPLICIT, A, lda, B, ldb, k, pen);
+        c.bias_sub = bias_sub;
+        return c;
+    }
+    // ... G [k, k] the Gramian every row shares
+    static CholCall implicit_rows(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const real_t *G, RowPenalty pen)
+    {
+        CholCall c = rows(CHOL_IMPLICIT, A, lda, B, ldb, k, pen);
+        c.Minit = G;
+        return c;
+    }
+    // Block systems of kt unknowns, the X block behind the first koff.  The dense side block (Minit [kc, kc] or null, kc,
+    // rows_with_u, p_side), koff and the scaling flags are set by name.  Mfull [kt, kt]: the matrix every row starts from, if any.
+    static CholCall collective(real_t *A, size_t lda, const real_t *B, size_t ldb, int kt, const real_t *bias_sub, RowPenalty pen,
+                               const real_t *Mfull = nullptr)
+    {
+        CholCall c = rows(CHOL_COLLECTIVE, A, lda, B, ldb, kt, pen);
+        c.bias_sub = bias_sub; c.Mfull = Mfull;
+        return c;
+    }
+    // ... of the implicit model: Mfull = blockdiag(lam I, B^T B + lam I); no bias, no scaling flags
+    static CholCall collective_implicit(real_t *A, size_t lda, const real_t *B, size_t ldb, int kt, const real_t *Mfull, RowPenalty pen)
+    {
+        CholCall c = rows(CHOL_COLLECTIVE_IMPLICIT, A, lda, B, ldb, kt, pen);
+        c.Mfull = Mfull;
+        return c;
+    }
+    // missing-as-zero: G [k, k] the matrix the rows share (CHOL_NAZ: the launch gathers right-hand sides, rhs_only, or solves
+    // every row on G; CHOL_NAZ_W: G plus the corrections of the row's entries, weights_override / values_override)
+    static CholCall naz_rhs(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const real_t *G, RowPenalty pen)
+    {
+        CholCall c = rows(CHOL_NAZ, A, lda, B, ldb, k, pen);
+        c.Minit = G;
+        return c;
+    }
+    static CholCall naz_weighted(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const real_t *G, RowPenalty pen)
+    {
+        CholCall c = rows(CHOL_NAZ_W, A, lda, B, ldb, k, pen);
+        c.Minit = G;
+        return c;
+    }
+    // second gather source: the entries of X2_ select rows of B2_ [*, kc_], weight w
+    void set_second_source(const SparseShard &X2_, const real_t *B2_, int kc_, real_t w)
+    {
+        X2 = &X2_; B2 = B2_; ldb2 = (size_t)kc_; kc2 = kc_; w2 = w;
+    }
+
+private:
+    CholCall() {}
+    static CholCall rows(CholMode mode, real_t *A, size_t lda, const real_t *B, size_t ldb, int k, RowPenalty pen)
+    {
+        CholCall c;
+        c.mode = mode; c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.kt = k; c.lam = pen.lam; c.lam_last = pen.lam_last;
+        return c;
+    }
 };
 
 // X may be null for CHOL_PREFILLED (then nrows_prefilled rows are solved in natural order)
 int launch_chol(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, int nrows_prefilled = 0);
+// the rows of A [count, lda] become M^-1 times themselves, M [k, k]
+int launch_chol_prefilled(const DeviceInfo &dev, real_t *A, size_t lda, int k, const real_t *M, int count);
 // the workgroup-per-row kernel over the positions [P.row_first, P.nrows) of the processing order
 int launch_chol_rows(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, CholParams<real_t> P, bool two_src, size_t smem_nonneg);
 int launch_plain_lowrank(const DeviceInfo &dev, const CholCall &c, const SparseShard &X);

@@ -582,8 +582,8 @@ int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X)
     // they lead the processing order -- take it, the others stay on the lane <-> unknown kernel (CgCall::skip_first).
     const int n_wide = X.rows_longer_than(256, X.n_nonempty);
     if (n_wide <= 0) return -1;
-    CholCall cc{c.A, c.lda, c.B, c.ldb, c.k, 0, c.bias_sub, nullptr, 0, 0, 0, c.lam, c.lam_last, c.scale_lam, c.scale_lam_sideinfo,
-                c.scale_bias_const, CHOL_EXPLICIT};
+    CholCall cc = CholCall::explicit_rows(c.A, c.lda, c.B, c.ldb, c.k, c.bias_sub, RowPenalty{c.lam, c.lam_last});
+    cc.scale_lam = c.scale_lam; cc.scale_lam_sideinfo = c.scale_lam_sideinfo; cc.scale_bias_const = c.scale_bias_const;
     cc.cg_wide = &P;
     cc.row_limit = n_wide;
     int rc = launch_chol(dev, cc, &X);                    // positions [0, n_wide)

@@ -64,6 +64,11 @@ static void chol_part_batches(const DeviceInfo &dev, const SparseShard &X, int n
     }
 }
 
+int launch_chol_prefilled(const DeviceInfo &dev, real_t *A, size_t lda, int k, const real_t *M, int count)
+{
+    return launch_chol(dev, CholCall::prefilled(A, lda, k, M), nullptr, count);
+}
+
 // X may be null for CHOL_PREFILLED (then nrows_prefilled rows are solved in natural order)
 int launch_chol(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, int nrows_prefilled)
 {

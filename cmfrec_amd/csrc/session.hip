@@ -652,8 +652,7 @@ int cmfrec_hip_session_sideinfo_finish(cmfrec_hip_session *s, int which)
             Scope(const DeviceInfo &d_, bool nn, int steps, real_t l1, real_t sc) : d(d_) { d.nonneg_now = nn; d.max_cd_steps = steps; d.l1_now = l1; d.l1_last_now = l1; d.l1_scale = sc; }
             ~Scope() { d.nonneg_now = false; d.l1_now = 0; d.l1_last_now = 0; d.l1_scale = 1; }
         } scope(dev, isC ? s->nonneg_C : s->nonneg_D, s->max_cd_steps, s->l16[isC ? 4 : 5] / w, scale_lam ? (real_t)rows_u : (real_t)1);
-        CholCall c{Cm, (size_t)kc, nullptr, 0, kc, 0, nullptr, s->gram.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-        return launch_chol(dev, c, nullptr, p);                                                    // common.c:2872-2875
+        return launch_chol_prefilled(dev, Cm, (size_t)kc, kc, s->gram.ptr, p);                     // common.c:2872-2875
     });
 }
 
@@ -1076,8 +1075,7 @@ static int solve_sideinfo_only_rows(cmfrec_hip_session *s, const HalfStepSide &v
     launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->betbe.ptr, (real_t)1,
                 (v.lam_self / v.w) * (real_t)(scale_lam ? p_self : 1));                                           // common.c:2824-2832
     side_times(dev, v.Um_blk.from_row(first, p_self), count, kc, p_self, (real_t)1, v.Cm, rows, v.ld_self);   // common.c:2847-2855
-    CholCall c{rows, v.ld_self, nullptr, 0, kc, 0, nullptr, s->betbe.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-    return launch_chol(dev, c, nullptr, count);                                                    // common.c:2872-2875
+    return launch_chol_prefilled(dev, rows, v.ld_self, kc, s->betbe.ptr, count);                   // common.c:2872-2875
 }
 
 // sum of the rows of F (leading dimension ldf; Bi / Ai, or the factors themselves) at every row's observed positions, by the
@@ -1128,16 +1126,6 @@ static void set_implicit_term(const cmfrec_hip_session *s, const HalfStepSide &v
     c.Bi = v.Fi; c.BiTBi = s->bitbi.ptr; c.ki = v.kk; c.w_imp = s->w_implicit;
 }
 
-// sparse side information: the row's attributes as the second gather source of the launch
-static void set_sparse_side(const HalfStepSide &v, CholCall &c)
-{
-    c.X2 = &v.Us; c.B2 = v.Cm; c.ldb2 = (size_t)v.kc; c.kc2 = v.kc; c.w2 = v.w;
-}
-static void set_sparse_side(const HalfStepSide &v, CgCall &c)
-{
-    c.X2 = &v.Us; c.C2 = v.Cm;
-}
-
 // ---- ... and the ones of the main matrix missing-as-zero ----
 static int naz_check_side_rows(int rows_u, int rows_self)
 {
@@ -1175,7 +1163,7 @@ static const real_t *naz_constant(cmfrec_hip_session *s, const HalfStepSide &v, 
 // :5753-5762), x_j from values_override when given, added into dst, which the caller has zeroed
 static int naz_gather_rhs_into(cmfrec_hip_session *s, const HalfStepSide &v, real_t *dst, size_t ld, const real_t *values_override = nullptr)
 {
-    CholCall c{dst, ld, v.oppx, v.ld_opp, v.ks, 0, nullptr, s->gram.ptr, 0, 0, 0, v.lam_self, v.lam_last_self, false, false, false, CHOL_NAZ};
+    CholCall c = CholCall::naz_rhs(dst, ld, v.oppx, v.ld_opp, v.ks, s->gram.ptr, RowPenalty{v.lam_self, v.lam_last_self});
     c.rhs_only = true; c.values_override = values_override;
     return launch_chol(s->dev, c, &v.X);
 }
@@ -1251,11 +1239,10 @@ static int update_factor_naz_sparse_side(cmfrec_hip_session *s, const HalfStepSi
         const real_t *zeros = naz_zeros(s, v.X.nnz);
         fill_mult();
         HIP_CHECK(hipGetLastError());
-        CgCall c{v.self, v.ld_self, v.oppx, v.ld_opp, ks, nullptr, nullptr, v.lam_self, v.lam_last_self, scaled, false, m.max_cg_steps, false,
-                 (bool)m.precondition_cg};
-        c.koff = v.k_side_self; c.kc = v.kc; c.w_side = v.w; c.rows_with_u = v.rows_u; c.p_side = v.p_self;
-        c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
-        set_sparse_side(v, c);
+        CgCall c = CgCall::explicit_rows(v.self, v.ld_self, v.oppx, v.ld_opp, ks, nullptr, RowPenalty{v.lam_self, v.lam_last_self}, m.max_cg_steps);
+        c.scale_lam = scaled; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo; c.precond = (bool)m.precondition_cg;
+        c.koff = v.k_side_self; c.rows_with_u = v.rows_u; c.p_side = v.p_self;
+        c.set_second_source(v.Us, v.Cm, v.kc, v.w);
         c.Gx = s->gram.ptr; c.rconst_x = s->naz_rhs.ptr; c.ldr_x = (size_t)ks;
         c.values_override = zeros; c.weights_override = zeros;
         if (scaled) c.wsum_override = s->naz_mult.ptr;
@@ -1271,9 +1258,10 @@ static int update_factor_naz_sparse_side(cmfrec_hip_session *s, const HalfStepSi
     if (v.Fi != nullptr) add_implicit_rhs(s, v, v.self, v.ld_self);
     fill_mult();
     HIP_CHECK(hipGetLastError());
-    CholCall c{v.self, v.ld_self, v.oppx, v.ld_opp, kt, v.k_side_self, nullptr, nullptr, v.kc, v.rows_u, v.p_self, v.lam_self, v.lam_last_self,
-               scaled, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE, s->naz_M.ptr};
-    set_sparse_side(v, c);
+    CholCall c = CholCall::collective(v.self, v.ld_self, v.oppx, v.ld_opp, kt, nullptr, RowPenalty{v.lam_self, v.lam_last_self}, s->naz_M.ptr);
+    c.koff = v.k_side_self; c.kc = v.kc; c.rows_with_u = v.rows_u; c.p_side = v.p_self;
+    c.scale_lam = scaled; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
+    c.set_second_source(v.Us, v.Cm, v.kc, v.w);
     c.rhs_prefilled_all = true; c.x_rhs_only = true;
     if (scaled) c.mult_override = s->naz_mult.ptr;
     return launch_chol(dev, c, &v.X);
@@ -1415,13 +1403,12 @@ static int update_factor_naz_weighted_side(cmfrec_hip_session *s, const HalfStep
         naz_constant(s, v, s->naz_rhs.ptr, (size_t)ks);
         const real_t *zeros = naz_zeros(s, v.X.nnz);
         HIP_CHECK(hipGetLastError());
-        CgCall c{v.self, v.ld_self, v.oppx, v.ld_opp, ks, nullptr, nullptr, v.lam_self, v.lam_last_self, scaled, false, m.max_cg_steps, false,
-                 (bool)m.precondition_cg};
+        CgCall c = CgCall::explicit_rows(v.self, v.ld_self, v.oppx, v.ld_opp, ks, nullptr, RowPenalty{v.lam_self, v.lam_last_self}, m.max_cg_steps);
+        c.scale_lam = scaled; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo; c.precond = (bool)m.precondition_cg;
         c.koff = v.k_side_self; c.kc = kc; c.w_side = v.w; c.rows_with_u = rows_u; c.p_side = p_self;
-        if (sparse_side) set_sparse_side(v, c);
+        if (sparse_side) c.set_second_source(v.Us, v.Cm, kc, v.w);
         else if (has_side) { c.CtC = s->ctc.ptr; c.UC = v.uc; }
         if (v.Fi != nullptr) set_implicit_term(s, v, c);
-        c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
         c.Gx = s->gram.ptr; c.rconst_x = s->naz_rhs.ptr; c.ldr_x = (size_t)ks;
         c.values_override = zeros; c.weights_override = s->naz_g.ptr;                // (the multipliers: X.wsum_naz, launch_cg)
         c.gx_all_rows = v.has_cst;
@@ -1435,10 +1422,11 @@ static int update_factor_naz_weighted_side(cmfrec_hip_session *s, const HalfStep
     naz_constant(s, v, v.self + v.k_side_self, v.ld_self);
     naz_entry_transform(s, v);
     HIP_CHECK(hipGetLastError());
-    CholCall c{v.self, v.ld_self, v.oppx, v.ld_opp, kt, v.k_side_self, nullptr, dense_side ? s->ctc.ptr : nullptr, kc, rows_u, p_self, v.lam_self,
-               v.lam_last_self, scaled, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE, s->naz_M.ptr};
+    CholCall c = CholCall::collective(v.self, v.ld_self, v.oppx, v.ld_opp, kt, nullptr, RowPenalty{v.lam_self, v.lam_last_self}, s->naz_M.ptr);
+    c.koff = v.k_side_self; c.Minit = dense_side ? s->ctc.ptr : nullptr; c.kc = kc; c.rows_with_u = rows_u; c.p_side = p_self;
+    c.scale_lam = scaled; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
     c.rhs_prefilled_all = true; c.entry_pairs = true; c.values_override = s->naz_xt.ptr; c.weights_override = s->naz_g.ptr;
-    if (sparse_side) set_sparse_side(v, c);
+    if (sparse_side) c.set_second_source(v.Us, v.Cm, v.kc, v.w);
     if (scaled) c.mult_override = v.X.wsum_naz.ptr;      // sum of the row's weights + its absent entries (cmfrec_hip_session_set_NA_as_zero_X)
     return launch_chol(dev, c, &v.X);
 }
@@ -1485,8 +1473,8 @@ static int update_factor_naz_weighted(cmfrec_hip_session *s, const HalfStepSide 
         s->naz_rhs.alloc_at_least((size_t)rows_self * ks);
         hipLaunchKernelGGL(set_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, (size_t)rows_self, ks, cst);
         // (rows without entries and without cst keep their factors: the kernel solves into naz_rhs, copied back below for the solved rows)
-        CholCall c{s->naz_rhs.ptr, (size_t)ks, opp, v.ld_opp, ks, 0, nullptr, s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, m.scale_lam != 0, false,
-                   s->scale_bias_const, CHOL_NAZ_W};
+        CholCall c = CholCall::naz_weighted(s->naz_rhs.ptr, (size_t)ks, opp, v.ld_opp, ks, s->gram.ptr, RowPenalty{lam_self, lam_last_self});
+        c.scale_lam = m.scale_lam != 0; c.scale_bias_const = s->scale_bias_const;
         c.values_override = s->naz_xt.ptr; c.weights_override = s->naz_g.ptr; c.rhs_prefilled_all = true; c.all_rows = has_cst;
         int rc = launch_chol(dev, c, &X);
         if (rc) return rc;
@@ -1500,7 +1488,8 @@ static int update_factor_naz_weighted(cmfrec_hip_session *s, const HalfStepSide 
     if (has_cst)
         hipLaunchKernelGGL(add_rowvec_kernel<real_t>, grid1d((size_t)rows_self * ks), dim3(256), 0, st, s->naz_rhs.ptr, (size_t)ks, (size_t)rows_self, ks, cst);
     // ... then the tiled kernels: shared matrix in LDS, rank-1 weights w - 1, values zero
-    CgCall c{v.self, v.ld_self, opp, v.ld_opp, ks, nullptr, nullptr, lam_self, lam_last_self, m.scale_lam != 0, s->scale_bias_const, m.max_cg_steps, false};
+    CgCall c = CgCall::explicit_rows(v.self, v.ld_self, opp, v.ld_opp, ks, nullptr, RowPenalty{lam_self, lam_last_self}, m.max_cg_steps);
+    c.scale_lam = m.scale_lam != 0; c.scale_bias_const = s->scale_bias_const;
     c.Gx = s->gram.ptr; c.rconst_x = s->naz_rhs.ptr; c.ldr_x = (size_t)ks;
     c.values_override = naz_zeros(s, X.nnz); c.weights_override = s->naz_g.ptr;
     // precondition_cg (round 6; factors_explicit_pcg_NA_as_zero_weighted, common.c:1443-1613): the lane <-> unknown kernel with the
@@ -1533,6 +1522,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
     const SparseShard &X = (part >= 0) ? *s->XrParts[part] : v.X;
     const bool sbc = s->scale_bias_const && !m.implicit;      // rows without side information: common.c:679-723
     const real_t lam_self = v.lam_self, lam_last_self = v.lam_last_self;
+    const RowPenalty pen{lam_self, lam_last_self};
     real_t *self_blk = v.self + (size_t)(begin + (part >= 0 ? s->partBegin[part] : 0)) * ld_self;
     if (part >= 0 && (!isA || p_self > 0)) {
         g_last_error = "cmfrec_hip: row parts are only built for A-steps without side information";
@@ -1555,8 +1545,9 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
             kx = v.ks;
             bias_sub_cg = v.bias;
         }
-        CgCall c{self_blk, ld_self, oppx, ld_opp, kx, bias_sub_cg, m.implicit ? s->gram.ptr : nullptr, lam_self, lam_last_self, scale_lam,
-                 scale_bias_const, m.max_cg_steps, (bool)m.implicit, (bool)m.precondition_cg};
+        CgCall c = m.implicit ? CgCall::implicit_rows(self_blk, ld_self, oppx, ld_opp, kx, s->gram.ptr, pen, m.max_cg_steps)
+                              : CgCall::explicit_rows(self_blk, ld_self, oppx, ld_opp, kx, bias_sub_cg, pen, m.max_cg_steps);
+        c.scale_lam = scale_lam; c.scale_bias_const = scale_bias_const; c.precond = (bool)m.precondition_cg;
         c.koff = k_side_self; c.kc = kc; c.w_side = w; c.p_side = p_self; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
         return c;
     };
@@ -1577,7 +1568,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
             // collective.c:2292-2298, :2609-2621, :2847-2860; implicit: :2993-2999 ff.), generic kernel
             CgCall c = block_cg_call(false);          // (scale_bias_const: not with sparse side information)
             c.rows_with_u = rows_u;
-            set_sparse_side(v, c);
+            c.set_second_source(v.Us, v.Cm, kc, w);
             add_implicit_term_cg(c);
             return launch_cg_any(dev, c, X, nullptr);
         }
@@ -1587,9 +1578,9 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
             launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, lam_self);
             hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d(kt * kt), dim3(256), 0, st, s->gram.ptr, kk, k_side_self, lam_self,
                                s->betbe.ptr);
-            CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, nullptr, kc, rows_u, p_self, lam_self,
-                       lam_last_self, false, false, false, CHOL_COLLECTIVE_IMPLICIT, s->betbe.ptr};
-            set_sparse_side(v, c);
+            CholCall c = CholCall::collective_implicit(self_blk, ld_self, oppx, ld_opp, kt, s->betbe.ptr, pen);
+            c.koff = k_side_self; c.kc = kc; c.rows_with_u = rows_u; c.p_side = p_self;
+            c.set_second_source(v.Us, v.Cm, kc, w);
             return launch_chol(dev, c, &X);
         }
         // (the explicit model's closed form: below, after the implicit-features term it may carry)
@@ -1620,8 +1611,8 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
         launch_gram(dev, s->gws, v.Cm, (size_t)kc, p_self, kc, s->ctc.ptr, w, (real_t)0);          // :6138-6160
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :6018-6019
         side_times(dev, v.Um_blk, local_u, kc, p_self, w, v.Cm, self_blk, ld_self);   // :6163-6168
-        CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, nullptr, s->ctc.ptr, kc, local_u,
-                   p_self, lam_self, lam_last_self, false, false, false, CHOL_COLLECTIVE_IMPLICIT, s->betbe.ptr};
+        CholCall c = CholCall::collective_implicit(self_blk, ld_self, oppx, ld_opp, kt, s->betbe.ptr, pen);
+        c.koff = k_side_self; c.Minit = s->ctc.ptr; c.kc = kc; c.rows_with_u = local_u; c.p_side = p_self;
         return launch_chol(dev, c, &X);
     }
     if (m.implicit) {
@@ -1630,12 +1621,10 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
             launch_gram(dev, s->gws, oppx, ld_opp, rows_opp, kk, s->gram.ptr, (real_t)1, chol ? lam_self : (real_t)0);
         if (chol) {
             if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st)); // :3334
-            CholCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, kk, 0, nullptr,
-                       s->gram.ptr, 0, 0, 0, lam_self, lam_last_self, false, false, false, CHOL_IMPLICIT};
-            return launch_chol(dev, c, &X);
+            return launch_chol(dev, CholCall::implicit_rows(self_blk + k_side_self, ld_self, oppx, ld_opp, kk, s->gram.ptr, pen), &X);
         }
-        CgCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, kk, nullptr, s->gram.ptr,
-                 lam_self, lam_last_self, false, false, m.max_cg_steps, true, (bool)m.precondition_cg};
+        CgCall c = CgCall::implicit_rows(self_blk + k_side_self, ld_self, oppx, ld_opp, kk, s->gram.ptr, pen, m.max_cg_steps);
+        c.precond = (bool)m.precondition_cg;
         return launch_cg_any(dev, c, X, v.bins);
     }
 
@@ -1666,21 +1655,22 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
             c.rhs_prefilled_all = true;
             return;
         }
-        c.X2 = &X; c.values2 = s->ones.ptr; c.B2 = Fi; c.ldb2 = (size_t)kk; c.kc2 = kk; c.koff2 = k_side_self;
-        c.w2 = s->w_implicit; c.w2_syr_zero = true; c.rows2 = X.nrows;
+        c.set_second_source(X, Fi, kk, s->w_implicit);
+        c.values2 = s->ones.ptr; c.koff2 = k_side_self; c.w2_syr_zero = true; c.rows2 = X.nrows;
     };
     if (p_self > 0 && v.sparse_side) {
         // sparse side information, closed form: the row's attributes as the second gather source (collective.c:1636-1653, :1719-1731);
         // round 6: together with the implicit-features term (its right-hand side by the segmented gather-sum)
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
-        CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, bias_sub, nullptr, kc, rows_u, p_self, lam_self,
-                   lam_last_self, scale_lam, (bool)m.scale_lam_sideinfo, false, CHOL_COLLECTIVE};
+        CholCall c = CholCall::collective(self_blk, ld_self, oppx, ld_opp, kt, bias_sub, pen);
+        c.koff = k_side_self; c.kc = kc; c.rows_with_u = rows_u; c.p_side = p_self;
+        c.scale_lam = scale_lam; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo;
         add_implicit_term(c);
         if (c.X2 != nullptr) {
             g_last_error = "cmfrec_hip: implicit features with sparse side information: k + k_main beyond the gather-sum's width";
             return 2;
         }
-        set_sparse_side(v, c);
+        c.set_second_source(v.Us, v.Cm, kc, w);
         return launch_chol(dev, c, &X);
     }
     if (p_self > 0) {
@@ -1689,8 +1679,9 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
         side_times(dev, v.Um_blk, local_u, kc, p_self, w, v.Cm, self_blk, ld_self);   // :5768-5773
         const int local_u_main = std::min(local_u, local_x);              // rows beyond X: solve_sideinfo_only_rows
-        CholCall c{self_blk, ld_self, oppx, ld_opp, kt, k_side_self, bias_sub, s->ctc.ptr, kc, local_u_main,
-                   p_self, lam_self, lam_last_self, scale_lam, (bool)m.scale_lam_sideinfo, sbc, CHOL_COLLECTIVE};
+        CholCall c = CholCall::collective(self_blk, ld_self, oppx, ld_opp, kt, bias_sub, pen);
+        c.koff = k_side_self; c.Minit = s->ctc.ptr; c.kc = kc; c.rows_with_u = local_u_main; c.p_side = p_self;
+        c.scale_lam = scale_lam; c.scale_lam_sideinfo = (bool)m.scale_lam_sideinfo; c.scale_bias_const = sbc;
         add_implicit_term(c);
         // rows with few entries against many unknowns: low-rank path (lowrank_kernels.hpp)
         if (Fi == nullptr && !sbc && local_u_main == X.nrows && part < 0) {
@@ -1714,18 +1705,18 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
     if (Fi != nullptr) {
         // without side information on this side the reference still takes optimizeA_collective (collective.c:8612, :8783)
         if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :4817-4822
-        CholCall c{self_blk, ld_self, oppx, ld_opp, ksolve, 0, bias_sub, nullptr, 0, 0, 0,
-                   lam_self, lam_last_self, scale_lam, false, false, CHOL_COLLECTIVE};
+        CholCall c = CholCall::collective(self_blk, ld_self, oppx, ld_opp, ksolve, bias_sub, pen);
+        c.scale_lam = scale_lam;
         add_implicit_term(c);
         return launch_chol(dev, c, &X);
     }
     if (chol) {
-        CholCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, ksolve, 0, bias_sub, nullptr, 0, 0, 0,
-                   lam_self, lam_last_self, scale_lam, false, sbc, CHOL_EXPLICIT};
+        CholCall c = CholCall::explicit_rows(self_blk + k_side_self, ld_self, oppx, ld_opp, ksolve, bias_sub, pen);
+        c.scale_lam = scale_lam; c.scale_bias_const = sbc;
         return launch_chol(dev, c, &X);
     }
-    CgCall c{self_blk + k_side_self, ld_self, oppx, ld_opp, ksolve, bias_sub, nullptr,
-             lam_self, lam_last_self, scale_lam, sbc, m.max_cg_steps, false, (bool)m.precondition_cg};
+    CgCall c = CgCall::explicit_rows(self_blk + k_side_self, ld_self, oppx, ld_opp, ksolve, bias_sub, pen, m.max_cg_steps);
+    c.scale_lam = scale_lam; c.scale_bias_const = sbc; c.precond = (bool)m.precondition_cg;
     // block CG with the implicit-features term (collective_block_cg without side information on this side,
     // collective.c:2624-2643, :2862-2868): generic kernel; rows without entries are zeroed (:1258-1268)
     add_implicit_term_cg(c);
@@ -1749,7 +1740,7 @@ static int update_implicit_feats(cmfrec_hip_session *s, bool isAi)
     const real_t lam = (v.lam_self / s->w_implicit) * (scale_lam ? (real_t)rows_f : (real_t)1);   // :8469, :8510
     launch_gram(dev, s->gws, F, ldf, rows_f, kk, s->gram.ptr, (real_t)1, lam);
     HIP_CHECK(hipMemsetAsync(self, 0, (size_t)rows_self * kk * sizeof(real_t), dev.stream));
-    CholCall c{self, (size_t)kk, F, ldf, kk, 0, nullptr, s->gram.ptr, 0, 0, 0, lam, lam, false, false, false, CHOL_NAZ};
+    CholCall c = CholCall::naz_rhs(self, (size_t)kk, F, ldf, kk, s->gram.ptr, RowPenalty{lam, lam});
     c.values_override = s->ones.ptr;
     if (dev.nonneg_now || dev.l1_now != (real_t)0 || dev.l1_last_now != (real_t)0)
         return launch_chol(dev, c, &X);             // coordinate descent: per row on the assembled system
@@ -1790,18 +1781,18 @@ static int update_sideinfo(cmfrec_hip_session *s, bool isC, bool chol, int cg_st
         // first k_side+k columns of the factor matrix (collective.c:8354-8386; attributes nobody has stay untouched)
         const SparseShard &Uc = isC ? s->Usc : s->Isc;
         if (!chol) {
-            CgCall cg{Cm, (size_t)kc, F, ldF, kc, nullptr, nullptr, lam, lam, scale_lam, false, cg_steps > 0 ? cg_steps : m.max_cg_steps, false,
-                      (bool)m.precondition_cg};
+            CgCall cg = CgCall::explicit_rows(Cm, (size_t)kc, F, ldF, kc, nullptr, RowPenalty{lam, lam}, cg_steps > 0 ? cg_steps : m.max_cg_steps);
+            cg.scale_lam = scale_lam; cg.precond = (bool)m.precondition_cg;
             return launch_cg_any(dev, cg, Uc);
         }
-        CholCall c{Cm, (size_t)kc, F, ldF, kc, 0, nullptr, nullptr, 0, 0, 0, lam, lam, scale_lam, false, false, CHOL_EXPLICIT};
+        CholCall c = CholCall::explicit_rows(Cm, (size_t)kc, F, ldF, kc, nullptr, RowPenalty{lam, lam});
+        c.scale_lam = scale_lam;
         return launch_chol(dev, c, &Uc);
     }
     real_t diag = scale_lam ? lam * (real_t)rows_u : lam;                                          // common.c:2832
     launch_gram(dev, s->gws, F, ldF, rows_u, kc, s->gram.ptr, (real_t)1, diag);                    // common.c:2824
     side_transposed_times(dev, Um, rows_u, kc, p, F, ldF, Cm, (size_t)kc);                         // common.c:2852-2855
-    CholCall c{Cm, (size_t)kc, nullptr, 0, kc, 0, nullptr, s->gram.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-    return launch_chol(dev, c, nullptr, p);                                                        // common.c:2872-2875
+    return launch_chol_prefilled(dev, Cm, (size_t)kc, kc, s->gram.ptr, p);                         // common.c:2872-2875
 }
 
 // The matrices the reference keeps for predictions on new data (the step after the path),
@@ -1848,8 +1839,7 @@ int cmfrec_hip_session_precompute(cmfrec_hip_session *s, int last_step_cholesky,
             if (lam_bias_diff != 0)
                 hipLaunchKernelGGL(add_diag_kernel<real_t>, grid1d(1), dim3(256), 0, st, M.ptr, kp, kp - 1, kp,
                                    lam_bias_diff * (real_t)(m.scale_lam ? m.n : 1));
-            CholCall c{Bp.ptr, (size_t)kp, nullptr, 0, kp, 0, nullptr, M.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-            int rc = launch_chol(dev, c, nullptr, m.n);
+            int rc = launch_chol_prefilled(dev, Bp.ptr, (size_t)kp, kp, M.ptr, m.n);
             if (rc) return rc;
             Bp.download(TransBtBinvBt, (size_t)m.n * kp, st);
         }
@@ -1864,8 +1854,7 @@ int cmfrec_hip_session_precompute(cmfrec_hip_session *s, int last_step_cholesky,
                 HIP_CHECK(hipMemcpyAsync(Cc.ptr, s->C.ptr, (size_t)m.p * kc * sizeof(real_t), hipMemcpyDeviceToDevice, st));
                 hipLaunchKernelGGL(add_diag_kernel<real_t>, grid1d(kc), dim3(256), 0, st, M.ptr, kc, 0, kc,
                                    lamA * (real_t)(m.scale_lam ? m.p : 1) / w);
-                CholCall c{Cc.ptr, (size_t)kc, nullptr, 0, kc, 0, nullptr, M.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-                int rc = launch_chol(dev, c, nullptr, m.p);
+                int rc = launch_chol_prefilled(dev, Cc.ptr, (size_t)kc, kc, M.ptr, m.p);
                 if (rc) return rc;
                 Cc.download(TransCtCinvCt, (size_t)m.p * kc, st);
             }
@@ -2329,13 +2318,13 @@ int cmfrec_hip_optimizeA_implicit(real_t *A, size_t lda, const real_t *B, size_t
         launch_gram(dev, gws, dB.ptr, ldb, n, k, dG.ptr, (real_t)1, use_cg ? (real_t)0 : lam);
         int rc;
         if (use_cg) {
-            CgCall c{dA.ptr, lda, dB.ptr, ldb, k, nullptr, dG.ptr, lam, lam, false, false, max_cg_steps, true, precondition_cg};
+            CgCall c = CgCall::implicit_rows(dA.ptr, lda, dB.ptr, ldb, k, dG.ptr, RowPenalty{lam, lam}, max_cg_steps);
+            c.precond = precondition_cg;
             rc = launch_cg_any(dev, c, X);
         } else {
             // common.c:3334 zeroes m*k - (lda-k) elements from A
             HIP_CHECK(hipMemsetAsync(dA.ptr, 0, ((size_t)m * lda - (lda - (size_t)k)) * sizeof(real_t), dev.stream));
-            CholCall c{dA.ptr, lda, dB.ptr, ldb, k, 0, nullptr, dG.ptr, 0, 0, 0, lam, lam, false, false, false, CHOL_IMPLICIT};
-            rc = launch_chol(dev, c, &X);
+            rc = launch_chol(dev, CholCall::implicit_rows(dA.ptr, lda, dB.ptr, ldb, k, dG.ptr, RowPenalty{lam, lam}), &X);
         }
         dA.download(A, (size_t)m * lda, dev.stream);
         if (BtB_out) dG.download(BtB_out, (size_t)k * k, dev.stream);
@@ -2374,12 +2363,12 @@ int cmfrec_hip_optimizeA_explicit_weighted(real_t *A, size_t lda, const real_t *
         }
         int rc;
         if (use_cg) {
-            CgCall c{dA.ptr, lda, dB.ptr, ldb, k, bias_sub ? dbias.ptr : nullptr, nullptr, lam, lam_last, scale_lam,
-                     scale_bias_const, max_cg_steps, false, precondition_cg};
+            CgCall c = CgCall::explicit_rows(dA.ptr, lda, dB.ptr, ldb, k, bias_sub ? dbias.ptr : nullptr, RowPenalty{lam, lam_last}, max_cg_steps);
+            c.scale_lam = scale_lam; c.scale_bias_const = scale_bias_const; c.precond = precondition_cg;
             rc = launch_cg_any(dev, c, X);
         } else {
-            CholCall c{dA.ptr, lda, dB.ptr, ldb, k, 0, bias_sub ? dbias.ptr : nullptr, nullptr, 0, 0, 0, lam, lam_last,
-                       scale_lam, false, scale_bias_const, CHOL_EXPLICIT};
+            CholCall c = CholCall::explicit_rows(dA.ptr, lda, dB.ptr, ldb, k, bias_sub ? dbias.ptr : nullptr, RowPenalty{lam, lam_last});
+            c.scale_lam = scale_lam; c.scale_bias_const = scale_bias_const;
             rc = launch_chol(dev, c, &X);
         }
         dA.download(A, (size_t)m * lda, dev.stream);
@@ -2407,8 +2396,7 @@ int cmfrec_hip_optimizeA_dense_full(real_t *A, size_t lda, const real_t *B, size
         launch_gram(dev, gws, dB.ptr, ldb, n, k, dG.ptr, (real_t)1, scale_lam ? lam * (real_t)n : lam);
         if (do_B) launch_gemm<true>(dev, m, k, n, (real_t)1, dX.ptr, ldX, dB.ptr, ldb, dA.ptr, lda);
         else      launch_gemm<false>(dev, m, k, n, (real_t)1, dX.ptr, ldX, dB.ptr, ldb, dA.ptr, lda);
-        CholCall c{dA.ptr, lda, nullptr, 0, k, 0, nullptr, dG.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-        int rc = launch_chol(dev, c, nullptr, m);
+        int rc = launch_chol_prefilled(dev, dA.ptr, lda, k, dG.ptr, m);
         // only the k solved columns are written back (padding columns are never touched by the reference)
         std::vector<real_t> tmp((size_t)m * lda);
         dA.download(tmp.data(), (size_t)m * lda, dev.stream);
@@ -2576,8 +2564,7 @@ int_t precompute_collective_explicit(
             hipLaunchKernelGGL(add_diag_kernel<real_t>, grid1d(kk), dim3(256), 0, st, M.ptr, kk, 0, kk - 1, lam_B);
             hipLaunchKernelGGL(add_diag_kernel<real_t>, grid1d(1), dim3(256), 0, st, M.ptr, kk, kk - 1, kk, lam_last_B);
             hipLaunchKernelGGL(copy_mat_kernel<real_t>, grid1d((size_t)n * kk), dim3(256), 0, st, dB.ptr + k_item, (size_t)ktB, Bp.ptr, (size_t)kk, (size_t)n, kk);
-            CholCall c{Bp.ptr, (size_t)kk, nullptr, 0, kk, 0, nullptr, M.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-            const int rc = launch_chol(dev, c, nullptr, n);
+            const int rc = launch_chol_prefilled(dev, Bp.ptr, (size_t)kk, kk, M.ptr, n);
             if (rc) return rc;
             Bp.download(TransBtBinvBt, (size_t)n * kk, st);
         }
@@ -2589,8 +2576,7 @@ int_t precompute_collective_explicit(
                 HIP_CHECK(hipMemcpyAsync(M.ptr, CtC.ptr, (size_t)kc * kc * sizeof(real_t), hipMemcpyDeviceToDevice, st));
                 HIP_CHECK(hipMemcpyAsync(Cc.ptr, dC.ptr, (size_t)p * kc * sizeof(real_t), hipMemcpyDeviceToDevice, st));
                 hipLaunchKernelGGL(add_diag_kernel<real_t>, grid1d(kc), dim3(256), 0, st, M.ptr, kc, 0, kc, lam_C / w_user);
-                CholCall c{Cc.ptr, (size_t)kc, nullptr, 0, kc, 0, nullptr, M.ptr, 0, 0, 0, 0, 0, false, false, false, CHOL_PREFILLED};
-                const int rc = launch_chol(dev, c, nullptr, p);
+                const int rc = launch_chol_prefilled(dev, Cc.ptr, (size_t)kc, kc, M.ptr, p);
                 if (rc) return rc;
                 Cc.download(TransCtCinvCt, (size_t)p * kc, st);
             }
@@ -2744,8 +2730,9 @@ int cmfrec_hip_optimizeA_collective(real_t *A, size_t lda, const real_t *B, size
         // collective.c:4817-4822 zeroes max(m,m_u)*lda - (lda-k_totA) elements
         HIP_CHECK(hipMemsetAsync(dA.ptr, 0, ((size_t)m * lda - (lda - (size_t)kt)) * sizeof(real_t), dev.stream));
         launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, lda);
-        CholCall c{dA.ptr, lda, dB.ptr + k_item, ldb, kt, k_user, bias_sub ? dbias.ptr : nullptr, dG.ptr, kc, m_u, p,
-                   lam, lam_last, (bool)(scale_lam || scale_lam_sideinfo), scale_lam_sideinfo, false, CHOL_COLLECTIVE};
+        CholCall c = CholCall::collective(dA.ptr, lda, dB.ptr + k_item, ldb, kt, bias_sub ? dbias.ptr : nullptr, RowPenalty{lam, lam_last});
+        c.koff = k_user; c.Minit = dG.ptr; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+        c.scale_lam = scale_lam || scale_lam_sideinfo; c.scale_lam_sideinfo = scale_lam_sideinfo;
         LowRankScratch lrs;
         int rc = (m_u >= m) ? launch_collective_lowrank(dev, lrs, c, X, dC.ptr, SideOperand{dU.ptr}, p, w_user, k, n) : -1;
         if (rc < 0) rc = launch_chol(dev, c, &X);
@@ -2792,14 +2779,15 @@ int cmfrec_hip_optimizeA_collective_sparse(real_t *A, size_t lda, const real_t *
             launch_gram(dev, gws, dB.ptr + k_item, ldb, n, kk, dG.ptr, (real_t)1, lam);
             hipLaunchKernelGGL(betbe_base_kernel<real_t>, grid1d((size_t)kt * kt), dim3(256), 0, dev.stream, dG.ptr, kk, k_user, lam,
                                dM.ptr);
-            CholCall c{dA.ptr, lda, dB.ptr + k_item, ldb, kt, k_user, nullptr, nullptr, kc, m_u, p, lam, lam, false, false, false,
-                       CHOL_COLLECTIVE_IMPLICIT, dM.ptr};
-            c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
+            CholCall c = CholCall::collective_implicit(dA.ptr, lda, dB.ptr + k_item, ldb, kt, dM.ptr, RowPenalty{lam, lam});
+            c.koff = k_user; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+            c.set_second_source(Us, dC.ptr, kc, w_user);
             rc = launch_chol(dev, c, &X);
         } else {
-            CholCall c{dA.ptr, lda, dB.ptr + k_item, ldb, kt, k_user, bias_sub ? dbias.ptr : nullptr, nullptr, kc, m_u, p, lam,
-                       lam_last, (bool)(scale_lam || scale_lam_sideinfo), scale_lam_sideinfo, false, CHOL_COLLECTIVE};
-            c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
+            CholCall c = CholCall::collective(dA.ptr, lda, dB.ptr + k_item, ldb, kt, bias_sub ? dbias.ptr : nullptr, RowPenalty{lam, lam_last});
+            c.koff = k_user; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+            c.scale_lam = scale_lam || scale_lam_sideinfo; c.scale_lam_sideinfo = scale_lam_sideinfo;
+            c.set_second_source(Us, dC.ptr, kc, w_user);
             rc = launch_chol(dev, c, &X);
         }
         std::vector<real_t> tmp((size_t)m * lda);
@@ -3037,6 +3025,15 @@ static size_t newrows_naz_tasks(NewRowsState &S, int rows, const std::vector<siz
     return slots;
 }
 
+// w_user C^T C of the rows with dense side information: the model's, built by the first batch that has such rows
+static void newrows_ensure_CtC(NewRowsState &S, int p)
+{
+    if (S.ctc_built) return;
+    S.dCtC.alloc((size_t)S.kc * S.kc);
+    launch_gram(S.dev, S.gws, S.dC.ptr, (size_t)S.kc, p, S.kc, S.dCtC.ptr, S.M.w_user, (real_t)0);
+    S.ctc_built = true;
+}
+
 // The batch side.  Xs / Us: the shards newrows_state_run has built (Us: sparse U, or empty); lenX / lenU: the rows' lengths on the
 // host; m_u / p: as newrows_state_run has reduced them (0 without side information in the batch); dense: dU holds the centred
 // dense U.  naz_x: NA_as_zero_X applies to this batch (a sparse X).  Leaves the factors in S.dA.
@@ -3077,17 +3074,11 @@ static int newrows_run_naz(NewRowsState &S, SparseShard &Xs, SparseShard &Us, co
         poison_lds(st, dev.num_cus);              // test hook (the kernel has no LDS: nothing may depend on it)
         S.naz_last_waves = naz_launch_rhs(st, dev.num_cus, P, max_waves);
     };
-    auto ensure_CtC = [&]() {
-        if (S.ctc_built) return;
-        S.dCtC.alloc((size_t)kc * kc);
-        launch_gram(dev, S.gws, S.dC.ptr, (size_t)kc, p, kc, S.dCtC.ptr, M.w_user, (real_t)0);
-        S.ctc_built = true;
-    };
     if (!naz_x) {
         // NA_as_zero_U with an ordinary X: the rows with entries through the collective row solver with the shared w_user C^T C as
         // its side block and the right-hand sides of the side block from the kernel's second source + CtUbias; the rows without
         // any entry ("cold") share w_user C^T C + lam I
-        ensure_CtC();
+        newrows_ensure_CtC(S, p);
         run_rhs(false, S.dA.ptr, ldA);
         if (!S.inv_cold.built) {
             S.inv_cold.M.alloc((size_t)kc * kc);
@@ -3099,8 +3090,9 @@ static int newrows_run_naz(NewRowsState &S, SparseShard &Xs, SparseShard &Us, co
         HIP_CHECK(hipMemcpy2DAsync(S.dcold.ptr, (size_t)kc * sizeof(real_t), S.dA.ptr, ldA * sizeof(real_t), (size_t)kc * sizeof(real_t), (size_t)m_u,
                                    hipMemcpyDeviceToDevice, st));
         newrows_naz_apply(S, S.inv_cold, S.dcold.ptr, (size_t)kc, m_u, S.dcold2.ptr, (size_t)kc);
-        CholCall c{S.dA.ptr, ldA, S.dB.ptr + M.k_item, ldB, kt, k_user, S.dbias.ptr, S.dCtC.ptr, kc, m_u, p, lam, lam_bias, M.scale_lam, false,
-                   M.scale_bias_const, CHOL_COLLECTIVE};
+        CholCall c = CholCall::collective(S.dA.ptr, ldA, S.dB.ptr + M.k_item, ldB, kt, S.dbias.ptr, RowPenalty{lam, lam_bias});
+        c.koff = k_user; c.Minit = S.dCtC.ptr; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+        c.scale_lam = M.scale_lam; c.scale_bias_const = M.scale_bias_const;
         if (int rc = launch_chol(dev, c, &Xs)) return rc;
         hipLaunchKernelGGL(cold_select_kernel<real_t>, dim3(m_u), dim3(64), 0, st, S.dA.ptr, ldA, kt, kc, S.dcold2.ptr, Xs.p.ptr, m_u);
         HIP_CHECK(hipGetLastError());
@@ -3117,8 +3109,8 @@ static int newrows_run_naz(NewRowsState &S, SparseShard &Xs, SparseShard &Us, co
         Xs.wsum_naz.alloc_at_least((size_t)m_max);
         hipLaunchKernelGGL(naz_wsum_kernel<real_t>, grid1d((size_t)m_max), dim3(256), 0, st, Xs.p.ptr, Xs.w.ptr, m_max, n, Xs.wsum_naz.ptr);
         HIP_CHECK(hipGetLastError());
-        CholCall c{S.dA.ptr + k_user, ldA, S.dB.ptr + M.k_item, ldB, kx, 0, nullptr, S.dBtB.ptr, 0, 0, 0, lam, lam_bias, scaled, false,
-                   M.scale_bias_const, CHOL_NAZ_W};
+        CholCall c = CholCall::naz_weighted(S.dA.ptr + k_user, ldA, S.dB.ptr + M.k_item, ldB, kx, S.dBtB.ptr, RowPenalty{lam, lam_bias});
+        c.scale_lam = scaled; c.scale_bias_const = M.scale_bias_const;
         c.values_override = S.dz.ptr; c.weights_override = S.dg.ptr; c.rhs_prefilled_all = true; c.all_rows = S.naz_has_cst;
         if (int rc = launch_chol(dev, c, &Xs)) return rc;
         if (scaled && !S.naz_has_cst) {
@@ -3142,7 +3134,7 @@ static int newrows_run_naz(NewRowsState &S, SparseShard &Xs, SparseShard &Us, co
     };
     const real_t mult_side = (M.scale_lam_sideinfo && !spU) ? (real_t)(n + p) : (scaled ? (real_t)n : (real_t)1);
     if (rows_side > 0 && (!S.inv_side.built || S.inv_side_mult != mult_side)) {
-        ensure_CtC();
+        newrows_ensure_CtC(S, p);
         const real_t mult = mult_side;
         DevBuf<real_t> Gd;
         Gd.alloc((size_t)kx * kx);
@@ -3461,13 +3453,6 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
             hipLaunchKernelGGL(sub_colmeans_kernel<real_t>, grid1d((size_t)m_u * p), dim3(256), 0, st, dU.ptr, (size_t)m_u, p,
                                S.dmeans.ptr);
     }
-    // w_user C^T C of the rows with dense side information: the model's, built by the first batch that has such rows
-    auto ensure_CtC = [&]() {
-        if (S.ctc_built) return;
-        S.dCtC.alloc((size_t)kc * kc);
-        launch_gram(dev, gws, dC.ptr, (size_t)kc, p, kc, S.dCtC.ptr, w_user, (real_t)0);
-        S.ctc_built = true;
-    };
     const real_t *opp = S.dB.ptr + M.k_item;
     const real_t *bias_sub = S.dbias.ptr;
     int rc = 0;
@@ -3478,19 +3463,17 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
         rc = newrows_run_naz(S, Xs, Us, lenX, lenU, m_max, m_u, p, spU, naz_x);
     } else if (implicit) {
         if (p == 0) {
-            CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk, 0, nullptr, S.dG.ptr, 0, 0, 0, lam, lam, false, false, false,
-                       CHOL_IMPLICIT};
-            rc = launch_chol(dev, c, &Xs);
+            rc = launch_chol(dev, CholCall::implicit_rows(dA.ptr + k_user, ldA, opp, ldB, kk, S.dG.ptr, RowPenalty{lam, lam}), &Xs);
         } else if (spU) {
-            CholCall c{dA.ptr, ldA, opp, ldB, ktA, k_user, nullptr, nullptr, kc, m_u, p, lam, lam, false, false, false,
-                       CHOL_COLLECTIVE_IMPLICIT, S.dM.ptr};
-            c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
+            CholCall c = CholCall::collective_implicit(dA.ptr, ldA, opp, ldB, ktA, S.dM.ptr, RowPenalty{lam, lam});
+            c.koff = k_user; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+            c.set_second_source(Us, dC.ptr, kc, w_user);
             rc = launch_chol(dev, c, &Xs);
         } else {
-            ensure_CtC();
+            newrows_ensure_CtC(S, p);
             launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
-            CholCall c{dA.ptr, ldA, opp, ldB, ktA, k_user, nullptr, S.dCtC.ptr, kc, m_u, p, lam, lam, false, false, false,
-                       CHOL_COLLECTIVE_IMPLICIT, S.dM.ptr};
+            CholCall c = CholCall::collective_implicit(dA.ptr, ldA, opp, ldB, ktA, S.dM.ptr, RowPenalty{lam, lam});
+            c.koff = k_user; c.Minit = S.dCtC.ptr; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
             rc = launch_chol(dev, c, &Xs);
         }
     } else if (Bi) {
@@ -3507,35 +3490,39 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
             sbc = false;
         }
         if (p > 0 && !spU) {
-            ensure_CtC();
+            newrows_ensure_CtC(S, p);
             launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
         }
         if (Xs.nnz > 0)
             hipLaunchKernelGGL(implicit_rhs_rows_kernel<real_t>, grid1d((size_t)m_max * 64), dim3(256), 0, st, Xs.p.ptr, Xs.i.ptr, S.dBi.ptr, kk,
                                M.w_implicit, m_max, dA.ptr, ldA, k_user);
         HIP_CHECK(hipGetLastError());
-        CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, (p > 0 && !spU) ? S.dCtC.ptr : nullptr, p > 0 ? kc : 0,
-                   all_u ? m_max : m_u, p, lam, lam_bias, (bool)(scale_lam || scale_lam_sideinfo),
-                   (bool)(scale_lam_sideinfo && !spU), sbc, CHOL_COLLECTIVE};
-        c.Mfull = S.dBiFull.ptr; c.rhs_prefilled_all = true;
-        if (spU) { c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user; c.rows2 = m_u; }
+        CholCall c = CholCall::collective(dA.ptr, ldA, opp, ldB, kt, bias_sub, RowPenalty{lam, lam_bias}, S.dBiFull.ptr);
+        c.koff = k_user; c.Minit = (p > 0 && !spU) ? S.dCtC.ptr : nullptr; c.kc = p > 0 ? kc : 0;
+        c.rows_with_u = all_u ? m_max : m_u; c.p_side = p;
+        // (a sparse U never arrives here with scale_lam_sideinfo: refused at the top, collective.c:3397-3411)
+        c.scale_lam = scale_lam || scale_lam_sideinfo; c.scale_lam_sideinfo = scale_lam_sideinfo && !spU; c.scale_bias_const = sbc;
+        c.rhs_prefilled_all = true;
+        if (spU) { c.set_second_source(Us, dC.ptr, kc, w_user); c.rows2 = m_u; }
         rc = launch_chol(dev, c, &Xs);
     } else if (p == 0) {
-        CholCall c{dA.ptr + k_user, ldA, opp, ldB, kk + ub, 0, bias_sub, nullptr, 0, 0, 0, lam, lam_bias,
-                   (bool)(scale_lam || scale_lam_sideinfo), false, scale_bias_const, CHOL_EXPLICIT};
+        CholCall c = CholCall::explicit_rows(dA.ptr + k_user, ldA, opp, ldB, kk + ub, bias_sub, RowPenalty{lam, lam_bias});
+        c.scale_lam = scale_lam || scale_lam_sideinfo; c.scale_bias_const = scale_bias_const;
         rc = launch_chol(dev, c, &Xs);
     } else if (spU) {
-        // rows with attributes but no observations come out of the same launch: without scale_lam_sideinfo the
-        // "cold" solution (collective.c:3309-3440 with u_vec_sp) is the block system with an empty X part
-        CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, nullptr, kc, m_u, p, lam, lam_bias, scale_lam, false,
-                   scale_bias_const, CHOL_COLLECTIVE};
-        c.X2 = &Us; c.B2 = dC.ptr; c.ldb2 = (size_t)kc; c.kc2 = kc; c.w2 = w_user;
+        // rows with attributes but no observations come out of the same launch: without scale_lam_sideinfo (refused at the top,
+        // collective.c:3397-3411) the "cold" solution (:3309-3440 with u_vec_sp) is the block system with an empty X part
+        CholCall c = CholCall::collective(dA.ptr, ldA, opp, ldB, kt, bias_sub, RowPenalty{lam, lam_bias});
+        c.koff = k_user; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+        c.scale_lam = scale_lam; c.scale_bias_const = scale_bias_const;
+        c.set_second_source(Us, dC.ptr, kc, w_user);
         rc = launch_chol(dev, c, &Xs);
     } else {
-        ensure_CtC();
+        newrows_ensure_CtC(S, p);
         launch_gemm<false>(dev, m_u, kc, p, w_user, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, dA.ptr, ldA);
-        CholCall c{dA.ptr, ldA, opp, ldB, kt, k_user, bias_sub, S.dCtC.ptr, kc, m_u, p, lam, lam_bias,
-                   (bool)(scale_lam || scale_lam_sideinfo), scale_lam_sideinfo, scale_bias_const, CHOL_COLLECTIVE};
+        CholCall c = CholCall::collective(dA.ptr, ldA, opp, ldB, kt, bias_sub, RowPenalty{lam, lam_bias});
+        c.koff = k_user; c.Minit = S.dCtC.ptr; c.kc = kc; c.rows_with_u = m_u; c.p_side = p;
+        c.scale_lam = scale_lam || scale_lam_sideinfo; c.scale_lam_sideinfo = scale_lam_sideinfo; c.scale_bias_const = scale_bias_const;
         rc = launch_chol(dev, c, &Xs);
         if (rc == 0) {
             // cold rows
@@ -3553,12 +3540,10 @@ int newrows_state_run(NewRowsState *sp, const NewRowsBatchArgs &bt, real_t *A, r
                     S.cold_built = true;
                 }
                 launch_gemm<false>(dev, m_u, kc, p, (real_t)1, dU.ptr, (size_t)p, dC.ptr, (size_t)kc, S.dcold.ptr, (size_t)kc);
-                CholCall cc{S.dcold.ptr, (size_t)kc, nullptr, 0, kc, 0, nullptr, S.dMcold.ptr, 0, 0, 0, 0, 0, false, false, false,
-                            CHOL_PREFILLED};
                 // factors_closed_form on C with l1_lam / w_user, scaled by p like lam except on the last unknown (collective.c:3385-3400)
                 dev.l1_last_now = l1_lam / w_user;
                 dev.l1_now = scale_lam_sideinfo ? dev.l1_last_now * (real_t)p : dev.l1_last_now;
-                rc = launch_chol(dev, cc, nullptr, m_u);
+                rc = launch_chol_prefilled(dev, S.dcold.ptr, (size_t)kc, kc, S.dMcold.ptr, m_u);
                 dev.l1_now = l1_lam; dev.l1_last_now = ub ? l1_lam_bias : l1_lam;
             }
             hipLaunchKernelGGL(cold_select_kernel<real_t>, dim3(m_u), dim3(64), 0, st, dA.ptr, ldA, kt, kc, S.dcold.ptr,
