@@ -15,6 +15,8 @@
 // is on (cmfrec_hip_ranker_set_filter) sends cmfrec_hip_ranker_topN of n_top <= 64 through topn_filter_kernel (topn_filter_kernels.hpp,
 // launched from topn_filter_tu.hip), topn_filter_refine_kernel over the shortlists -- with the arithmetic of the kernel the call
 // would run unfiltered -- and topn_filter_certify_kernel; the users that are not certified take the route above in a second batch.
+// A diversified call (cmfrec_hip_ranker_rerank_mmr / _topN_diverse) launches topn_mmr_kernel (topn_mmr_kernels.hpp, from
+// topn_mmr_tu.hip) over per-user pools that are on the device: the caller's, or the lists the full ranking above left there.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -29,6 +31,7 @@
 #include "topn_cand_kernels.hpp"
 #include "topn_rank_kernels.hpp"
 #include "topn_filter.hpp"
+#include "topn_mmr_kernels.hpp"
 #include "rank_metrics_kernels.hpp"
 
 using namespace cmfhip;
@@ -69,6 +72,8 @@ struct cmfrec_hip_ranker {
     bool fs_valid = false;
     hipEvent_t fev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the filter, the refinement and the certificate
     float f_ms[3] = {0, 0, 0};
+    DevBuf<int> mmr_ids;                     // the result of a diversified call: [nu][n_top] (its pools use ids / sc)
+    DevBuf<real_t> mmr_sc, mmr_v;
     const real_t *item_bias() const { return has_bias ? bias.ptr : nullptr; }
     ~cmfrec_hip_ranker()
     {
@@ -85,6 +90,7 @@ namespace {
 constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
 constexpr const char *RANK_LIMITS = "needs k <= 272";
 constexpr const char *DEEP_LIMITS = "needs k <= 272 and 1 <= n_top <= n";
+constexpr const char *MMR_LIMITS = "needs k <= 272, 1 <= n_top <= pool <= min(128, n) and 0 <= theta <= 1";
 
 // User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
 // unless fewer finish the nu users in fewer or cheaper waves of workgroups.  A workgroup's time per item round is about
@@ -309,15 +315,18 @@ void download_and_wait(cmfrec_hip_ranker *r, size_t cells, int_t *out_ids, real_
 // the ranking of users who are on the device already: the launch, the timing events and the download of cmfrec_hip_ranker_topN
 // (the caller holds the DeviceScope and has checked the limits)
 // dcand_p != null: over each user's candidate list (device CSR) on topn_cand_kernel
+// stay: ids and scores stay on the device (r->ids, r->sc) for the kernel behind the launch; nothing is downloaded and the stream
+// is not waited for
 int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t *out_ids, real_t *out_scores,
-                const size_t *dcand_p = nullptr, const int *dcand_i = nullptr)
+                const size_t *dcand_p = nullptr, const int *dcand_i = nullptr, bool stay = false)
 {
+    const bool want_scores = out_scores != nullptr || stay;
     const cmfrec_hip_ranker::Device &dev = r->dev;
     const int k = r->k;
     const int_t nu = users.nu;
     const size_t cells = (size_t)nu * n_top;
     r->ids.alloc_at_least(cells);
-    if (out_scores) r->sc.alloc_at_least(cells);
+    if (want_scores) r->sc.alloc_at_least(cells);
     if (dcand_p) {
         r->next.alloc_at_least(1);
         HIP_CHECK(hipMemsetAsync(r->next.ptr, 0, sizeof(unsigned), dev.stream));
@@ -334,7 +343,7 @@ int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t
     int users_per_workgroup = 0, grid = 0;
     if (dcand_p) {
         auto P = ranking_params<TopnCandParams<real_t>>(r, users);
-        set_lists(P, r, n_top, out_scores != nullptr);
+        set_lists(P, r, n_top, want_scores);
         P.cand_p = dcand_p; P.cand_i = dcand_i;
         P.next = r->next.ptr; P.order = r->corder.ptr;
         grid = launch_topn_cand(dev.stream, dev.num_cus, P, switches().topn_cand_waves);
@@ -346,7 +355,7 @@ int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t
         P.slice_items = slice_items; P.s0 = P.s1 = 0;
         TopnMergeParams<real_t> M;
         M.part_scores = r->part_sc.ptr; M.part_ids = r->part_id.ptr; M.slices = slices; M.nu = nu;
-        set_lists(M, r, n_top, out_scores != nullptr);
+        set_lists(M, r, n_top, want_scores);
         int bpc = 1;
         const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
         grid = slices * with_tiles(nut, [&](auto t) {
@@ -359,7 +368,7 @@ int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t
         users_per_workgroup = 16 * nut;
     } else if (k <= TOPN_KMAX && !switches().topn_wide && !split) {
         auto P = ranking_params<TopnParams<real_t>>(r, users);
-        set_lists(P, r, n_top, out_scores != nullptr);
+        set_lists(P, r, n_top, want_scores);
         const size_t smem = topn_lds_bytes(sizeof(real_t));
         HIP_CHECK(hipFuncSetAttribute((const void *)topn_kernel<real_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         grid = std::min((nu + TOPN_UT - 1) / TOPN_UT, dev.num_cus * 2);
@@ -367,7 +376,7 @@ int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t
         users_per_workgroup = TOPN_UT;
     } else {
         auto P = ranking_params<TopnWideParams<real_t>>(r, users);
-        set_lists(P, r, n_top, out_scores != nullptr);
+        set_lists(P, r, n_top, want_scores);
         int bpc = 1;
         const int nut = pick_user_tiles(nu, k, n_top, dev.num_cus, &bpc);
         grid = with_tiles(nut, [&](auto t) {
@@ -377,7 +386,7 @@ int rank_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, int_t
     }
     HIP_CHECK(hipGetLastError());
     end_timed(r, users_per_workgroup, grid, slices);
-    download_and_wait(r, cells, out_ids, out_scores);
+    if (!stay) download_and_wait(r, cells, out_ids, out_scores);
     return 0;
 }
 
@@ -551,6 +560,43 @@ int ranks_device(cmfrec_hip_ranker *r, const RankUsers &users, size_t total, siz
     });
     end_timed(r, 16 * nut, grid, 1);
     if (!stay) download_and_wait(r, total, out_rank, out_scores, &r->pool, out_pool, (size_t)users.nu);
+    return 0;
+}
+
+// what a diversified call refuses beyond "invalid arguments" (DESIGN.md section 3.19), before a device is touched
+int check_mmr(const char *fn, int_t k, int_t n, int_t pool, int_t n_top, double theta)
+{
+    const bool ok = k <= TOPNW_KMAX && n_top >= 1 && n_top <= pool && pool <= TOPNM_POOL_MAX && pool <= n && theta >= 0.0 && theta <= 1.0;
+    return ok ? 0 : refuse(fn, MMR_LIMITS);
+}
+
+// The MMR pass over the pools that are on the device, r->ids / r->sc [nu, pool]: the launch, the timing events and the download.
+// CMFREC_HIP_MMR_GROUPS (test hook, read per call) caps the workgroups, so that a small batch gives one of them many users.
+// (the caller holds the DeviceScope and has checked the limits)
+int mmr_device(cmfrec_hip_ranker *r, int_t nu, int_t pool, double theta, int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    const size_t cells = (size_t)nu * (size_t)n_top;
+    ensure_inverse_norms(r);                                             // outside the timed interval
+    r->mmr_ids.alloc_at_least(cells);
+    r->mmr_sc.alloc_at_least(cells);
+    if (out_mmr) r->mmr_v.alloc_at_least(cells);
+    TopnMmrParams<real_t> P;
+    set_items(P, r);
+    P.rn = r->rn.ptr;
+    P.pool_ids = r->ids.ptr; P.pool_scores = r->sc.ptr; P.nu = nu; P.pool = pool;
+    P.theta = (real_t)theta; P.n_top = n_top;
+    P.out_ids = r->mmr_ids.ptr; P.out_scores = r->mmr_sc.ptr; P.out_mmr = out_mmr ? r->mmr_v.ptr : nullptr;
+    const char *cap = getenv("CMFREC_HIP_MMR_GROUPS");
+    const int max_groups = (cap != nullptr && cap[0] != 0) ? atoi(cap) : 0;
+    poison_lds(dev.stream, dev.num_cus);                                 // (every LDS word the kernel reads it has written)
+    HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    const int grid = topn_mmr_launch(dev.stream, dev.num_cus, P, max_groups);
+    end_timed(r, 1, grid, 1);
+    r->mmr_ids.download(out_ids, cells, dev.stream);
+    r->mmr_sc.download(out_scores, cells, dev.stream);
+    if (out_mmr) r->mmr_v.download(out_mmr, cells, dev.stream);
+    HIP_CHECK(hipStreamSynchronize(dev.stream));
     return 0;
 }
 
@@ -1088,6 +1134,41 @@ int cmfrec_hip_ranker_similar(cmfrec_hip_ranker *r, const int_t *query_ids, int_
     });
 }
 
+int cmfrec_hip_ranker_rerank_mmr(cmfrec_hip_ranker *r, int_t nu, int_t pool, const int_t *pool_ids, const real_t *pool_scores, double theta,
+                                 int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr)
+{
+    const char *fn = "cmfrec_hip_ranker_rerank_mmr";
+    return guarded([&]() {
+        if (r == nullptr || nu <= 0 || !pool_ids || !pool_scores || !out_ids || !out_scores)
+            return refuse(fn, std::string("invalid arguments; ") + MMR_LIMITS);
+        if (int rc = check_mmr(fn, r->k, r->n, pool, n_top, theta)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        const size_t cells = (size_t)nu * (size_t)pool;
+        r->ids.upload(pool_ids, cells, r->dev.stream);
+        r->sc.upload(pool_scores, cells, r->dev.stream);
+        return mmr_device(r, nu, pool, theta, n_top, out_ids, out_scores, out_mmr);
+    });
+}
+
+int cmfrec_hip_ranker_topN_diverse(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t excl_p[], const int_t excl_i[],
+                                   int_t pool, double theta, int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr)
+{
+    const char *fn = "cmfrec_hip_ranker_topN_diverse";
+    return guarded([&]() {
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || !out_ids || !out_scores) return refuse(fn, std::string("invalid arguments; ") + MMR_LIMITS);
+        if (int rc = check_mmr(fn, r->k, r->n, pool, n_top, theta)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
+        // the pool: the full ranking of n_top = pool by the handle's exact route (a filtered handle's certified lists are these
+        // lists bit for bit), left on the device
+        if (int rc = rank_device(r, users, pool, nullptr, nullptr, nullptr, nullptr, true)) return rc;
+        return mmr_device(r, nu, pool, theta, n_top, out_ids, out_scores, out_mmr);
+    });
+}
+
 int cmfrec_hip_ranker_inverse_norms(cmfrec_hip_ranker *r, real_t *out)
 {
     return guarded([&]() {
@@ -1189,6 +1270,18 @@ int cmfrec_hip_topN_deep_batch(const real_t *A, size_t lda, int_t nu, const real
     if (!out_ids) return refuse(fn, "invalid arguments");
     return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
         return cmfrec_hip_ranker_topN_deep(r, A, lda, nu, excl_p, excl_i, n_top, out_ids, out_scores);
+    });
+}
+
+int cmfrec_hip_topN_diverse_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB,
+                                  const size_t excl_p[], const int_t excl_i[], int_t pool, double theta, int_t n_top, int_t *out_ids,
+                                  real_t *out_scores, real_t *out_mmr)
+{
+    const char *fn = "cmfrec_hip_topN_diverse_batch";
+    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B || !out_ids || !out_scores) return refuse(fn, std::string("invalid arguments; ") + MMR_LIMITS);
+    if (int rc = check_mmr(fn, k, n, pool, n_top, theta)) return rc;
+    return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_topN_diverse(r, A, lda, nu, excl_p, excl_i, pool, theta, n_top, out_ids, out_scores, out_mmr);
     });
 }
 

@@ -89,6 +89,22 @@ def _topN_deep(self, users, n, exclude, biasB):
     return ops.topN_deep_batch(A, B, n, biasB=biasB, exclude=excl)
 
 
+def _topN_diverse(self, users, n, pool, tradeoff, exclude, biasB):
+    """Shared body of ``CMF.topN_diverse`` / ``CMF_implicit.topN_diverse``."""
+    from . import ops
+    _, A, excl = _topN_inputs(self, users, exclude)
+    B = np.ascontiguousarray(self.B_[:, self.k_item:])
+    return ops.topN_diverse_batch(A, B, n_top=n, pool=pool, tradeoff=tradeoff, biasB=biasB, exclude=excl)
+
+
+_TOPN_DIVERSE_DOC = """Diversified top-``n``: (ids [len(users), n] int32, scores).  The ``pool`` best items of every user as ``topN_batch``
+        ranks them are re-ranked on the device by maximal marginal relevance (``ops.topN_diverse_batch``): the best score first,
+        then whatever maximises ``tradeoff * (score scaled to [0, 1] over the pool) - (1 - tradeoff) * (largest cosine to an item
+        already picked)`` over ``B_[:, k_item:]``.  ``tradeoff`` = 1 is ``topN_batch``'s order, smaller values trade score for
+        variety.  ``users`` and ``exclude`` as in ``topN_batch``; ``n <= pool <= min(128, items)``.  The scores are the ranker's own,
+        A_u . B_i (+ the item bias), as in ``topN_deep``.  To ask for several batches, hold ``ranker()`` and call its ``topN_diverse``."""
+
+
 _TOPN_DEEP_DOC = """``topN_batch`` without its limit of 128: (ids [len(users), n] int32, scores) for any ``1 <= n <= items``, built on the
         device in pages that each admit only what lies strictly behind the page before (``ops.topN_deep_batch``); ``users`` and
         ``exclude`` as in ``topN_batch``.  The scores are exactly what the ranker returns, A_u . B_i (+ the item bias): the global
@@ -132,6 +148,12 @@ class ModelRanker:
         Scores as ``topN_deep`` returns them."""
         _, A, excl = _topN_inputs(self._model, users, exclude)
         return self._ranker.topN_after(A, after_ids, after_scores, n=n, exclude=excl)
+
+    def topN_diverse(self, users, n=10, pool=64, tradeoff=0.7, exclude=None, output_mmr=False):
+        """(ids, scores[, values]) for user ids of the fitted model: their ``pool`` best items re-ranked by maximal marginal relevance
+        without leaving the device (``Ranker.topN_diverse``).  Scores as ``topN_deep`` returns them."""
+        _, A, excl = _topN_inputs(self._model, users, exclude)
+        return self._ranker.topN_diverse(A, n=n, pool=pool, tradeoff=tradeoff, exclude=excl, output_mmr=output_mmr)
 
     def pages(self):
         """(launches, page length) of the most recent ``topN_deep`` call."""
@@ -576,6 +598,10 @@ class CMF_implicit(_Base):
         return _topN_deep(self, users, n, exclude, None)
     topN_deep.__doc__ = _TOPN_DEEP_DOC
 
+    def topN_diverse(self, users, n=10, pool=64, tradeoff=0.7, exclude=None):
+        return _topN_diverse(self, users, n, pool, tradeoff, exclude, None)
+    topN_diverse.__doc__ = _TOPN_DIVERSE_DOC
+
     def ranks_batch(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by A_u . B_i, counted
         on the GPU (``ops.ranks_batch``).  ``heldout``: (indptr, indices) CSR over the users OF THIS CALL or a SciPy CSR matrix
@@ -913,6 +939,10 @@ class CMF(_Base):
     def topN_deep(self, users, n, exclude=None):
         return _topN_deep(self, users, n, exclude, self.item_bias_ if self.item_bias else None)
     topN_deep.__doc__ = _TOPN_DEEP_DOC
+
+    def topN_diverse(self, users, n=10, pool=64, tradeoff=0.7, exclude=None):
+        return _topN_diverse(self, users, n, pool, tradeoff, exclude, self.item_bias_ if self.item_bias else None)
+    topN_diverse.__doc__ = _TOPN_DIVERSE_DOC
 
     def ranks_batch(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by

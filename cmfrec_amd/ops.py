@@ -393,6 +393,53 @@ def similar_batch(B, ids, n_top=10, metric="cosine", exclude=None):
     return out, sc
 
 
+def _mmr_pools(pool_ids, pool_scores, dtype, what):
+    """(ids int32 [nu, pool], scores [nu, pool]) of a re-ranking call, checked without a device."""
+    ids = np.asarray(pool_ids); sc = np.asarray(pool_scores)
+    if ids.ndim != 2 or ids.shape != sc.shape or ids.shape[0] < 1:
+        raise ValueError("%s: pool_ids and pool_scores must be [users, pool] of one shape, got %s and %s" % (what, ids.shape, sc.shape))
+    if not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError("%s: pool_ids must be integers, got %s" % (what, ids.dtype))
+    if sc.dtype != np.dtype(dtype):
+        raise ValueError("%s: pool_scores is %s, the items are %s" % (what, sc.dtype, np.dtype(dtype)))
+    return np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(sc)
+
+
+def rerank_mmr(B, pool_ids, pool_scores, n_top=10, tradeoff=0.7, output_mmr=False):
+    """Maximal-marginal-relevance re-ranking of per-user shortlists on the device: (ids [nu, n_top] int32, scores [nu, n_top]) picked
+    greedily from ``pool_ids`` / ``pool_scores`` [nu, pool] by ``tradeoff * rel - (1 - tradeoff) * (largest cosine to a picked item)``
+    over the rows of ``B`` [n, k], ``rel`` the pool's scores scaled to [0, 1]; ties go to the earlier pool position, -1 / -inf once a
+    pool's valid pairs (id in [0, n), finite score) have run out.  ``tradeoff`` = 1 is the pool by descending score, 0 spreads the
+    list as far as it can.  ``output_mmr``: a third array, the value of every pick.  k <= 272, n_top <= pool <= min(128, n).
+    B is uploaded on every call: to re-rank several batches, hold a ``cmfrec_amd.Ranker`` and call its ``rerank_mmr``."""
+    from .rank import Ranker
+    with Ranker(np.asarray(B)) as r:
+        return r.rerank_mmr(pool_ids, pool_scores, n=n_top, tradeoff=tradeoff, output_mmr=output_mmr)
+
+
+def topN_diverse_batch(A, B, n_top=10, pool=64, tradeoff=0.7, biasB=None, exclude=None, output_mmr=False):
+    """Diversified top-N for every row of ``A``: the ``pool`` best items by score = A_u . B_i (+ biasB[i]) as ``topN_batch`` ranks
+    them stay on the device and are re-ranked there by maximal marginal relevance (``rerank_mmr``); one download.  Returns
+    (ids [nu, n_top] int32, scores [nu, n_top]) and, with ``output_mmr``, the value of every pick.  k <= 272,
+    n_top <= pool <= min(128, n), 0 <= tradeoff <= 1.  B is uploaded on every call: hold a ``cmfrec_amd.Ranker`` otherwise."""
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B, A.dtype)
+    lib, R = _prep(A, B)
+    nu, lda = A.shape
+    n, ldb = B.shape
+    n_top = int(n_top)
+    ids = np.empty((nu, max(n_top, 0)), np.int32); sc = np.empty((nu, max(n_top, 0)), A.dtype)
+    mmr = np.empty((nu, max(n_top, 0)), A.dtype) if output_mmr else None
+    bs = None if biasB is None else np.ascontiguousarray(biasB, A.dtype)
+    if exclude is not None and _is_csr(exclude):
+        exclude = (exclude.indptr, exclude.indices)
+    ep, ei = _sorted_exclude(exclude, nu)
+    rc = lib.cmfrec_hip_topN_diverse_batch(_lib.ptr(A), C.c_size_t(lda), C.c_int(nu), _lib.ptr(B), C.c_size_t(ldb), C.c_int(n), C.c_int(lda),
+                                           _lib.ptr(bs), _lib.ptr(ep), _lib.ptr(ei), C.c_int(int(pool)), C.c_double(float(tradeoff)),
+                                           C.c_int(n_top), _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(mmr))
+    _lib.check(rc, lib, "topN_diverse_batch")
+    return (ids, sc, mmr) if output_mmr else (ids, sc)
+
+
 DENSE_OPS = {"gemm": 0, "gemm_ta": 1, "gram": 2, "potrf": 3, "trtri": 4, "potrs_rows": 5}
 
 

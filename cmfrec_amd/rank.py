@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _heldout_lists, _is_csr, _similar_args, _sorted_exclude, _sorted_include, after_cursor
+from .ops import _heldout_lists, _is_csr, _mmr_pools, _similar_args, _sorted_exclude, _sorted_include, after_cursor
 
 
 def check_rankset(users, heldout, exclude):
@@ -377,6 +377,45 @@ class Ranker:
                                                 _lib.ptr(out), _lib.ptr(sc))
         _lib.check(rc, self.lib, "Ranker.similar")
         return out, sc
+
+    def rerank_mmr(self, pool_ids, pool_scores, n=10, tradeoff=0.7, output_mmr=False):
+        """Maximal-marginal-relevance re-ranking of the caller's shortlists against the resident items: (ids [nu, n] int32,
+        scores [nu, n]) picked greedily from ``pool_ids`` / ``pool_scores`` [nu, pool] -- the first pick is the best score, every
+        later one the unpicked pair of the largest ``tradeoff * rel - (1 - tradeoff) * (largest cosine to a picked item)``, ``rel``
+        the pool's scores scaled to [0, 1], the cosine over the factors without the bias (a zero row is similar to nothing); ties
+        go to the earlier pool position.  A pair whose id is outside the items or whose score is not finite (the -1 / -inf of a
+        short ``topN`` list) is never picked; -1 / -inf once the valid pairs have run out.  ``tradeoff`` = 1: the pool by
+        descending score, exactly.  ``output_mmr``: a third array, the value of every pick.  ``n <= pool <= min(128, items)``."""
+        h = self._live()
+        ids, sc = _mmr_pools(pool_ids, pool_scores, self.dtype, "Ranker.rerank_mmr")
+        nu, pool = ids.shape
+        n = int(n)
+        out = np.empty((nu, max(n, 0)), np.int32); osc = np.empty((nu, max(n, 0)), self.dtype)
+        mmr = np.empty((nu, max(n, 0)), self.dtype) if output_mmr else None
+        rc = self.lib.cmfrec_hip_ranker_rerank_mmr(h, C.c_int(nu), C.c_int(pool), _lib.ptr(ids), _lib.ptr(sc), C.c_double(float(tradeoff)),
+                                                   C.c_int(n), _lib.ptr(out), _lib.ptr(osc), _lib.ptr(mmr))
+        _lib.check(rc, self.lib, "Ranker.rerank_mmr")
+        return (out, osc, mmr) if output_mmr else (out, osc)
+
+    def topN_diverse(self, A, n=10, pool=64, tradeoff=0.7, exclude=None, output_mmr=False):
+        """Diversified top-N: ``rerank_mmr(*topN(A, pool, exclude), n, tradeoff)`` -- the same bytes -- without the pool leaving the
+        device: the ranking of ``pool`` items per user stays there, is re-ranked there, and one download brings (ids [nu, n] int32,
+        scores [nu, n]) and, with ``output_mmr``, the value of every pick.  ``n <= pool <= min(128, items)``, ``0 <= tradeoff <= 1``.
+        The pool is ranked by ``topN``'s exact route (``split`` applies, ``filter`` does not)."""
+        h = self._live()
+        A = self._users(A, "Ranker.topN_diverse")
+        nu = A.shape[0]
+        n = int(n)
+        if exclude is not None and _is_csr(exclude):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, nu)
+        ids = np.empty((nu, max(n, 0)), np.int32); sc = np.empty((nu, max(n, 0)), self.dtype)
+        mmr = np.empty((nu, max(n, 0)), self.dtype) if output_mmr else None
+        rc = self.lib.cmfrec_hip_ranker_topN_diverse(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(ep), _lib.ptr(ei),
+                                                     C.c_int(int(pool)), C.c_double(float(tradeoff)), C.c_int(n), _lib.ptr(ids), _lib.ptr(sc),
+                                                     _lib.ptr(mmr))
+        _lib.check(rc, self.lib, "Ranker.topN_diverse")
+        return (ids, sc, mmr) if output_mmr else (ids, sc)
 
     def inverse_norms(self):
         """[n]: 1 / |B_i| of every row as the cosine scores use it (made on the device by the first call that needs it, resident

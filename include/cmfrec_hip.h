@@ -751,6 +751,35 @@ int cmfrec_hip_ranker_set_filter(cmfrec_hip_ranker *r, int mode);
 int cmfrec_hip_ranker_filter_stats(cmfrec_hip_ranker *r, int *users, int *filtered, int *certified);
 int cmfrec_hip_ranker_filter_ms(cmfrec_hip_ranker *r, double ms[4]);
 int cmfrec_hip_ranker_filter_keys(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, float *keys_out);
+
+/* Diversified top-N: maximal marginal relevance (MMR, Carbonell & Goldstein) over a per-user shortlist, on the device (DESIGN.md
+ * section 3.19, topn_mmr_kernels.hpp).  A user's pool is `pool` (id, score) pairs in pool order; a pair whose id is outside [0, n) or
+ * whose score is not finite is invalid and never picked (the -1 / -inf a short top-N list ends with).  Over the valid pairs
+ *   rel_i     = (s_i - s_min) / (s_max - s_min), 0 for all when s_max == s_min;
+ *   sim(i, j) = (B_i . B_j) * inv_i * inv_j over the k scored columns, without the bias; inv = cmfrec_hip_ranker_inverse_norms' value,
+ *               0 where that is NaN: a zero row is similar to nothing;
+ *   pick 1 is the valid pair of the largest rel; pick t + 1 the valid, unpicked pair of the largest
+ *               v_i = theta * rel_i - (1 - theta) * max over the picked j of sim(i, j); equal values go to the earlier position.
+ * out_ids / out_scores [nu, n_top] (both required): the picked ids and their scores as they came in; out_mmr (optional): v at the
+ * moment of the pick, theta * rel for the first; -1 / -inf in all three once the valid pairs have run out.  theta == 1 returns the
+ * valid pairs in descending score, earlier position first, exactly.  Arithmetic in the working precision (theta is rounded to it).
+ * Limits: k <= 272, 1 <= n_top <= pool <= min(128, n), 0 <= theta <= 1; beyond them, and for a null handle or pointer, code 2 with
+ * the limits in the message, before anything touches the device, the outputs untouched.
+ * rerank_mmr: the caller's pools, pool_ids / pool_scores [nu, pool] host arrays, against the resident items.
+ * topN_diverse: the handle's own ranking of n_top = pool for the users A [nu, lda] (exclusion lists as in ranker_topN) stays on the
+ * device, is re-ranked there, and one download brings the result: the bytes of rerank_mmr over ranker_topN(..., pool)'s output.
+ * The pool takes the exact route of ranker_topN (a split handle its slices); a filtered handle's pool is ranked unfiltered.
+ * kernel_ms / launch_shape report the MMR kernel after such a call: one user per workgroup at a time, and the workgroups
+ * (CMFREC_HIP_MMR_GROUPS caps them -- a test hook, read per call; the result does not depend on it).
+ * cmfrec_hip_topN_diverse_batch is create, one topN_diverse call, destroy. */
+int cmfrec_hip_ranker_rerank_mmr(cmfrec_hip_ranker *r, int_t nu, int_t pool, const int_t *pool_ids, const real_t *pool_scores,
+                                 double theta, int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr);
+int cmfrec_hip_ranker_topN_diverse(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                                   const size_t excl_p[], const int_t excl_i[], int_t pool, double theta, int_t n_top,
+                                   int_t *out_ids, real_t *out_scores, real_t *out_mmr);
+int cmfrec_hip_topN_diverse_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                                  const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t pool, double theta,
+                                  int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
 
 /* New rows against a model that stays on the device: factors and top-N of users who were not part of the fit, batch after
