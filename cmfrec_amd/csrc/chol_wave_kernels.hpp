@@ -148,6 +148,12 @@ __global__ void tile_pack_kernel(const T *__restrict__ M, int lim, int NB, T *__
 // WMODE 0: a row per work item.  WMODE 1 (producer): work items are slices, the kernel stops after the rank-k update and
 // stores the partials.  WMODE 2: rows whose rank-k update is the sum of their slices' partials.  (Separate builds: the
 // register allocation of the plain build must not pay for the other two.)
+// WMODE 3: the producer (WMODE 1) with the right-hand side of the implicit model's CG (gram_cg_wide_kernels.hpp): the reference's
+// first residual (factors_implicit_cg, common.c:1932-1943) weights the gathered row b_j by  x_j - (x_j + 1) (b_j . a)  for the row's
+// current a, where the closed form has  x_j + 1.  The row's a rides in NB registers per lane (unknown 16 b + lm, the border unknown
+// apart), the lane's share of b_j . a is NB FMAs on the operands it already holds, the 16 lanes of the entry's group add up by DPP
+// (lanes::row_sum16).  The tiles (ws = x_j) are those of WMODE 1; a is fixed during the gather, so the slices of a split row add
+// up as before.  In the sweep builds only the sweep that carries the right-hand side pays for it (it loads every block anyway).
 // EV: right-hand side and border column are forward-substituted on the vector ALU after the factorisation (their
 // per-group partial sums stay in registers, 2 NB values) instead of riding as the tile column E (NB more tiles).
 template <typename T, int NB, bool BORDER, int PD, int WPS, int NOV = 0, int WMODE = 0, bool EV = false>
@@ -157,12 +163,13 @@ chol_wave_kernel(const CholParams<T> P, const RowDesc *__restrict__ desc, const 
     using Mf = CholMfma<T>;
     using vec = typename Mf::vec;
     constexpr int NT = NB * (NB + 1) / 2;
-    constexpr int NRES = (WMODE == 1) ? NT : NT - NOV;   // tiles [0, NRES) are MFMA accumulators, [NRES, NT) overflow tiles
+    constexpr int NRES = (WMODE == 1 || WMODE == 3) ? NT : NT - NOV;   // tiles [0, NRES) are MFMA accumulators, [NRES, NT) overflow tiles
                                                          // (producer build: NOV = tiles per sweep instead)
     constexpr int LDR = Mf::LDR, RSZ = 16 * LDR;
     constexpr int NV = 16 * NB + 16;
     constexpr size_t PART = chol_wave_part_elems(NB);
-    constexpr bool PRODUCER = (WMODE == 1);
+    constexpr bool PRODUCER = (WMODE == 1 || WMODE == 3);
+    constexpr bool CGQ = (WMODE == 3);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lm = lane & 15, g = lane >> 4;
@@ -325,6 +332,13 @@ chol_wave_kernel(const CholParams<T> P, const RowDesc *__restrict__ desc, const 
             if (BORDER && !PRODUCER) { const T q = border_init(16 * b + lm_o); gp[b] = (g == 0 && u < kq) ? q : T(0); }
         }
         T gam = T(0), rbs = T(0);            // border diagonal and border right-hand side (partial over g, equal over lm)
+        // CG coefficients: the row's current a, unknown 16 b + lm per lane (zero beyond kq), the border unknown apart
+        T av[CGQ ? NB : 1], ab = T(0);
+        if constexpr (CGQ) {
+#pragma unroll
+            for (int b = 0; b < NB; b++) { const T q = arow[colb[b] + koff]; av[b] = ((vmask >> b) & 1u) ? q : T(0); }
+            if (BORDER) ab = arow[kt - 1];
+        }
         if (BORDER && !PRODUCER) {
             if (g == 0) {
                 gam = (add_lam ? lam_last : T(0));
@@ -405,6 +419,16 @@ chol_wave_kernel(const CholParams<T> P, const RowDesc *__restrict__ desc, const 
                             a[b] = o[b] * ws;
                         }
                         const T bv = bvb[s];
+                        if constexpr (VEC && CGQ) {
+                            // c_j = b_j . a on the 16 lanes of the entry's group;  x_j - (x_j + 1) c_j  in place of  x_j + 1
+                            // (common.c:1939; an entry beyond the row's end keeps its zero)
+                            T cp = T(0);
+#pragma unroll
+                            for (int b = 0; b < NB; b++) cp += o[b] * av[b];
+                            T cj = lanes::row_sum16(cp);
+                            if (BORDER) cj += bv * ab;
+                            xw = vld[s] ? x - xw * cj : T(0);
+                        }
                         // the next use of this buffer: step (it + 1) PD + s
                         if (it + 1 < niter) { issue_rows(s); load_entry(s, (it + 2) * PD + s); }
                         static_for<0, NB>([&](auto bic) {

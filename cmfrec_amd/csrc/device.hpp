@@ -117,6 +117,7 @@ struct SparseShard {
         int n;
         if (maxlen >= max_nnz) n = 0;
         else if (maxlen >= LONG_ROW) n = n_long;
+        else if (maxlen >= 512) n = n_gt512;
         else if (maxlen >= 256) n = bin_first[BIN_MED4];
         else if (maxlen >= 128) n = bin_first[BIN_MED2];
         else if (maxlen >= 96) n = n_gt96;

@@ -1,4 +1,5 @@
-// gram_cg_wide_kernels.hpp -- explicit-model CG row update for 64 < k_t <= 145 through the row's own Gramian (round 4).
+// gram_cg_wide_kernels.hpp -- CG row update for 64 < k_t <= 129 through the row's own Gramian: the explicit model (round 4) and
+// the implicit one.
 //
 // The register tiles of cg_kernels.hpp end at 64 unknowns; beyond that every row used to run on cg_rows_generic_kernel
 // (lane <-> unknown, one wave-wide reduction per gathered row and pass: config 3's shape under CG took 59 ms per iteration
@@ -14,9 +15,16 @@
 // and runs the reference's CG steps on it with the same absolute thresholds (1e-12 / 1e-8).  Same arithmetic as the reference
 // up to the order of the sums, as on the split rows of the k <= 64 path (gram_cg_kernels.hpp).
 //
-// The implicit model is not served here: its first residual weights the gathered rows by x + 1 and its products by x (quirk Q1,
-// common.c:1939 against :1965), i.e. it needs B_j . a per gathered row inside the producer, which the Cholesky producer does
-// not compute.
+// The implicit model (factors_implicit_cg, common.c:1932-1985; IMPLICIT build).  Its first residual weights the gathered rows by
+// x + 1 and its products by x (quirk Q1, :1939 against :1965).  With c_j = B_j . a for the row's current a:
+//     r0 = -BtB a - lam a + sum_j [ -(c_j - 1) x_j - c_j ] B_j  =  q - (BtB + lam I) a,     q = sum_j [ x_j - (x_j + 1) c_j ] B_j
+//     Ap = (BtB + lam I) p + sum_j x_j (B_j . p) B_j            =  (BtB + lam I + G) p,     G = sum_j x_j B_j B_j^T
+// G is what the producer builds for the implicit closed form (ws = x), q its right-hand side with another coefficient per entry:
+// the producer's WMODE 3 (chol_wave_kernels.hpp) computes c_j per gathered row and leaves q where the right-hand side goes; q is
+// linear over the slices of a split row, so the partials and their layout stay.  Here the shared BtB (CgParams::BtB, without
+// lambda, as cg_rows_generic_kernel takes it) joins the summed tiles in LDS, the first residual takes BtB a straight from BtB --
+// NOT from the matrix in LDS: G must not meet a, Q1 is carried by q alone -- and lambda stays outside the matrix, added to the
+// products as the reference does (:1943, :1969).  No scaling of lambda, no bias column, no side information.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,7 +51,7 @@ struct WideCgParams {
 template <typename T>
 __host__ __device__ constexpr size_t gcw_lds_elems(int kt) { return (size_t)kt * (size_t)(kt | 1) + (1 + GCW_NW) * 64 * (size_t)GCW_NF; }
 
-template <typename T>
+template <typename T, bool IMPLICIT = false>
 __global__ void __launch_bounds__(64 * GCW_NW)
 gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
 {
@@ -72,7 +80,7 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
                 if (P.scale_lam_sideinfo) mult += (T)P.p_side;
                 lam *= mult; lam_last *= mult;
             }
-        } else if (P.scale_lam) {                           // common.c:679-723
+        } else if (!IMPLICIT && P.scale_lam) {              // common.c:679-723
             const T mult = row_lam_mult(P, row, nnz);
             lam *= mult;
             if (!P.scale_bias_const) lam_last *= mult;
@@ -102,6 +110,8 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
                 if (j >= i && j < kq) {                     // diagonal tiles: the upper half only, mirrored
                     T s = accq[q];
                     if (has_u && j < kc) s += P.w_side * P.CtC[(size_t)i * kc + j];
+                    if constexpr (IMPLICIT) s += P.BtB[(size_t)i * kt + j];        // upper triangle, 16 consecutive j per lane row
+                    else
                     if (i == j) s += (i == kt - 1) ? lam_last : lam;
                     M[i * ldm + j] = s;
                     M[j * ldm + i] = s;
@@ -127,6 +137,7 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
                     T g = T(0);
                     for (int sl = s0; sl < s1; sl++) g += W.part[(size_t)(sl - W.part_base) * PART + (size_t)NT * 256 + 16 * NB + u];
                     if (has_u && kt - 1 < kc) g += P.w_side * P.CtC[(size_t)u * kc + (kt - 1)];
+                    if constexpr (IMPLICIT) g += P.BtB[(size_t)u * kt + (kt - 1)];
                     M[u * ldm + (kt - 1)] = g;
                     M[(kt - 1) * ldm + u] = g;
                 }
@@ -134,6 +145,8 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
                 T gam = T(0);
                 for (int sl = s0; sl < s1; sl++) gam += W.part[(size_t)(sl - W.part_base) * PART + (size_t)NT * 256 + 32 * NB];
                 if (has_u && kt - 1 < kc) gam += P.w_side * P.CtC[(size_t)(kt - 1) * kc + (kt - 1)];
+                if constexpr (IMPLICIT) M[(kt - 1) * ldm + (kt - 1)] = gam + P.BtB[(size_t)(kt - 1) * kt + (kt - 1)];
+                else
                 M[(kt - 1) * ldm + (kt - 1)] = gam + lam_last;
             }
         }
@@ -146,8 +159,8 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
             if (has_u && u < kc) v[c] += P.w_side * P.UC[(size_t)row * kc + u];       // + w (U C)_row
         }
         // (M x)[u] for the unknowns of this lane; x is the same on the four waves: every wave takes the columns j = wv (mod NW),
-        // the partial products meet in LDS and are summed in wave order
-        auto mul = [&](const T (&x)[GCW_NF], T (&y)[GCW_NF]) {
+        // the partial products meet in LDS and are summed in wave order.  at(u, j): element (u, j) of the matrix
+        auto mul_by = [&](auto at, const T (&x)[GCW_NF], T (&y)[GCW_NF]) {
             if (wv == 0) {
 #pragma unroll
                 for (int c = 0; c < GCW_NF; c++) xs[lane + 64 * c] = x[c];
@@ -161,7 +174,7 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
 #pragma unroll
                 for (int c = 0; c < GCW_NF; c++) {
                     const int u = lane + 64 * c;
-                    if (u < kt) part[c] += M[u * ldm + j] * xj;
+                    if (u < kt) part[c] += at(u, j) * xj;
                 }
             }
 #pragma unroll
@@ -176,6 +189,7 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
                 y[c] = (u < kt) ? sum : T(0);
             }
         };
+        auto mul = [&](const T (&x)[GCW_NF], T (&y)[GCW_NF]) { mul_by([&](int u, int j) { return M[u * ldm + j]; }, x, y); };
         auto dot = [&](const T (&x)[GCW_NF], const T (&y)[GCW_NF]) {
             T s = T(0);
 #pragma unroll
@@ -184,6 +198,12 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
         };
         __syncthreads();                                    // M is complete
         T Ma[GCW_NF];
+        if constexpr (IMPLICIT) {
+            // BtB a from the shared matrix itself (row j, 64 consecutive u per wave: symmetric), then - lam a   (common.c:1932-1943)
+            mul_by([&](int u, int j) { return P.BtB[(size_t)j * kt + u]; }, a, Ma);
+#pragma unroll
+            for (int c = 0; c < GCW_NF; c++) Ma[c] += lam * a[c];
+        } else
         mul(a, Ma);
 #pragma unroll
         for (int c = 0; c < GCW_NF; c++) { r[c] = (lane + 64 * c < kt) ? v[c] - Ma[c] : T(0); p[c] = r[c]; }   // common.c:1112-1139
@@ -193,6 +213,10 @@ gram_cg_wide_kernel(const CgParams<T> P, const WideCgParams<T> W)
             for (int step = 0; step < P.max_cg_steps; step++) {
                 T Ap[GCW_NF];
                 mul(p, Ap);
+                if constexpr (IMPLICIT) {
+#pragma unroll
+                    for (int c = 0; c < GCW_NF; c++) Ap[c] += lam * p[c];       // common.c:1969
+                }
                 const T alpha = cg_div(r_old, dot(Ap, p));
 #pragma unroll
                 for (int c = 0; c < GCW_NF; c++) { a[c] += alpha * p[c]; r[c] -= alpha * Ap[c]; }

@@ -167,6 +167,15 @@ template <typename T, typename Op> __device__ __forceinline__ T wave_fold(T v, O
     v = tswap32_op(v, v, op);
     return v;
 }
+// sum over the 16 lanes of a row, identical on the row's lanes: the four DPP levels of wave_fold, no permlane swap
+template <typename T> __device__ __forceinline__ T row_sum16(T v)
+{
+    v += xor1(v);
+    v += xor2(v);
+    v += qxor4(v);
+    v += xor8(v);
+    return v;
+}
 // full wave sum, identical on every lane
 // (tried in round 4: rows 1 / 3 adding lane 15 of the row below, rows 2 / 3 lane 31 -- the row_bcast controls -- and v_readlane 63:
 //  the compiler does not fold the masked move into the add, 801 -> 815 vector instructions in the fp32 tiny kernel; not kept)

@@ -33,8 +33,9 @@ void init_device(DeviceInfo &dev, int device);             // session.hip (open_
 // ---- CG row updates (launch_cg.hip) --------------------------------------------------------
 void poison_lds(hipStream_t st, int num_cus);              // test hook (CMFREC_HIP_POISON_LDS=1) in front of the row kernels' launches
 int launch_cg(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinTimers *tm = nullptr);
-int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X);
-int launch_cg_any(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinTimers *tm = nullptr);
+// (wide_rows, where given: the rows the launch solved on the Gramian CG beyond 64 unknowns, 0 when that route was not taken)
+int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, int *wide_rows = nullptr);
+int launch_cg_any(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinTimers *tm = nullptr, int *wide_rows = nullptr);
 #ifdef CMF_CG_TICKS
 unsigned long long *cg_ticks_buffer();
 #endif
@@ -84,6 +85,9 @@ struct CholCall {
     // CG on the row's Gramian instead of the factorisation (gram_cg_wide_kernels.hpp): the producer build of the wave kernel runs
     // every row's rank-k update, gram_cg_wide_kernel takes the partials; the parameters of the CG (explicit model)
     const CgParams<real_t> *cg_wide = nullptr;
+    // ... of the implicit model: the producer leaves the CG's right-hand side  sum_j [x_j - (x_j + 1) B_j . a] B_j  for the row's
+    // current a (chol_wave_kernel, WMODE 3) where the closed form's goes.  Only with cg_wide: no factorisation reads such partials.
+    bool cg_coef = false;
 
     // A [rows, lda]: the right-hand sides in, the solutions out; M [k, k] the matrix of every row, diagonal included
     static CholCall prefilled(real_t *A, size_t lda, int k, const real_t *M)
@@ -104,6 +108,15 @@ struct CholCall {
     {
         CholCall c = rows(CHOL_IMPLICIT, A, lda, B, ldb, k, pen);
         c.Minit = G;
+        return c;
+    }
+    // Implicit rows, producer only, CG coefficients: A [rows, lda] holds the rows' current factors (read by the producer, solved in
+    // place by the CG on the row's Gramian); cg carries the CG's parameters, BtB [k, k] without lambda among them.  No shared
+    // matrix and no penalty enter the partials.
+    static CholCall implicit_cg_rows(real_t *A, size_t lda, const real_t *B, size_t ldb, int k, const CgParams<real_t> *cg)
+    {
+        CholCall c = rows(CHOL_IMPLICIT, A, lda, B, ldb, k, RowPenalty{0, 0});
+        c.cg_wide = cg; c.cg_coef = true;
         return c;
     }
     // Block systems of kt unknowns, the X block behind the first koff.  The dense side block (Minit [kc, kc] or null, kc,

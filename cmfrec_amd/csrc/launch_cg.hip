@@ -555,14 +555,26 @@ int launch_cg(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinT
     return 2;
 }
 
-// CG of the explicit model beyond 64 unknowns (k_t <= 129): through the row's Gramian (gram_cg_wide_kernels.hpp) instead of the
-// lane <-> unknown kernel.  -1: not applicable (the caller takes launch_cg).  CMFREC_HIP_CG_KERNEL=generic keeps the generic kernel
-// (A/B switch and on-device cross-check).
-int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X)
+// CMFREC_HIP_CG_WIDE_MIN (test and measurement hook, read per call): rows with MORE entries than this take the Gramian route of
+// launch_cg_wide, both models.  A row-length boundary of the processing order: 128, 256 (default), 512 or 1024; other values
+// take the next boundary below (SparseShard::rows_longer_than).
+static int cg_wide_min()
 {
+    const char *e = getenv("CMFREC_HIP_CG_WIDE_MIN");
+    const int v = (e != nullptr) ? atoi(e) : 0;
+    return v >= 128 ? v : 256;
+}
+
+// CG beyond 64 unknowns (k_t <= 129): through the row's Gramian (gram_cg_wide_kernels.hpp) instead of the lane <-> unknown kernel --
+// the explicit model, and the implicit one without side information (its first residual's coefficients come from the producer,
+// CholCall::implicit_cg_rows).  -1: not applicable (the caller takes launch_cg).  CMFREC_HIP_CG_KERNEL=generic keeps the generic
+// kernel (A/B switch and on-device cross-check).
+int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, int *wide_rows)
+{
+    if (wide_rows) *wide_rows = 0;
     const bool border = (c.k > 16) && ((c.k - 1) % 16 == 0);
     const int nbw = (c.k - (border ? 1 : 0) + 15) / 16;
-    if (c.implicit || c.k <= 64 || nbw > 8 || c.precond || c.X2 != nullptr || c.Bi != nullptr || c.koff != 0 || X.weighted() ||
+    if ((c.implicit && (c.BtB == nullptr || c.kc != 0)) || c.k <= 64 || nbw > 8 || c.precond || c.X2 != nullptr || c.Bi != nullptr || c.koff != 0 || X.weighted() ||
         dev.nonneg_now || dev.l1_now != (real_t)0 || dev.l1_last_now != (real_t)0 ||      // (launch_chol's wave path is off then)
         cg_variant_from_env() == CgVariant::Generic || switches().chol == 1 ||
         (c.kc > 0 && (c.CtC == nullptr || c.UC == nullptr || c.kc > c.k)) || gcw_lds_elems<real_t>(c.k) * sizeof(real_t) > (size_t)160 * 1024)
@@ -570,7 +582,7 @@ int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X)
     CgParams<real_t> P;
     P.A = c.A; P.lda = c.lda; P.B = c.B; P.ldb = c.ldb; P.k = c.k;
     P.indptr = X.p.ptr; P.indices = X.i.ptr; P.values = X.v.ptr;
-    P.bias_sub = c.bias_sub; P.order = X.order.ptr; P.desc = X.desc.ptr; P.nrows = 0; P.BtB = nullptr;
+    P.bias_sub = c.bias_sub; P.order = X.order.ptr; P.desc = X.desc.ptr; P.nrows = 0; P.BtB = c.implicit ? c.BtB : nullptr;
     P.lam = c.lam; P.lam_last = c.lam_last;
     P.scale_lam = c.scale_lam; P.scale_bias_const = c.scale_bias_const;
     P.max_cg_steps = c.max_cg_steps; P.precond = 0;
@@ -580,21 +592,25 @@ int launch_cg_wide(const DeviceInfo &dev, const CgCall &c, const SparseShard &X)
     // generic kernel's wave-wide reduction per gathered row: it pays on the long rows (config 3's items under CG: 18.1 -> 6.8 ms)
     // and loses on the short ones (its users, 143 entries per row on average: 8.6 -> 15.8 ms).  So the rows beyond 256 entries --
     // they lead the processing order -- take it, the others stay on the lane <-> unknown kernel (CgCall::skip_first).
-    const int n_wide = X.rows_longer_than(256, X.n_nonempty);
+    // (The implicit model keeps the same boundary: at the benchmark's shape, k = 100 / 128, the iteration is 0.70-0.72 of the generic
+    //  kernel's there and the route still gains at 128, the lowest boundary measured -- DESIGN.md 3.2, profiles/implicit_cg_wide.)
+    const int n_wide = X.rows_longer_than(cg_wide_min(), X.n_nonempty);
     if (n_wide <= 0) return -1;
-    CholCall cc = CholCall::explicit_rows(c.A, c.lda, c.B, c.ldb, c.k, c.bias_sub, RowPenalty{c.lam, c.lam_last});
+    CholCall cc = c.implicit ? CholCall::implicit_cg_rows(c.A, c.lda, c.B, c.ldb, c.k, &P)
+                             : CholCall::explicit_rows(c.A, c.lda, c.B, c.ldb, c.k, c.bias_sub, RowPenalty{c.lam, c.lam_last});
     cc.scale_lam = c.scale_lam; cc.scale_lam_sideinfo = c.scale_lam_sideinfo; cc.scale_bias_const = c.scale_bias_const;
     cc.cg_wide = &P;
     cc.row_limit = n_wide;
     int rc = launch_chol(dev, cc, &X);                    // positions [0, n_wide)
     if (rc) return rc;
+    if (wide_rows) *wide_rows = n_wide;
     CgCall rest = c;
     rest.skip_first = n_wide;
     return launch_cg(dev, rest, X, nullptr);              // the shorter rows, and a block system's rows without entries
 }
-int launch_cg_any(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinTimers *tm)
+int launch_cg_any(const DeviceInfo &dev, const CgCall &c, const SparseShard &X, BinTimers *tm, int *wide_rows)
 {
-    const int rc = launch_cg_wide(dev, c, X);
+    const int rc = launch_cg_wide(dev, c, X, wide_rows);
     return rc >= 0 ? rc : launch_cg(dev, c, X, tm);
 }
 

@@ -137,6 +137,12 @@ int launch_chol(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, 
                              (c.mode == CHOL_EXPLICIT || c.mode == CHOL_IMPLICIT || c.mode == CHOL_COLLECTIVE ||
                               c.mode == CHOL_COLLECTIVE_IMPLICIT) &&
                              chol_sw != 1;
+        if (c.cg_coef && (!wave_ok || c.cg_wide == nullptr || c.mode != CHOL_IMPLICIT || c.koff != 0 || nbw < 4)) {
+            // partials with the implicit CG's coefficients are no closed form's input: only gram_cg_wide_kernel may take them
+            g_last_error = "cmfrec_hip: internal: the CG coefficients of the implicit model exist only in the wave-per-row producer in front of "
+                           "the Gramian CG (64 < k_t <= 129, no offset; weights, nonneg, L1 or CMFREC_HIP_CHOL=rows keep it off)";
+            return 2;
+        }
         if (wave_ok) {
             // rows beyond 1024 entries: sliced (their slice tables are the ones of the split-row CG path, SparseShard::sl_*);
             // CMFREC_HIP_CHOL=noslices leaves them to the workgroup-per-row kernel (A/B switch)
@@ -161,6 +167,21 @@ int launch_chol(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, 
 #define WAVE_KERN_M(nb_, pd, wps, nov, wm) (border ? chol_wave_kernel<real_t, nb_, true, pd, wps, nov, wm, false> : chol_wave_kernel<real_t, nb_, false, pd, wps, nov, wm, false>)
 #define WAVE_KERN(nb_, pd, wps, nov) \
     (wmode == 1 ? WAVE_KERN_M(nb_, pd, wps, nov, 1) : wmode == 2 ? WAVE_KERN_M(nb_, pd, wps, nov, 2) : WAVE_KERN_M(nb_, pd, wps, nov, 0))
+                // the implicit model's CG (CholCall::implicit_cg_rows, 64 < k_t <= 129): the producer builds with the CG's coefficients
+                // (WMODE 3), each with the gather depth and occupancy of its closed-form twin
+                if (wmode == 1 && c.cg_coef) {
+#ifdef CMFREC_HIP_FLOAT
+                    if (nbw <= 4) wlaunch(WAVE_KERN_M(4, 4, 2, 0, 3), 4, 2);
+                    else if (nbw <= 6) wlaunch(WAVE_KERN_M(6, 3, 2, 0, 3), 6, 2);
+                    else wlaunch(WAVE_KERN_M(8, 2, 1, 0, 3), 8, 1);
+#else
+                    // (8 blocks: the one-wavefront producer in two sweeps also where the closed form takes the two-wavefront parts kernels)
+                    if (nbw <= 4) wlaunch(WAVE_KERN_M(4, 3, 2, 0, 3), 4, 2);
+                    else if (nbw <= 6) wlaunch(WAVE_KERN_M(6, 2, 1, 0, 3), 6, 1);
+                    // (with the border column three gather steps in flight spill 24 registers: two there)
+                    else wlaunch((border ? chol_wave_kernel<real_t, 8, true, 2, 1, 32, 3, false> : chol_wave_kernel<real_t, 8, false, 3, 1, 32, 3, false>), 8, 1);
+#endif
+                } else
 #ifdef CMFREC_HIP_FLOAT
                 if (nbw <= 2) wlaunch(WAVE_KERN(2, 4, 4, 0), 2, 4);
                 else if (nbw <= 4) wlaunch(WAVE_KERN(4, 4, 2, 0), 4, 2);
@@ -258,7 +279,7 @@ int launch_chol(const DeviceInfo &dev, const CholCall &c, const SparseShard *X, 
                         Wp.row_off = X->row_sl_off.ptr; Wp.n_heavy = n_heavy; Wp.n_slices = SL.n_slices;
                         Wp.row_first = row0; Wp.row_last = row1;
                         const size_t smem = gcw_lds_elems<real_t>(c.kt) * sizeof(real_t);
-                        auto kern = gram_cg_wide_kernel<real_t>;
+                        auto kern = c.cg_coef ? gram_cg_wide_kernel<real_t, true> : gram_cg_wide_kernel<real_t, false>;
                         HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
                         const int per_cu = std::max(1, (int)((size_t)160 * 1024 / smem));
                         poison_lds(dev.stream, dev.num_cus);

@@ -132,7 +132,8 @@ struct cmfrec_hip_session {
     // low-rank row updates (lowrank_kernels.hpp): eigenvectors / values of w C^T C, rotated C and opposing factors,
     // rotated right-hand sides and solutions
     LowRankScratch lr;
-    EigCache eigA, eigB;          // eigenvectors of w_user C^T C (A-steps) / w_item D^T D (B-steps), see EigCache
+    long cg_wide_rows[2] = {0, 0};  // rows the most recent A-step / B-step solved on the Gramian CG beyond 64 unknowns (launch_cg_wide)
+    EigCache eigA, eigB;         // eigenvectors of w_user C^T C (A-steps) / w_item D^T D (B-steps), see EigCache
     // row-block shards of the explicit / collective model (distributed.py): U / I hold only the rows of this
     // rank's block, and the C / D update is split into partial sums over the local rows (side_part: [kc x kc | p x kc]),
     // an all-reduce by the caller, and the identical small solve on every rank
@@ -1510,6 +1511,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
 {
     // "self" = matrix being updated, "opp" = the fixed one
     const HalfStepSide v(s, isA);
+    if (part <= 0) s->cg_wide_rows[isA ? 0 : 1] = 0;          // (the parts of a block add up)
     if (s->naz_X && !s->mdl.implicit && s->Xr.weighted()) return update_factor_naz_weighted(s, v, chol);
     if (s->naz_X && !s->mdl.implicit) return update_factor_naz(s, v, chol);
     const cmfrec_hip_model &m = s->mdl;
@@ -1532,6 +1534,13 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
     const int rows_x_self = v.rows_x_self;                    // rows of this matrix X has
     const real_t w = v.w;
     const bool scale_lam = m.scale_lam || m.scale_lam_sideinfo;                                     // :7465
+    // a CG launch of this half-step; the rows it solved on the Gramian CG are kept for cmfrec_hip_session_cg_wide_rows
+    auto cg_any = [&](const CgCall &c, BinTimers *tm) {
+        int wide = 0;
+        const int rc = launch_cg_any(dev, c, X, tm, &wide);
+        s->cg_wide_rows[isA ? 0 : 1] += wide;
+        return rc;
+    };
 
     // the X block of a block-CG system: the implicit model's Gramian, or the explicit model's fixed bias column and fused "X - bias"
     auto block_cg_call = [&](bool scale_bias_const) {
@@ -1570,7 +1579,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
             c.rows_with_u = rows_u;
             c.set_second_source(v.Us, v.Cm, kc, w);
             add_implicit_term_cg(c);
-            return launch_cg_any(dev, c, X, nullptr);
+            return cg_any(c, nullptr);
         }
         if (m.implicit) {
             if (X.nrows) HIP_CHECK(hipMemsetAsync(self_blk, 0, (size_t)X.nrows * ld_self * sizeof(real_t), st));   // :6018-6019
@@ -1598,7 +1607,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
         const int local_u_main = m.implicit ? local_u : std::min(local_u, local_x);
         c.CtC = s->ctc.ptr; c.UC = v.uc; c.rows_with_u = local_u_main;
         add_implicit_term_cg(c);
-        int rc = launch_cg_any(dev, c, X, nullptr);
+        int rc = cg_any(c, nullptr);
         if (rc) return rc;
         return solve_sideinfo_only_rows(s, v, false, local_u_main, local_u - local_u_main);
     }
@@ -1625,7 +1634,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
         }
         CgCall c = CgCall::implicit_rows(self_blk + k_side_self, ld_self, oppx, ld_opp, kk, s->gram.ptr, pen, m.max_cg_steps);
         c.precond = (bool)m.precondition_cg;
-        return launch_cg_any(dev, c, X, v.bins);
+        return cg_any(c, v.bins);
     }
 
     // ---- explicit ----
@@ -1720,7 +1729,7 @@ static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = 
     // block CG with the implicit-features term (collective_block_cg without side information on this side,
     // collective.c:2624-2643, :2862-2868): generic kernel; rows without entries are zeroed (:1258-1268)
     add_implicit_term_cg(c);
-    return launch_cg_any(dev, c, X, v.bins);
+    return cg_any(c, v.bins);
 }
 
 // Ai / Bi update: optimizeA Case 3 on the binary indicator of X (collective.c:8448-8534; common.c:3116-3205): one
@@ -2270,6 +2279,14 @@ int cmfrec_hip_session_lowrank_info(cmfrec_hip_session *s, int *rows, int *eig)
 {
     if (rows) *rows = s->lr.last_rows;
     if (eig) *eig = s->lr.last_eig;
+    return 0;
+}
+
+// rows the most recent A-step (which = 0) / B-step (1) solved on the Gramian CG beyond 64 unknowns; 0: the route was not taken
+int cmfrec_hip_session_cg_wide_rows(cmfrec_hip_session *s, int which, long *rows)
+{
+    if (s == nullptr || rows == nullptr || (which != 0 && which != 1)) return 1;
+    *rows = s->cg_wide_rows[which];
     return 0;
 }
 

@@ -339,6 +339,13 @@ class AlsSession:
         self.lib.cmfrec_hip_session_lowrank_info(self.handle, C.byref(rows), C.byref(eig))
         return int(rows.value), int(eig.value)
 
+    def cg_wide_rows(self, which):
+        """Rows that the most recent A-step (``which`` = 0) / B-step (1) solved by the CG on the row's own Gramian beyond 64
+        unknowns (gram_cg_wide_kernels.hpp); 0 when that route was not taken."""
+        rows = C.c_long(0)
+        _lib.check(self.lib.cmfrec_hip_session_cg_wide_rows(self.handle, C.c_int(int(which)), C.byref(rows)), self.lib, "cg_wide_rows")
+        return int(rows.value)
+
     def vh_mode(self, which):
         """0: no split rows on that side; 1: streamed per CG pass; 2: single gather + CG on the row's Gramian."""
         return int(self.lib.cmfrec_hip_session_vh_mode(self.handle, C.c_int(ord(which))))

@@ -580,6 +580,10 @@ int cmfrec_hip_session_vh_min(cmfrec_hip_session *s, int which);
 /* the most recent collective Cholesky half-step: rows solved by the low-rank kernels (0: path not taken) and the
    eigen-decomposition behind them (3 tridiagonalisation + implicit QL, 2 the one-workgroup Jacobi kernel; CMFREC_HIP_EIG=jacobi forces 2) */
 int cmfrec_hip_session_lowrank_info(cmfrec_hip_session *s, int *rows, int *eig);
+/* rows that the most recent A-step (which = 0) or B-step (which = 1) solved by the CG on the row's own Gramian beyond 64
+   unknowns (rows of more than 256 entries of a CG fit with 64 < k_t <= 129: the explicit model, and the implicit one without
+   side information); 0 when that route was not taken.  Host bookkeeping, no device work.  Returns 1 on a bad argument. */
+int cmfrec_hip_session_cg_wide_rows(cmfrec_hip_session *s, int which, long *rows);
 void cmfrec_hip_session_reset_timers(cmfrec_hip_session *s);
 
 /* Batched top-N (the step after the path; the reference ranks one user per call: topN, src/common.c:5127-5380).
