@@ -123,6 +123,13 @@ class FitObjective(C.Structure):
                 ("iters_run", C.POINTER(C.c_int))]
 
 
+class ExplainArgs(C.Structure):
+    """``cmfrec_hip_explain_args`` (include/cmfrec_hip.h): the same layout in both precisions."""
+    _fields_ = [("nu", C.c_int32), ("n_top", C.c_int32), ("bias", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("hist_p", "hist_i", "hist_g", "hist_y", "targ_p", "targ_i", "G0", "diag_u", "diag_bias_u")] + \
+        [("diag", C.c_double), ("diag_bias", C.c_double)] + [(n, C.c_void_p) for n in ("out_total", "out_ids", "out_contrib")]
+
+
 class EarlyStop(C.Structure):
     """``cmfrec_hip_early_stop``: the state of ``cmfrec_hip_early_stop_step``."""
     _fields_ = [("every", C.c_int), ("patience", C.c_int), ("higher_is_better", C.c_int), ("min_delta", C.c_double),
@@ -148,6 +155,7 @@ EXPORTED = [
     "cmfrec_hip_ranker_set_split", "cmfrec_hip_ranker_slices", "cmfrec_hip_topn_split_plan", "cmfrec_hip_newrows_set_split",
     "cmfrec_hip_ranker_set_filter", "cmfrec_hip_ranker_filter_stats", "cmfrec_hip_ranker_filter_ms", "cmfrec_hip_ranker_filter_keys",
     "cmfrec_hip_ranker_rerank_mmr", "cmfrec_hip_ranker_topN_diverse", "cmfrec_hip_topN_diverse_batch",
+    "cmfrec_hip_ranker_explain", "cmfrec_hip_explain_batch",
     "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
     "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
     "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
@@ -228,6 +236,8 @@ def load(dtype=np.float64):
                                                    C.c_int] + [C.c_void_p] * 3
     lib.cmfrec_hip_topN_diverse_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
         [C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 3
+    lib.cmfrec_hip_ranker_explain.argtypes = [C.c_void_p, C.POINTER(ExplainArgs)]
+    lib.cmfrec_hip_explain_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(ExplainArgs)]
     nrm = newrows_model_mirror(dtype)
     lib.cmfrec_hip_newrows_create.restype = C.c_void_p
     lib.cmfrec_hip_newrows_create.argtypes = [C.POINTER(nrm), C.c_int]

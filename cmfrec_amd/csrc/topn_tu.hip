@@ -17,6 +17,8 @@
 // would run unfiltered -- and topn_filter_certify_kernel; the users that are not certified take the route above in a second batch.
 // A diversified call (cmfrec_hip_ranker_rerank_mmr / _topN_diverse) launches topn_mmr_kernel (topn_mmr_kernels.hpp, from
 // topn_mmr_tu.hip) over per-user pools that are on the device: the caller's, or the lists the full ranking above left there.
+// An explanation call (cmfrec_hip_ranker_explain) launches topn_explain_kernel (topn_explain_kernels.hpp, from topn_explain_tu.hip)
+// over per-user histories and target lists; it reads the resident rows and none of the handle's split or filter settings.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,6 +34,7 @@
 #include "topn_rank_kernels.hpp"
 #include "topn_filter.hpp"
 #include "topn_mmr_kernels.hpp"
+#include "topn_explain_kernels.hpp"
 #include "rank_metrics_kernels.hpp"
 
 using namespace cmfhip;
@@ -74,6 +77,9 @@ struct cmfrec_hip_ranker {
     float f_ms[3] = {0, 0, 0};
     DevBuf<int> mmr_ids;                     // the result of a diversified call: [nu][n_top] (its pools use ids / sc)
     DevBuf<real_t> mmr_sc, mmr_v;
+    DevBuf<size_t> x_hp, x_tp;               // an explanation call: histories and targets (CSR over the users) ...
+    DevBuf<int> x_hi, x_ti;
+    DevBuf<real_t> x_g, x_y, x_g0, x_du, x_dbu, x_tot;   // ... their coefficients, G0, the per-user diagonals, the totals (lists: ids / sc)
     const real_t *item_bias() const { return has_bias ? bias.ptr : nullptr; }
     ~cmfrec_hip_ranker()
     {
@@ -90,6 +96,7 @@ namespace {
 constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
 constexpr const char *RANK_LIMITS = "needs k <= 272";
 constexpr const char *DEEP_LIMITS = "needs k <= 272 and 1 <= n_top <= n";
+constexpr const char *EXPLAIN_LIMITS = "needs k + bias <= 128 and 1 <= n_top <= 64";
 constexpr const char *MMR_LIMITS = "needs k <= 272, 1 <= n_top <= pool <= min(128, n) and 0 <= theta <= 1";
 
 // User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
@@ -597,6 +604,82 @@ int mmr_device(cmfrec_hip_ranker *r, int_t nu, int_t pool, double theta, int_t n
     r->mmr_sc.download(out_scores, cells, dev.stream);
     if (out_mmr) r->mmr_v.download(out_mmr, cells, dev.stream);
     HIP_CHECK(hipStreamSynchronize(dev.stream));
+    return 0;
+}
+
+// what an explanation call refuses, before a device is touched: 0, or 2 with the message set
+int check_explain(const char *fn, int_t n, int_t k, const cmfrec_hip_explain_args *a)
+{
+    if (a == nullptr || a->nu <= 0 || !a->hist_p || !a->targ_p) return refuse(fn, std::string("invalid arguments; ") + EXPLAIN_LIMITS);
+    const int_t nu = a->nu;
+    if (k + (a->bias ? 1 : 0) > TOPNX_KMAX || a->n_top < 1 || a->n_top > TOPNX_NTOP_MAX) return refuse(fn, EXPLAIN_LIMITS);
+    if (a->G0 != nullptr && a->bias) return refuse(fn, "G0 together with a bias unknown is not supported");
+    size_t longest = 0;
+    if (!csr_ok(a->hist_p, a->hist_i, nu, &longest) || longest > (size_t)0x7fffff00)
+        return refuse(fn, "invalid arguments (hist_p is not a CSR over the users: offsets that do not decrease)");
+    if (!csr_ok(a->targ_p, a->targ_i, nu)) return refuse(fn, "invalid arguments (targ_p is not a CSR over the users: offsets that do not decrease)");
+    if (a->hist_p[nu] > a->hist_p[0] && (!a->hist_g || !a->hist_y)) return refuse(fn, "invalid arguments (hist_g and hist_y are required)");
+    if (a->targ_p[nu] > a->targ_p[0] && (!a->out_total || !a->out_ids || !a->out_contrib)) return refuse(fn, "invalid arguments (the outputs are required)");
+    if (!(a->diag > 0.0) || (a->bias && a->diag_bias_u == nullptr && !(a->diag_bias > 0.0))) return refuse(fn, "diag (and diag_bias with a bias) must be > 0");
+    if (a->diag_u != nullptr)
+        for (int_t u = 0; u < nu; u++)
+            if (!(a->diag_u[u] > (real_t)0)) return refuse(fn, "diag_u[" + std::to_string(u) + "] must be > 0");
+    if (a->bias && a->diag_bias_u != nullptr)
+        for (int_t u = 0; u < nu; u++)
+            if (!(a->diag_bias_u[u] > (real_t)0)) return refuse(fn, "diag_bias_u[" + std::to_string(u) + "] must be > 0");
+    for (size_t e = a->hist_p[0]; e < a->hist_p[nu]; e++)
+        if (a->hist_i[e] < 0 || a->hist_i[e] >= n)
+            return refuse(fn, "history id " + std::to_string(a->hist_i[e]) + " (entry " + std::to_string(e) + ") is not a row of the ranker's " + std::to_string(n));
+    for (size_t e = a->targ_p[0]; e < a->targ_p[nu]; e++)
+        if (a->targ_i[e] < 0 || a->targ_i[e] >= n)
+            return refuse(fn, "target id " + std::to_string(a->targ_i[e]) + " (entry " + std::to_string(e) + ") is not a row of the ranker's " + std::to_string(n));
+    return 0;
+}
+
+// The explanation pass: uploads, the launch, the timing events and the download.  CMFREC_HIP_EXPLAIN_GROUPS (test hook, read per
+// call) caps the workgroups, so that a small batch gives one of them many users.  (the caller holds the DeviceScope and has
+// checked the arguments)
+int explain_device(cmfrec_hip_ranker *r, const cmfrec_hip_explain_args *a)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    hipStream_t st = dev.stream;
+    const int_t nu = a->nu;
+    const size_t nh = a->hist_p[nu], nt = a->targ_p[nu], t_first = a->targ_p[0], cells = nt * (size_t)a->n_top;
+    if (nt == t_first) return 0;                                         // no targets: nothing is written
+    upload_csr(r->x_hp, r->x_hi, a->hist_p, a->hist_i, nu, st);
+    upload_csr(r->x_tp, r->x_ti, a->targ_p, a->targ_i, nu, st);
+    r->x_g.alloc_at_least(std::max<size_t>(nh, 1));
+    r->x_y.alloc_at_least(std::max<size_t>(nh, 1));
+    if (nh > 0) { r->x_g.upload(a->hist_g, nh, st); r->x_y.upload(a->hist_y, nh, st); }
+    if (a->G0) r->x_g0.upload(a->G0, (size_t)r->k * r->k, st);
+    if (a->diag_u) r->x_du.upload(a->diag_u, (size_t)nu, st);
+    const bool bias_u = a->bias && a->diag_bias_u != nullptr;
+    if (bias_u) r->x_dbu.upload(a->diag_bias_u, (size_t)nu, st);
+    r->x_tot.alloc_at_least(nt);
+    r->ids.alloc_at_least(cells);
+    r->sc.alloc_at_least(cells);
+    TopnExplainParams<real_t> P;
+    set_items(P, r);
+    P.nu = nu; P.bias = a->bias ? 1 : 0; P.n_top = a->n_top;
+    P.sr = topnx_slab_rows(r->k + P.bias, a->n_top, sizeof(real_t));
+    P.hist_p = r->x_hp.ptr; P.hist_i = r->x_hi.ptr; P.hist_g = r->x_g.ptr; P.hist_y = r->x_y.ptr;
+    P.targ_p = r->x_tp.ptr; P.targ_i = r->x_ti.ptr;
+    P.G0 = a->G0 ? r->x_g0.ptr : nullptr;
+    P.diag = (real_t)a->diag; P.diag_bias = (real_t)a->diag_bias; P.diag_u = a->diag_u ? r->x_du.ptr : nullptr;
+    P.diag_bias_u = bias_u ? r->x_dbu.ptr : nullptr;
+    P.out_total = r->x_tot.ptr; P.out_ids = r->ids.ptr; P.out_contrib = r->sc.ptr;
+    const char *cap = getenv("CMFREC_HIP_EXPLAIN_GROUPS");
+    const int max_groups = (cap != nullptr && cap[0] != 0) ? atoi(cap) : 0;
+    poison_lds(st, dev.num_cus);                                         // (every LDS word the kernel reads it has written)
+    HIP_CHECK(hipEventRecord(r->ev0, st));
+    const int grid = topn_explain_launch(st, dev.num_cus, P, max_groups);
+    end_timed(r, 1, grid, 1);
+    // (the targets of users [0, nu) are entries [targ_p[0], targ_p[nu]) of the outputs, as they are of targ_i)
+    HIP_CHECK(hipMemcpyAsync(a->out_total + t_first, r->x_tot.ptr + t_first, (nt - t_first) * sizeof(real_t), hipMemcpyDeviceToHost, st));
+    const size_t c0 = t_first * (size_t)a->n_top;
+    HIP_CHECK(hipMemcpyAsync(a->out_ids + c0, r->ids.ptr + c0, (cells - c0) * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(a->out_contrib + c0, r->sc.ptr + c0, (cells - c0) * sizeof(real_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -1169,6 +1252,18 @@ int cmfrec_hip_ranker_topN_diverse(cmfrec_hip_ranker *r, const real_t *A, size_t
     });
 }
 
+int cmfrec_hip_ranker_explain(cmfrec_hip_ranker *r, const cmfrec_hip_explain_args *args)
+{
+    const char *fn = "cmfrec_hip_ranker_explain";
+    return guarded([&]() {
+        if (r == nullptr) return refuse(fn, std::string("invalid arguments; ") + EXPLAIN_LIMITS);
+        if (int rc = check_explain(fn, r->n, r->k, args)) return rc;
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        return explain_device(r, args);
+    });
+}
+
 int cmfrec_hip_ranker_inverse_norms(cmfrec_hip_ranker *r, real_t *out)
 {
     return guarded([&]() {
@@ -1283,6 +1378,14 @@ int cmfrec_hip_topN_diverse_batch(const real_t *A, size_t lda, int_t nu, const r
     return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
         return cmfrec_hip_ranker_topN_diverse(r, A, lda, nu, excl_p, excl_i, pool, theta, n_top, out_ids, out_scores, out_mmr);
     });
+}
+
+int cmfrec_hip_explain_batch(const real_t *B, size_t ldb, int_t n, int_t k, const cmfrec_hip_explain_args *args)
+{
+    const char *fn = "cmfrec_hip_explain_batch";
+    if (n <= 0 || k <= 0 || !B) return refuse(fn, std::string("invalid arguments; ") + EXPLAIN_LIMITS);
+    if (int rc = check_explain(fn, n, k, args)) return rc;
+    return with_ranker(B, ldb, n, k, nullptr, [&](cmfrec_hip_ranker *r) { return cmfrec_hip_ranker_explain(r, args); });
 }
 
 int cmfrec_hip_topN_candidates_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,

@@ -454,6 +454,51 @@ def _penalty(value, name):
     return 0.0, arr
 
 
+_EXPLAIN_DOC = """Why these items: for every user of ``X`` (the users' own interactions, a SciPy sparse matrix or a (row, col, val)
+        triplet as ``factors_multiple`` takes them) and every item of ``items`` [users, targets] -- for instance the rows ``topN_batch``
+        returned -- the score the user's closed-form factors give the item, split without remainder into one term per item of
+        the user's history, on the device (``Ranker.explain``).  Returns a dict: ``score`` [users, targets], ``ids`` [users,
+        targets, n] the history items of the largest terms (-1 behind a short history) and ``contributions`` [users, targets, n]
+        (-inf there); every user's terms sum to its score (less the global mean and the item bias of the explicit model).
+        Refused with ValueError, because the split is not linear or not this one: side information, k_user / k_item, implicit
+        features, nonneg, an L1 penalty, NA_as_zero, a dense X, per-matrix lambdas, and scale_lam without a user bias."""
+
+
+def _explain_refusals(self, X):
+    what = type(self).__name__ + ".explain: "
+    if isinstance(X, np.ndarray):
+        raise ValueError(what + "a dense 'X' is not supported (pass the users' interactions as a sparse matrix or a triplet)")
+    if self.C_.shape[0] or self.D_.shape[0]:
+        raise ValueError(what + "a model with side information has no such decomposition")
+    if self.k_user or self.k_item:
+        raise ValueError(what + "k_user / k_item are not supported")
+    if getattr(self, "add_implicit_features", False):
+        raise ValueError(what + "implicit features are not supported")
+    if self.nonneg:
+        raise ValueError(what + "a non-negative model's factors are not linear in the history")
+    if self.l1_lambda or self._l16 is not None:
+        raise ValueError(what + "an L1 penalty makes the factors non-linear in the history")
+    if self._lam6 is not None:
+        raise ValueError(what + "per-matrix lambdas are not supported")
+    if getattr(self, "NA_as_zero", False) or self.NA_as_zero_user or self.NA_as_zero_item:
+        raise ValueError(what + "NA_as_zero models are not supported")
+
+
+def _explain_history(self, X, items, W):
+    """(indptr, item ids, values, weights or None, targets [users, t]) of an explanation call: X's entries by user, in X's order."""
+    row, col, val, m_x = _new_rows(X, self.B_.shape[0], self.dtype_)
+    Wv = _new_rows_weights(X, W, row, col, self.dtype_)
+    items = np.asarray(items)
+    if items.ndim != 2 or not np.issubdtype(items.dtype, np.integer):
+        raise ValueError("explain: 'items' must be an integer array [users, targets]")
+    nu = items.shape[0]
+    if m_x > nu:
+        raise ValueError("explain: 'X' has %d rows, 'items' %d" % (m_x, nu))
+    order = np.argsort(row, kind="stable")
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=nu))]).astype(np.uint64)
+    return indptr, col[order], val[order], None if Wv is None else Wv[order], items
+
+
 class CMF_implicit(_Base):
     """Implicit-feedback model (iALS / WRMF), reference class ``CMF_implicit``."""
 
@@ -585,6 +630,27 @@ class CMF_implicit(_Base):
             _lib.ptr(self._BeTBeChol) if has(self._BeTBeChol) else None, None, C.c_int(self.nthreads))
         _lib.check(rc, lib, "factors_collective_implicit_multiple")
         return A
+
+    def explain(self, X, items, n=10):
+        from . import ops
+        _explain_refusals(self, X)
+        indptr, col, val, _, items = _explain_history(self, X, items, None)
+        dt = np.dtype(self.dtype_)
+        # the transform of factors_multiple: log, then alpha; the confidence is that + 1 (fit.hip, new-rows intake)
+        x = np.log(val) if self.apply_log_transf else val
+        g = np.ascontiguousarray(x * dt.type(self.alpha), dt)
+        B = np.ascontiguousarray(self.B_, dt)
+        kk = B.shape[1]
+        G0 = ops.dense_op("gram", 0, B.shape[0], kk, np.zeros(kk * kk, dt), kk, B_img=B.ravel(), ldb=kk).reshape(kk, kk)   # B'B on the device
+        # the lambda beside B'B, as factors_multiple meets it: the matrix the fit precomputed carries lambda / (w_main x its
+        # multiplier) (precompute_collective_implicit); without that matrix the new-rows code adds the plain lambda
+        lam = self.lambda_
+        if self._BtB is not None and self._BtB.shape[0] > 0:
+            lam = lam / (self.w_main * self._w_main_multiplier)
+        with self.ranker() as mr:
+            total, ids, con = mr._ranker.explain((indptr, col, g, g + dt.type(1)), items, n=n, gram=G0, lam=lam)
+        return {"score": total, "ids": ids, "contributions": con}
+    explain.__doc__ = _EXPLAIN_DOC
 
     def topN_batch(self, users, n=10, exclude=None, include=None, filter=None):
         """Top-``n`` item ids and scores (A_u . B_i) for a batch of users, ranked on the GPU; ``exclude``: CSR of items
@@ -935,6 +1001,37 @@ class CMF(_Base):
         one 1-D array shared by all: each user is ranked over its own list only."""
         ids, sc = _topN(self, users, n, exclude, self.item_bias_ if self.item_bias else None, include, filter)
         return ids, self._finish_scores(np.atleast_1d(np.asarray(users, np.int64)), sc)
+
+    def explain(self, X, items, n=10, W=None):
+        _explain_refusals(self, X)
+        if self.scale_lam and not self.user_bias:
+            raise ValueError("CMF.explain: scale_lam without a user bias keeps one factor's lambda unscaled; not supported")
+        indptr, col, val, Wv, items = _explain_history(self, X, items, W)
+        dt = np.dtype(self.dtype_)
+        w = np.ones(len(val), dt) if Wv is None else Wv
+        centred = val - dt.type(self.glob_mean_)
+        if self.item_bias:
+            centred = centred - self.item_bias_[col]
+        # the lambdas of the new-rows code (fit.hip, factors_collective_explicit_single): / w_main; under scale_lam times the
+        # user's count or weight sum, the bias' lambda too unless scale_bias_const holds it at scaling_biasA
+        lam = self.lambda_ / self.w_main
+        bias_lam = lam * (self._scaling_biasA if (self.scale_lam and self.scale_bias_const) else 1.) if self.user_bias else None
+        lam_user = None
+        if self.scale_lam:
+            starts = indptr[:-1].astype(np.int64)
+            mult = np.add.reduceat(np.append(w.astype(np.float64), 0.), starts) * (np.diff(indptr.astype(np.int64)) > 0)
+            mult = np.where(mult > 0, mult, 1.)                     # (a user without entries: every term is zero anyway)
+            lam_user = (lam * mult).astype(dt)
+            if self.user_bias and not self.scale_bias_const:
+                bias_lam = (bias_lam * mult).astype(dt)
+        with self.ranker() as mr:
+            total, ids, con = mr._ranker.explain((indptr, col, w, np.ascontiguousarray(w * centred, dt)), items, n=n, lam=lam,
+                                                 lam_user=lam_user, bias_lam=bias_lam)
+        score = total + dt.type(self.glob_mean_)
+        if self.item_bias:
+            score = score + self.item_bias_[items]
+        return {"score": score, "ids": ids, "contributions": con}
+    explain.__doc__ = _EXPLAIN_DOC
 
     def topN_deep(self, users, n, exclude=None):
         return _topN_deep(self, users, n, exclude, self.item_bias_ if self.item_bias else None)

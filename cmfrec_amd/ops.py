@@ -440,6 +440,76 @@ def topN_diverse_batch(A, B, n_top=10, pool=64, tradeoff=0.7, biasB=None, exclud
     return (ids, sc, mmr) if output_mmr else (ids, sc)
 
 
+def _explain_args(history, targets, n, gram, lam, lam_user, bias_lam, dtype, k, what):
+    """The ``cmfrec_hip_explain_args`` of an explanation call and what must outlive it: (args, keep-alive list, outputs
+    (total, ids, contributions), shape of the targets or None).  Checked without a device as far as the shapes go; the ids, the
+    limits and the signs are the library's to refuse."""
+    dtype = np.dtype(dtype)
+    if not (isinstance(history, (tuple, list)) and len(history) == 4):
+        raise ValueError("%s: history must be (indptr, items, g, y)" % what)
+    hp = np.ascontiguousarray(history[0], np.uint64); hi = np.ascontiguousarray(history[1], np.int32)
+    hg = np.ascontiguousarray(history[2], dtype); hy = np.ascontiguousarray(history[3], dtype)
+    nu = len(hp) - 1
+    if hp.ndim != 1 or nu < 1 or not (hi.shape == hg.shape == hy.shape == (int(hp[-1]),)):
+        raise ValueError("%s: history is a CSR over the users: indptr [users + 1], items / g / y [indptr[-1]]" % what)
+    shape = None
+    if isinstance(targets, (tuple, list)) and len(targets) == 2 and np.ndim(targets[0]) == 1 and len(targets[0]) == nu + 1:
+        tp = np.ascontiguousarray(targets[0], np.uint64); ti = np.ascontiguousarray(targets[1], np.int32)
+    else:
+        t2 = np.asarray(targets)
+        if t2.ndim != 2 or t2.shape[0] != nu or not np.issubdtype(t2.dtype, np.integer):
+            raise ValueError("%s: targets must be an integer array [users, targets] or (indptr, items) over the %d users" % (what, nu))
+        shape = t2.shape
+        tp = (np.arange(nu + 1, dtype=np.uint64) * np.uint64(shape[1])); ti = np.ascontiguousarray(t2, np.int32).ravel()
+    if ti.shape != (int(tp[-1]),):
+        raise ValueError("%s: targets' items must have indptr[-1] entries" % what)
+    G0 = None
+    if gram is not None:
+        G0 = np.ascontiguousarray(gram, dtype)
+        if G0.shape != (k, k):
+            raise ValueError("%s: gram must be [%d, %d], got %s" % (what, k, k, G0.shape))
+    du = None
+    if lam_user is not None:
+        du = np.ascontiguousarray(lam_user, dtype)
+        if du.shape != (nu,):
+            raise ValueError("%s: lam_user must have one entry per user (%d), got shape %s" % (what, nu, du.shape))
+    dbu = None
+    if bias_lam is not None and np.ndim(bias_lam) > 0:
+        dbu = np.ascontiguousarray(bias_lam, dtype)
+        if dbu.shape != (nu,):
+            raise ValueError("%s: bias_lam must be a number or have one entry per user (%d), got shape %s" % (what, nu, dbu.shape))
+    n = int(n); nt = len(ti)
+    total = np.empty(nt, dtype); ids = np.empty((nt, max(n, 0)), np.int32); con = np.empty((nt, max(n, 0)), dtype)
+    a = _lib.ExplainArgs()
+    a.nu, a.n_top, a.bias = nu, n, int(bias_lam is not None)
+    a.hist_p, a.hist_i, a.hist_g, a.hist_y = (_lib.ptr(x) for x in (hp, hi, hg, hy))
+    a.targ_p, a.targ_i, a.G0, a.diag_u, a.diag_bias_u = (_lib.ptr(x) for x in (tp, ti, G0, du, dbu))
+    a.diag, a.diag_bias = float(lam), float(bias_lam) if (bias_lam is not None and dbu is None) else 0.0
+    a.out_total, a.out_ids, a.out_contrib = (_lib.ptr(x) for x in (total, ids, con))
+    return a, [hp, hi, hg, hy, tp, ti, G0, du, dbu], (total, ids, con), shape
+
+
+def _explain_result(out, shape):
+    total, ids, con = out
+    if shape is None:
+        return total, ids, con
+    return total.reshape(shape), ids.reshape(shape + ids.shape[1:]), con.reshape(shape + con.shape[1:])
+
+
+def explain_batch(B, history, targets, n=10, gram=None, lam=1.0, lam_user=None, bias_lam=None):
+    """Why an item scores what it scores: one call of ``Ranker.explain`` against the rows of ``B`` [items, k] (see there).
+    B is uploaded on every call: to explain several batches, hold a ``cmfrec_amd.Ranker``."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.dtype.type not in (np.float64, np.float32):
+        raise ValueError("explain_batch: B must be a 2-D float64 or float32 array, got %d-D %s" % (B.ndim, B.dtype))
+    B = np.ascontiguousarray(B)
+    lib = _lib.load(B.dtype)
+    a, keep, out, shape = _explain_args(history, targets, n, gram, lam, lam_user, bias_lam, B.dtype, B.shape[1], "explain_batch")
+    rc = lib.cmfrec_hip_explain_batch(_lib.ptr(B), C.c_size_t(B.shape[1]), C.c_int(B.shape[0]), C.c_int(B.shape[1]), C.byref(a))
+    _lib.check(rc, lib, "explain_batch")
+    return _explain_result(out, shape)
+
+
 DENSE_OPS = {"gemm": 0, "gemm_ta": 1, "gram": 2, "potrf": 3, "trtri": 4, "potrs_rows": 5}
 
 

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _heldout_lists, _is_csr, _mmr_pools, _similar_args, _sorted_exclude, _sorted_include, after_cursor
+from .ops import _explain_args, _explain_result, _heldout_lists, _is_csr, _mmr_pools, _similar_args, _sorted_exclude, _sorted_include, after_cursor
 
 
 def check_rankset(users, heldout, exclude):
@@ -416,6 +416,22 @@ class Ranker:
                                                      _lib.ptr(mmr))
         _lib.check(rc, self.lib, "Ranker.topN_diverse")
         return (ids, sc, mmr) if output_mmr else (ids, sc)
+
+    def explain(self, history, targets, n=10, gram=None, lam=1.0, lam_user=None, bias_lam=None):
+        """Why an item scores what it scores: for every (user, target) pair the score ``b_t . a_u`` of the user's closed-form
+        factors ``a_u = W_u^-1 sum_j y_j b_j``, ``W_u = gram + lam I + sum_j g_j b_j b_j^T`` over the user's history, split without
+        remainder into one term ``c_tj = y_j b_t' W_u^-1 b_j`` per history item, on the device.
+        ``history`` = (indptr, items, g, y), a CSR over the users; ``targets`` an integer array [users, targets] or (indptr,
+        items).  ``gram``: [k, k] or None; ``lam`` > 0 on the diagonal, ``lam_user`` [users] in its place per user;
+        ``bias_lam`` not None: every row is [b, 1] -- one more unknown with that diagonal (a user bias) -- and ``gram`` must be None.
+        Returns (total, ids, contributions): per pair the sum of all terms, the ``n`` history items of the largest terms
+        (int32, descending, ties to the earlier history position, -1 behind a short history) and the terms (-inf there) --
+        [pairs], [pairs, n], [pairs, n] in the order of ``targets``' items, or [users, targets(, n)] for a 2-D ``targets``.  A user
+        whose ``W_u`` is not positive definite gets NaN and -1.  ``k + (bias) <= 128``, ``1 <= n <= 64``."""
+        h = self._live()
+        a, keep, out, shape = _explain_args(history, targets, n, gram, lam, lam_user, bias_lam, self.dtype, self.k, "Ranker.explain")
+        _lib.check(self.lib.cmfrec_hip_ranker_explain(h, C.byref(a)), self.lib, "Ranker.explain")
+        return _explain_result(out, shape)
 
     def inverse_norms(self):
         """[n]: 1 / |B_i| of every row as the cosine scores use it (made on the device by the first call that needs it, resident

@@ -784,6 +784,45 @@ int cmfrec_hip_ranker_topN_diverse(cmfrec_hip_ranker *r, const real_t *A, size_t
 int cmfrec_hip_topN_diverse_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
                                   const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t pool, double theta,
                                   int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr);
+
+/* Why an item was recommended: the score of a (user, target) pair split into one term per item of the user's history, on the
+ * device (topn_explain_kernels.hpp).  For the models this library fits a user's closed-form factors are
+ *   a_u = W_u^-1 sum_j y_j b_j,    W_u = G0 + diag I + sum_j g_j b_j b_j^T    over the user's own items j,
+ * b_j the handle's resident row j (its k scored columns, without the handle's item bias), so for any target item t
+ *   c_tj = y_j * b_t^T W_u^-1 b_j,    total_t = sum_j c_tj = b_t . a_u
+ * without remainder.  The model enters through G0, diag, diag_u, bias and the two coefficients per history entry.
+ * args: nu users.  hist_p / hist_i / hist_g / hist_y: the histories, a CSR over the users (offsets that do not decrease) with
+ *   the item id and the coefficients g_j (weight of b_j b_j^T) and y_j (weight of b_j in the right-hand side) per entry; a
+ *   history may be empty, may repeat an item, need not be sorted and has no length limit.  targ_p / targ_i: the targets to
+ *   explain, a second CSR over the users; a list may be empty, may repeat a target and may name items of the history.
+ *   G0: host [k, k] row-major, symmetric, or NULL.  diag > 0 is added to the diagonal; diag_u [nu] (optional, every entry > 0)
+ *   replaces it per user.  bias != 0: every item row, targets included, is [b_j, 1] -- one more unknown with the diagonal
+ *   diag_bias > 0, per user diag_bias_u [nu] (optional) in its place --, so total = b_t . a_u + beta_u for a model with a user
+ *   bias.
+ * Outputs, one row per entry of targ_i, in its order: out_total [targ_p[nu]] = sum_j c_tj over the whole history, added in
+ *   double in history order (0 for an empty history); out_ids / out_contrib [targ_p[nu], n_top]: the n_top history items of the
+ *   largest c_tj and those c_tj, descending, equal values to the earlier history position.  A history shorter than n_top is
+ *   padded the way cmfrec_hip_ranker_topN_candidates pads a short candidate list: id -1, contribution -inf.  A user whose W_u
+ *   has a pivot that is not positive (W_u is not positive definite) gets NaN in out_total and out_contrib and -1 in out_ids
+ *   for all its targets; the other users of the batch are not affected.
+ * Arithmetic in the working precision on the matrix cores; no atomics: the same call returns the same bytes, whatever the
+ *   launch shape (CMFREC_HIP_EXPLAIN_GROUPS caps the workgroups -- a test hook, read per call).
+ * Limits: k + (bias != 0) <= 128 and 1 <= n_top <= 64.  Beyond them, and for: a null handle or required pointer, nu <= 0, G0
+ *   together with bias, diag <= 0 (diag_bias <= 0 with bias, an entry of diag_u or diag_bias_u <= 0), hist_p or targ_p with a decreasing offset, an
+ *   id of either list outside [0, n) -- code 2 with a message, decided on the host before anything touches the device, the outputs
+ *   untouched.  The handle's split and filter settings are not read: the call has one route.
+ * kernel_ms / launch_shape report the explanation kernel after such a call: one user per workgroup at a time, and the workgroups.
+ * cmfrec_hip_explain_batch is create (without a bias), one such call, destroy. */
+typedef struct cmfrec_hip_explain_args {
+    int32_t nu, n_top, bias;
+    const size_t *hist_p; const int_t *hist_i; const real_t *hist_g, *hist_y;
+    const size_t *targ_p; const int_t *targ_i;
+    const real_t *G0, *diag_u, *diag_bias_u;
+    double diag, diag_bias;                              /* double in both precisions: one layout */
+    real_t *out_total; int_t *out_ids; real_t *out_contrib;
+} cmfrec_hip_explain_args;
+int cmfrec_hip_ranker_explain(cmfrec_hip_ranker *r, const cmfrec_hip_explain_args *args);
+int cmfrec_hip_explain_batch(const real_t *B, size_t ldb, int_t n, int_t k, const cmfrec_hip_explain_args *args);
 void cmfrec_hip_ranker_destroy(cmfrec_hip_ranker *r);
 
 /* New rows against a model that stays on the device: factors and top-N of users who were not part of the fit, batch after
