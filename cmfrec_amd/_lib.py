@@ -156,6 +156,7 @@ EXPORTED = [
     "cmfrec_hip_ranker_set_filter", "cmfrec_hip_ranker_filter_stats", "cmfrec_hip_ranker_filter_ms", "cmfrec_hip_ranker_filter_keys",
     "cmfrec_hip_ranker_rerank_mmr", "cmfrec_hip_ranker_topN_diverse", "cmfrec_hip_topN_diverse_batch",
     "cmfrec_hip_ranker_explain", "cmfrec_hip_explain_batch",
+    "cmfrec_hip_ranker_topN_sample", "cmfrec_hip_topN_sample_batch",
     "cmfrec_hip_scorer_create", "cmfrec_hip_scorer_predict", "cmfrec_hip_scorer_kernel_ms", "cmfrec_hip_scorer_destroy", "cmfrec_hip_score_pairs",
     "cmfrec_hip_evalset_create", "cmfrec_hip_evalset_kernel_ms", "cmfrec_hip_evalset_launch_waves", "cmfrec_hip_evalset_destroy", "cmfrec_hip_scorer_errors", "cmfrec_hip_session_errors", "cmfrec_hip_pair_errors",
     "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
@@ -236,6 +237,10 @@ def load(dtype=np.float64):
                                                    C.c_int] + [C.c_void_p] * 3
     lib.cmfrec_hip_topN_diverse_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
         [C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 3
+    lib.cmfrec_hip_ranker_topN_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                                  C.c_uint64, C.c_int] + [C.c_void_p] * 4
+    lib.cmfrec_hip_topN_sample_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
+        [C.c_int, C.c_double, C.c_uint64, C.c_int] + [C.c_void_p] * 4
     lib.cmfrec_hip_ranker_explain.argtypes = [C.c_void_p, C.POINTER(ExplainArgs)]
     lib.cmfrec_hip_explain_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(ExplainArgs)]
     nrm = newrows_model_mirror(dtype)

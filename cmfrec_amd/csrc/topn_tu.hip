@@ -17,6 +17,9 @@
 // would run unfiltered -- and topn_filter_certify_kernel; the users that are not certified take the route above in a second batch.
 // A diversified call (cmfrec_hip_ranker_rerank_mmr / _topN_diverse) launches topn_mmr_kernel (topn_mmr_kernels.hpp, from
 // topn_mmr_tu.hip) over per-user pools that are on the device: the caller's, or the lists the full ranking above left there.
+// A sampling call (cmfrec_hip_ranker_topN_sample) launches topn_sample_kernel -- the wide kernel's body under a policy that adds
+// Gumbel noise to the scores -- and topn_sample_scores_kernel behind it (topn_sample_kernels.hpp, from topn_sample_tu.hip), for
+// every k; temperature 0 launches topn_wide_kernel.  It reads none of the handle's split or filter settings.
 // An explanation call (cmfrec_hip_ranker_explain) launches topn_explain_kernel (topn_explain_kernels.hpp, from topn_explain_tu.hip)
 // over per-user histories and target lists; it reads the resident rows and none of the handle's split or filter settings.
 #include <algorithm>
@@ -35,6 +38,7 @@
 #include "topn_filter.hpp"
 #include "topn_mmr_kernels.hpp"
 #include "topn_explain_kernels.hpp"
+#include "topn_sample_kernels.hpp"
 #include "rank_metrics_kernels.hpp"
 
 using namespace cmfhip;
@@ -79,6 +83,8 @@ struct cmfrec_hip_ranker {
     DevBuf<real_t> mmr_sc, mmr_v;
     DevBuf<size_t> x_hp, x_tp;               // an explanation call: histories and targets (CSR over the users) ...
     DevBuf<int> x_hi, x_ti;
+    DevBuf<real_t> sm_keys;                  // a sampling call: the keys of the lists (their ids and scores: ids / sc) ...
+    DevBuf<double> sm_lse;                   // ... and the users' log-partitions
     DevBuf<real_t> x_g, x_y, x_g0, x_du, x_dbu, x_tot;   // ... their coefficients, G0, the per-user diagonals, the totals (lists: ids / sc)
     const real_t *item_bias() const { return has_bias ? bias.ptr : nullptr; }
     ~cmfrec_hip_ranker()
@@ -97,6 +103,7 @@ constexpr const char *LIMITS = "needs k <= 272 and n_top <= min(128, n)";
 constexpr const char *RANK_LIMITS = "needs k <= 272";
 constexpr const char *DEEP_LIMITS = "needs k <= 272 and 1 <= n_top <= n";
 constexpr const char *EXPLAIN_LIMITS = "needs k + bias <= 128 and 1 <= n_top <= 64";
+constexpr const char *SAMPLE_LIMITS = "needs k <= 272, 1 <= n_top <= min(128, n) and a finite temperature >= 0 whose inverse is finite";
 constexpr const char *MMR_LIMITS = "needs k <= 272, 1 <= n_top <= pool <= min(128, n) and 0 <= theta <= 1";
 
 // User tiles per workgroup of the wide kernel (DESIGN.md "Top-N for wide models"): as many as the LDS holds beside the lists,
@@ -104,12 +111,14 @@ constexpr const char *MMR_LIMITS = "needs k <= 272, 1 <= n_top <= pool <= min(12
 // (nut + 1/2) -- its MFMAs and the item fetch they share -- times the workgroups that share its CU.
 // CMFREC_HIP_TOPN_TILES (test hook) asks for a number of tiles; it is clamped to what fits.
 // extra_per_tile: LDS bytes per user tile beyond topnw_lds_bytes (the neighbour kernel's ids and inverse norms).
-int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu, size_t extra_per_tile = 0, size_t sizeof_real = sizeof(real_t))
+// max_nut: a kernel that cannot take all TOPNW_MAX_NUT tiles (the sampling kernel with its log-partition, in double precision).
+int pick_user_tiles(int nu, int k, int n_top, int num_cus, int *blocks_per_cu, size_t extra_per_tile = 0, size_t sizeof_real = sizeof(real_t),
+                    int max_nut = TOPNW_MAX_NUT)
 {
     const int forced = switches().topn_tiles;
     int best = 1, best_bpc = 1;
     double best_cost = 0;
-    for (int nut = 1; nut <= TOPNW_MAX_NUT; nut++) {
+    for (int nut = 1; nut <= max_nut; nut++) {
         const size_t smem = topnw_lds_bytes(nut, k, n_top, sizeof_real) + nut * extra_per_tile;
         if (smem > TOPNW_LDS_MAX) break;
         const int bpc = (int)std::min<size_t>(TOPNW_LDS_MAX / smem, (size_t)(2048 / TOPNW_TH));
@@ -683,6 +692,60 @@ int explain_device(cmfrec_hip_ranker *r, const cmfrec_hip_explain_args *a)
     return 0;
 }
 
+// what a sampling call refuses beyond "invalid arguments" (DESIGN.md section 3.21), before a device is touched
+int check_sample(const char *fn, int_t k, int_t n, int_t n_top, double temperature)
+{
+    if (k > TOPNW_KMAX || k <= 0 || n_top < 1 || n_top > TOPN_NMAX || n_top > n) return refuse(fn, SAMPLE_LIMITS);
+    if (!(temperature >= 0.0) || !std::isfinite(temperature) || (temperature > 0.0 && !((real_t)temperature > 0 && std::isfinite((real_t)(1.0 / temperature)))))
+        return refuse(fn, SAMPLE_LIMITS);
+    return 0;
+}
+
+// The sampling pass over users that are on the device: the launches, the timing events and the download.  temperature == 0 is
+// topn_wide_kernel itself -- the full ranking on the MFMA arithmetic for every k -- with the keys equal to the scores and a NaN
+// log-partition.  The handle's split and filter settings play no part.  (the caller holds the DeviceScope and has checked the limits)
+int sample_device(cmfrec_hip_ranker *r, const RankUsers &users, int_t n_top, double temperature, unsigned long long seed, bool with_lse,
+                  int_t *out_ids, real_t *out_scores, real_t *out_keys, double *out_lse)
+{
+    const cmfrec_hip_ranker::Device &dev = r->dev;
+    const int_t nu = users.nu;
+    const size_t cells = (size_t)nu * n_top;
+    const bool noise = temperature > 0.0;
+    r->ids.alloc_at_least(cells);
+    r->sc.alloc_at_least(cells);
+    if (noise) r->sm_keys.alloc_at_least(cells);
+    if (noise && with_lse) r->sm_lse.alloc_at_least((size_t)nu);
+    int bpc = 1, nut = 1, grid = 0;
+    poison_lds(dev.stream, dev.num_cus);                                 // (the policy's LDS too is written before it is read)
+    HIP_CHECK(hipEventRecord(r->ev0, dev.stream));
+    if (!noise) {
+        auto P = ranking_params<TopnWideParams<real_t>>(r, users);
+        set_lists(P, r, n_top, true);
+        nut = pick_user_tiles(nu, r->k, n_top, dev.num_cus, &bpc);
+        grid = with_tiles(nut, [&](auto t) {
+            return launch_tiled(dev, topn_wide_kernel<real_t, t()>, t(), topnw_lds_bytes(t(), r->k, n_top, sizeof(real_t)), P, bpc);
+        });
+    } else {
+        auto P = ranking_params<TopnSampleParams<real_t>>(r, users);
+        P.n_top = n_top; P.out_ids = r->ids.ptr; P.out_scores = r->sm_keys.ptr;
+        P.temperature = (real_t)temperature; P.inv_t = (float)(1.0 / temperature); P.seed = seed;
+        P.out_lse = with_lse ? r->sm_lse.ptr : nullptr;
+        nut = pick_user_tiles(nu, r->k, n_top, dev.num_cus, &bpc, 16 * topnsm_extra_per_user(with_lse), sizeof(real_t),
+                              topnsm_max_tiles(sizeof(real_t), with_lse));
+        grid = topn_sample_launch(dev.stream, dev.num_cus, nut, bpc, P, r->sc.ptr);
+    }
+    end_timed(r, 16 * nut, grid, 1);
+    download_and_wait(r, cells, out_ids, out_scores);                    // (and the stream is idle)
+    if (out_keys) {
+        if (noise) r->sm_keys.download(out_keys, cells, dev.stream);
+        else r->sc.download(out_keys, cells, dev.stream);
+    }
+    if (with_lse && noise) r->sm_lse.download(out_lse, (size_t)nu, dev.stream);
+    HIP_CHECK(hipStreamSynchronize(dev.stream));
+    if (with_lse && !noise) std::fill(out_lse, out_lse + nu, std::nan(""));
+    return 0;
+}
+
 // a ranker of its own on the current device for one call
 template <class F>
 int with_ranker(const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB, F &&call)
@@ -1252,6 +1315,23 @@ int cmfrec_hip_ranker_topN_diverse(cmfrec_hip_ranker *r, const real_t *A, size_t
     });
 }
 
+int cmfrec_hip_ranker_topN_sample(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu, const size_t excl_p[], const int_t excl_i[],
+                                  int_t n_top, double temperature, uint64_t seed, int with_lse, int_t *out_ids, real_t *out_scores,
+                                  real_t *out_keys, double *out_lse)
+{
+    const char *fn = "cmfrec_hip_ranker_topN_sample";
+    return guarded([&]() {
+        if (bad_users(r, A, lda, nu, excl_p, excl_i) || !out_ids || (with_lse && !out_lse)) return refuse(fn, std::string("invalid arguments; ") + SAMPLE_LIMITS);
+        if (int rc = check_sample(fn, r->k, r->n, n_top, temperature)) return rc;
+        if (excl_p != nullptr && !csr_ok(excl_p, excl_i, nu)) return refuse(fn, "invalid arguments (the exclusion lists are not a CSR over the users)");
+        DeviceScope scope(r->dev.device);
+        switches_mut().reload();
+        RankUsers users = stage_users(r, A, lda, nu);
+        stage_exclusions(r, users, excl_p, excl_i);
+        return sample_device(r, users, n_top, temperature, (unsigned long long)seed, with_lse != 0, out_ids, out_scores, out_keys, out_lse);
+    });
+}
+
 int cmfrec_hip_ranker_explain(cmfrec_hip_ranker *r, const cmfrec_hip_explain_args *args)
 {
     const char *fn = "cmfrec_hip_ranker_explain";
@@ -1377,6 +1457,18 @@ int cmfrec_hip_topN_diverse_batch(const real_t *A, size_t lda, int_t nu, const r
     if (int rc = check_mmr(fn, k, n, pool, n_top, theta)) return rc;
     return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
         return cmfrec_hip_ranker_topN_diverse(r, A, lda, nu, excl_p, excl_i, pool, theta, n_top, out_ids, out_scores, out_mmr);
+    });
+}
+
+int cmfrec_hip_topN_sample_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k, const real_t *biasB,
+                                 const size_t excl_p[], const int_t excl_i[], int_t n_top, double temperature, uint64_t seed, int with_lse,
+                                 int_t *out_ids, real_t *out_scores, real_t *out_keys, double *out_lse)
+{
+    const char *fn = "cmfrec_hip_topN_sample_batch";
+    if (nu <= 0 || n <= 0 || k <= 0 || !A || !B || !out_ids || (with_lse && !out_lse)) return refuse(fn, std::string("invalid arguments; ") + SAMPLE_LIMITS);
+    if (int rc = check_sample(fn, k, n, n_top, temperature)) return rc;
+    return with_ranker(B, ldb, n, k, biasB, [&](cmfrec_hip_ranker *r) {
+        return cmfrec_hip_ranker_topN_sample(r, A, lda, nu, excl_p, excl_i, n_top, temperature, seed, with_lse, out_ids, out_scores, out_keys, out_lse);
     });
 }
 

@@ -76,6 +76,16 @@ struct TopnWideParams {
 //   out_stride(P)                  elements between two users' rows of out_ids / out_scores
 //   item_begin(P), item_end(P)     the items [begin, end) the workgroup ranks: 0 and P.n, but for a slice of the items
 //                                  (topn_split_kernels.hpp) -- begin a multiple of TOPNW_ITEMS, so the rows keep their lanes
+// EXT = true (topn_sample_kernels.hpp) asks for more: per-lane state that lives as long as a tile, a word at the head of every
+// round, and a score that sees the pair and its user's threshold.  With EXT = false none of it exists.
+//   TileState<NUT>                 default-constructed per tile, one per lane
+//   round_begin(P, xs, c0, ...)    all threads, at the head of the round of items [c0, c0 + TOPNW_ITEMS)
+//   pair_key(P, ts, 4 t + r, acc, iv, xs, UT, u, u0 + u, item, ok, thr[u])
+//                                  in score's place; ok = the pair is of a live item and a user of the tile
+//   tile_end(P, ts, xs, ...)       all threads, behind the tile's last round (it may hold a barrier)
+template <typename POL, int NUT, bool EXT> struct TopnwTileState { struct type {}; };
+template <typename POL, int NUT> struct TopnwTileState<POL, NUT, true> { using type = typename POL::template TileState<NUT>; };
+
 template <typename T>
 struct TopnWidePolicy {
     using Params = TopnWideParams<T>;
@@ -94,7 +104,7 @@ struct TopnWidePolicy {
     static __device__ __forceinline__ int item_end(const Params &P) { return P.n; }
 };
 
-template <typename T, int NUT, typename POL>
+template <typename T, int NUT, typename POL, bool EXT = false>
 __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
 {
     using Acc = MfmaAcc<T>;
@@ -128,6 +138,7 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
         for (int e = tid; e < UT * LS; e += TOPNW_TH) { ssc[e] = NEG; sid[e] = 0x7fffffff; }
         if (tid < UT) { cnt[tid] = 0; thr[tid] = NEG; }
         __syncthreads();
+        [[maybe_unused]] typename TopnwTileState<POL, NUT, EXT>::type ts;
         const T *arow = As + col * KS + grp * V;
         // the item rows arrive through a ring of PF loads in flight per lane: a chunk's load is issued PF chunks ahead, and the
         // first PF of the NEXT round before this round's filter and merge, so those overlap the fetch
@@ -140,6 +151,7 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
             const int item = c0 + 16 * wave + col;
             const bool live = item < i1;
             const auto iv = POL::item_value(P, item, live);
+            if constexpr (EXT) POL::round_begin(P, xs, c0, u0, nu_t, UT, tid);
             vec acc[NUT];
 #pragma unroll
             for (int t = 0; t < NUT; t++) acc[t] = vec{0, 0, 0, 0};
@@ -173,7 +185,8 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int u = 16 * t + Acc::row_of(lane, r);
-                    acc[t][r] = POL::score(acc[t][r], iv, xs, UT, u);
+                    if constexpr (EXT) acc[t][r] = POL::pair_key(P, ts, 4 * t + r, acc[t][r], iv, xs, UT, u, u0 + u, item, live && u < nu_t, thr[min(u, UT - 1)]);
+                    else acc[t][r] = POL::score(acc[t][r], iv, xs, UT, u);
                     if (live && u < nu_t && acc[t][r] >= thr[u] && POL::admit(xs, UT, u, item, acc[t][r])) {   // NaN never enters
                         bool skip = false;
                         if (P.excl_p != nullptr) {                               // sorted list of the user: binary search
@@ -263,6 +276,7 @@ __device__ __forceinline__ void topn_wide_body(const typename POL::Params P)
                 __syncthreads();
             } while (more);
         }
+        if constexpr (EXT) POL::tile_end(P, ts, xs, u0, nu_t, UT, tid);
         const size_t ldo = POL::out_stride(P);
         for (int e = tid; e < nu_t * ntop; e += TOPNW_TH) {
             const int u = e / ntop, j = e % ntop;

@@ -97,6 +97,22 @@ def _topN_diverse(self, users, n, pool, tradeoff, exclude, biasB):
     return ops.topN_diverse_batch(A, B, n_top=n, pool=pool, tradeoff=tradeoff, biasB=biasB, exclude=excl)
 
 
+def _topN_sample(self, users, n, temperature, seed, exclude, biasB):
+    """Shared body of ``CMF.topN_sample`` / ``CMF_implicit.topN_sample``."""
+    from . import ops
+    _, A, excl = _topN_inputs(self, users, exclude)
+    B = np.ascontiguousarray(self.B_[:, self.k_item:])
+    return ops.topN_sample_batch(A, B, n_top=n, temperature=temperature, seed=seed, biasB=biasB, exclude=excl)
+
+
+_TOPN_SAMPLE_DOC = """Stochastic top-``n``: (ids [len(users), n] int32, scores, keys) -- per user ``n`` items drawn without replacement with
+        probability proportional to ``exp(score / temperature)`` on the device (``ops.topN_sample_batch``): exploration traffic
+        that is reproducible from ``seed``.  The noise of a pair depends on the user's position in ``users``, not on its id.
+        ``users`` and ``exclude`` as in ``topN_batch``; ``n <= min(128, items)``.  The scores are the ranker's own, A_u . B_i (+ the
+        item bias), as in ``topN_deep``.  For the log-partition (propensities), or several batches, hold ``ranker()`` and call its
+        ``topN_sample``."""
+
+
 _TOPN_DIVERSE_DOC = """Diversified top-``n``: (ids [len(users), n] int32, scores).  The ``pool`` best items of every user as ``topN_batch``
         ranks them are re-ranked on the device by maximal marginal relevance (``ops.topN_diverse_batch``): the best score first,
         then whatever maximises ``tradeoff * (score scaled to [0, 1] over the pool) - (1 - tradeoff) * (largest cosine to an item
@@ -154,6 +170,13 @@ class ModelRanker:
         without leaving the device (``Ranker.topN_diverse``).  Scores as ``topN_deep`` returns them."""
         _, A, excl = _topN_inputs(self._model, users, exclude)
         return self._ranker.topN_diverse(A, n=n, pool=pool, tradeoff=tradeoff, exclude=excl, output_mmr=output_mmr)
+
+    def topN_sample(self, users, n=10, temperature=1.0, seed=0, exclude=None, with_lse=False):
+        """(ids, scores, keys[, lse]) for user ids of the fitted model: ``n`` items each, drawn without replacement with
+        probability proportional to ``exp(score / temperature)`` (``Ranker.topN_sample``; the noise of a pair depends on the
+        user's position in ``users``).  Scores as ``topN_deep`` returns them."""
+        _, A, excl = _topN_inputs(self._model, users, exclude)
+        return self._ranker.topN_sample(A, n=n, temperature=temperature, seed=seed, exclude=excl, with_lse=with_lse)
 
     def pages(self):
         """(launches, page length) of the most recent ``topN_deep`` call."""
@@ -668,6 +691,10 @@ class CMF_implicit(_Base):
         return _topN_diverse(self, users, n, pool, tradeoff, exclude, None)
     topN_diverse.__doc__ = _TOPN_DIVERSE_DOC
 
+    def topN_sample(self, users, n=10, temperature=1.0, seed=0, exclude=None):
+        return _topN_sample(self, users, n, temperature, seed, exclude, None)
+    topN_sample.__doc__ = _TOPN_SAMPLE_DOC
+
     def ranks_batch(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by A_u . B_i, counted
         on the GPU (``ops.ranks_batch``).  ``heldout``: (indptr, indices) CSR over the users OF THIS CALL or a SciPy CSR matrix
@@ -1040,6 +1067,10 @@ class CMF(_Base):
     def topN_diverse(self, users, n=10, pool=64, tradeoff=0.7, exclude=None):
         return _topN_diverse(self, users, n, pool, tradeoff, exclude, self.item_bias_ if self.item_bias else None)
     topN_diverse.__doc__ = _TOPN_DIVERSE_DOC
+
+    def topN_sample(self, users, n=10, temperature=1.0, seed=0, exclude=None):
+        return _topN_sample(self, users, n, temperature, seed, exclude, self.item_bias_ if self.item_bias else None)
+    topN_sample.__doc__ = _TOPN_SAMPLE_DOC
 
     def ranks_batch(self, users, heldout, exclude=None):
         """(indptr, items, ranks, pool): the 0-based place of each held-out item in its user's full ranking by

@@ -440,6 +440,46 @@ def topN_diverse_batch(A, B, n_top=10, pool=64, tradeoff=0.7, biasB=None, exclud
     return (ids, sc, mmr) if output_mmr else (ids, sc)
 
 
+def _sample_args(n_top, n_items, temperature, seed, what):
+    """(n_top, temperature, seed) of a sampling call, checked without a device: ``ValueError`` for what the library would refuse."""
+    if isinstance(n_top, (bool, float)) or int(n_top) != n_top or not 1 <= int(n_top) <= min(128, int(n_items)):
+        raise ValueError("%s: n must be an integer in 1 .. min(128, items = %d), got %r" % (what, n_items, n_top))
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError("%s: temperature must be a number, got %r" % (what, temperature))
+    if not (t >= 0.0) or not np.isfinite(t):
+        raise ValueError("%s: temperature must be finite and >= 0, got %r" % (what, temperature))
+    if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("%s: seed must be an integer in 0 .. 2^64 - 1, got %r" % (what, seed))
+    return int(n_top), t, int(seed)
+
+
+def topN_sample_batch(A, B, n_top=10, temperature=1.0, seed=0, biasB=None, exclude=None, with_lse=False):
+    """Stochastic top-N for every row of ``A``: ``n_top`` items drawn without replacement with probability proportional to
+    ``exp(score / temperature)``, score = A_u . B_i (+ biasB[i]) -- the ``n_top`` largest of ``score + temperature * g`` with one
+    standard Gumbel variable ``g`` per (row of A, item) from a counter-based hash of ``seed`` (``Ranker.topN_sample`` has the
+    definition).  Returns (ids [nu, n_top] int32, scores, keys) and, with ``with_lse``, lse [nu] float64 = log sum over the user's
+    items that are not excluded of exp(score / temperature).  k <= 272, n_top <= min(128, n).  B is uploaded on every call: hold a
+    ``cmfrec_amd.Ranker`` otherwise."""
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B, A.dtype)
+    n_top, t, seed = _sample_args(n_top, B.shape[0] if B.ndim == 2 else 0, temperature, seed, "topN_sample_batch")
+    lib, R = _prep(A, B)
+    nu, lda = A.shape
+    n, ldb = B.shape
+    ids = np.empty((nu, n_top), np.int32); sc = np.empty((nu, n_top), A.dtype); keys = np.empty((nu, n_top), A.dtype)
+    lse = np.empty(nu, np.float64) if with_lse else None
+    bs = None if biasB is None else np.ascontiguousarray(biasB, A.dtype)
+    if exclude is not None and _is_csr(exclude):
+        exclude = (exclude.indptr, exclude.indices)
+    ep, ei = _sorted_exclude(exclude, nu)
+    rc = lib.cmfrec_hip_topN_sample_batch(_lib.ptr(A), C.c_size_t(lda), C.c_int(nu), _lib.ptr(B), C.c_size_t(ldb), C.c_int(n), C.c_int(lda),
+                                          _lib.ptr(bs), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n_top), C.c_double(t), C.c_uint64(seed),
+                                          C.c_int(1 if with_lse else 0), _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(keys), _lib.ptr(lse))
+    _lib.check(rc, lib, "topN_sample_batch")
+    return (ids, sc, keys, lse) if with_lse else (ids, sc, keys)
+
+
 def _explain_args(history, targets, n, gram, lam, lam_user, bias_lam, dtype, k, what):
     """The ``cmfrec_hip_explain_args`` of an explanation call and what must outlive it: (args, keep-alive list, outputs
     (total, ids, contributions), shape of the targets or None).  Checked without a device as far as the shapes go; the ids, the

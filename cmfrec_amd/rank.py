@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ops import _explain_args, _explain_result, _heldout_lists, _is_csr, _mmr_pools, _similar_args, _sorted_exclude, _sorted_include, after_cursor
+from .ops import _explain_args, _explain_result, _heldout_lists, _is_csr, _mmr_pools, _sample_args, _similar_args, _sorted_exclude, _sorted_include, after_cursor
 
 
 def check_rankset(users, heldout, exclude):
@@ -416,6 +416,34 @@ class Ranker:
                                                      _lib.ptr(mmr))
         _lib.check(rc, self.lib, "Ranker.topN_diverse")
         return (ids, sc, mmr) if output_mmr else (ids, sc)
+
+    def topN_sample(self, A, n=10, temperature=1.0, seed=0, exclude=None, with_lse=False):
+        """Stochastic top-N: (ids [nu, n] int32, scores [nu, n], keys [nu, n]) -- per row of ``A`` ``n`` items drawn without
+        replacement with probability proportional to ``exp(score / temperature)`` (Plackett-Luce), as the ``n`` largest of
+        ``key = score + temperature * g``, in descending key (ties by lower id, -1 / -inf / -inf where fewer remain).  ``g`` is one
+        standard Gumbel variable per pair from a counter-based hash, so a call is reproducible: for the row at position ``u`` of
+        THIS batch and item ``i``, ``h = splitmix64(seed ^ (u * 0x9E3779B97F4A7C15 + i))``, ``U = ((h >> 11) + 0.5) * 2^-53``
+        (float32: ``((h >> 40) + 0.5) * 2^-24``), ``g = -log(-log(U))`` in the working precision.  ``scores`` are the bits ``topN``
+        gives for the pair on the MFMA kernel (k > 64, or ``CMFREC_HIP_TOPN=wide``).  ``with_lse``: a fourth value, lse [nu] float64
+        = log sum over the user's items that are not excluded of exp(score / temperature) (-inf when none is left), the
+        exponentials in single precision: ``exp(score / temperature - lse)`` is the probability of the first draw, and the chain
+        of such terms the propensity of the list.  ``temperature`` = 0: no noise, ``topN``'s ids and scores of that kernel, the keys
+        equal the scores, lse NaN.  ``n <= min(128, items)``.  ``include``, deep lists and cursors are not combined with sampling;
+        the handle's ``split`` and ``filter`` are ignored."""
+        h = self._live()
+        A = self._users(A, "Ranker.topN_sample")
+        n, t, seed = _sample_args(n, self.n, temperature, seed, "Ranker.topN_sample")
+        nu = A.shape[0]
+        if exclude is not None and _is_csr(exclude):
+            exclude = (exclude.indptr, exclude.indices)
+        ep, ei = _sorted_exclude(exclude, nu)
+        ids = np.empty((nu, n), np.int32); sc = np.empty((nu, n), self.dtype); keys = np.empty((nu, n), self.dtype)
+        lse = np.empty(nu, np.float64) if with_lse else None
+        rc = self.lib.cmfrec_hip_ranker_topN_sample(h, _lib.ptr(A), C.c_size_t(self.k), C.c_int(nu), _lib.ptr(ep), _lib.ptr(ei), C.c_int(n),
+                                                    C.c_double(t), C.c_uint64(seed), C.c_int(1 if with_lse else 0), _lib.ptr(ids),
+                                                    _lib.ptr(sc), _lib.ptr(keys), _lib.ptr(lse))
+        _lib.check(rc, self.lib, "Ranker.topN_sample")
+        return (ids, sc, keys, lse) if with_lse else (ids, sc, keys)
 
     def explain(self, history, targets, n=10, gram=None, lam=1.0, lam_user=None, bias_lam=None):
         """Why an item scores what it scores: for every (user, target) pair the score ``b_t . a_u`` of the user's closed-form

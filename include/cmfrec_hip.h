@@ -785,6 +785,34 @@ int cmfrec_hip_topN_diverse_batch(const real_t *A, size_t lda, int_t nu, const r
                                   const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t pool, double theta,
                                   int_t n_top, int_t *out_ids, real_t *out_scores, real_t *out_mmr);
 
+/* Stochastic top-N: n_top items per user drawn without replacement with probability proportional to exp(score / temperature)
+ * (Plackett-Luce), on the device (topn_sample_kernels.hpp).  For user u -- its PLACE IN THE CALL'S BATCH --,
+ * item i and the 64-bit seed:
+ *   h   = splitmix64(seed ^ (u * 0x9E3779B97F4A7C15 + i))               (the standard finaliser, arithmetic modulo 2^64)
+ *   U   = ((h >> 11) + 1/2) * 2^-53 in double, ((h >> 40) + 1/2) * 2^-24 in single precision: strictly inside (0, 1)
+ *   g   = -log(-log(U)), evaluated in the working precision (for U > 1/2 through the exact 1 - U and log1p)
+ *   key = score + temperature * g (one fused multiply-add), score exactly what ranker_topN scores on the MFMA route
+ * out_ids [nu, n_top] (required): per user the n_top items of the largest key among those not excluded, in descending key, equal
+ * keys to the lower id, -1 where fewer remain.  out_scores (optional): their scores, the bits ranker_topN gives for the pair under
+ * CMFREC_HIP_TOPN=wide, -inf behind a short list.  out_keys (optional): their keys, -inf likewise.  with_lse != 0: out_lse [nu]
+ * (then required) = log sum over the user's items that are not excluded of exp(score / temperature), in double, the exponentials
+ * evaluated in single precision; -inf for a user with nothing left.  Same seed, same batch: the same bytes; the result does not
+ * depend on the launch shape.
+ * temperature == 0: no noise is evaluated; ids and scores are ranker_topN's under CMFREC_HIP_TOPN=wide for every k, the keys equal
+ * the scores, out_lse is NaN.
+ * Limits: k <= 272, 1 <= n_top <= min(128, n), temperature finite, >= 0 and, where > 0, with a finite inverse in the working
+ * precision; excl_p / excl_i a CSR over the users, each list ascending.  Beyond them, and for a null handle or pointer, code 2 with
+ * the limits in the message, before anything touches the device, the outputs untouched.  Candidate lists, deep lists and
+ * cursors are not combined with sampling (there is no argument for them); the handle's split and filter settings are ignored, as
+ * ranker_similar ignores them.  kernel_ms / launch_shape report the sampling kernel and the score kernel behind it.
+ * cmfrec_hip_topN_sample_batch is create, one such call, destroy. */
+int cmfrec_hip_ranker_topN_sample(cmfrec_hip_ranker *r, const real_t *A, size_t lda, int_t nu,
+                                  const size_t excl_p[], const int_t excl_i[], int_t n_top, double temperature, uint64_t seed,
+                                  int with_lse, int_t *out_ids, real_t *out_scores, real_t *out_keys, double *out_lse);
+int cmfrec_hip_topN_sample_batch(const real_t *A, size_t lda, int_t nu, const real_t *B, size_t ldb, int_t n, int_t k,
+                                 const real_t *biasB, const size_t excl_p[], const int_t excl_i[], int_t n_top, double temperature,
+                                 uint64_t seed, int with_lse, int_t *out_ids, real_t *out_scores, real_t *out_keys, double *out_lse);
+
 /* Why an item was recommended: the score of a (user, target) pair split into one term per item of the user's history, on the
  * device (topn_explain_kernels.hpp).  For the models this library fits a user's closed-form factors are
  *   a_u = W_u^-1 sum_j y_j b_j,    W_u = G0 + diag I + sum_j g_j b_j b_j^T    over the user's own items j,
