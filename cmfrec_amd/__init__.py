@@ -7,6 +7,7 @@ from .rank import Ranker, RankSet  # noqa: F401
 from .new_users import NewUsers  # noqa: F401
 from .score import EvalSet, Scorer  # noqa: F401
 from . import metrics  # noqa: F401
-from .validation import Validation, Objective  # noqa: F401
+from .validation import Validation, Objective, Subspace  # noqa: F401
 
-__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "RankSet", "NewUsers", "Scorer", "EvalSet", "Validation", "Objective", "ops", "metrics"]
+__all__ = ["CMF", "CMF_implicit", "AlsSession", "Ranker", "RankSet", "NewUsers", "Scorer", "EvalSet", "Validation", "Objective", "Subspace", "ops",
+           "metrics"]

@@ -162,6 +162,7 @@ EXPORTED = [
     "cmfrec_hip_session_snapshot", "cmfrec_hip_session_restore", "cmfrec_hip_fit_set_monitor", "cmfrec_hip_early_stop_step",
     "cmfrec_hip_rankset_create", "cmfrec_hip_rankset_destroy", "cmfrec_hip_ranker_metrics", "cmfrec_hip_session_ranking",
     "cmfrec_hip_session_objective", "cmfrec_hip_objective_value", "cmfrec_hip_fit_set_objective",
+    "cmfrec_hip_session_set_subspace", "cmfrec_hip_fit_set_subspace",
     "cmfrec_hip_sizeof_newrows_model", "cmfrec_hip_newrows_create", "cmfrec_hip_newrows_factors", "cmfrec_hip_newrows_topN", "cmfrec_hip_newrows_topN_candidates", "cmfrec_hip_newrows_ranks", "cmfrec_hip_newrows_impute", "cmfrec_hip_newrows_predict", "cmfrec_hip_newrows_kernel_ms", "cmfrec_hip_newrows_destroy", "cmfrec_hip_factors_multiple_naz", "cmfrec_hip_sizeof_newrows_model_ex", "cmfrec_hip_newrows_create_ex", "cmfrec_hip_newrows_naz_launch_waves",
     "cmfrec_hip_session_create", "cmfrec_hip_session_destroy", "cmfrec_hip_last_error", "cmfrec_hip_last_error_code",
     "cmfrec_hip_session_set_X", "cmfrec_hip_session_set_A_parts", "cmfrec_hip_session_nparts", "cmfrec_hip_session_part_range", "cmfrec_hip_session_stream_wait_part", "cmfrec_hip_session_set_X_coo", "cmfrec_hip_session_set_X_coo_weighted", "cmfrec_hip_session_set_X_weighted", "cmfrec_hip_session_set_X_coo_device", "cmfrec_hip_session_precompute", "cmfrec_hip_session_init_biases", "cmfrec_hip_session_get_X", "cmfrec_hip_session_set_factors", "cmfrec_hip_session_get_factors",
@@ -296,6 +297,8 @@ def load(dtype=np.float64):
     lib.cmfrec_hip_objective_value.restype = C.c_double
     lib.cmfrec_hip_objective_value.argtypes = [C.POINTER(ObjectiveRecord), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int]
     lib.cmfrec_hip_fit_set_objective.argtypes = [C.POINTER(FitObjective)]
+    lib.cmfrec_hip_session_set_subspace.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.cmfrec_hip_fit_set_subspace.argtypes = [C.c_int, C.c_int]
     lib.cmfrec_hip_early_stop_step.argtypes = [C.POINTER(EarlyStop), C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.cmfrec_hip_pair_errors.argtypes = lib.cmfrec_hip_score_pairs.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Errors)]
     for name in EXPORTED_OTHER[1:]:

@@ -152,6 +152,28 @@ int check_objective(const FitObjective &obj, const FitMonitor &mon, const char *
     if (kk < 1 || kk > 272) return refuse_monitor(verbose, name + ": the objective needs 1 <= k + k_main <= 272");
     return 0;
 }
+// ---- the subspace solver of a fit (cmfrec_hip_fit_set_subspace, include/cmfrec_hip.h) ---------------------------------
+// Waits per thread for the next fit call, as the monitor does; take_subspace() empties the slot on every path out of a fit.
+struct FitSubspace {
+    int block = 0, sweeps = 1;
+};
+thread_local FitSubspace g_subspace;
+FitSubspace take_subspace()
+{
+    FitSubspace out = g_subspace;
+    g_subspace = FitSubspace();
+    return out;
+}
+// the refusals before the fit writes to any output: 0 or 2.  unsupported: what of the call's options
+// cmfrec_hip_session_set_subspace would refuse (the fit functions name it from their arguments, in the setter's words), or null
+int check_subspace(const FitSubspace &sub, const char *unsupported, bool verbose)
+{
+    if (sub.block == 0) return 0;
+    if (unsupported == nullptr && sharded_fit_wanted(devices_from_env()))
+        unsupported = "a session that does not own all rows (set_A_parts, several devices)";
+    if (unsupported == nullptr) return 0;
+    return refuse_monitor(verbose, std::string("cmfrec_hip: the subspace solver is not implemented for ") + unsupported);
+}
 double watched_value(const cmfrec_hip_errors &r, int metric)
 {
     const double sw = r.sum_w[0] + r.sum_w[1];
@@ -728,6 +750,20 @@ int cmfrec_hip_fit_set_objective(const cmfrec_hip_fit_objective *objective)
     return 0;
 }
 
+/* the subspace solver (include/cmfrec_hip.h): handed to this thread's next fit call */
+int cmfrec_hip_fit_set_subspace(int block, int sweeps)
+{
+    g_subspace = FitSubspace();
+    if (block == 0) return 0;
+    if (block != 16 || sweeps < 1) {
+        cmfhip::g_last_error = std::string("cmfrec_hip: the subspace solver is not implemented for ") +
+                               (block != 16 ? "a block other than 0 or 16" : "sweeps < 1");
+        return 2;
+    }
+    g_subspace.block = block; g_subspace.sweeps = sweeps;
+    return 0;
+}
+
 /* the rule of the monitor, host only: which iterations are evaluated, what improves, when to stop */
 int cmfrec_hip_early_stop_step(cmfrec_hip_early_stop *st, int iter, int niter, const double *value)
 {
@@ -775,10 +811,16 @@ int_t fit_collective_implicit_als(
     (void)nthreads;
     FitMonitor mon = take_monitor();
     FitObjective obj = take_objective();
+    const FitSubspace sub = take_subspace();
     if (const int rc_mon = check_monitor(mon, "fit_collective_implicit_als", m, n, k + k_main, niter, verbose)) return rc_mon;
     {
         const char *unsupported = (U || II || nnz_U || nnz_I || k_user || k_item) ? "side information" : (l1_lam != 0 || l1_lam_unique) ? "an L1 penalty" : nullptr;
         if (const int rc_obj = check_objective(obj, mon, "fit_collective_implicit_als", k + k_main, niter, unsupported, verbose)) return rc_obj;
+    }
+    {
+        const char *unsupported = (U || II || nnz_U || nnz_I || k_user || k_item) ? "side information" : nonneg ? "nonneg"
+                                  : (l1_lam != 0 || l1_lam_unique) ? "an L1 penalty" : lam_unique ? "lam_unique" : nullptr;
+        if (const int rc_sub = check_subspace(sub, unsupported, verbose)) return rc_sub;
     }
     // collective.c:9406-9435
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
@@ -924,6 +966,7 @@ int_t fit_collective_implicit_als(
     if (!rc && (lam_unique || l1_lam_unique))
         rc = cmfrec_hip_session_set_lam_unique(s, lam_unique ? lam6 : nullptr, l1_lam_unique ? l16 : nullptr, (int)max_cd_steps);
     if (!rc) rc = cmfrec_hip_session_set_factors(s, A, B, nullptr, nullptr, C, D);
+    if (!rc && sub.block) rc = cmfrec_hip_session_set_subspace(s, sub.block, sub.sweeps);
     if (verbose && !rc) { printf("Starting ALS optimization routine\n\n"); fflush(stdout); }
     if (tm.on) cmfrec_hip_session_sync(s);
     tm.lap("set_factors");
@@ -968,11 +1011,19 @@ int_t fit_collective_explicit_als(
     (void)precomputedBiTBi;        // with add_implicit_features the prediction matrices are not produced here
     FitMonitor mon = take_monitor();
     FitObjective obj = take_objective();
+    const FitSubspace sub = take_subspace();
     if (const int rc_mon = check_monitor(mon, "fit_collective_explicit_als", m, n, k + k_main, niter, verbose)) return rc_mon;
     {
         const char *unsupported = (U || II || nnz_U || nnz_I || k_user || k_item) ? "side information" : add_implicit_features ? "implicit features"
                                   : NA_as_zero_X ? "NA_as_zero_X" : Xfull ? "a dense X" : (l1_lam != 0 || l1_lam_unique) ? "an L1 penalty" : nullptr;
         if (const int rc_obj = check_objective(obj, mon, "fit_collective_explicit_als", k + k_main, niter, unsupported, verbose)) return rc_obj;
+    }
+    {
+        const char *unsupported = (U || II || nnz_U || nnz_I || k_user || k_item) ? "side information" : add_implicit_features ? "implicit features"
+                                  : nonneg ? "nonneg" : (l1_lam != 0 || l1_lam_unique) ? "an L1 penalty" : lam_unique ? "lam_unique"
+                                  : NA_as_zero_X ? "NA_as_zero_X" : Xfull ? "a dense X" : weight ? "observation weights"
+                                  : (scale_lam || scale_lam_sideinfo) ? "scale_lam" : nullptr;
+        if (const int rc_sub = check_subspace(sub, unsupported, verbose)) return rc_sub;
     }
     // collective.c:7308-7329
     if (k_user && U == nullptr && nnz_U == 0) return fail(verbose, "Cannot pass 'k_user' without U data.");
@@ -1414,6 +1465,7 @@ int_t fit_collective_explicit_als(
     // dense X under scale_lam: the rows' lambda multipliers (n for a row that misses few entries, its present entries otherwise)
     if (!rc && !dense_mult_A.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, 'A', dense_mult_A.data());
     if (!rc && !dense_mult_B.empty()) rc = cmfrec_hip_session_set_lambda_multipliers(s, 'B', dense_mult_B.data());
+    if (!rc && sub.block) rc = cmfrec_hip_session_set_subspace(s, sub.block, sub.sweeps);
     if (verbose && !rc) { printf("Starting ALS optimization routine\n\n"); fflush(stdout); }
     mon.glob_mean = gm;
     // the penalties in the caller's units, as the row solvers see them: lam6 x w_main, the biases' with scaling_biasA / _biasB inside

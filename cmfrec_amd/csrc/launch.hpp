@@ -42,6 +42,20 @@ unsigned long long *cg_ticks_buffer();
 // (gram_wave_tu.hip)
 void launch_gram_wave(dim3 grid, hipStream_t st, const CgParams<real_t> &P, const GramParams<real_t> &G, bool implicit, int rem);
 
+// ---- subspace (iALS++) row updates (subspace_tu.hip) ----------------------------------------
+// A [rows, lda] in and out, B [*, ldb] the opposing factors, k unknowns per row; G0 [k, k] = B^T B without lambda for the implicit
+// model (g_j = the stored value, y_j = g_j + 1), null for the explicit one (g_j = 1, y_j = x_j - bias_sub[j])
+struct SubspaceCall {
+    real_t *A = nullptr; size_t lda = 0;
+    const real_t *B = nullptr; size_t ldb = 0;
+    int k = 0;
+    const real_t *bias_sub = nullptr, *G0 = nullptr;
+    real_t lam = 0, lam_last = 0;
+    int sweeps = 1;
+};
+// every row of X with entries; yhat: the session's scratch for the rows beyond the LDS cap (sized here)
+int launch_subspace(const DeviceInfo &dev, const SubspaceCall &c, const SparseShard &X, DevBuf<real_t> &yhat);
+
 // ---- closed-form row updates (launch_chol.hip, launch_lowrank.hip) --------------------------
 // (chol_wg_tu.hip: the four-wavefront factorisation of the eight-block rows, double precision)
 hipError_t launch_chol_wg8(int num_cus, bool border, int waves_per_row, hipStream_t st, const CholParams<real_t> &W, const RowDesc *desc, const CholSlices<real_t> &SL);

@@ -132,6 +132,10 @@ struct cmfrec_hip_session {
     // low-rank row updates (lowrank_kernels.hpp): eigenvectors / values of w C^T C, rotated C and opposing factors,
     // rotated right-hand sides and solutions
     LowRankScratch lr;
+    // cmfrec_hip_session_set_subspace: 16 = the A / B updates that would take the CG route take the subspace half-step
+    // (subspace_kernels.hpp) instead, `subspace_sweeps` passes over the blocks; sub_yhat: its scratch for the rows beyond the LDS cap
+    int subspace_block = 0, subspace_sweeps = 1;
+    DevBuf<real_t> sub_yhat;
     long cg_wide_rows[2] = {0, 0};  // rows the most recent A-step / B-step solved on the Gramian CG beyond 64 unknowns (launch_cg_wide)
     EigCache eigA, eigB;         // eigenvectors of w_user C^T C (A-steps) / w_item D^T D (B-steps), see EigCache
     // row-block shards of the explicit / collective model (distributed.py): U / I hold only the rows of this
@@ -1507,11 +1511,56 @@ static int update_factor_naz_weighted(cmfrec_hip_session *s, const HalfStepSide 
     return 0;
 }
 
+// What of the session the subspace half-step does not cover (cmfrec_hip_session_set_subspace), or null
+static const char *subspace_unsupported(const cmfrec_hip_session *s)
+{
+    const cmfrec_hip_model &m = s->mdl;
+    if (m.p > 0 || m.q > 0 || m.k_user > 0 || m.k_item > 0 || s->sparseU || s->sparseI || s->zerosU.on() || s->zerosI.on() ||
+        s->n_zrowsA > 0 || s->n_zrowsB > 0 || s->has_cfA || s->has_cfB)
+        return "side information";
+    if (s->implicit_feats) return "implicit features";
+    if (s->nonneg) return "nonneg";
+    for (int e = 0; e < 6; e++) if (s->l16[e] != 0) return "an L1 penalty";
+    for (int e = 0; e < 6; e++) if (s->lam6[e] != m.lam) return "lam_unique";
+    if (s->naz_X) return "NA_as_zero_X";
+    if (s->Xr.weighted() || s->Xc.weighted()) return "observation weights";
+    if (m.scale_lam || m.scale_lam_sideinfo) return "scale_lam";
+    if (m.row_begin != 0 || m.row_end != m.m || m.col_begin != 0 || m.col_end != m.n || !s->XrParts.empty())
+        return "a session that does not own all rows (set_A_parts, several devices)";
+    return nullptr;
+}
+static int subspace_refuse(const char *what)
+{
+    g_last_error = std::string("cmfrec_hip: the subspace solver is not implemented for ") + what;
+    return 2;
+}
+
+// The subspace (iALS++) half-step in the place of the CG route: subspace_kernels.hpp, DESIGN.md section 3.22.  Rows without
+// entries are not touched, as the CG route leaves them.
+static int update_factor_subspace(cmfrec_hip_session *s, const HalfStepSide &v)
+{
+    if (const char *what = subspace_unsupported(s)) return subspace_refuse(what);
+    const cmfrec_hip_model &m = s->mdl;
+    SubspaceCall c;
+    c.A = v.self; c.lda = v.ld_self; c.B = v.oppx; c.ldb = v.ld_opp;
+    c.lam = v.lam_self; c.lam_last = v.lam_last_self; c.sweeps = s->subspace_sweeps;
+    if (m.implicit) {
+        launch_gram(s->dev, s->gws, v.oppx, v.ld_opp, v.rows_x_opp, v.kk, s->gram.ptr, (real_t)1, (real_t)0);
+        c.k = v.kk; c.G0 = s->gram.ptr;
+    } else {
+        fill_fixed_bias_column(s, v);
+        HIP_CHECK(hipGetLastError());
+        c.k = v.ks; c.bias_sub = v.bias;
+    }
+    return launch_subspace(s->dev, c, v.X, s->sub_yhat);
+}
+
 static int update_factor(cmfrec_hip_session *s, bool isA, bool chol, int part = -1)
 {
     // "self" = matrix being updated, "opp" = the fixed one
     const HalfStepSide v(s, isA);
     if (part <= 0) s->cg_wide_rows[isA ? 0 : 1] = 0;          // (the parts of a block add up)
+    if (s->subspace_block != 0 && !chol) return update_factor_subspace(s, v);
     if (s->naz_X && !s->mdl.implicit && s->Xr.weighted()) return update_factor_naz_weighted(s, v, chol);
     if (s->naz_X && !s->mdl.implicit) return update_factor_naz(s, v, chol);
     const cmfrec_hip_model &m = s->mdl;
@@ -1940,7 +1989,8 @@ int cmfrec_hip_session_update(cmfrec_hip_session *s, int which, int use_cholesky
                           : which == 'b' ? s->l16[3] / s->w_implicit
                           : (which == 'C' ? s->l16[4] / s->mdl.w_user : s->l16[5] / s->mdl.w_item);
         const real_t l1_last = which == 'A' ? s->l16[ub ? 0 : 2] : which == 'B' ? s->l16[ib ? 1 : 3] : l1;
-        const bool chol = use_cholesky || !s->mdl.use_cg || nn || l1 != 0 || l1_last != 0;   // common.c:725, :2781, :3320: no CG with nonneg / L1
+        // common.c:725, :2781, :3320: no CG with nonneg / L1 (the subspace route of A / B stands in for the CG route, use_cg or not)
+        const bool chol = use_cholesky || (!s->mdl.use_cg && !(isAB && s->subspace_block != 0)) || nn || l1 != 0 || l1_last != 0;
         struct SolveScope {                                           // the closed-form launches of this update
             const DeviceInfo &d;
             SolveScope(const DeviceInfo &d_, bool on, int steps, real_t l1_, real_t l1l, real_t sc) : d(d_)
@@ -2037,6 +2087,17 @@ int cmfrec_hip_session_update(cmfrec_hip_session *s, int which, int use_cholesky
         g_last_error = "cmfrec_hip: unknown update target";
         return 2;
     });
+}
+
+int cmfrec_hip_session_set_subspace(cmfrec_hip_session *s, int block, int sweeps)
+{
+    if (s == nullptr) { g_last_error = "cmfrec_hip_session_set_subspace: invalid arguments"; return 2; }
+    if (block != 0 && block != 16) return subspace_refuse("a block other than 0 or 16");
+    if (block != 0 && sweeps < 1) return subspace_refuse("sweeps < 1");
+    if (block != 0) if (const char *what = subspace_unsupported(s)) return subspace_refuse(what);
+    s->subspace_block = block;
+    s->subspace_sweeps = block != 0 ? sweeps : 1;
+    return 0;
 }
 
 int cmfrec_hip_session_iterate(cmfrec_hip_session *s, int niter, int finalize_chol)

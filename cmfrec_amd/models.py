@@ -14,6 +14,7 @@ import multiprocessing
 import numpy as np
 
 from . import _lib
+from .validation import Subspace
 
 
 def _coo_triplet(X, shape=None):
@@ -431,11 +432,17 @@ def _side_info(M, dt):
     return np.ascontiguousarray(M, dt), None
 
 
-def _monitored(watch, fit, *args):
-    """The fit call of ``fit(..., validation=)``: whatever it does, the monitor and its resident set do not outlive it."""
+def _monitored(watch, lib, subspace, fit, *args):
+    """The fit call of ``fit(..., validation=, subspace=)``: whatever it does, the monitor and its resident set do not outlive it,
+    and no subspace solver waits for the thread's next fit (the slot is cleared whether or not this fit handed one over)."""
     try:
+        if subspace is not None:
+            if not isinstance(subspace, Subspace):
+                raise TypeError("'subspace' must be a cmfrec_amd.Subspace")
+            subspace._begin(lib)
         return fit(*args)
     finally:
+        lib.cmfrec_hip_fit_set_subspace(C.c_int(0), C.c_int(1))
         if watch is not None:
             watch.close()
 
@@ -551,14 +558,15 @@ class CMF_implicit(_Base):
         self.nonneg_C = bool(nonneg_C); self.nonneg_D = bool(nonneg_D); self.max_cd_steps = int(max_cd_steps)
         self.l1_lambda, self._l16 = _penalty(l1_lambda, "l1_lambda")
 
-    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, validation=None, objective=None):
+    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, validation=None, objective=None, subspace=None):
         """Fits the model.  ``A0``/``B0`` (optional) inject the start values instead of drawing
         them from ``random_state`` (C argument ``reset_values=false``).  ``U`` / ``I``: dense side
         information without missing values, or SciPy sparse matrices (missing = absent).
         ``validation``: a ``cmfrec_amd.Validation`` -- a held-out set evaluated on the device while fitting, early stopping and the
         best iterate (default metric "ndcg" at ``k=10``, the training items left out of every ranking).
         ``objective``: a ``cmfrec_amd.Objective`` -- the training objective evaluated on the device while fitting and a ``tol``
-        that stops the fit; the model then has ``objective_history_`` and ``n_iter_``.  Not together with ``validation``."""
+        that stops the fit; the model then has ``objective_history_`` and ``n_iter_``.  Not together with ``validation``.
+        ``subspace``: a ``cmfrec_amd.Subspace`` -- the half-steps run the subspace (iALS++) solver; ``solver_`` names the solver."""
         self.close()                                # the one-user handles hold the factors of the fit that was
         row, col, val, m, n = _coo_triplet(X, shape)
         lib, R = self._lib()
@@ -592,7 +600,7 @@ class CMF_implicit(_Base):
         CtUbias = np.zeros(self.k_user + self.k, dt) if (pre and p and Us is not None and self.NA_as_zero_user) else None
         owatch = _objective_begin(objective, validation, lib, self.niter)
         watch = None if validation is None else validation._begin(lib, dt, self.niter, "ndcg", (row, col, m, n))
-        rc = _monitored(watch or owatch, lib.fit_collective_implicit_als,
+        rc = _monitored(watch or owatch, lib, subspace, lib.fit_collective_implicit_als,
             _lib.ptr(A), _lib.ptr(B), _lib.ptr(Cm), _lib.ptr(Dm), C.c_bool(reset), C.c_int(self.random_state),
             _lib.ptr(Ucm) if (p and self.center_U) else None, _lib.ptr(Icm) if (q and self.center_I) else None,
             C.c_int(m), C.c_int(n), C.c_int(self.k), _lib.ptr(row), _lib.ptr(col), _lib.ptr(val),
@@ -610,6 +618,7 @@ class CMF_implicit(_Base):
         # an interrupted fit returns 3 with usable factors; like the reference's wrapper, raise only when the caller did
         # not ask for the interrupt to be handled (cmfrec/wrapper_untyped.pxi: `if ret_code == 3 and not handle_interrupt`)
         _lib.check(rc, lib, "fit_collective_implicit_als", interrupt_ok=self.handle_interrupt)
+        self.solver_ = "subspace" if subspace is not None else ("cg" if self.use_cg else "cholesky")
         _validation_results(self, watch)
         _objective_results(self, owatch)
         self.A_, self.B_ = A, B
@@ -854,14 +863,16 @@ class CMF(_Base):
         self.handle_interrupt = bool(handle_interrupt)
         self._setup(use_float, nthreads, n_jobs)
 
-    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, biasA0=None, biasB0=None, W=None, validation=None, objective=None):
+    def fit(self, X, U=None, I=None, shape=None, A0=None, B0=None, biasA0=None, biasB0=None, W=None, validation=None, objective=None,
+            subspace=None):
         """``X``: SciPy sparse matrix / COO triplet, or a dense 2-D array with NaN for the missing entries (the plain model:
         no side information).  ``W``: observation weights, one per entry of ``X`` in its COO order (reference
         ``CMF.fit(X, ..., W=...)``, cmfrec/__init__.py:3066; an array(nnz,) for sparse ``X``, an array(m, n) for dense ``X``).
         ``validation``: a ``cmfrec_amd.Validation`` -- a held-out set evaluated on the device while fitting (default metric
         "rmse"), early stopping and the best iterate; the model then has ``validation_history_``, ``best_iteration_``, ``n_iter_``.
         ``objective``: a ``cmfrec_amd.Objective`` -- the training objective evaluated on the device while fitting and a ``tol``
-        that stops the fit; the model then has ``objective_history_`` and ``n_iter_``.  Not together with ``validation``."""
+        that stops the fit; the model then has ``objective_history_`` and ``n_iter_``.  Not together with ``validation``.
+        ``subspace``: a ``cmfrec_amd.Subspace`` -- the half-steps run the subspace (iALS++) solver; ``solver_`` names the solver."""
         self.close()                                # the one-user handles hold the factors of the fit that was
         lib, R = self._lib()
         dt = self.dtype_
@@ -925,7 +936,7 @@ class CMF(_Base):
         owatch = _objective_begin(objective, validation, lib, self.niter)
         watch = None if validation is None else validation._begin(
             lib, dt, self.niter, "rmse", (row, col, m, n) if Xfull is None else (*np.nonzero(~np.isnan(Xfull)), m, n))
-        rc = _monitored(watch or owatch, lib.fit_collective_explicit_als,
+        rc = _monitored(watch or owatch, lib, subspace, lib.fit_collective_explicit_als,
             _lib.ptr(biasA), _lib.ptr(biasB), _lib.ptr(A), _lib.ptr(B), _lib.ptr(Cm), _lib.ptr(Dm), _lib.ptr(Ai), _lib.ptr(Bi),
             C.c_bool(imp), C.c_bool(reset), C.c_int(self.random_state), _lib.ptr(glob_mean),
             # no column means = the side information is used as given (cmfrec/__init__.py passes an empty array for center_U=False)
@@ -946,6 +957,7 @@ class CMF(_Base):
             C.c_bool(pre), C.c_bool(True), _lib.ptr(Bpb), _lib.ptr(BtB), _lib.ptr(TBt), _lib.ptr(BtXbias), _lib.ptr(BeChol), None,
             _lib.ptr(TCt), _lib.ptr(CtCw), _lib.ptr(CtUbias))
         _lib.check(rc, lib, "fit_collective_explicit_als", interrupt_ok=self.handle_interrupt)
+        self.solver_ = "subspace" if subspace is not None else ("cg" if self.use_cg else "cholesky")
         _validation_results(self, watch)
         _objective_results(self, owatch)
         # precomputed matrices for predictions on new data, reference attribute names (cmfrec/__init__.py:3211-3247)

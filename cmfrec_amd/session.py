@@ -242,6 +242,15 @@ class AlsSession:
         _lib.check(self.lib.cmfrec_hip_session_update(self.handle, C.c_int(ord(which)), C.c_int(int(use_cholesky))),
                    self.lib, "update(%s)" % which)
 
+    def set_subspace(self, block=16, sweeps=1):
+        """The subspace (iALS++) solver for the A / B updates (``cmfrec_hip_session_set_subspace``): ``update(which)`` and ``iterate``
+        then run ``sweeps`` passes of block Gauss-Seidel over blocks of 16 unknowns from the rows' current factors;
+        ``use_cholesky=True`` / ``finalize_chol`` still take the closed form.  ``block=0`` switches it off.  Refused
+        (``RuntimeError``, code 2, the session unchanged): side information, implicit features, nonneg, L1, lam_unique,
+        NA_as_zero_X, observation weights, scale_lam, a session that does not own all rows."""
+        _lib.check(self.lib.cmfrec_hip_session_set_subspace(self.handle, C.c_int(int(block)), C.c_int(int(sweeps))), self.lib,
+                   "set_subspace")
+
     def after_gather(self, which):
         _lib.check(self.lib.cmfrec_hip_session_after_gather(self.handle, C.c_int(ord(which))), self.lib, "after_gather")
 

@@ -111,6 +111,23 @@ class Validation:
         return users.astype(np.int32), take(held), excl
 
 
+class Subspace:
+    """The subspace (iALS++) solver, for ``CMF.fit(..., subspace=)`` / ``CMF_implicit.fit(..., subspace=)``: every A / B half-step
+    runs ``sweeps`` passes of block Gauss-Seidel over blocks of ``block`` = 16 unknowns of each row's normal equations, from the
+    row's current factors, in the place of the CG steps (``cmfrec_hip_fit_set_subspace``).  The fixed
+    point is the closed form's; the iterates are not the reference's.  ``finalize_chol`` still ends on the closed form.  Refused
+    with the library's message: side information, implicit features, nonneg, L1, per-matrix lambdas, NA_as_zero, a dense X,
+    observation weights, scale_lam, fits on several devices.  The fitted model has ``solver_ == "subspace"``."""
+
+    def __init__(self, block=16, sweeps=1):
+        self.block = int(block)
+        self.sweeps = int(sweeps)
+
+    def _begin(self, lib):
+        """Hands the solver to this thread's next fit call, which consumes it whatever it returns."""
+        _lib.check(lib.cmfrec_hip_fit_set_subspace(C.c_int(self.block), C.c_int(self.sweeps)), lib, "fit(subspace=)")
+
+
 class Objective:
     """The training objective while fitting, for ``CMF.fit(..., objective=)`` / ``CMF_implicit.fit(..., objective=)``: evaluated on
     the device after every ``every``-th iteration and after the last one (``cmfrec_hip_fit_set_objective``).  ``tol``: the fit

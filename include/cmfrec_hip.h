@@ -533,6 +533,16 @@ int cmfrec_hip_session_update(cmfrec_hip_session *s, int which, int use_cholesky
 /* niter full ALS iterations in the reference's order C, D, B, A (collective.c:8334-8898 /
  * :9827-10045) on a single-GPU session. */
 int cmfrec_hip_session_iterate(cmfrec_hip_session *s, int niter, int finalize_chol);
+/* The subspace (iALS++) solver for the A / B updates: block = 16 switches it on, 0 (the default) off.  Once on,
+ * cmfrec_hip_session_update(s, 'A' | 'B', 0) and cmfrec_hip_session_iterate run block Gauss-Seidel on each row's normal
+ * equations -- blocks of 16 consecutive unknowns in ascending order, each solved exactly while the others stay fixed, `sweeps`
+ * passes per half-step, starting from the row's current factors -- in the place of the CG (or, with use_cg = 0, the closed-form)
+ * route; use_cholesky != 0 / finalize_chol still take the closed form.  The fixed point is the closed form's, the iterates are
+ * not the reference's.  Rows without entries are not touched.  Returns 2 with a message, the session as it was, for: side
+ * information in any form, implicit features, nonneg, an L1 penalty, lam_unique, NA_as_zero_X, observation weights, scale_lam,
+ * a session that does not own all rows (cmfrec_hip_session_set_A_parts, several devices), a block other than 0 / 16,
+ * sweeps < 1.  An update of a session that took such an option afterwards is refused the same way. */
+int cmfrec_hip_session_set_subspace(cmfrec_hip_session *s, int block, int sweeps);
 int cmfrec_hip_session_sync(cmfrec_hip_session *s);
 
 /* Device pointers for torch.distributed / RCCL plumbing (factor all-gather between half-steps).
@@ -1234,6 +1244,10 @@ typedef struct cmfrec_hip_fit_objective {
     int *iters_run;
 } cmfrec_hip_fit_objective;
 int cmfrec_hip_fit_set_objective(const cmfrec_hip_fit_objective *objective);
+/* The subspace solver for a fit (cmfrec_hip_session_set_subspace): handed over like the monitor, per thread, consumed by the next
+ * fit_collective_*_als call on that thread whatever it returns; block = 0 clears it.  A fit whose options the session's setter
+ * refuses -- and a dense X, CMFREC_HIP_DEVICES naming several devices or CMFREC_HIP_SHARDED=1 -- returns 2 with the same message. */
+int cmfrec_hip_fit_set_subspace(int block, int sweeps);
 
 /* Replace predict_X_old_collective_explicit / _implicit and predict_X_new_collective_explicit / _implicit of the reference's
  * src/cmfrec.h (bodies src/collective.c:11797-12069 over predict_multiple, src/common.c:5066-5110) -- the same positional
